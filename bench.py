@@ -163,6 +163,27 @@ def pmc_traffic(kernel, slots, N, prec="fp64"):
         return None, None
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, seed=0):
+    """--dump-outputs: the arrays of the last timed step -> <outdir>/<name>.npy (float64; integer status codes converted), so that
+    two builds run with the same arguments can be compared output for output.  All arrays run along the delay grid; above
+    DUMP_MAX_BYTES in all, the same fixed, seeded sample of grid positions is kept of each, and those positions go to index.npy."""
+    arrays = {k: np.asarray(v).reshape(-1).astype(np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    assert all(len(v) == n for v in arrays.values()), {k: v.shape for k, v in arrays.items()}
+    files = len(arrays) + 1                                 # + index.npy when sampled
+    if n * 8 * len(arrays) > DUMP_MAX_BYTES - 4096 * files:   # (4 KiB per file for the .npy header)
+        keep = (DUMP_MAX_BYTES - 4096 * files) // (8 * files)
+        idx = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["index"] = idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), v)
+
+
 def delay_grid(L, Gtot):
     """The whole grid (Gtot x L): 2 bands tau_2 in linspace(0, 20, Gtot); 3 bands (tau_2, tau_3) on a square over [0.5, 6]^2
     (README.md:227), flattened row-major."""
@@ -336,6 +357,8 @@ def native_multi(args, ndev):
                 ll, info, p = step()
             elapsed = time.perf_counter() - t0
         gstate = smp.summary()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"loglik": ll, "info": info, "probabilities": p})
         mode = {1: "rccl", 2: "host"}.get(obj.get_option("gather_mode"), "?")
         comp_ms, gather_ms, total_ms = obj.multi_stats()     # of the LAST step: where a scaling loss would come from
         roofline = cpu_baseline = None
@@ -387,7 +410,12 @@ def main():
                     help="also time the sweep with the shared-prefix mode asserted (reported separately, never as `value`)")
     ap.add_argument("--option", action="append", default=[], help="handle option key=value (gpcc_set_option), repeatable")
     ap.add_argument("--cpu-sample", type=int, default=0, help="CPU baseline: evaluations per worker process (0: 24)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (log-likelihoods, info, posterior probabilities of "
+                         "the whole grid) as DIR/<name>.npy, float64, at most 64 MB (a fixed seeded sample of the grid above that)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -492,6 +520,16 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+
+    if args.dump_outputs:       # before the legs below run the sweep again into the same buffers
+        info_all = d_info
+        if use_dist:            # every rank takes part; the blocks lie in grid order, padding after Gtot
+            src_info = d_info if backend == "nccl" else d_info.cpu()
+            info_all = torch.empty(G * world, dtype=torch.int32, device=src_info.device)
+            dist.all_gather_into_tensor(info_all, src_info)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"loglik": (d_all if use_dist else d_ll)[:Gtot].cpu().numpy(),
+                                             "info": info_all[:Gtot].cpu().numpy(), "probabilities": d_prob.cpu().numpy()})
 
     # Extra, NOT the headline: the same sweep with the shared-prefix mode asserted (all delays of the grid have the
     # same band-1 amplitude, delay and rho, so each group factorises the leading band-1 tile rows once; results are
