@@ -277,6 +277,31 @@ class Objective:
             raise PosDefException(int(info[0]))
         return float(ll[0])
 
+    def loglik_grad_batch(self, delays, alpha, rho):
+        """objective and its gradient for M (tau, alpha, rho) triples -> (loglik[M], grad[M, 2L+1], info[M]).
+        A row of grad is [d/dalpha_1..alpha_L, d/drho, d/dtau_1..tau_L] in the reference's (constrained) parameters; NaN where
+        info != 0 (info as loglik_batch).  Always fp64; a multi-device handle computes on its first device."""
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        ll = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, 2 * self.L + 1), dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        self._chk(_capi.load().gpcc_loglik_grad_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _dp(grad),
+                                                      _ip(info)))
+        return ll, grad, info
+
+    def value_and_grad(self, alpha, rho, delays):
+        """(objective(alpha, rho), gradient) for one delay vector: the gradient is a dict {"alpha": (L,), "rho": float,
+        "delays": (L,)}; raises what __call__ raises."""
+        ll, grad, info = self.loglik_grad_batch([delays], [alpha], [rho])
+        if info[0] == -1:
+            raise AssertionError("all(scale .> 0)")
+        if info[0] == -2:
+            raise ValueError("ρ=%.8f is <= 0" % rho)
+        if info[0] > 0:
+            raise PosDefException(int(info[0]))
+        g = grad[0]
+        return float(ll[0]), {"alpha": g[:self.L].copy(), "rho": float(g[self.L]), "delays": g[self.L + 1:].copy()}
+
     def loglik_batch_device(self, delays, alpha, rho, out=None, info=None):
         """Same on torch CUDA tensors (float64, contiguous), asynchronous on torch's current stream."""
         import torch

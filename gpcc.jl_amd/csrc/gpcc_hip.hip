@@ -2,6 +2,7 @@
 // kernels of gpcc_kernels.hip.h.  No CPU fallback: every compute entry needs a HIP device.
 #include "gpcc_kernels.hip.h"
 #include "gpcc_small.hip.h"
+#include "gpcc_grad.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 
@@ -183,6 +184,10 @@ struct gpcc_handle_s {
     int *d_info = nullptr;
     double *d_kdiag = nullptr, *d_cond = nullptr;   // fp32 mode: diag(K) as assembled, pivot-ratio sums (GpccCtx)
     double *d_gpart = nullptr;                      // fp32 mode: per-tile partials of X' K0 X (refinement)
+    // gradient (gpcc_loglik_grad_batch): allocated on its first call, per workspace slot -- every inv(L_kk) (nt tiles), a scratch
+    // column of the triangular inverse (nt tiles), w = K^-1 r (Np) and the per-tile partials (nt(nt+1)/2 x 3 L^2)
+    double *d_glinv = nullptr, *d_gscr = nullptr, *d_gw = nullptr, *d_gpart3 = nullptr, *d_ggrad = nullptr;
+    long grad_slots = 0, ggrad_cap = 0;
     double *d_sep = nullptr, *d_seps = nullptr;     // separable factors of the points, the distance scale (GpccCtx::sep, ::seps)
     int *d_sepflag = nullptr;                       // per-tile-row flags (GpccCtx::sepflag)
     int fp32_refine = 1;                            // option "fp32_refine": 0 = no refinement of the quadratic forms
@@ -449,6 +454,8 @@ static void free_workspace(gpcc_handle_t h)
     hipFree(h->d_logdet); hipFree(h->d_quad); hipFree(h->d_info); hipFree(h->d_kdiag); hipFree(h->d_cond); hipFree(h->d_gpart);
     hipFree(h->d_sep); hipFree(h->d_seps); hipFree(h->d_sepflag);
     hipFree(h->d_chain_words); hipFree(h->d_ximg); hipFree(h->d_stepval); hipFree(h->d_chain_trace);
+    hipFree(h->d_glinv); hipFree(h->d_gscr); hipFree(h->d_gw); hipFree(h->d_gpart3);
+    h->d_glinv = h->d_gscr = h->d_gw = h->d_gpart3 = nullptr; h->grad_slots = 0;
     h->d_chain_words = nullptr; h->d_ximg = h->d_stepval = nullptr; h->d_chain_trace = nullptr; h->chain_streams = 0;
     h->d_tiles = h->d_linv = h->d_z = h->d_w = h->d_logdet = h->d_quad = h->d_kdiag = h->d_cond = h->d_gpart = nullptr;
     h->d_sep = h->d_seps = nullptr;
@@ -474,7 +481,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_t); hipFree(h->d_sig2); hipFree(h->d_resid); hipFree(h->d_band); hipFree(h->d_yv);
     hipFree(h->d_par); hipFree(h->d_out); hipFree(h->d_oinfo);
     for (auto &ln : h->lanes) ln.release();
-    hipFree(h->d_cand);
+    hipFree(h->d_cand); hipFree(h->d_ggrad);
     hipFree(h->d_ocond); hipFree(h->d_fb_idx); hipFree(h->d_fb_par); hipFree(h->d_fb_out); hipFree(h->d_fb_info);
     if (h->fb) gpcc_destroy(h->fb);
     if (h->main_stream) hipStreamDestroy(h->main_stream);
@@ -1533,6 +1540,138 @@ extern "C" int gpcc_loglik_batch(gpcc_handle_t h, int M, const double *delays, c
         if (info[i] == GPCC_INFO_TIMEOUT)
             return fail(h, GPCC_ERR_STATE, "the persistent few-evaluation launch was abandoned (a bounded wait expired: evaluation %d); "
                                            "gpcc_set_option(handle, \"chain_max\", 0) selects the launch-per-step path", i);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Gradient of objective(alpha, rho) (gpcc_loglik_grad_batch; kernels: gpcc_grad.hip.h).  A gradient group always runs
+// the same path, whatever its size: assembly, then the launch-per-step left-looking factorisation (gpcc_panel_update, gpcc_diag_factor,
+// gpcc_panel_trsm) with every inv(L_kk) kept -- no persistent launch, shared prefix, split halves, fold, hybrid tail or small-N family --
+// so that an evaluation's bits do not depend on the batch it came in.  Then the triangular inverse, w = K^-1 r, the fused K^-1 tiles
+// with their derivative sums, and the finish.  The buffers are allocated on the first call (ensure_grad); a handle that never asks for a
+// gradient holds none of them and runs exactly as before.
+// ------------------------------------------------------------------------------------------
+static int ensure_grad(gpcc_handle_t h)
+{
+    const long slots = (long)h->ws_streams * h->ws_slots;
+    if (h->grad_slots == slots && h->d_glinv) return 0;
+    hipFree(h->d_glinv); hipFree(h->d_gscr); hipFree(h->d_gw); hipFree(h->d_gpart3);
+    h->d_glinv = h->d_gscr = h->d_gw = h->d_gpart3 = nullptr; h->grad_slots = 0;
+    const long ntri = (long)h->nt * (h->nt + 1) / 2;
+    HIPCHK(h, hipMalloc(&h->d_glinv, sizeof(double) * GPCC_TILE_ELEMS * h->nt * slots));
+    HIPCHK(h, hipMalloc(&h->d_gscr, sizeof(double) * GPCC_TILE_ELEMS * h->nt * slots));
+    HIPCHK(h, hipMalloc(&h->d_gw, sizeof(double) * h->Np * slots));
+    HIPCHK(h, hipMalloc(&h->d_gpart3, sizeof(double) * ntri * 3 * h->L * h->L * slots));
+    h->grad_slots = slots;
+    return 0;
+}
+
+static int enqueue_grad_group(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g_in, double *d_grad, hipStream_t s)
+{
+    GpccGroup g = g_in;
+    g.spread = (g.cnt < 8) ? 1 : 0;   // (job order only: every evaluation's arithmetic is the same either way)
+    const int cnt8 = g.spread ? g.cnt : 8 * ((g.cnt + 7) / 8);
+    launch_assemble(h, c, g, s, false, false);
+    for (int k = 0; k < c.nt; ++k) {
+        if (k > 0) {
+            ProfScope pr(h, GPCC_PROF_PANEL_UPDATE, s);
+            gpcc_panel_update<double, false><<<cnt8 * (c.nt - k), GPCC_GEMM_THREADS, GPCC_GEMM_LDS_BYTES, s>>>(c, g, k, k, 0);
+        }
+        {
+            ProfScope pr(h, GPCC_PROF_DIAG, s);
+            gpcc_diag_factor<double><<<g.cnt, GPCC_DIAG_THREADS, GPCC_DIAG_LDS_BYTES, s>>>(c, g, k);
+        }
+        if (k < c.nt - 1) {
+            ProfScope pr(h, GPCC_PROF_TRSM, s);
+            gpcc_panel_trsm<double><<<cnt8 * (c.nt - k - 1), GPCC_GEMM_THREADS, GPCC_GEMM_LDS_BYTES, s>>>(c, g, k);
+        }
+    }
+    for (int j = c.nt - 2; j >= 0; --j) {
+        const int jobs = g.cnt * (c.nt - 1 - j);
+        gpcc_grad_trtri<<<jobs, 512, 0, s>>>(c, g, j, h->d_gscr);
+        gpcc_grad_copy<<<jobs, 256, 0, s>>>(c, g, j, h->d_gscr);
+    }
+    gpcc_grad_w<<<g.cnt * c.nt, GPCC_TILE, 0, s>>>(c, g, h->d_gw);
+    const int tiles = g.cnt * (c.nt * (c.nt + 1) / 2);
+    switch (c.kernel_id) {
+    case 0: gpcc_grad_tiles<0><<<tiles, 512, 0, s>>>(c, g, h->d_gw, h->d_gpart3); break;
+    case 1: gpcc_grad_tiles<1><<<tiles, 512, 0, s>>>(c, g, h->d_gw, h->d_gpart3); break;
+    case 2: gpcc_grad_tiles<2><<<tiles, 512, 0, s>>>(c, g, h->d_gw, h->d_gpart3); break;
+    default: gpcc_grad_tiles<3><<<tiles, 512, 0, s>>>(c, g, h->d_gw, h->d_gpart3); break;
+    }
+    gpcc_grad_finish<<<g.cnt, 256, 0, s>>>(c, g, h->d_gpart3, d_grad);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int gpcc_loglik_grad_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                      double *loglik, double *grad, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (M == 0) return 0;
+    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    if (h->is_multi()) {   // device_ids[0], like the single-matrix utilities
+        const int rc = gpcc_loglik_grad_batch(primary(h), M, delays, alpha, rho, loglik, grad, info);
+        return rc ? fail(h, rc, "%s", primary(h)->err.c_str()) : 0;
+    }
+    if (h->precision == GPCC_PRECISION_FP32) {   // always fp64: on the handle's fp64 twin
+        int rc = ensure_fb(h, 0);
+        if (rc) return rc;
+        rc = gpcc_loglik_grad_batch(h->fb, M, delays, alpha, rho, loglik, grad, info);
+        return rc ? fail(h, rc, "fp32 handle, gradient in fp64: %s", h->fb->err.c_str()) : 0;
+    }
+    GPCC_ON_DEVICE(h, h->device);
+    int rc = ensure_workspace(h);
+    if (!rc) rc = ensure_grad(h);
+    if (!rc) rc = ensure_staging(h, M);
+    if (rc) return rc;
+    const long W = 2L * h->L + 1;
+    if (M > h->ggrad_cap) {
+        hipFree(h->d_ggrad);
+        h->d_ggrad = nullptr; h->ggrad_cap = 0;
+        HIPCHK(h, hipMalloc(&h->d_ggrad, sizeof(double) * W * M));
+        h->ggrad_cap = M;
+    }
+    const long ML = (long)M * h->L;
+    double *dd = h->d_par, *da = h->d_par + ML, *dr = h->d_par + 2 * ML;
+    HIPCHK(h, hipMemcpyAsync(dd, delays, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(da, alpha, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(dr, rho, sizeof(double) * M, hipMemcpyHostToDevice, h->main_stream));
+    GpccCtx c = make_ctx(h);
+    c.linv = h->d_glinv;
+    c.linv_keep = 1;
+    const int S = h->prof ? 1 : h->ws_streams, cs = h->ws_slots;
+    const int ngroups = (M + cs - 1) / cs, used = ngroups < S ? ngroups : S;
+    HIPCHK(h, hipEventRecord(h->ev_start, h->main_stream));
+    for (int s = 0; s < used; ++s) HIPCHK(h, hipStreamWaitEvent(h->str[s], h->ev_start, 0));
+    for (int gi = 0; gi < ngroups && !rc; ++gi) {
+        const int s = gi % S;
+        GpccGroup g;
+        g.delays = dd; g.alpha = da; g.rho = dr;
+        g.out_loglik = h->d_out; g.out_info = h->d_oinfo; g.out_cond = nullptr;
+        g.first = gi * cs;
+        g.slot0 = s * cs;
+        g.cnt = (M - g.first < cs) ? (M - g.first) : cs;
+        g.spread = 0;
+        rc = enqueue_grad_group(h, c, g, h->d_ggrad, h->str[s]);
+    }
+    if (rc) {   // nothing may be left running when the error is returned
+        const std::string msg = h->err;
+        for (int s = 0; s < used; ++s) (void)hipStreamSynchronize(h->str[s]);
+        (void)hipGetLastError();
+        h->err = msg;
+        return rc;
+    }
+    for (int s = 0; s < used; ++s) {
+        HIPCHK(h, hipEventRecord(h->ev_done[s], h->str[s]));
+        HIPCHK(h, hipStreamWaitEvent(h->main_stream, h->ev_done[s], 0));
+    }
+    HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(grad, h->d_ggrad, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
+    HIPCHK(h, hipStreamSynchronize(h->main_stream));
     return 0;
 }
 

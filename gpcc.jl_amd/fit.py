@@ -39,6 +39,21 @@ def invtransformbetween(y, a, b):
     return np.log(u) - np.log1p(-u)
 
 
+def unpack_grad(X, grad, L, rhomin, rhomax):
+    """Chain rule through `unpack` (marginaliseb.jl:112-126): X (..., L+1) unconstrained vectors, grad (..., L+1 or 2L+1) the
+    gradient in the constrained parameters [alpha_1..alpha_L, rho(, tau_1..tau_L)] (Objective.loglik_grad_batch) -> the same
+    gradient in the optimiser's coordinates.  alpha = makepositive(x) + 1e-8: times makepositive'(x) = logistic(x) (1 where
+    makepositive is the identity, x > 30); rho = transformbetween(x, a, b): times (b - a) s (1 - s), s = logistic(x).  The delays
+    are not transformed: their columns pass through."""
+    X = np.asarray(X, dtype=np.float64)
+    out = np.array(grad, dtype=np.float64, copy=True)
+    xa, xr = X[..., :L], X[..., L]
+    out[..., :L] *= np.where(xa > 30.0, 1.0, 1.0 / (1.0 + np.exp(-np.minimum(xa, 30.0))))
+    sr = 1.0 / (1.0 + np.exp(-xr))
+    out[..., L] *= (rhomax - rhomin) * sr * (1.0 - sr)
+    return out
+
+
 def nearestposdef(A, minimumeigenvalue=1e-6):
     """MiscUtil.nearestposdef(A; minimumeigenvalue) as used at marginaliseb.jl:331 -- MiscUtil's source is not
     available (unregistered dependency), so this is the assumed definition: symmetrise, eigendecompose, lift every

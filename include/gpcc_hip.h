@@ -191,6 +191,22 @@ int gpcc_get_conditioning(gpcc_handle_t handle, int M, double *out);
 int gpcc_loglik_batch(gpcc_handle_t handle, int M, const double *delays, const double *alpha,
                       const double *rho, double *loglik, int *info);
 
+/* objective(alpha, rho) and its gradient for M independent (tau, alpha, rho): loglik[M], info[M] as gpcc_loglik_batch;
+ * grad: M rows of 2L+1 doubles [d/d alpha_1..alpha_L, d/d rho, d/d tau_1..tau_L] in the reference's (constrained)
+ * parameters; NaN row where info != 0.  Always fp64 (an fp32 handle evaluates it on its fp64 twin).
+ * The value is that of src/gpccfixdelay_marginaliseb.jl:133-141 (src/gpccfixdelay.jl:131-139 when marginalise_b == 0); the
+ * reference itself has no gradient.  With r = Y - bbar, w = K^-1 r and G = w w' - K^-1, d loglik / d theta = 1/2 sum_ij G_ij
+ * d Kd_ij / d theta (Sobs and B do not depend on alpha, rho, tau).  OU is not differentiable at s = 0 (coinciding shifted
+ * times); there it takes dk/ds = 0, the mean of the one-sided derivatives.  Argument checks and info codes are gpcc_loglik_batch's;
+ * a failed item never touches the others.  Every group runs the launch-per-step tile factorisation (N <= 383 padded to tiles: the
+ * small-N family is not used), then a blocked triangular inverse and one fused pass over the lower tiles of K^-1: about three times
+ * the value's fp64 work.  Results are bitwise repeatable, also across batch sizes.  A multi-device handle computes on
+ * device_ids[0].  Memory: allocated on the first call, on top of bytes_per_slot, for each of workspace_streams x workspace_slots
+ * slots: 2 nt tiles (every inv(L_kk) and a scratch column: 2 x nt x 131072 bytes, nt = Np / 128), Np doubles and
+ * 3 L^2 nt (nt + 1) / 2 doubles; a handle that never asks for a gradient allocates none of it.  Blocking. */
+int gpcc_loglik_grad_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                           double *loglik, double *grad, int *info);
+
 /* Same with DEVICE pointers, enqueued behind `stream` (a hipStream_t, NULL = default stream) and
  * joined back into it: asynchronous, outputs valid once `stream` has drained. */
 int gpcc_loglik_batch_device(gpcc_handle_t handle, int M, const double *d_delays,

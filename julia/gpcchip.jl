@@ -58,6 +58,20 @@ function loglik_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}
     return ll, info
 end
 
+"objective and its gradient for M triples: (ll[M], grad (2L+1)×M, info[M]); a column of grad is [∂/∂α_1..α_L, ∂/∂ρ, ∂/∂τ_1..τ_L]
+in the constrained parameters, NaN where info != 0.  The reference has no gradient: this is the derivative of objective(α, ρ)."
+function loglik_grad_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    grad = Matrix{Float64}(undef, 2h.L + 1, M)                            # column-major (2L+1)×M == row-major M×(2L+1)
+    rc = ccall((:gpcc_loglik_grad_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, ll, grad, info)
+    rc == 0 || error("gpcc_loglik_grad_batch: " * lasterror(h.ptr))
+    return ll, grad, info
+end
+
 "Drop-in body of objective(α, ρ) (gpccfixdelay_marginaliseb.jl:133-141): throws what the Julia code throws."
 function objective(h::Handle, τ, α, ρ)
     ll, info = loglik_batch(h, reshape(Float64.(τ), :, 1), reshape(Float64.(α), :, 1), [Float64(ρ)])
