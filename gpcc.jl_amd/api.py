@@ -289,6 +289,22 @@ class Objective:
                                                       _ip(info)))
         return ll, grad, info
 
+    def loglik_hess_batch(self, delays, alpha, rho):
+        """objective, gradient, Hessian and expected (Fisher) information for M (tau, alpha, rho) triples -> (loglik[M],
+        grad[M, P], hess[M, P, P], fisher[M, P, P], info[M]), P = 2L+1 in a gradient row's order [alpha_1..alpha_L, rho,
+        tau_1..tau_L].  loglik and grad are bitwise loglik_grad_batch's; hess and fisher are bitwise symmetric; NaN where
+        info != 0.  Always fp64; a multi-device handle computes on its first device."""
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        P = 2 * self.L + 1
+        ll = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, P), dtype=np.float64)
+        hess = np.empty((M, P, P), dtype=np.float64)
+        fisher = np.empty((M, P, P), dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        self._chk(_capi.load().gpcc_loglik_hess_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _dp(grad),
+                                                      _dp(hess), _dp(fisher), _ip(info)))
+        return ll, grad, hess, fisher, info
+
     def value_and_grad(self, alpha, rho, delays):
         """(objective(alpha, rho), gradient) for one delay vector: the gradient is a dict {"alpha": (L,), "rho": float,
         "delays": (L,)}; raises what __call__ raises."""

@@ -3,6 +3,7 @@
 #include "gpcc_kernels.hip.h"
 #include "gpcc_small.hip.h"
 #include "gpcc_grad.hip.h"
+#include "gpcc_hess.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 
@@ -188,6 +189,10 @@ struct gpcc_handle_s {
     // column of the triangular inverse (nt tiles), w = K^-1 r (Np) and the per-tile partials (nt(nt+1)/2 x 3 L^2)
     double *d_glinv = nullptr, *d_gscr = nullptr, *d_gw = nullptr, *d_gpart3 = nullptr, *d_ggrad = nullptr;
     long grad_slots = 0, ggrad_cap = 0;
+    // Hessian (gpcc_loglik_hess_batch): allocated on its first call, for hess_slots <= workspace slots (hess_bytes_per_slot each: the
+    // dense K^-1, M_theta = K^-1 D_theta for every parameter, u, z and the partials) and the outputs of the batch (hess and fisher blocks)
+    double *d_hc = nullptr, *d_hm = nullptr, *d_hu = nullptr, *d_hz = nullptr, *d_htab = nullptr, *d_htr = nullptr, *d_hout = nullptr;
+    long hess_slots = 0, hess_ws = 0, hout_cap = 0;
     double *d_sep = nullptr, *d_seps = nullptr;     // separable factors of the points, the distance scale (GpccCtx::sep, ::seps)
     int *d_sepflag = nullptr;                       // per-tile-row flags (GpccCtx::sepflag)
     int fp32_refine = 1;                            // option "fp32_refine": 0 = no refinement of the quadratic forms
@@ -456,6 +461,8 @@ static void free_workspace(gpcc_handle_t h)
     hipFree(h->d_chain_words); hipFree(h->d_ximg); hipFree(h->d_stepval); hipFree(h->d_chain_trace);
     hipFree(h->d_glinv); hipFree(h->d_gscr); hipFree(h->d_gw); hipFree(h->d_gpart3);
     h->d_glinv = h->d_gscr = h->d_gw = h->d_gpart3 = nullptr; h->grad_slots = 0;
+    hipFree(h->d_hc); hipFree(h->d_hm); hipFree(h->d_hu); hipFree(h->d_hz); hipFree(h->d_htab); hipFree(h->d_htr);
+    h->d_hc = h->d_hm = h->d_hu = h->d_hz = h->d_htab = h->d_htr = nullptr; h->hess_slots = h->hess_ws = 0;
     h->d_chain_words = nullptr; h->d_ximg = h->d_stepval = nullptr; h->d_chain_trace = nullptr; h->chain_streams = 0;
     h->d_tiles = h->d_linv = h->d_z = h->d_w = h->d_logdet = h->d_quad = h->d_kdiag = h->d_cond = h->d_gpart = nullptr;
     h->d_sep = h->d_seps = nullptr;
@@ -481,7 +488,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_t); hipFree(h->d_sig2); hipFree(h->d_resid); hipFree(h->d_band); hipFree(h->d_yv);
     hipFree(h->d_par); hipFree(h->d_out); hipFree(h->d_oinfo);
     for (auto &ln : h->lanes) ln.release();
-    hipFree(h->d_cand); hipFree(h->d_ggrad);
+    hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout);
     hipFree(h->d_ocond); hipFree(h->d_fb_idx); hipFree(h->d_fb_par); hipFree(h->d_fb_out); hipFree(h->d_fb_info);
     if (h->fb) gpcc_destroy(h->fb);
     if (h->main_stream) hipStreamDestroy(h->main_stream);
@@ -593,6 +600,14 @@ extern "C" int gpcc_set_option(gpcc_handle_t h, const char *key, long v)
     return 0;
 }
 
+// per slot: the dense K^-1 and M_theta for the P = 2L + 1 parameters (Np^2 doubles each), u and z (P Np each), the six band-pair tables
+// per lower tile (6 L^2) and the trace partials per tile pair (P^2)
+static long hess_bytes_per_slot(gpcc_handle_t h)
+{
+    const long P = 2L * h->L + 1, ntri = (long)h->nt * (h->nt + 1) / 2, Np = h->Np;
+    return 8L * ((1 + P) * Np * Np + 2 * P * Np + ntri * (6L * h->L * h->L + P * P));
+}
+
 extern "C" long gpcc_get_option(gpcc_handle_t h, const char *key)
 {
     if (!h || !key) return -1;
@@ -625,6 +640,8 @@ extern "C" long gpcc_get_option(gpcc_handle_t h, const char *key)
         return (long)(((long)h->nt * (h->nt + 1) / 2 + (h->precision ? h->nt : 1)) * GPCC_TILE_ELEMS) * (h->precision ? 4 : 8) + 16L * h->Np * h->nrhs +
                32L * h->Np + 4L * h->nt + 32L +
                (h->precision ? 8L * h->Np + 8L * GPCC_MAXRHS * GPCC_MAXRHS * ((long)h->nt * (h->nt + 1) / 2) + 16L : 0L);
+    if (!strcmp(key, "hess_bytes_per_slot")) return hess_bytes_per_slot(h);
+    if (!strcmp(key, "hess_slots")) return h->hess_slots;
     if (!strcmp(key, "precision")) return h->precision;
     if (!strcmp(key, "fused_solve")) return h->fused_solve;
     if (!strcmp(key, "fused_solve_min")) return h->fused_solve_min;
@@ -1671,6 +1688,168 @@ extern "C" int gpcc_loglik_grad_batch(gpcc_handle_t h, int M, const double *dela
     HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, h->main_stream));
     HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, h->main_stream));
     HIPCHK(h, hipMemcpyAsync(grad, h->d_ggrad, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
+    HIPCHK(h, hipStreamSynchronize(h->main_stream));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Hessian and Fisher information of objective(alpha, rho) (gpcc_loglik_hess_batch; kernels: gpcc_hess.hip.h).  A Hessian
+// group first runs the gradient group unchanged (enqueue_grad_group: loglik and grad are the gradient path's bits), then the curvature
+// kernels on the same slots.  Its buffers are allocated on the first call (ensure_hess), for as many slots as fit a quarter of the
+// device's memory (at most every workspace slot): with fewer, the Hessian runs smaller groups -- every evaluation's arithmetic is the
+// same in any group -- and gpcc_last_error carries a note.  A handle that never asks holds none of it.
+// ------------------------------------------------------------------------------------------
+static int ensure_hess(gpcc_handle_t h)
+{
+    const long ws = (long)h->ws_streams * h->ws_slots;
+    if (h->hess_ws == ws && h->d_hc) return 0;
+    hipFree(h->d_hc); hipFree(h->d_hm); hipFree(h->d_hu); hipFree(h->d_hz); hipFree(h->d_htab); hipFree(h->d_htr);
+    h->d_hc = h->d_hm = h->d_hu = h->d_hz = h->d_htab = h->d_htr = nullptr; h->hess_slots = h->hess_ws = 0;
+    const long per = hess_bytes_per_slot(h), P = 2L * h->L + 1, ntri = (long)h->nt * (h->nt + 1) / 2, NN = (long)h->Np * h->Np;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) total_b = (size_t)64 << 30;
+    long slots = (long)(0.25 * (double)total_b / (double)per);
+    if (slots > ws) slots = ws;
+    if (slots < 1) slots = 1;
+    for (;;) {
+        hipError_t e = hipMalloc(&h->d_hc, sizeof(double) * NN * slots);
+        if (e == hipSuccess) e = hipMalloc(&h->d_hm, sizeof(double) * NN * P * slots);
+        if (e == hipSuccess) e = hipMalloc(&h->d_hu, sizeof(double) * h->Np * P * slots);
+        if (e == hipSuccess) e = hipMalloc(&h->d_hz, sizeof(double) * h->Np * P * slots);
+        if (e == hipSuccess) e = hipMalloc(&h->d_htab, sizeof(double) * ntri * 6 * h->L * h->L * slots);
+        if (e == hipSuccess) e = hipMalloc(&h->d_htr, sizeof(double) * ntri * P * P * slots);
+        if (e == hipSuccess) break;
+        (void)hipGetLastError();
+        hipFree(h->d_hc); hipFree(h->d_hm); hipFree(h->d_hu); hipFree(h->d_hz); hipFree(h->d_htab); hipFree(h->d_htr);
+        h->d_hc = h->d_hm = h->d_hu = h->d_hz = h->d_htab = h->d_htr = nullptr;
+        if (e != hipErrorOutOfMemory || slots <= 1)
+            return fail(h, GPCC_ERR_HIP, "Hessian buffers of %ld slots (%ld bytes each): %s", slots, per, hipGetErrorString(e));
+        slots /= 2;
+    }
+    h->hess_slots = slots;
+    h->hess_ws = ws;
+    if (slots < ws) {   // a note, not an error
+        char buf[256];
+        snprintf(buf, sizeof buf, "note: the Hessian's buffers (%ld bytes per slot) fit %ld of the %ld workspace slots; its groups run "
+                 "through %ld slots (results unchanged)", per, slots, ws, slots);
+        h->err = buf;
+    }
+    return 0;
+}
+
+template <int KID>
+static void launch_hess_kernels(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g, const GpccHessBuf &hb, double *d_hess,
+                                double *d_fisher, hipStream_t s)
+{
+    const int ntri = c.nt * (c.nt + 1) / 2;
+    gpcc_hess_ctab<KID><<<g.cnt * ntri, 512, 0, s>>>(c, g, h->d_gw, hb);
+    gpcc_hess_u<KID><<<g.cnt * c.nt, GPCC_TILE, 0, s>>>(c, g, h->d_gw, hb);
+    gpcc_hess_z<<<g.cnt * c.nt, GPCC_TILE, 0, s>>>(c, g, hb);
+    gpcc_hess_gemm<KID><<<(unsigned)((long)g.cnt * hb.P * c.nt * c.nt), 512, 0, s>>>(c, g, hb);
+    gpcc_hess_trace<<<g.cnt * ntri, 256, 0, s>>>(c, g, hb);
+    gpcc_hess_finish<<<g.cnt, 512, 0, s>>>(c, g, hb, d_hess, d_fisher);
+}
+
+static int enqueue_hess_group(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g, const GpccHessBuf &hb, double *d_hess,
+                              double *d_fisher, hipStream_t s)
+{
+    int rc = enqueue_grad_group(h, c, g, h->d_ggrad, s);
+    if (rc) return rc;
+    switch (c.kernel_id) {
+    case 0: launch_hess_kernels<0>(h, c, g, hb, d_hess, d_fisher, s); break;
+    case 1: launch_hess_kernels<1>(h, c, g, hb, d_hess, d_fisher, s); break;
+    case 2: launch_hess_kernels<2>(h, c, g, hb, d_hess, d_fisher, s); break;
+    default: launch_hess_kernels<3>(h, c, g, hb, d_hess, d_fisher, s); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int gpcc_loglik_hess_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                      double *loglik, double *grad, double *hess, double *fisher, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (M == 0) return 0;
+    if (!delays || !alpha || !rho || !loglik || !grad || !hess || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    if (h->is_multi()) {   // device_ids[0], like the gradient
+        const int rc = gpcc_loglik_hess_batch(primary(h), M, delays, alpha, rho, loglik, grad, hess, fisher, info);
+        return rc ? fail(h, rc, "%s", primary(h)->err.c_str()) : 0;
+    }
+    if (h->precision == GPCC_PRECISION_FP32) {   // always fp64: on the handle's fp64 twin
+        int rc = ensure_fb(h, 0);
+        if (rc) return rc;
+        rc = gpcc_loglik_hess_batch(h->fb, M, delays, alpha, rho, loglik, grad, hess, fisher, info);
+        return rc ? fail(h, rc, "fp32 handle, Hessian in fp64: %s", h->fb->err.c_str()) : 0;
+    }
+    GPCC_ON_DEVICE(h, h->device);
+    int rc = ensure_workspace(h);
+    if (!rc) rc = ensure_grad(h);
+    if (!rc) rc = ensure_hess(h);
+    if (!rc) rc = ensure_staging(h, M);
+    if (rc) return rc;
+    const long W = 2L * h->L + 1, W2 = W * W;
+    if (M > h->ggrad_cap) {
+        hipFree(h->d_ggrad);
+        h->d_ggrad = nullptr; h->ggrad_cap = 0;
+        HIPCHK(h, hipMalloc(&h->d_ggrad, sizeof(double) * W * M));
+        h->ggrad_cap = M;
+    }
+    if (M > h->hout_cap) {
+        hipFree(h->d_hout);
+        h->d_hout = nullptr; h->hout_cap = 0;
+        HIPCHK(h, hipMalloc(&h->d_hout, sizeof(double) * 2 * W2 * M));
+        h->hout_cap = M;
+    }
+    double *d_hess = h->d_hout, *d_fisher = h->d_hout + W2 * M;
+    const long ML = (long)M * h->L;
+    double *dd = h->d_par, *da = h->d_par + ML, *dr = h->d_par + 2 * ML;
+    HIPCHK(h, hipMemcpyAsync(dd, delays, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(da, alpha, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(dr, rho, sizeof(double) * M, hipMemcpyHostToDevice, h->main_stream));
+    GpccCtx c = make_ctx(h);
+    c.linv = h->d_glinv;
+    c.linv_keep = 1;
+    GpccHessBuf hb;
+    hb.c = h->d_hc; hb.m = h->d_hm; hb.u = h->d_hu; hb.z = h->d_hz; hb.tab = h->d_htab; hb.tr = h->d_htr;
+    hb.P = (int)W;
+    hb.off[0] = 0;
+    for (int l = 0; l < GPCC_MAXL; ++l) hb.off[l + 1] = hb.off[l] + (l < h->L ? h->Nl[l] : 0);
+    // groups of at most hess_slots evaluations, on as many streams as the Hessian's slots hold
+    const int cs = (int)(h->hess_slots < h->ws_slots ? h->hess_slots : h->ws_slots);
+    int S = h->prof ? 1 : (int)(h->hess_slots / cs);
+    if (S > h->ws_streams) S = h->ws_streams;
+    const int ngroups = (M + cs - 1) / cs, used = ngroups < S ? ngroups : S;
+    HIPCHK(h, hipEventRecord(h->ev_start, h->main_stream));
+    for (int s = 0; s < used; ++s) HIPCHK(h, hipStreamWaitEvent(h->str[s], h->ev_start, 0));
+    for (int gi = 0; gi < ngroups && !rc; ++gi) {
+        const int s = gi % S;
+        GpccGroup g;
+        g.delays = dd; g.alpha = da; g.rho = dr;
+        g.out_loglik = h->d_out; g.out_info = h->d_oinfo; g.out_cond = nullptr;
+        g.first = gi * cs;
+        g.slot0 = s * cs;
+        g.cnt = (M - g.first < cs) ? (M - g.first) : cs;
+        g.spread = 0;
+        rc = enqueue_hess_group(h, c, g, hb, d_hess, d_fisher, h->str[s]);
+    }
+    if (rc) {   // nothing may be left running when the error is returned
+        const std::string msg = h->err;
+        for (int s = 0; s < used; ++s) (void)hipStreamSynchronize(h->str[s]);
+        (void)hipGetLastError();
+        h->err = msg;
+        return rc;
+    }
+    for (int s = 0; s < used; ++s) {
+        HIPCHK(h, hipEventRecord(h->ev_done[s], h->str[s]));
+        HIPCHK(h, hipStreamWaitEvent(h->main_stream, h->ev_done[s], 0));
+    }
+    HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(grad, h->d_ggrad, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(hess, d_hess, sizeof(double) * W2 * M, hipMemcpyDeviceToHost, h->main_stream));
+    if (fisher) HIPCHK(h, hipMemcpyAsync(fisher, d_fisher, sizeof(double) * W2 * M, hipMemcpyDeviceToHost, h->main_stream));
     HIPCHK(h, hipStreamSynchronize(h->main_stream));
     return 0;
 }

@@ -54,6 +54,61 @@ def unpack_grad(X, grad, L, rhomin, rhomax):
     return out
 
 
+def unpack_hessian(X, grad, hess, L, rhomin, rhomax):
+    """Second-order chain rule through `unpack`, the companion of unpack_grad: X (..., L+1) unconstrained vectors, grad (..., n) and
+    hess (..., n, n) in the constrained parameters (n = L+1, or 2L+1 with the delays: Objective.loglik_hess_batch) -> the Hessian in
+    the optimiser's coordinates, J' H J + diag(grad * x''), with J = diag(x') over alpha and rho and the identity over the delays.
+    alpha = makepositive(x) + 1e-8: x' = s, x'' = s (1 - s), s = logistic(x) (x' = 1, x'' = 0 where makepositive is the identity,
+    x > 30); rho = transformbetween(x, a, b): x' = (b - a) s (1 - s), x'' = (b - a) s (1 - s) (1 - 2 s)."""
+    X = np.asarray(X, dtype=np.float64)
+    g = np.asarray(grad, dtype=np.float64)
+    H = np.array(hess, dtype=np.float64, copy=True)
+    n = H.shape[-1]
+    xa, xr = X[..., :L], X[..., L]
+    sa = 1.0 / (1.0 + np.exp(-np.minimum(xa, 30.0)))
+    big = xa > 30.0
+    d1 = np.ones(X.shape[:-1] + (n,))
+    d2 = np.zeros(X.shape[:-1] + (n,))
+    d1[..., :L] = np.where(big, 1.0, sa)
+    d2[..., :L] = np.where(big, 0.0, sa * (1.0 - sa))
+    sr = 1.0 / (1.0 + np.exp(-xr))
+    d1[..., L] = (rhomax - rhomin) * sr * (1.0 - sr)
+    d2[..., L] = (rhomax - rhomin) * sr * (1.0 - sr) * (1.0 - 2.0 * sr)
+    H *= d1[..., :, None] * d1[..., None, :]
+    idx = np.arange(n)
+    H[..., idx, idx] += g[..., :n] * d2
+    return H
+
+
+def laplace_covariance(H, free, L=None):
+    """(-H_ff)^-1, the Laplace (normal) approximation's covariance over the parameters `free` (indices, or a boolean mask, into a
+    Hessian in [alpha_1..alpha_L, rho, tau_1..tau_L] order; L defaults to (n - 1) / 2) -> (cov, ok).  The likelihood does not
+    change when every delay shifts together, so `free` must leave out at least one delay (ValueError otherwise).  ok is False and
+    cov all NaN when -H_ff is not positive definite (not a maximum, or numerically singular): never a silent result."""
+    H = np.asarray(H, dtype=np.float64)
+    n = H.shape[0]
+    if H.shape != (n, n):
+        raise ValueError("H must be square, got %s" % (H.shape,))
+    free = np.asarray(free)
+    idx = np.flatnonzero(free) if free.dtype == bool else free.astype(int).ravel()
+    if L is None:
+        L = (n - 1) // 2
+    delays = set(range(L + 1, 2 * L + 1)) if n == 2 * L + 1 else set()
+    if delays and delays <= set(idx.tolist()):
+        raise ValueError("free holds every delay: a common shift of all delays leaves the likelihood unchanged, fix at least one")
+    A = -H[np.ix_(idx, idx)]
+    A = 0.5 * (A + A.T)
+    try:
+        Lc = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:
+        return np.full((len(idx), len(idx)), np.nan), False
+    Li = np.linalg.solve(Lc, np.eye(len(idx)))
+    cov = Li.T @ Li
+    if not np.all(np.isfinite(cov)):
+        return np.full((len(idx), len(idx)), np.nan), False
+    return cov, True
+
+
 def nearestposdef(A, minimumeigenvalue=1e-6):
     """MiscUtil.nearestposdef(A; minimumeigenvalue) as used at marginaliseb.jl:331 -- MiscUtil's source is not
     available (unregistered dependency), so this is the assumed definition: symmetrise, eigendecompose, lift every

@@ -155,7 +155,8 @@ int gpcc_multi_stats(gpcc_handle_t handle, double *compute_ms, double *gather_ms
  *                                     evaluated in fp64 by it, on the handle's internal fp64 twin: the fp64 handle's bits, conditioning
  *                                     estimates 0; 0 = fp32 tiles on the launch-per-step path ("fp32_chain_count": evaluations so far)
  *
- * Read-only keys of gpcc_get_option: "N", "Np", "precision", "bytes_per_slot", "share_tiles", "n_devices", "gather_mode",
+ * Read-only keys of gpcc_get_option: "N", "Np", "precision", "bytes_per_slot", "hess_bytes_per_slot" / "hess_slots" (the Hessian's
+ * memory per slot and the slots it holds, 0 before its first call: gpcc_loglik_hess_batch), "share_tiles", "n_devices", "gather_mode",
  * "gather_width", "small_n_max" (383), "small_n_active", "small_n_count", "chain_count" (evaluations that took the persistent
  * launch so far), "chain_last_grid" (workgroups of the last one), "fp32_guard_count", "fp32_chain_count", "workspace_streams" / "workspace_slots" (what the workspace really holds: smaller than "streams" /
  * "slots_per_stream" only if the device's memory was short when it was allocated -- then gpcc_last_error carries a note; the
@@ -206,6 +207,25 @@ int gpcc_loglik_batch(gpcc_handle_t handle, int M, const double *delays, const d
  * 3 L^2 nt (nt + 1) / 2 doubles; a handle that never asks for a gradient allocates none of it.  Blocking. */
 int gpcc_loglik_grad_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                            double *loglik, double *grad, int *info);
+
+/* objective(alpha, rho), its gradient, its Hessian and the expected (Fisher) information for M independent (tau, alpha, rho), with
+ * theta = [alpha_1..alpha_L, rho, tau_1..tau_L], P = 2L+1 (a gradient row's order): loglik[M], info[M] and grad (M rows of P) are
+ * bitwise what gpcc_loglik_grad_batch returns; hess and fisher: M row-major P x P blocks, bitwise symmetric; fisher may be NULL.
+ * NaN rows / blocks where info != 0 (info as gpcc_loglik_batch; a failed item never touches the others).  With C = K^-1, w = C r,
+ * G = w w' - C and D_theta = d Kd / d theta:
+ *     H = 1/2 tr(G d2Kd/dtheta dphi) - (D_theta w)' C (D_phi w) + 1/2 tr(C D_theta C D_phi),   F = E[-H] = 1/2 tr(C D_theta C D_phi).
+ * The first term needs k and its derivatives k_r, k_s, k_rr, k_rs, k_ss (by rho and by the shifted-time difference s); OU is not
+ * differentiable at s = 0 (coinciding shifted times of two bands): there, as the gradient takes k_s = 0, the Hessian takes k_rs = 0 and
+ * k_ss = 1/rho^2 (the one-sided limit, the kink's delta left out).  rbf, Matern-3/2 and Matern-5/2 are twice differentiable at 0
+ * (Matern-3/2: k_ss(0) = -3/rho^2).  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].
+ * Each group runs the gradient's path unchanged, then forms K^-1 densely, M_theta = K^-1 D_theta for every theta (fp64 MFMA, the tiles of
+ * D_theta generated on the fly: 2 Np^3 flops per parameter) and the pairwise traces.  Results are bitwise repeatable, also across batch
+ * sizes.  Memory: the gradient's, plus "hess_bytes_per_slot" = 8 ((P+1) Np^2 + 2 P Np + nt(nt+1)/2 (6 L^2 + P^2)) bytes for each of
+ * "hess_slots" slots, allocated on the first call: as many as fit a quarter of the device's memory, at most the workspace's slots (with
+ * fewer, the Hessian runs smaller groups with the same arithmetic, and gpcc_last_error carries a note); a handle that never asks for a
+ * Hessian allocates none of it.  Blocking. */
+int gpcc_loglik_hess_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                           double *loglik, double *grad, double *hess, double *fisher, int *info);
 
 /* Same with DEVICE pointers, enqueued behind `stream` (a hipStream_t, NULL = default stream) and
  * joined back into it: asynchronous, outputs valid once `stream` has drained. */

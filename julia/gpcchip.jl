@@ -72,6 +72,22 @@ function loglik_grad_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Flo
     return ll, grad, info
 end
 
+"objective, gradient, Hessian and expected (Fisher) information for M triples: (ll[M], grad (2L+1)×M, hess and fisher
+(2L+1)×(2L+1)×M, info[M]) in [α_1..α_L, ρ, τ_1..τ_L] order, symmetric blocks, NaN where info != 0; fisher = 1/2 tr(K⁻¹D_iK⁻¹D_j)."
+function loglik_hess_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
+    M, P = length(rho), 2h.L + 1
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    grad = Matrix{Float64}(undef, P, M)
+    hess, fisher = Array{Float64}(undef, P, P, M), Array{Float64}(undef, P, P, M)   # symmetric: row- or column-major alike
+    rc = ccall((:gpcc_loglik_hess_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, ll, grad, hess, fisher, info)
+    rc == 0 || error("gpcc_loglik_hess_batch: " * lasterror(h.ptr))
+    return ll, grad, hess, fisher, info
+end
+
 "Drop-in body of objective(α, ρ) (gpccfixdelay_marginaliseb.jl:133-141): throws what the Julia code throws."
 function objective(h::Handle, τ, α, ρ)
     ll, info = loglik_batch(h, reshape(Float64.(τ), :, 1), reshape(Float64.(α), :, 1), [Float64(ρ)])
