@@ -20,6 +20,11 @@ PROF_NAMES = ("assemble", "panel_update", "diag_factor", "panel_trsm", "refine",
 BATCH_OBJECTIVE = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.POINTER(ctypes.c_long),
                                    ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double))
 
+BATCH_HESSIAN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_long, ctypes.POINTER(ctypes.c_long),
+                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                 ctypes.POINTER(ctypes.c_double))
+LAPLACE_NOT_CONVERGED, LAPLACE_NOT_MAXIMUM, LAPLACE_ON_BOUND, LAPLACE_BAD_START = -10, -11, -12, -13   # include/gpcc_hip.h
+
 SIGNATURES = {
     "gpcc_version": (ctypes.c_int, []),
     "gpcc_build_info": (ctypes.c_char_p, []),
@@ -41,6 +46,14 @@ SIGNATURES = {
                                               c_double_p, c_double_p, c_int_p]),
     "gpcc_loglik_hess_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                               c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "gpcc_loglik_hess_hyper_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
+                                                    c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "gpcc_laplace_evidence": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, ctypes.c_double,
+                                             ctypes.c_double, ctypes.c_int, ctypes.c_double, c_double_p, c_double_p, c_double_p,
+                                             c_double_p, c_double_p, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_longlong)]),
+    "gpcc_newton_batch": (ctypes.c_int, [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_double_p, c_double_p,
+                                         c_double_p, BATCH_HESSIAN, ctypes.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                         c_int_p, c_int_p, ctypes.POINTER(ctypes.c_longlong)]),
     "gpcc_loglik_batch_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gpcc_model_matrix": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, ctypes.c_double, c_double_p]),

@@ -305,6 +305,48 @@ class Objective:
                                                       _dp(hess), _dp(fisher), _ip(info)))
         return ll, grad, hess, fisher, info
 
+    def loglik_hess_hyper_batch(self, delays, alpha, rho):
+        """The hyper-parameter block of loglik_hess_batch -> (loglik[M], grad[M, P], hess[M, L+1, L+1], fisher[M, L+1, L+1], info[M]):
+        loglik, grad and info bitwise loglik_grad_batch's, hess and fisher bitwise the leading [alpha_1..alpha_L, rho] block of
+        loglik_hess_batch's (the kernels form only that block).  NaN blocks where info != 0."""
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        P, n = 2 * self.L + 1, self.L + 1
+        ll = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, P), dtype=np.float64)
+        hess = np.empty((M, n, n), dtype=np.float64)
+        fisher = np.empty((M, n, n), dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        self._chk(_capi.load().gpcc_loglik_hess_hyper_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _dp(grad),
+                                                            _dp(hess), _dp(fisher), _ip(info)))
+        return ll, grad, hess, fisher, info
+
+    def laplace_evidence(self, delays, alpha0, rho0, rhomin=0.1, rhomax=20.0, max_rounds=50, g_tol=1e-6):
+        """The Laplace-marginalised evidence over alpha and rho per row of delays (G, L), from (alpha0[G, L], rho0[G]) (usually
+        grid_loglik's output) -> (loglik[G], alpha[G, L], rho[G], log_evidence[G], cov[G, L+1, L+1], info[G], rounds[G],
+        (evaluations, batches)).  Prior log-uniform in alpha and in rho on [rhomin, rhomax]: log_evidence is log Z(tau) up to one
+        additive constant shared by all delays (getprobabilities(log_evidence) is the delay posterior).  cov: the posterior
+        covariance of u = (log alpha, log rho).  info: 0, laplace.NOT_CONVERGED / NOT_MAXIMUM / ON_BOUND (NaN log_evidence), or
+        the device's code of a start it could not evaluate."""
+        cand = np.ascontiguousarray(np.atleast_2d(delays), dtype=np.float64)
+        G = cand.shape[0]
+        if cand.shape[1] != self.L:
+            raise ValueError("delays must be (G, %d)" % self.L)
+        n = self.L + 1
+        a0 = np.ascontiguousarray(np.asarray(alpha0, dtype=np.float64).reshape(G, self.L))
+        r0 = np.ascontiguousarray(np.asarray(rho0, dtype=np.float64).reshape(G))
+        ll = np.empty(G, dtype=np.float64)
+        alpha = np.empty((G, self.L), dtype=np.float64)
+        rho = np.empty(G, dtype=np.float64)
+        logz = np.empty(G, dtype=np.float64)
+        cov = np.empty((G, n, n), dtype=np.float64)
+        info = np.empty(G, dtype=np.int32)
+        rounds = np.empty(G, dtype=np.int32)
+        stats = (ctypes.c_longlong * 2)()
+        self._chk(_capi.load().gpcc_laplace_evidence(self._h, G, _dp(cand), _dp(a0), _dp(r0), float(rhomin), float(rhomax),
+                                                     int(max_rounds), float(g_tol), _dp(ll), _dp(alpha), _dp(rho), _dp(logz),
+                                                     _dp(cov), _ip(info), _ip(rounds), stats))
+        return ll, alpha, rho, logz, cov, info, rounds, (int(stats[0]), int(stats[1]))
+
     def value_and_grad(self, alpha, rho, delays):
         """(objective(alpha, rho), gradient) for one delay vector: the gradient is a dict {"alpha": (L,), "rho": float,
         "delays": (L,)}; raises what __call__ raises."""

@@ -20,6 +20,10 @@
 //   gpcc_hess_trace        per tile pair (I >= J) and theta <= phi: sum of M_theta,ij M_phi,ji over (i in I, j in J) and, for I != J, over
 //                          (i in J, j in I) -> P^2 partials per (slot, tile pair)
 //   gpcc_hess_finish       every partial in a fixed order, T1 from the six tables, H and F for theta <= phi, mirrored: bitwise symmetric.
+// Block mode (gpcc_loglik_hess_hyper_batch): only the leading Pa <= P parameters are active (Pa = L + 1: alpha and rho).
+// u, z and M_theta are formed for theta < Pa, the traces for theta <= phi < Pa, and the finish writes Pa x Pa blocks; the buffers keep
+// their stride P.  Every active entry is computed by exactly the arithmetic of the full Hessian (Pa = P), so the block is bitwise the
+// leading block of gpcc_loglik_hess_batch.
 // No atomics: every sum has a fixed order, so a result is bitwise repeatable whatever the batch.  Padding (band -1) has D = 0 and
 // G is only summed over real points.
 #pragma once
@@ -30,9 +34,10 @@
 
 // The Hessian's buffers, per slot: c = dense C (Np^2), m = M_theta (P Np^2), u, z (P Np each), tab = six band-pair
 // tables per lower tile (ntri 6 L^2), tr = trace partials per tile pair (ntri P^2).  off: first point of every band (off[L] = N).
+// Pa: the active parameters (the leading Pa of theta; Pa = P for the full Hessian).
 struct GpccHessBuf {
     double *c, *m, *u, *z, *tab, *tr;
-    int P;
+    int P, Pa;
     int off[GPCC_MAXL + 1];
 };
 
@@ -208,7 +213,7 @@ __global__ __launch_bounds__(GPCC_TILE) void gpcc_hess_u(GpccCtx c, GpccGroup g,
     double *U = hb.u + (long)slot * P * c.Np;
     const int p = c.band[i];
     if (p < 0) {
-        for (int th = 0; th < P; ++th) U[(long)th * c.Np + i] = 0.0;
+        for (int th = 0; th < hb.Pa; ++th) U[(long)th * c.Np + i] = 0.0;
         return;
     }
     const double ui = c.t[i] - dl[p], ir = 1.0 / g.rho[g.first + m];
@@ -239,7 +244,7 @@ __global__ __launch_bounds__(GPCC_TILE) void gpcc_hess_u(GpccCtx c, GpccGroup g,
     for (int l = 0; l < GPCC_MAXL; ++l)
         if (l < L) {
             U[(long)l * c.Np + i] = ((p == l) ? ak : 0.0) + ap * Uk[l];                             // alpha_l
-            U[(long)(L + 1 + l) * c.Np + i] = ap * (al[l] * Us[l] - ((p == l) ? as : 0.0));       // tau_l
+            if (L + 1 + l < hb.Pa) U[(long)(L + 1 + l) * c.Np + i] = ap * (al[l] * Us[l] - ((p == l) ? as : 0.0));   // tau_l
         }
     U[(long)L * c.Np + i] = ap * ar;                                                              // rho
 }
@@ -251,7 +256,7 @@ static __global__ __launch_bounds__(GPCC_TILE) void gpcc_hess_z(GpccCtx c, GpccG
     if (m >= g.cnt) return;
     const int slot = g.slot0 + m;
     if (c.info[slot] != 0) return;
-    const int P = hb.P;
+    const int P = hb.P, Pa = hb.Pa;
     const long Np = c.Np, i = (long)T * GPCC_TILE + threadIdx.x;
     const double *Cd = hb.c + (long)slot * Np * Np, *U = hb.u + (long)slot * P * Np;
     double z[GPCC_HESS_MAXP];
@@ -261,26 +266,26 @@ static __global__ __launch_bounds__(GPCC_TILE) void gpcc_hess_z(GpccCtx c, GpccG
         const double cv = Cd[k * Np + i];
 #pragma unroll
         for (int th = 0; th < GPCC_HESS_MAXP; ++th)
-            if (th < P) z[th] = fma(cv, U[th * Np + k], z[th]);
+            if (th < Pa) z[th] = fma(cv, U[th * Np + k], z[th]);
     }
     double *Z = hb.z + (long)slot * P * Np;
 #pragma unroll
     for (int th = 0; th < GPCC_HESS_MAXP; ++th)
-        if (th < P) Z[th * Np + i] = z[th];
+        if (th < Pa) Z[th * Np + i] = z[th];
 }
 
-// M_theta = C D_theta, tile (I, J) (grid: cnt x nt x P x nt -- J fastest, then theta, so that the workgroups running together share the
+// M_theta = C D_theta, tile (I, J) (grid: cnt x nt x Pa x nt -- J fastest, then theta, so that the workgroups running together share the
 // column strip I of C; 512 threads).  Wave w holds rows 16w .. 16w+15 of the tile, all 128 columns (C/D: row 16w + q + 4 reg,
 // column 16 f + lane & 15).  A operand C[i][k] = C[k][i] from the dense copy (16 consecutive doubles per quarter wave), B operand
 // D_theta[k][j] from LDS, generated 64 rows at a time.
 template <int KID>
 __global__ __launch_bounds__(512) void gpcc_hess_gemm(GpccCtx c, GpccGroup g, GpccHessBuf hb)
 {
-    const int nt = c.nt, P = hb.P;
-    const long per = (long)nt * P * nt;
+    const int nt = c.nt, P = hb.P, Pa = hb.Pa;
+    const long per = (long)nt * Pa * nt;
     const int m = (int)(blockIdx.x / per);
     const int rem = (int)(blockIdx.x % per);
-    const int I = rem / (P * nt), th = (rem / nt) % P, J = rem % nt;
+    const int I = rem / (Pa * nt), th = (rem / nt) % Pa, J = rem % nt;
     if (m >= g.cnt) return;
     const int slot = g.slot0 + m;
     if (c.info[slot] != 0) return;
@@ -342,7 +347,7 @@ __global__ __launch_bounds__(512) void gpcc_hess_gemm(GpccCtx c, GpccGroup g, Gp
             Mt[((long)I * GPCC_TILE + 16 * w + GpccP64::crow(q, r)) * Np + (long)J * GPCC_TILE + 16 * f + lr] = acc[f][r];
 }
 
-// T3 partials (grid: cnt x nt(nt+1)/2 tile pairs; 256 threads): for theta <= phi, tr[slot][pair][theta][phi] = sum over i in I, j in J
+// T3 partials (grid: cnt x nt(nt+1)/2 tile pairs; 256 threads): for theta <= phi < Pa, tr[slot][pair][theta][phi] = sum over i in I, j in J
 // of M_theta[i][j] M_phi[j][i], plus (I != J) the same over i in J, j in I.  A wave reads 8 x 8 blocks: both M[a][b] and M[b][a] come
 // as 8 rows of 64 contiguous bytes.
 static __global__ __launch_bounds__(256) void gpcc_hess_trace(GpccCtx c, GpccGroup g, GpccHessBuf hb)
@@ -354,13 +359,13 @@ static __global__ __launch_bounds__(256) void gpcc_hess_trace(GpccCtx c, GpccGro
     if (c.info[slot] != 0) return;
     int I, J;
     gpcc_grad_tile_ij(tt, I, J);
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, P = hb.P;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, P = hb.P, Pa = hb.Pa;
     const long Np = c.Np, NN = Np * Np;
     const double *Mb = hb.m + (long)slot * P * NN;
     __shared__ double sred[4][GPCC_HESS_MAXP];
     double *dst = hb.tr + ((long)slot * ntri + tt) * P * P;
     const bool off = I != J;
-    for (int th = 0; th < P; ++th) {
+    for (int th = 0; th < Pa; ++th) {
         const double *Mt = Mb + th * NN;
         double acc[GPCC_HESS_MAXP];
 #pragma unroll
@@ -370,7 +375,7 @@ static __global__ __launch_bounds__(256) void gpcc_hess_trace(GpccCtx c, GpccGro
             const double xa = Mt[a * Np + b], xb = off ? Mt[b * Np + a] : 0.0;
 #pragma unroll
             for (int ph = 0; ph < GPCC_HESS_MAXP; ++ph)
-                if (ph >= th && ph < P) {
+                if (ph >= th && ph < Pa) {
                     const double *Mp = Mb + ph * NN;
                     acc[ph] = fma(xa, Mp[b * Np + a], acc[ph]);
                     if (off) acc[ph] = fma(xb, Mp[a * Np + b], acc[ph]);
@@ -378,26 +383,27 @@ static __global__ __launch_bounds__(256) void gpcc_hess_trace(GpccCtx c, GpccGro
         }
 #pragma unroll
         for (int ph = 0; ph < GPCC_HESS_MAXP; ++ph)
-            if (ph >= th && ph < P) {
+            if (ph >= th && ph < Pa) {
                 double v = acc[ph];
 #pragma unroll
                 for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
                 if (lane == 0) sred[w][ph] = v;
             }
         __syncthreads();
-        if (tid >= th && tid < P) dst[th * P + tid] = ((sred[0][tid] + sred[1][tid]) + sred[2][tid]) + sred[3][tid];
+        if (tid >= th && tid < Pa) dst[th * P + tid] = ((sred[0][tid] + sred[1][tid]) + sred[2][tid]) + sred[3][tid];
         __syncthreads();
     }
 }
 
 // One workgroup per evaluation (512 threads): the six tables (tiles in storage order, an off-diagonal tile's transposed pair added,
-// negated for the odd k_s and k_rs), the T3 partials, T2 = u' z, then H and F for theta <= phi, written to both halves.  NaN blocks where
-// the evaluation failed (info != 0).
+// negated for the odd k_s and k_rs), the T3 partials, T2 = u' z, then H and F for theta <= phi < Pa, written to both halves of a Pa x Pa
+// block.  NaN blocks where the evaluation failed (info != 0).
 static __global__ __launch_bounds__(512) void gpcc_hess_finish(GpccCtx c, GpccGroup g, GpccHessBuf hb, double *hess, double *fisher)
 {
     const int m = blockIdx.x;
     if (m >= g.cnt) return;
-    const int slot = g.slot0 + m, L = c.L, L2 = L * L, P = hb.P, P2 = P * P, ntri = c.nt * (c.nt + 1) / 2, tid = threadIdx.x;
+    const int slot = g.slot0 + m, L = c.L, L2 = L * L, P = hb.P, P2 = P * P, Pa = hb.Pa, Pa2 = Pa * Pa, ntri = c.nt * (c.nt + 1) / 2;
+    const int tid = threadIdx.x;
     __shared__ double sT[6 * GPCC_MAXL * GPCC_MAXL], s2[GPCC_HESS_MAXP * GPCC_HESS_MAXP], s3[GPCC_HESS_MAXP * GPCC_HESS_MAXP];
     const bool ok = c.info[slot] == 0;
     if (ok && tid < 6 * L2) {
@@ -413,8 +419,8 @@ static __global__ __launch_bounds__(512) void gpcc_hess_finish(GpccCtx c, GpccGr
             }
         sT[tid] = v;
     }
-    const int th = tid / P, ph = tid % P;
-    if (ok && tid < P2 && th <= ph) {
+    const int th = tid / Pa, ph = tid % Pa;
+    if (ok && tid < Pa2 && th <= ph) {
         double t3 = 0.0;
         for (int tt = 0; tt < ntri; ++tt) t3 += hb.tr[((long)slot * ntri + tt) * P2 + th * P + ph];
         const long Np = c.Np;
@@ -425,12 +431,12 @@ static __global__ __launch_bounds__(512) void gpcc_hess_finish(GpccCtx c, GpccGr
         s2[tid] = 0.5 * t2;
     }
     __syncthreads();
-    if (tid >= P2 || th > ph) return;
-    double *H = hess + (long)(g.first + m) * P2;
-    double *F = fisher + (long)(g.first + m) * P2;
+    if (tid >= Pa2 || th > ph) return;
+    double *H = hess + (long)(g.first + m) * Pa2;
+    double *F = fisher + (long)(g.first + m) * Pa2;
     if (!ok) {
-        H[th * P + ph] = H[ph * P + th] = __builtin_nan("");
-        F[th * P + ph] = F[ph * P + th] = __builtin_nan("");
+        H[th * Pa + ph] = H[ph * Pa + th] = __builtin_nan("");
+        F[th * Pa + ph] = F[ph * Pa + th] = __builtin_nan("");
         return;
     }
     const double *alpha = g.alpha + (long)(g.first + m) * L;
@@ -457,6 +463,6 @@ static __global__ __launch_bounds__(512) void gpcc_hess_finish(GpccCtx c, GpccGr
     } else if (k1 == 1) t1 = -alpha[n] * asum(4, n);                                                     // rho, tau_l
     else t1 = ((l == n) ? alpha[l] * asum(5, l) : 0.0) - alpha[l] * alpha[n] * tab(5, l, n);             // tau_l, tau_m
     const double hv = t1 - s2[tid] + s3[tid];
-    H[th * P + ph] = H[ph * P + th] = hv;
-    F[th * P + ph] = F[ph * P + th] = s3[tid];
+    H[th * Pa + ph] = H[ph * Pa + th] = hv;
+    F[th * Pa + ph] = F[ph * Pa + th] = s3[tid];
 }

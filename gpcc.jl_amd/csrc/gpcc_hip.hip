@@ -6,6 +6,7 @@
 #include "gpcc_hess.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
+#include "gpcc_laplace.h"
 
 #include "../../include/gpcc_hip.h"
 
@@ -1745,7 +1746,7 @@ static void launch_hess_kernels(gpcc_handle_t h, const GpccCtx &c, const GpccGro
     gpcc_hess_ctab<KID><<<g.cnt * ntri, 512, 0, s>>>(c, g, h->d_gw, hb);
     gpcc_hess_u<KID><<<g.cnt * c.nt, GPCC_TILE, 0, s>>>(c, g, h->d_gw, hb);
     gpcc_hess_z<<<g.cnt * c.nt, GPCC_TILE, 0, s>>>(c, g, hb);
-    gpcc_hess_gemm<KID><<<(unsigned)((long)g.cnt * hb.P * c.nt * c.nt), 512, 0, s>>>(c, g, hb);
+    gpcc_hess_gemm<KID><<<(unsigned)((long)g.cnt * hb.Pa * c.nt * c.nt), 512, 0, s>>>(c, g, hb);
     gpcc_hess_trace<<<g.cnt * ntri, 256, 0, s>>>(c, g, hb);
     gpcc_hess_finish<<<g.cnt, 512, 0, s>>>(c, g, hb, d_hess, d_fisher);
 }
@@ -1766,21 +1767,23 @@ static int enqueue_hess_group(gpcc_handle_t h, const GpccCtx &c, const GpccGroup
     return 0;
 }
 
-extern "C" int gpcc_loglik_hess_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
-                                      double *loglik, double *grad, double *hess, double *fisher, int *info)
+// hyper = 0: the full P x P Hessian (gpcc_loglik_hess_batch); 1: only its leading (L+1) x (L+1) block over alpha and rho
+// (gpcc_loglik_hess_hyper_batch) -- the kernels' block mode, on a prefix of the same buffers
+static int loglik_hess(gpcc_handle_t h, int hyper, int M, const double *delays, const double *alpha, const double *rho,
+                       double *loglik, double *grad, double *hess, double *fisher, int *info)
 {
     if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
     if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
     if (M == 0) return 0;
     if (!delays || !alpha || !rho || !loglik || !grad || !hess || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
     if (h->is_multi()) {   // device_ids[0], like the gradient
-        const int rc = gpcc_loglik_hess_batch(primary(h), M, delays, alpha, rho, loglik, grad, hess, fisher, info);
+        const int rc = loglik_hess(primary(h), hyper, M, delays, alpha, rho, loglik, grad, hess, fisher, info);
         return rc ? fail(h, rc, "%s", primary(h)->err.c_str()) : 0;
     }
     if (h->precision == GPCC_PRECISION_FP32) {   // always fp64: on the handle's fp64 twin
         int rc = ensure_fb(h, 0);
         if (rc) return rc;
-        rc = gpcc_loglik_hess_batch(h->fb, M, delays, alpha, rho, loglik, grad, hess, fisher, info);
+        rc = loglik_hess(h->fb, hyper, M, delays, alpha, rho, loglik, grad, hess, fisher, info);
         return rc ? fail(h, rc, "fp32 handle, Hessian in fp64: %s", h->fb->err.c_str()) : 0;
     }
     GPCC_ON_DEVICE(h, h->device);
@@ -1802,7 +1805,8 @@ extern "C" int gpcc_loglik_hess_batch(gpcc_handle_t h, int M, const double *dela
         HIPCHK(h, hipMalloc(&h->d_hout, sizeof(double) * 2 * W2 * M));
         h->hout_cap = M;
     }
-    double *d_hess = h->d_hout, *d_fisher = h->d_hout + W2 * M;
+    const long Pa = hyper ? h->L + 1 : W, Pa2 = Pa * Pa;   // the block: a prefix of the same allocation
+    double *d_hess = h->d_hout, *d_fisher = h->d_hout + Pa2 * M;
     const long ML = (long)M * h->L;
     double *dd = h->d_par, *da = h->d_par + ML, *dr = h->d_par + 2 * ML;
     HIPCHK(h, hipMemcpyAsync(dd, delays, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
@@ -1814,6 +1818,7 @@ extern "C" int gpcc_loglik_hess_batch(gpcc_handle_t h, int M, const double *dela
     GpccHessBuf hb;
     hb.c = h->d_hc; hb.m = h->d_hm; hb.u = h->d_hu; hb.z = h->d_hz; hb.tab = h->d_htab; hb.tr = h->d_htr;
     hb.P = (int)W;
+    hb.Pa = (int)Pa;
     hb.off[0] = 0;
     for (int l = 0; l < GPCC_MAXL; ++l) hb.off[l + 1] = hb.off[l] + (l < h->L ? h->Nl[l] : 0);
     // groups of at most hess_slots evaluations, on as many streams as the Hessian's slots hold
@@ -1848,10 +1853,22 @@ extern "C" int gpcc_loglik_hess_batch(gpcc_handle_t h, int M, const double *dela
     HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, h->main_stream));
     HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, h->main_stream));
     HIPCHK(h, hipMemcpyAsync(grad, h->d_ggrad, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
-    HIPCHK(h, hipMemcpyAsync(hess, d_hess, sizeof(double) * W2 * M, hipMemcpyDeviceToHost, h->main_stream));
-    if (fisher) HIPCHK(h, hipMemcpyAsync(fisher, d_fisher, sizeof(double) * W2 * M, hipMemcpyDeviceToHost, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(hess, d_hess, sizeof(double) * Pa2 * M, hipMemcpyDeviceToHost, h->main_stream));
+    if (fisher) HIPCHK(h, hipMemcpyAsync(fisher, d_fisher, sizeof(double) * Pa2 * M, hipMemcpyDeviceToHost, h->main_stream));
     HIPCHK(h, hipStreamSynchronize(h->main_stream));
     return 0;
+}
+
+extern "C" int gpcc_loglik_hess_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                      double *loglik, double *grad, double *hess, double *fisher, int *info)
+{
+    return loglik_hess(h, 0, M, delays, alpha, rho, loglik, grad, hess, fisher, info);
+}
+
+extern "C" int gpcc_loglik_hess_hyper_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                            double *loglik, double *grad, double *hess, double *fisher, int *info)
+{
+    return loglik_hess(h, 1, M, delays, alpha, rho, loglik, grad, hess, fisher, info);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2250,6 +2267,122 @@ extern "C" int gpcc_neldermead_batch(long P, int n, int iterations, double g_tol
     if (stats_out) {
         stats_out[0] = nm.f_calls;
         stats_out[1] = nm.rounds;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The Laplace-marginalised evidence over alpha and rho (host logic in gpcc_laplace.h): a lock-step damped Newton
+// polish of the mode in u = (log alpha, log rho), every round one gpcc_loglik_hess_hyper_batch over the delays still active.
+// ------------------------------------------------------------------------------------------
+extern "C" int gpcc_newton_batch(long P, int n, int max_rounds, double g_tol, const double *lo, const double *hi, const double *u0,
+                                 gpcc_batch_hessian_t f, void *ctx, double *umax, double *fmax, double *log_evidence, double *cov,
+                                 int *info, int *rounds_out, long long *stats_out)
+{
+    if (P < 0 || n < 1 || max_rounds < 1) return fail(nullptr, GPCC_ERR_ARGUMENT, "bad P=%ld, n=%d or max_rounds=%d", P, n, max_rounds);
+    if (!(g_tol >= 0.0)) return fail(nullptr, GPCC_ERR_ARGUMENT, "g_tol=%g < 0", g_tol);
+    if (P == 0) return 0;
+    if (!u0 || !f || !umax || !fmax || !info) return fail(nullptr, GPCC_ERR_ARGUMENT, "NULL pointer");
+    gpcclap::BatchedNewton nt(P, n, max_rounds, g_tol, lo, hi);
+    const int rc = nt.run(f, ctx, u0);
+    if (rc) return rc;
+    const size_t nn = (size_t)n * n;
+    memcpy(umax, nt.u.data(), sizeof(double) * P * n);
+    memcpy(fmax, nt.f.data(), sizeof(double) * P);
+    memcpy(info, nt.info.data(), sizeof(int) * P);
+    if (log_evidence) memcpy(log_evidence, nt.logz.data(), sizeof(double) * P);
+    if (cov) memcpy(cov, nt.cov.data(), sizeof(double) * P * nn);
+    if (rounds_out) memcpy(rounds_out, nt.rounds.data(), sizeof(int) * P);
+    if (stats_out) {
+        stats_out[0] = nt.f_calls;
+        stats_out[1] = nt.batches;
+    }
+    return 0;
+}
+
+namespace {
+struct LaplaceEval {
+    gpcc_handle_t h;
+    const double *delays;   // G x L
+    int L;
+    std::vector<double> d, a, r, ll, grad, hess;
+    std::vector<int> inf;
+    std::vector<int> start_info;   // the device's info at each delay's start (the first round)
+    bool first = true;
+};
+
+int laplace_eval(void *vctx, long K, const long *pidx, const double *U, double *val, double *gu, double *Hu)
+{
+    LaplaceEval &e = *static_cast<LaplaceEval *>(vctx);
+    const int L = e.L, n = L + 1, P = 2 * L + 1;
+    if (K > 0x7fffffffL) return fail(e.h, GPCC_ERR_ARGUMENT, "Newton round of %ld evaluations", K);
+    e.d.resize((size_t)K * L); e.a.resize((size_t)K * L); e.r.resize(K); e.ll.resize(K); e.inf.resize(K);
+    e.grad.resize((size_t)K * P); e.hess.resize((size_t)K * n * n);
+    for (long i = 0; i < K; ++i) {
+        for (int l = 0; l < L; ++l) {
+            e.d[i * L + l] = e.delays[pidx[i] * L + l];
+            e.a[i * L + l] = std::exp(U[i * n + l]);
+        }
+        e.r[i] = std::exp(U[i * n + L]);
+    }
+    const int rc = gpcc_loglik_hess_hyper_batch(e.h, (int)K, e.d.data(), e.a.data(), e.r.data(), e.ll.data(), e.grad.data(), e.hess.data(),
+                                                nullptr, e.inf.data());
+    if (rc) return rc;
+    double theta[GPCC_MAXL + 1];
+    for (long i = 0; i < K; ++i) {
+        if (e.first) e.start_info[pidx[i]] = e.inf[i];
+        for (int l = 0; l < L; ++l) theta[l] = e.a[i * L + l];
+        theta[L] = e.r[i];
+        val[i] = e.inf[i] == 0 ? e.ll[i] : std::numeric_limits<double>::quiet_NaN();
+        gpcclap::hyper_to_u(n, theta, &e.grad[(size_t)i * P], &e.hess[(size_t)i * n * n], gu + (size_t)i * n, Hu + (size_t)i * n * n);
+    }
+    e.first = false;
+    return 0;
+}
+}   // namespace
+
+extern "C" int gpcc_laplace_evidence(gpcc_handle_t h, int G, const double *delays, const double *alpha0, const double *rho0,
+                                     double rhomin, double rhomax, int max_rounds, double g_tol, double *loglik_out, double *alpha_out,
+                                     double *rho_out, double *log_evidence_out, double *cov_out, int *info_out, int *rounds_out,
+                                     long long *stats_out)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (G < 0) return fail(h, GPCC_ERR_ARGUMENT, "G=%d < 0", G);
+    if (G == 0) return 0;
+    if (!delays || !alpha0 || !rho0 || !loglik_out || !alpha_out || !rho_out || !log_evidence_out || !info_out)
+        return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    if (!(rhomin > 0.0) || !(rhomax > rhomin) || max_rounds < 1 || !(g_tol >= 0.0))
+        return fail(h, GPCC_ERR_ARGUMENT, "bad options (rho in (%g, %g), max_rounds %d, g_tol %g)", rhomin, rhomax, max_rounds, g_tol);
+    const int L = primary(h)->L, n = L + 1;
+    std::vector<double> u0((size_t)G * n), lo(n, -std::numeric_limits<double>::infinity()), hi(n, std::numeric_limits<double>::infinity());
+    for (long g = 0; g < G; ++g) {
+        for (int l = 0; l < L; ++l) {
+            if (!(alpha0[g * L + l] > 0.0)) return fail(h, GPCC_ERR_ARGUMENT, "alpha0[%ld][%d] = %g is not > 0", g, l, alpha0[g * L + l]);
+            u0[g * n + l] = std::log(alpha0[g * L + l]);
+        }
+        if (!(rho0[g] > 0.0)) return fail(h, GPCC_ERR_ARGUMENT, "rho0[%ld] = %g is not > 0", g, rho0[g]);
+        u0[g * n + L] = std::log(rho0[g]);
+    }
+    lo[L] = std::log(rhomin);
+    hi[L] = std::log(rhomax);
+    LaplaceEval ev{h, delays, L, {}, {}, {}, {}, {}, {}, {}, std::vector<int>(G, 0)};
+    gpcclap::BatchedNewton nt(G, n, max_rounds, g_tol, lo.data(), hi.data());
+    const int rc = nt.run(laplace_eval, &ev, u0.data());
+    if (rc) return rc;
+    for (long g = 0; g < G; ++g) {
+        const double *ug = &nt.u[(size_t)g * n];
+        for (int l = 0; l < L; ++l) alpha_out[g * L + l] = std::exp(ug[l]);   // (the values the device evaluated)
+        rho_out[g] = std::exp(ug[L]);
+        loglik_out[g] = nt.f[g];
+        log_evidence_out[g] = nt.logz[g];
+        // a start the device could not evaluate keeps the device's own code (a pivot index, -1, -2)
+        info_out[g] = (nt.info[g] == gpcclap::BAD_START && ev.start_info[g] != 0) ? ev.start_info[g] : nt.info[g];
+        if (cov_out) memcpy(cov_out + (size_t)g * n * n, &nt.cov[(size_t)g * n * n], sizeof(double) * n * n);
+        if (rounds_out) rounds_out[g] = nt.rounds[g];
+    }
+    if (stats_out) {
+        stats_out[0] = nt.f_calls;
+        stats_out[1] = nt.batches;
     }
     return 0;
 }

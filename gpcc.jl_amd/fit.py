@@ -15,6 +15,7 @@ a + (b - a) * logistic(x), the package's documented purpose; `safewrapper` is ta
 (PosDefException) into +Inf of the negative objective."""
 import numpy as np
 
+from . import laplace
 from .api import Objective, PosDefException, mvnormal_logpdf
 from .neldermead import BatchedNelderMead
 
@@ -143,23 +144,33 @@ def logrange(a, b, n):
 
 class GridFit:
     """Result of gpcc_grid: loglikel[G] (= -minimum, what README.md:172-174 feeds to
-    getprobabilities), alpha[G, L], rho[G], f_calls, rounds."""
+    getprobabilities), alpha[G, L], rho[G], f_calls, rounds.  With evidence="laplace" also log_evidence[G] (the
+    Laplace-marginalised evidence over alpha and rho, up to one constant shared by all delays: feed it to getprobabilities),
+    hyper_cov[G, L+1, L+1] (posterior covariance of (log alpha, log rho)), laplace_info[G] and laplace_rounds[G]
+    (DESIGN.md 4.11); None otherwise."""
 
     def __init__(self, loglikel, alpha, rho, f_calls, rounds, iterations_done):
         self.loglikel, self.alpha, self.rho = loglikel, alpha, rho
         self.f_calls, self.rounds, self.iterations_done = f_calls, rounds, iterations_done
+        self.log_evidence = self.hyper_cov = self.laplace_info = self.laplace_rounds = None
 
 
 def gpcc_grid(tarray, yarray, stdarray, *, kernel, candidatedelays, iterations, seed=1, numberofrestarts=1,
               initialrandom=5, rhomin=0.1, rhomax=20.0, objective=None, device=0, marginalise_b=True, engine=None,
-              unpack=None):
+              unpack=None, evidence=None, laplace_rounds=50, laplace_g_tol=1e-6):
     """Fits the GPCC model for each row of candidatedelays (G, L): the README's
     `map(delay -> gpcc(...; delays = [0; delay])[1], candidatedelays)` as one lock-step batch.
 
     engine "native" (default with a device Objective): the whole fit is one gpcc_grid_loglik call, the random
     candidates drawn here (numpy) and handed over as init_params.  engine "python" (default when another
     objective is injected): the same algorithm in numpy (neldermead.py) over objective.loglik_batch; `unpack`
-    may replace the numpy parameter transforms (api.unpack_params = the library's own)."""
+    may replace the numpy parameter transforms (api.unpack_params = the library's own).
+
+    evidence "laplace": after the fit, the Laplace-marginalised evidence over alpha and rho at every delay, from the fitted
+    (alpha, rho) (Objective.laplace_evidence with the native engine, laplace.laplace_evidence otherwise) -> GridFit.log_evidence,
+    .hyper_cov, .laplace_info, .laplace_rounds.  None (default): the profile likelihood only, as before."""
+    if evidence not in (None, "laplace"):
+        raise ValueError("evidence must be None or 'laplace', got %r" % (evidence,))
     cand = np.ascontiguousarray(np.atleast_2d(candidatedelays), dtype=np.float64)
     G, L = cand.shape
     assert L == len(tarray) == len(yarray) == len(stdarray)          # marginaliseb.jl:78
@@ -187,7 +198,8 @@ def gpcc_grid(tarray, yarray, stdarray, *, kernel, candidatedelays, iterations, 
             ll, alpha, rho, info, its, (f_calls, rounds) = obj.grid_loglik(
                 cand, iterations, numberofrestarts=R, initialrandom=initialrandom, rhomin=rhomin, rhomax=rhomax,
                 seed=seed, init_params=cands)
-            return GridFit(ll, alpha, rho, f_calls, rounds, its.astype(np.int64))
+            return _with_evidence(GridFit(ll, alpha, rho, f_calls, rounds, its.astype(np.int64)), obj, cand, engine, evidence,
+                                  rhomin, rhomax, laplace_rounds, laplace_g_tol)
 
         def negobj(pidx, X):
             if unpack is not None:
@@ -211,11 +223,32 @@ def gpcc_grid(tarray, yarray, stdarray, *, kernel, candidatedelays, iterations, 
         xsel = xmin.reshape(G, R, L + 1)[np.arange(G), pick]
         a_sel, r_sel = (unpack(xsel, L, rhomin, rhomax) if unpack is not None else
                         (makepositive(xsel[:, :L]) + 1e-8, transformbetween(xsel[:, L], rhomin, rhomax)))
-        return GridFit(-fmin[np.arange(G), pick], a_sel, r_sel, nm.f_calls + P * initialrandom, nm.rounds + 1,
-                       nm.iterations_done.reshape(G, R)[np.arange(G), pick])
+        return _with_evidence(GridFit(-fmin[np.arange(G), pick], a_sel, r_sel, nm.f_calls + P * initialrandom, nm.rounds + 1,
+                                      nm.iterations_done.reshape(G, R)[np.arange(G), pick]), obj, cand, engine, evidence,
+                              rhomin, rhomax, laplace_rounds, laplace_g_tol)
     finally:
         if own:
             obj.close()
+
+
+def _with_evidence(res, obj, cand, engine, evidence, rhomin, rhomax, max_rounds, g_tol):
+    if evidence is None:
+        return res
+    ok = np.all(np.isfinite(res.alpha), axis=1) & np.isfinite(res.rho) & np.all(res.alpha > 0, axis=1) & (res.rho > 0)
+    G, n = cand.shape[0], cand.shape[1] + 1
+    a0 = np.where(ok[:, None], res.alpha, 1.0)     # a delay whose fit found no valid point: a placeholder start, info set below
+    r0 = np.where(ok, res.rho, np.sqrt(rhomin * rhomax))
+    if engine == "native":
+        _, _, _, logz, cov, info, rounds, _ = obj.laplace_evidence(cand, a0, r0, rhomin=rhomin, rhomax=rhomax, max_rounds=max_rounds,
+                                                                   g_tol=g_tol)
+    else:
+        _, _, _, logz, cov, info, rounds = laplace.laplace_evidence(obj, cand, a0, r0, rhomin=rhomin, rhomax=rhomax,
+                                                                    max_rounds=max_rounds, g_tol=g_tol)
+    info = np.where(ok, info, laplace.BAD_START).astype(np.int32)
+    res.log_evidence = np.where(ok, logz, np.nan)
+    res.hyper_cov = np.where(ok[:, None, None], cov, np.nan).reshape(G, n, n)
+    res.laplace_info, res.laplace_rounds = info, rounds
+    return res
 
 
 class Predictor:

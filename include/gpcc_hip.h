@@ -17,7 +17,7 @@
  *   - ragged light curves are passed flattened in band order, user order inside a band
  *     (Y = reduce(vcat, yarray), src/gpccfixdelay_marginaliseb.jl:85).
  *   - per-evaluation parameter blocks are ROW-major M x L (Julia passes an L x M Matrix).
- *   - no callbacks on the likelihood path (only gpcc_neldermead_batch, the optimiser on its own, takes one), no
+ *   - no callbacks on the likelihood path (only gpcc_neldermead_batch and gpcc_newton_batch, the optimisers on their own, take one), no
  *     retained caller pointers, all device memory owned by the handle;
  *     one handle per thread/process; several handles (and processes) may share a GPU.
  *   - there is NO CPU fallback: without a HIP device every compute entry returns an error.
@@ -227,6 +227,14 @@ int gpcc_loglik_grad_batch(gpcc_handle_t h, int M, const double *delays, const d
 int gpcc_loglik_hess_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                            double *loglik, double *grad, double *hess, double *fisher, int *info);
 
+/* The hyper-parameter block of gpcc_loglik_hess_batch: loglik[M], info[M] and grad (M rows of P = 2L+1) as there (bitwise
+ * gpcc_loglik_grad_batch's); hess and fisher (may be NULL): M row-major (L+1) x (L+1) blocks over [alpha_1..alpha_L, rho], bitwise
+ * the leading block of gpcc_loglik_hess_batch's and bitwise symmetric, NaN where info != 0.  The kernels form K^-1 D_theta and the
+ * traces for the L+1 hyper-parameters only (their block mode; the buffers and "hess_bytes_per_slot" are the full Hessian's).  The
+ * same rules: fp64 only (an fp32 handle on its fp64 twin), a multi-device handle on device_ids[0].  Blocking. */
+int gpcc_loglik_hess_hyper_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                 double *loglik, double *grad, double *hess, double *fisher, int *info);
+
 /* Same with DEVICE pointers, enqueued behind `stream` (a hipStream_t, NULL = default stream) and
  * joined back into it: asynchronous, outputs valid once `stream` has drained. */
 int gpcc_loglik_batch_device(gpcc_handle_t handle, int M, const double *d_delays,
@@ -302,6 +310,47 @@ int gpcc_initial_params(gpcc_handle_t h, int numberofrestarts, int initialrandom
 typedef int (*gpcc_batch_objective_t)(void *ctx, long K, const long *pidx, const double *X, double *out);
 int gpcc_neldermead_batch(long P, int n, int iterations, double g_tol, const double *x0, gpcc_batch_objective_t f,
                           void *ctx, double *xmin, double *fmin, int *iterations_out, long long *stats_out);
+
+/* Per-delay codes of gpcc_laplace_evidence / gpcc_newton_batch (negative: they cannot clash with a factorisation's pivot index). */
+enum {
+    GPCC_LAPLACE_NOT_CONVERGED = -10,   /* the polish did not converge within max_rounds evaluations (or its step collapsed) */
+    GPCC_LAPLACE_NOT_MAXIMUM = -11,     /* -Hessian not positive definite at the last point */
+    GPCC_LAPLACE_ON_BOUND = -12,        /* the mode lies on the box (gpcc_laplace_evidence: rho = rhomin or rhomax) */
+    GPCC_LAPLACE_BAD_START = -13        /* gpcc_newton_batch: the start was rejected (non-finite value) */
+};
+
+/* The Newton polish of gpcc_laplace_evidence on its own (host only): P independent maximisations of l(u), u in R^n, in lock-step.
+ * f(ctx, K, pidx, U, val, grad, hess) must write, for row i of U (K x n) of problem pidx[i], val[i] = l, grad[i] (n) and hess[i] (n x n,
+ * row-major); a non-finite val = rejected point; non-zero return aborts with that code.  From u0 (P x n, clipped to the box lo..hi:
+ * n entries each, NULL = unbounded), damped Newton: the step solves (-H + lambda I) d = g (lambda = 0, or Levenberg damping while -H
+ * is not positive definite; coordinates on a bound with g pointing out stay fixed), is clipped to the box, accepted if l does not
+ * decrease (beyond 1e-12 max(1, |l|), the rounding of an evaluated l) and halved otherwise.  Converged when the projected gradient's |.|_inf <= g_tol.  Outputs (P rows): umax, fmax = l(umax),
+ * info (0 or GPCC_LAPLACE_*), and, each may be NULL: log_evidence = l + n/2 log(2 pi) - 1/2 log det(-H) (NaN where info != 0),
+ * cov = (-H)^-1 (n x n; NaN unless -H is positive definite), rounds_out = evaluations per problem (the start included; at most
+ * max_rounds), stats_out = {evaluations, batches}.  The (n x n) systems use an explicit scalar Cholesky without FMA contraction:
+ * gpcc.jl_amd/laplace.py reproduces every step bitwise. */
+typedef int (*gpcc_batch_hessian_t)(void *ctx, long K, const long *pidx, const double *U, double *val, double *grad, double *hess);
+int gpcc_newton_batch(long P, int n, int max_rounds, double g_tol, const double *lo, const double *hi, const double *u0,
+                      gpcc_batch_hessian_t f, void *ctx, double *umax, double *fmax, double *log_evidence, double *cov,
+                      int *info, int *rounds_out, long long *stats_out);
+
+/* The Laplace-marginalised evidence over alpha and rho at each of G delays (rows of delays, G x L), for the delay posterior
+ * getprobabilities(log_evidence_out).  Prior: log-uniform in every alpha_l on (0, inf) and in rho on [rhomin, rhomax],
+ * i.e. flat in u = (log alpha_1 .. log alpha_L, log rho), the same measure at every delay.  Its normalising constant (improper in alpha)
+ * is common to all delays and cancels in getprobabilities: log_evidence_out is log Z(tau) UP TO ONE ADDITIVE CONSTANT SHARED BY ALL
+ * DELAYS -- only differences and normalised probabilities mean anything.  tau is not marginalised.
+ *   From (alpha0, rho0) per delay (usually gpcc_grid_loglik's output), gpcc_newton_batch's polish over u with log rho boxed to
+ *   [log rhomin, log rhomax], every round one gpcc_loglik_hess_hyper_batch over the delays still active; gradient and Hessian in u:
+ *   g_u = theta g_theta, H_u = diag(theta) H_theta diag(theta) + diag(theta g_theta), theta = (alpha, rho).  At the mode u^:
+ *     log_evidence = l(u^) + (L+1)/2 log(2 pi) - 1/2 log det(-H_u(u^)).
+ * Outputs (G rows): loglik_out = l(u^), alpha_out (G x L), rho_out = exp(u^), log_evidence_out, cov_out (may be NULL: G x (L+1)^2, the
+ * posterior covariance (-H_u)^-1 of u), info_out: 0, GPCC_LAPLACE_NOT_CONVERGED / _NOT_MAXIMUM / _ON_BOUND (NaN log_evidence), or the
+ * device's code (pivot index, -1, -2) where the start itself could not be evaluated (NaN loglik and log_evidence); rounds_out (may be
+ * NULL) = Newton rounds per delay (the start's evaluation included), stats_out (may be NULL) = {evaluations, batches}.  fp64 on any
+ * handle (as the Hessian).  Blocking. */
+int gpcc_laplace_evidence(gpcc_handle_t h, int G, const double *delays, const double *alpha0, const double *rho0, double rhomin,
+                          double rhomax, int max_rounds, double g_tol, double *loglik_out, double *alpha_out, double *rho_out,
+                          double *log_evidence_out, double *cov_out, int *info_out, int *rounds_out, long long *stats_out);
 
 /* `unpack` of marginaliseb.jl:112-126 for M parameter vectors X (M x (L+1)): alpha = makepositive(x[1:L]) + 1e-8,
  * rho = transformbetween(x[L+1], rhomin, rhomax).  MiscUtil.jl's source is not part of the reference tree:

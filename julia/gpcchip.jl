@@ -88,6 +88,41 @@ function loglik_hess_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Flo
     return ll, grad, hess, fisher, info
 end
 
+"the [α_1..α_L, ρ] block of loglik_hess_batch, bitwise its leading (L+1)×(L+1) block: (ll[M], grad (2L+1)×M, hess and fisher
+(L+1)×(L+1)×M, info[M]); only that block is formed on the device."
+function loglik_hess_hyper_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
+    M, P, n = length(rho), 2h.L + 1, h.L + 1
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    grad = Matrix{Float64}(undef, P, M)
+    hess, fisher = Array{Float64}(undef, n, n, M), Array{Float64}(undef, n, n, M)   # symmetric: row- or column-major alike
+    rc = ccall((:gpcc_loglik_hess_hyper_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, ll, grad, hess, fisher, info)
+    rc == 0 || error("gpcc_loglik_hess_hyper_batch: " * lasterror(h.ptr))
+    return ll, grad, hess, fisher, info
+end
+
+"Laplace-marginalised evidence over α and ρ per delay (columns of delays, L×G), from (alpha0 L×G, rho0[G]), usually the fit's
+output.  Prior log-uniform in α and in ρ on [rhomin, rhomax]: log_evidence is log Z(τ) up to ONE additive constant shared by all
+delays -- use it only through getprobabilities (or differences).  -> (ll[G], alpha L×G, rho[G], log_evidence[G], cov (L+1)×(L+1)×G
+of (log α, log ρ), info[G]: 0, -10 not converged, -11 not a maximum, -12 mode on the ρ bound, or the start's own code; rounds[G])."
+function laplace_evidence(h::Handle, delays::Matrix{Float64}, alpha0::Matrix{Float64}, rho0::Vector{Float64};
+                          rhomin = 0.1, rhomax = 20.0, max_rounds = 50, g_tol = 1e-6)
+    G, n = length(rho0), h.L + 1
+    @assert size(delays) == (h.L, G) && size(alpha0) == (h.L, G)
+    ll, alpha, rho = Vector{Float64}(undef, G), Matrix{Float64}(undef, h.L, G), Vector{Float64}(undef, G)
+    logz, cov = Vector{Float64}(undef, G), Array{Float64}(undef, n, n, G)   # symmetric: row- or column-major alike
+    info, rounds = Vector{Cint}(undef, G), Vector{Cint}(undef, G)
+    rc = ccall((:gpcc_laplace_evidence, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble, Cint, Cdouble, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cint}, Ptr{Clonglong}),
+               h.ptr, G, delays, alpha0, rho0, rhomin, rhomax, max_rounds, g_tol, ll, alpha, rho, logz, cov, info, rounds, C_NULL)
+    rc == 0 || error("gpcc_laplace_evidence: " * lasterror(h.ptr))
+    return ll, alpha, rho, logz, cov, info, rounds
+end
+
 "Drop-in body of objective(α, ρ) (gpccfixdelay_marginaliseb.jl:133-141): throws what the Julia code throws."
 function objective(h::Handle, τ, α, ρ)
     ll, info = loglik_batch(h, reshape(Float64.(τ), :, 1), reshape(Float64.(α), :, 1), [Float64(ρ)])
