@@ -419,6 +419,37 @@ class Objective:
             raise PosDefException(info.value)
         return mu, Sig.T
 
+    def predict_batch(self, delays, alpha, rho, ttest, weights=None):
+        """The diagonal posterior predictive at M rows (tau, alpha, rho) on the test times ttest (a list of L arrays, shared by every row),
+        and its average over the rows with weights -> (mu[M, T], var[M, T], loglik[M], info[M], mix_mu[T], mix_var[T]) (gpcc_predict_batch).
+        Row m is predict()'s mu and diag(Sigma) at that row (JITTER included); loglik and info are bitwise loglik_grad_batch's, and
+        failed rows (info != 0) are NaN.  mix_mu = sum p mu, mix_var = sum p (var + (mu - mix_mu)^2), p = weights / sum(weights);
+        zero-weight rows are skipped; None without weights.  Always fp64; a multi-device handle computes on its first device."""
+        if len(ttest) != self.L:
+            raise AssertionError("length(ttest) == L")
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        Nt, tt = _flatten(ttest)
+        T = int(Nt.sum())
+        mu = np.empty((M, T), dtype=np.float64)
+        var = np.empty((M, T), dtype=np.float64)
+        ll = np.empty(M, dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        w = mix_mu = mix_var = None
+        if weights is not None:
+            w = _d(np.asarray(weights, dtype=np.float64).ravel())
+            if w.shape != (M,):
+                raise ValueError("weights must have M = %d entries" % M)
+            mix_mu = np.empty(T, dtype=np.float64)
+            mix_var = np.empty(T, dtype=np.float64)
+        try:
+            self._chk(_capi.load().gpcc_predict_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _ip(Nt), _dp(tt),
+                                                      _dp(w) if w is not None else None, _dp(mu), _dp(var),
+                                                      _dp(mix_mu) if w is not None else None,
+                                                      _dp(mix_var) if w is not None else None, _dp(ll), _ip(info)))
+        except GpccError as e:
+            _raise_reference_error(e)
+        return mu, var, ll, info, mix_mu, mix_var
+
     def posterior_offsets(self, delays, alpha, rho):
         """(mu_postb, Sigma_postb) of marginaliseb.jl:248-252 (the reference wraps them in MvNormal)."""
         delays, alpha = _d(delays), _d(alpha)

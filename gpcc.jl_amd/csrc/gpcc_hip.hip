@@ -4,6 +4,7 @@
 #include "gpcc_small.hip.h"
 #include "gpcc_grad.hip.h"
 #include "gpcc_hess.hip.h"
+#include "gpcc_pred.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -194,6 +195,12 @@ struct gpcc_handle_s {
     // dense K^-1, M_theta = K^-1 D_theta for every parameter, u, z and the partials) and the outputs of the batch (hess and fisher blocks)
     double *d_hc = nullptr, *d_hm = nullptr, *d_hu = nullptr, *d_hz = nullptr, *d_htab = nullptr, *d_htr = nullptr, *d_hout = nullptr;
     long hess_slots = 0, hess_ws = 0, hout_cap = 0;
+    // predictive (gpcc_predict_batch): allocated on its first call -- the shared test points (pred_tp doubles + ints), per workspace slot
+    // the partials (nt x pred_tp) and one row of mu and var (pred_tp each), the mixture state (6 pred_tp) and the weights (pw_cap)
+    double *d_ptt = nullptr, *d_ppart = nullptr, *d_pmu = nullptr, *d_pvar = nullptr, *d_pmix = nullptr, *d_pw = nullptr;
+    int *d_ptb = nullptr;
+    long pred_slots = 0, pred_tp = 0, pw_cap = 0;
+    hipEvent_t ev_pmix = nullptr;   // orders the mixture steps of consecutive groups (on different streams) by row
     double *d_sep = nullptr, *d_seps = nullptr;     // separable factors of the points, the distance scale (GpccCtx::sep, ::seps)
     int *d_sepflag = nullptr;                       // per-tile-row flags (GpccCtx::sepflag)
     int fp32_refine = 1;                            // option "fp32_refine": 0 = no refinement of the quadratic forms
@@ -464,6 +471,8 @@ static void free_workspace(gpcc_handle_t h)
     h->d_glinv = h->d_gscr = h->d_gw = h->d_gpart3 = nullptr; h->grad_slots = 0;
     hipFree(h->d_hc); hipFree(h->d_hm); hipFree(h->d_hu); hipFree(h->d_hz); hipFree(h->d_htab); hipFree(h->d_htr);
     h->d_hc = h->d_hm = h->d_hu = h->d_hz = h->d_htab = h->d_htr = nullptr; h->hess_slots = h->hess_ws = 0;
+    hipFree(h->d_ptt); hipFree(h->d_ptb); hipFree(h->d_ppart); hipFree(h->d_pmu); hipFree(h->d_pvar); hipFree(h->d_pmix);
+    h->d_ptt = h->d_ppart = h->d_pmu = h->d_pvar = h->d_pmix = nullptr; h->d_ptb = nullptr; h->pred_slots = h->pred_tp = 0;
     h->d_chain_words = nullptr; h->d_ximg = h->d_stepval = nullptr; h->d_chain_trace = nullptr; h->chain_streams = 0;
     h->d_tiles = h->d_linv = h->d_z = h->d_w = h->d_logdet = h->d_quad = h->d_kdiag = h->d_cond = h->d_gpart = nullptr;
     h->d_sep = h->d_seps = nullptr;
@@ -489,7 +498,8 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_t); hipFree(h->d_sig2); hipFree(h->d_resid); hipFree(h->d_band); hipFree(h->d_yv);
     hipFree(h->d_par); hipFree(h->d_out); hipFree(h->d_oinfo);
     for (auto &ln : h->lanes) ln.release();
-    hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout);
+    hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
+    if (h->ev_pmix) hipEventDestroy(h->ev_pmix);
     hipFree(h->d_ocond); hipFree(h->d_fb_idx); hipFree(h->d_fb_par); hipFree(h->d_fb_out); hipFree(h->d_fb_info);
     if (h->fb) gpcc_destroy(h->fb);
     if (h->main_stream) hipStreamDestroy(h->main_stream);
@@ -1584,10 +1594,18 @@ static int ensure_grad(gpcc_handle_t h)
     return 0;
 }
 
-static int enqueue_grad_group(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g_in, double *d_grad, hipStream_t s)
+// the job order of a gradient group's factorisation (every evaluation's arithmetic is the same either way)
+static GpccGroup grad_group(const GpccGroup &g_in)
 {
     GpccGroup g = g_in;
-    g.spread = (g.cnt < 8) ? 1 : 0;   // (job order only: every evaluation's arithmetic is the same either way)
+    g.spread = (g.cnt < 8) ? 1 : 0;
+    return g;
+}
+
+// part 1 of a gradient group, shared with the predictive (gpcc_predict_batch): assembly, the launch-per-step factorisation with every
+// inv(L_kk) kept, X = L^-1 over the slot's lower tiles and w = K^-1 r (h->d_gw).  g: from grad_group.
+static void enqueue_grad_inverse(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g, hipStream_t s)
+{
     const int cnt8 = g.spread ? g.cnt : 8 * ((g.cnt + 7) / 8);
     launch_assemble(h, c, g, s, false, false);
     for (int k = 0; k < c.nt; ++k) {
@@ -1610,6 +1628,11 @@ static int enqueue_grad_group(gpcc_handle_t h, const GpccCtx &c, const GpccGroup
         gpcc_grad_copy<<<jobs, 256, 0, s>>>(c, g, j, h->d_gscr);
     }
     gpcc_grad_w<<<g.cnt * c.nt, GPCC_TILE, 0, s>>>(c, g, h->d_gw);
+}
+
+// part 2: the fused K^-1 tiles with their derivative sums, and the finish
+static void enqueue_grad_tiles(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g, double *d_grad, hipStream_t s)
+{
     const int tiles = g.cnt * (c.nt * (c.nt + 1) / 2);
     switch (c.kernel_id) {
     case 0: gpcc_grad_tiles<0><<<tiles, 512, 0, s>>>(c, g, h->d_gw, h->d_gpart3); break;
@@ -1618,6 +1641,13 @@ static int enqueue_grad_group(gpcc_handle_t h, const GpccCtx &c, const GpccGroup
     default: gpcc_grad_tiles<3><<<tiles, 512, 0, s>>>(c, g, h->d_gw, h->d_gpart3); break;
     }
     gpcc_grad_finish<<<g.cnt, 256, 0, s>>>(c, g, h->d_gpart3, d_grad);
+}
+
+static int enqueue_grad_group(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g_in, double *d_grad, hipStream_t s)
+{
+    const GpccGroup g = grad_group(g_in);
+    enqueue_grad_inverse(h, c, g, s);
+    enqueue_grad_tiles(h, c, g, d_grad, s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     return 0;
@@ -1869,6 +1899,181 @@ extern "C" int gpcc_loglik_hess_hyper_batch(gpcc_handle_t h, int M, const double
                                             double *loglik, double *grad, double *hess, double *fisher, int *info)
 {
     return loglik_hess(h, 1, M, delays, alpha, rho, loglik, grad, hess, fisher, info);
+}
+
+// ------------------------------------------------------------------------------------------
+// Batched posterior predictive and its delay average (gpcc_predict_batch; kernels: gpcc_pred.hip.h).  A group runs part
+// 1 of the gradient group unchanged (enqueue_grad_inverse: loglik and info are the gradient path's bits), then the predictive kernels
+// on the same slots.  The buffers are allocated on the first call (ensure_pred) and grow with the test points; a handle that never
+// predicts holds none of them.
+// ------------------------------------------------------------------------------------------
+static int ensure_pred(gpcc_handle_t h, long Tp, long M)
+{
+    const long slots = (long)h->ws_streams * h->ws_slots;
+    if (!(h->pred_slots == slots && h->pred_tp >= Tp && h->d_ppart)) {
+        hipFree(h->d_ptt); hipFree(h->d_ptb); hipFree(h->d_ppart); hipFree(h->d_pmu); hipFree(h->d_pvar); hipFree(h->d_pmix);
+        h->d_ptt = h->d_ppart = h->d_pmu = h->d_pvar = h->d_pmix = nullptr; h->d_ptb = nullptr; h->pred_slots = h->pred_tp = 0;
+        HIPCHK(h, hipMalloc(&h->d_ptt, sizeof(double) * Tp));
+        HIPCHK(h, hipMalloc(&h->d_ptb, sizeof(int) * Tp));
+        HIPCHK(h, hipMalloc(&h->d_ppart, sizeof(double) * h->nt * Tp * slots));
+        HIPCHK(h, hipMalloc(&h->d_pmu, sizeof(double) * Tp * slots));
+        HIPCHK(h, hipMalloc(&h->d_pvar, sizeof(double) * Tp * slots));
+        HIPCHK(h, hipMalloc(&h->d_pmix, sizeof(double) * 6 * Tp));
+        h->pred_slots = slots;
+        h->pred_tp = Tp;
+    }
+    if (M > h->pw_cap) {
+        hipFree(h->d_pw);
+        h->d_pw = nullptr; h->pw_cap = 0;
+        HIPCHK(h, hipMalloc(&h->d_pw, sizeof(double) * M));
+        h->pw_cap = M;
+    }
+    if (!h->ev_pmix) HIPCHK(h, hipEventCreateWithFlags(&h->ev_pmix, hipEventDisableTiming));
+    return 0;
+}
+
+template <int KID>
+static void launch_pred_tiles(const GpccCtx &c, const GpccGroup &g, const GpccPredBuf &pb, hipStream_t s)
+{
+    gpcc_pred_tiles<KID><<<(unsigned)((long)g.cnt * c.nt * pb.ntT), 512, 0, s>>>(c, g, pb);
+}
+
+extern "C" int gpcc_predict_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                  const int *Ntest, const double *ttest, const double *weights, double *mu_out, double *var_out,
+                                  double *mix_mu, double *mix_var, double *loglik, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (!delays || !alpha || !rho || !Ntest || !ttest || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    if ((mu_out == nullptr) != (var_out == nullptr)) return fail(h, GPCC_ERR_ARGUMENT, "mu_out and var_out are both given or both NULL");
+    if (weights && (!mix_mu || !mix_var)) return fail(h, GPCC_ERR_ARGUMENT, "weights given: mix_mu and mix_var are required");
+    if (!weights && (mix_mu || mix_var)) return fail(h, GPCC_ERR_ARGUMENT, "mix_mu and mix_var need weights");
+    if (!weights && !mu_out) return fail(h, GPCC_ERR_ARGUMENT, "NULL mu_out / var_out without weights: nothing to return");
+    if (h->is_multi()) {   // device_ids[0], like the gradient
+        const int rc = gpcc_predict_batch(primary(h), M, delays, alpha, rho, Ntest, ttest, weights, mu_out, var_out, mix_mu, mix_var,
+                                          loglik, info);
+        return rc ? fail(h, rc, "%s", primary(h)->err.c_str()) : 0;
+    }
+    if (h->precision == GPCC_PRECISION_FP32) {   // always fp64: on the handle's fp64 twin
+        int rc = ensure_fb(h, 0);
+        if (rc) return rc;
+        rc = gpcc_predict_batch(h->fb, M, delays, alpha, rho, Ntest, ttest, weights, mu_out, var_out, mix_mu, mix_var, loglik, info);
+        return rc ? fail(h, rc, "fp32 handle, predictive in fp64: %s", h->fb->err.c_str()) : 0;
+    }
+    long T = 0;
+    for (int l = 0; l < h->L; ++l) { if (Ntest[l] < 0) return fail(h, GPCC_ERR_ARGUMENT, "negative Ntest"); T += Ntest[l]; }
+    if (T <= 0 || T > 32768) return fail(h, GPCC_ERR_ARGUMENT, "total number of test points %ld outside [1, 32768]", T);
+    // the normalised weights p_m = w_m / sum w (sums in row order), checked before any device work
+    std::vector<double> p;
+    if (weights) {
+        double sw = 0.0;
+        for (int m = 0; m < M; ++m) {
+            if (!std::isfinite(weights[m]) || weights[m] < 0.0)
+                return fail(h, GPCC_ERR_ARGUMENT, "weight %d = %g: weights must be finite and >= 0", m, weights[m]);
+            sw += weights[m];
+        }
+        if (!(sw > 0.0) || !std::isfinite(sw)) return fail(h, GPCC_ERR_ARGUMENT, "the weights sum to %g: need a finite sum > 0", sw);
+        p.resize(M);
+        for (int m = 0; m < M; ++m) p[m] = weights[m] / sw;
+    }
+    if (M == 0) return 0;
+    GPCC_ON_DEVICE(h, h->device);
+    const int ntT = (int)((T + GPCC_TILE - 1) / GPCC_TILE);
+    const long Tp = (long)ntT * GPCC_TILE;
+    int rc = ensure_workspace(h);
+    if (!rc) rc = ensure_grad(h);
+    if (!rc) rc = ensure_pred(h, Tp, weights ? M : 0);
+    if (!rc) rc = ensure_staging(h, M);
+    if (rc) return rc;
+    std::vector<double> tt(Tp, 0.0);
+    std::vector<int> tb(Tp, -1);
+    {
+        long o = 0;
+        for (int l = 0; l < h->L; ++l)
+            for (int n = 0; n < Ntest[l]; ++n, ++o) { tt[o] = ttest[o]; tb[o] = l; }
+    }
+    const long ML = (long)M * h->L;
+    double *dd = h->d_par, *da = h->d_par + ML, *dr = h->d_par + 2 * ML;
+    hipStream_t ms = h->main_stream;
+    HIPCHK(h, hipMemcpyAsync(dd, delays, sizeof(double) * ML, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(da, alpha, sizeof(double) * ML, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(dr, rho, sizeof(double) * M, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_ptt, tt.data(), sizeof(double) * Tp, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_ptb, tb.data(), sizeof(int) * Tp, hipMemcpyHostToDevice, ms));
+    if (weights) {
+        HIPCHK(h, hipMemcpyAsync(h->d_pw, p.data(), sizeof(double) * M, hipMemcpyHostToDevice, ms));
+        HIPCHK(h, hipMemsetAsync(h->d_pmix, 0, sizeof(double) * 4 * Tp, ms));
+    }
+    GpccCtx c = make_ctx(h);
+    c.linv = h->d_glinv;
+    c.linv_keep = 1;
+    GpccPredBuf pb;
+    pb.tt = h->d_ptt; pb.tb = h->d_ptb; pb.gw = h->d_gw;
+    pb.part = h->d_ppart; pb.mu = h->d_pmu; pb.var = h->d_pvar; pb.mix = h->d_pmix;
+    pb.T = (int)T; pb.Tp = (int)Tp; pb.ntT = ntT;
+    for (int l = 0; l < GPCC_MAXL; ++l) pb.mean_b[l] = (l < h->L) ? h->mean_b[l] : 0.0;
+    const int S = h->prof ? 1 : h->ws_streams, cs = h->ws_slots;
+    const int ngroups = (M + cs - 1) / cs, used = ngroups < S ? ngroups : S;
+    HIPCHK(h, hipEventRecord(h->ev_start, ms));
+    for (int s = 0; s < used; ++s) HIPCHK(h, hipStreamWaitEvent(h->str[s], h->ev_start, 0));
+    for (int gi = 0; gi < ngroups && !rc; ++gi) {
+        const int s = gi % S;
+        hipStream_t st = h->str[s];
+        GpccGroup g0;
+        g0.delays = dd; g0.alpha = da; g0.rho = dr;
+        g0.out_loglik = h->d_out; g0.out_info = h->d_oinfo; g0.out_cond = nullptr;
+        g0.first = gi * cs;
+        g0.slot0 = s * cs;
+        g0.cnt = (M - g0.first < cs) ? (M - g0.first) : cs;
+        g0.spread = 0;
+        const GpccGroup g = grad_group(g0);
+        enqueue_grad_inverse(h, c, g, st);
+        switch (c.kernel_id) {
+        case 0: launch_pred_tiles<0>(c, g, pb, st); break;
+        case 1: launch_pred_tiles<1>(c, g, pb, st); break;
+        case 2: launch_pred_tiles<2>(c, g, pb, st); break;
+        default: launch_pred_tiles<3>(c, g, pb, st); break;
+        }
+        gpcc_pred_finish<<<g.cnt * ntT, GPCC_TILE, 0, st>>>(c, g, pb);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { rc = fail(h, GPCC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e)); break; }
+        if (mu_out) {   // the group's rows (stride Tp on the device, T in the caller's arrays)
+            e = hipMemcpy2DAsync(mu_out + (long)g.first * T, sizeof(double) * T, h->d_pmu + (long)g.slot0 * Tp, sizeof(double) * Tp,
+                                 sizeof(double) * T, g.cnt, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess)
+                e = hipMemcpy2DAsync(var_out + (long)g.first * T, sizeof(double) * T, h->d_pvar + (long)g.slot0 * Tp, sizeof(double) * Tp,
+                                     sizeof(double) * T, g.cnt, hipMemcpyDeviceToHost, st);
+            if (e != hipSuccess) { rc = fail(h, GPCC_ERR_HIP, "predictive rows: %s", hipGetErrorString(e)); break; }
+        }
+        if (weights) {   // after the previous group's mixture step, whichever stream ran it
+            if (gi > 0) e = hipStreamWaitEvent(st, h->ev_pmix, 0);
+            if (e == hipSuccess) {
+                gpcc_pred_mix<<<ntT, GPCC_TILE, 0, st>>>(g, pb, h->d_pw, gi == ngroups - 1 ? 1 : 0);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipEventRecord(h->ev_pmix, st);
+            if (e != hipSuccess) { rc = fail(h, GPCC_ERR_HIP, "predictive mixture: %s", hipGetErrorString(e)); break; }
+        }
+    }
+    if (rc) {   // nothing may be left running when the error is returned
+        const std::string msg = h->err;
+        for (int s = 0; s < used; ++s) (void)hipStreamSynchronize(h->str[s]);
+        (void)hipGetLastError();
+        h->err = msg;
+        return rc;
+    }
+    for (int s = 0; s < used; ++s) {
+        HIPCHK(h, hipEventRecord(h->ev_done[s], h->str[s]));
+        HIPCHK(h, hipStreamWaitEvent(ms, h->ev_done[s], 0));
+    }
+    HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
+    if (weights) {
+        HIPCHK(h, hipMemcpyAsync(mix_mu, h->d_pmix + 4 * Tp, sizeof(double) * T, hipMemcpyDeviceToHost, ms));
+        HIPCHK(h, hipMemcpyAsync(mix_var, h->d_pmix + 5 * Tp, sizeof(double) * T, hipMemcpyDeviceToHost, ms));
+    }
+    HIPCHK(h, hipStreamSynchronize(ms));
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------

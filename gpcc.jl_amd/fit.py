@@ -285,6 +285,41 @@ class Predictor:
                 [np.sqrt(np.maximum(d[l * n:(l + 1) * n], 1e-6)) for l in range(L)])      # :301-303
 
 
+class DelayAveragedPredictor:
+    """Light-curve predictions averaged over a posterior of delays: the mixture over the rows (delays[g], alpha[g], rho[g]) with
+    weights[g] of the per-row posterior predictives, all rows in one batched device call (Objective.predict_batch).  delays (G, L),
+    alpha (G, L) and rho (G) are typically the candidate grid and a GridFit's fitted values; weights typically
+    getprobabilities(res.log_evidence) or getprobabilities(res.loglikel).  Call forms, as Predictor's per-band form (:293-307):
+      pred(ttest)    ttest = one array / range  -> (mu per band, sigma per band) at those times in every band
+      pred(ttest)    ttest = list of L arrays   -> the same per-band lists at each band's own times
+    mu = sum p mu_g and sigma = sqrt(max(var, 1e-6)) with var = sum p (var_g + (mu_g - mu)^2), the mixture's mean and variance.
+    There is no joint form: a mixture of Gaussians has no single joint Gaussian to return, so neither a joint covariance nor a test
+    log-likelihood is offered."""
+
+    def __init__(self, objective, delays, alpha, rho, weights):
+        self.obj = objective
+        self.delays = np.atleast_2d(np.asarray(delays, dtype=np.float64))
+        self.alpha = np.atleast_2d(np.asarray(alpha, dtype=np.float64))
+        self.rho = np.atleast_1d(np.asarray(rho, dtype=np.float64))
+        self.weights = np.atleast_1d(np.asarray(weights, dtype=np.float64))
+        G, L = len(self.rho), objective.L
+        if self.delays.shape != (G, L) or self.alpha.shape != (G, L) or self.weights.shape != (G,):
+            raise ValueError("delays and alpha must be (G, L) = (%d, %d) and weights (G,)" % (G, L))
+        if not np.all(np.isfinite(self.weights)) or np.any(self.weights < 0) or not self.weights.sum() > 0:
+            raise ValueError("weights must be finite, >= 0 and not all zero")
+
+    def __call__(self, ttest):
+        L = self.obj.L
+        if isinstance(ttest, (list, tuple)) and len(ttest) == L and all(np.ndim(a) == 1 for a in ttest):
+            bands = [np.asarray(a, dtype=np.float64) for a in ttest]
+        else:
+            bands = [np.asarray(ttest, dtype=np.float64).ravel()] * L
+        _, _, _, _, mu, var = self.obj.predict_batch(self.delays, self.alpha, self.rho, bands, weights=self.weights)
+        off = np.concatenate([[0], np.cumsum([len(b) for b in bands])])
+        return ([mu[off[l]:off[l + 1]] for l in range(L)],
+                [np.sqrt(np.maximum(var[off[l]:off[l + 1]], 1e-6)) for l in range(L)])      # :301-303
+
+
 def gpcc(tarray, yarray, stdarray, *, kernel, delays, iterations, seed=1, numberofrestarts=1, initialrandom=5,
          rhomin=0.1, rhomax, device=0):
     """loglikel, pred, (alpha, postb, rho) = gpcc(tarray, yarray, stdarray; kernel, delays, iterations, ...)

@@ -259,6 +259,28 @@ int gpcc_predict(gpcc_handle_t handle, const double *delays, const double *alpha
                  const int *Ntest, const double *ttest, double *mu_out, double *Sigma_out,
                  double *loglik, int *info);
 
+/* The posterior predictive at M rows (tau, alpha, rho) -- row-major M x L delays and alpha, rho[M], gpcc_loglik_batch's layout -- on one
+ * set of test times shared by every row (Ntest[l] per band, flattened in band order in ttest, 1 <= T = sum Ntest <= 32768, as
+ * gpcc_predict), and its average over the rows.  Per row m: mu_out[m, :] is gpcc_predict's mu_out, kB*' K^-1 (Y - bbar) + Q* mu_b, and
+ * var_out[m, :] the diagonal of its Sigma_out, diag(cB) - diag(kB*' K^-1 kB*) + JITTER (1e-8; src/gpccfixdelay_marginaliseb.jl:275-285;
+ * with marginalise_b == 0 no B term and the fixed-b offsets, src/gpccfixdelay.jl:244-266).  loglik[m] and info[m] are bitwise what
+ * gpcc_loglik_grad_batch returns; where info[m] != 0 row m of mu_out and var_out is NaN and no other row is touched.
+ * Mixture (weights != NULL, M entries): p_m = w_m / sum w, mix_mu = sum p_m mu_m, mix_var = sum p_m (var_m + (mu_m - mix_mu)^2), over
+ * the rows in row order (a running weighted mean and sum of squared deviations); rows with p_m = 0 are skipped, failed or not; a failed
+ * row with p_m > 0 makes mix_mu and mix_var NaN (the call still returns 0).  A negative or non-finite weight, or sum w = 0, returns
+ * GPCC_ERR_ARGUMENT before any device work.  mix_mu and mix_var (T each) are required exactly when weights are given; mu_out and
+ * var_out (M x T each, row-major) may then both be NULL (mixture only: the rows are never copied back); loglik and info are required.
+ * Path: each group runs the gradient's assembly, factorisation, X = L^-1 and w = K^-1 r unchanged, then V = X kB* with fp64 MFMA over
+ * the tiles of kB* generated on the fly (about N^3/3 + N^2 T flops per row on top of the factorisation), reduced to column sums of
+ * squares, and kB*' w.  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Results are
+ * bitwise repeatable and do not depend on the batch, its grouping or the stream / slot options.  Memory: the gradient's buffers, plus,
+ * allocated on the first call with Tp = 128 ceil(T / 128): 12 Tp bytes of test points, 48 Tp bytes of mixture state, 8 M bytes of
+ * weights, and for each of workspace_streams x workspace_slots slots 8 (nt + 2) Tp bytes (nt = Np / 128: the partial sums of squares,
+ * one row of mu and var); they grow with T; a handle that never predicts allocates none of it.  Blocking. */
+int gpcc_predict_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const int *Ntest,
+                       const double *ttest, const double *weights, double *mu_out, double *var_out, double *mix_mu,
+                       double *mix_var, double *loglik, int *info);
+
 /* Posterior of the offsets b (src/gpccfixdelay_marginaliseb.jl:248-252): mu_postb[L], Sigma_postb[L x L]
  * (column-major, symmetrised).  The N x N solves (Sobs + K) \ [Q Y] run on the device as an augmented
  * factorisation; only the final L x L inverse is host arithmetic. */

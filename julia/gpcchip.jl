@@ -123,6 +123,28 @@ function laplace_evidence(h::Handle, delays::Matrix{Float64}, alpha0::Matrix{Flo
     return ll, alpha, rho, logz, cov, info, rounds
 end
 
+"posterior predictive at the columns (τ, α, ρ) of delays, alpha (L×M) and rho[M] on test times shared by all of them (ttest: L
+vectors), and its average over the columns with weights (M, or nothing) -> (mu T×M, var T×M (the diagonal of predict's Σ, JITTER
+included), ll[M], info[M] (bitwise loglik_grad_batch's; NaN columns where info != 0), mix_mu[T], mix_var[T] (nothing without weights)).
+mix_mu = Σ p μ, mix_var = Σ p (var + (μ - mix_mu)²), p = weights / sum(weights); a mixture of Gaussians has no joint covariance."
+function predict_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64}, ttest; weights = nothing)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M) && length(ttest) == h.L
+    Nt = Cint[length(a) for a in ttest]
+    tt = Float64.(reduce(vcat, ttest))
+    T = length(tt)
+    mu, var = Matrix{Float64}(undef, T, M), Matrix{Float64}(undef, T, M)   # column-major T×M == row-major M×T
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    w = weights === nothing ? C_NULL : Float64.(weights)
+    mm, mv = weights === nothing ? (C_NULL, C_NULL) : (Vector{Float64}(undef, T), Vector{Float64}(undef, T))
+    rc = ccall((:gpcc_predict_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, Nt, tt, w, mu, var, mm, mv, ll, info)
+    rc == 0 || error("gpcc_predict_batch: " * lasterror(h.ptr))
+    return mu, var, ll, info, (weights === nothing ? nothing : mm), (weights === nothing ? nothing : mv)
+end
+
 "Drop-in body of objective(α, ρ) (gpccfixdelay_marginaliseb.jl:133-141): throws what the Julia code throws."
 function objective(h::Handle, τ, α, ρ)
     ll, info = loglik_batch(h, reshape(Float64.(τ), :, 1), reshape(Float64.(α), :, 1), [Float64(ρ)])
