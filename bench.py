@@ -17,7 +17,10 @@ Launch: python bench.py [--gpus 1]            or, for N > 1,
         python bench.py --gpus N [--native]                                      (no torchrun: ONE process, multi-device handle,
                                                                                   RCCL all-gather inside libgpcc_hip.so; --native takes
                                                                                   that entry also for --gpus 1: comparable scaling points)
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run measures the headline alone: set-up, warm-up, the timed steps, --dump-outputs, the line.
+--full adds what the headline does not need, after the timed steps: the roofline pass (one more sweep, every launch timed with HIP
+events) and, on one GPU, the CPU baseline (the CPU port timed in a process of its own, about 30 s); "roofline" and "cpu_baseline" are
+null in the line without it.
 """
 import argparse
 import json
@@ -362,7 +365,7 @@ def native_multi(args, ndev):
         mode = {1: "rccl", 2: "host"}.get(obj.get_option("gather_mode"), "?")
         comp_ms, gather_ms, total_ms = obj.multi_stats()     # of the LAST step: where a scaling loss would come from
         roofline = cpu_baseline = None
-        if N_ == 1:     # a SCALE point at N = 1 through this entry is comparable with the BENCH line field by field
+        if N_ == 1 and args.full:     # a SCALE point at N = 1 through this entry is comparable with the BENCH line field by field
             if not args.no_roofline:
                 roofline = roofline_leg(obj, args, L * Nb, L, G, Gtot, elapsed, lambda: obj.loglik_batch(delays, alphas, rhos))
             if not args.no_cpu_baseline:
@@ -381,10 +384,10 @@ def native_multi(args, ndev):
                       "call_ms": round(total_ms, 3)},
         "clock_mhz": gstate["sclk_mhz"], "power_w": gstate["power_w"], "gpu_state": gstate,
         "info_nonzero": int((info != 0).sum()), "posterior_sum": float(p.sum()), "roofline": roofline, "cpu_baseline": cpu_baseline,
-        "entry": "native_multi", "build": build}))
+        "full": args.full, "entry": "native_multi", "build": build}))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -404,8 +407,11 @@ def main():
                          "timing behind `roofline` and the committed rocprofv3 averages all describe the same non-overlapping launches; "
                          "--streams 2 is +0.9 %% on the headline, +5 %% at N = 2048 with 4096 delays (profiles/r03/two_streams_ab.log)")
     ap.add_argument("--slots", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the roofline pass and, on one GPU, "
+                         "the CPU baseline (off by default: a plain run times the steps and prints the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out the roofline pass")
     ap.add_argument("--shared-extra", action="store_true",
                     help="also time the sweep with the shared-prefix mode asserted (reported separately, never as `value`)")
     ap.add_argument("--option", action="append", default=[], help="handle option key=value (gpcc_set_option), repeatable")
@@ -413,9 +419,14 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (log-likelihoods, info, posterior probabilities of "
                          "the whole grid) as DIR/<name>.npy, float64, at most 64 MB (a fixed seeded sample of the grid above that)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def main():
+    args = parse_args()
 
     import torch
     import torch.distributed as dist
@@ -555,14 +566,14 @@ def main():
     value = Gtot * args.steps / elapsed
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         def run_once():
             obj.loglik_batch_device(d_delays, d_alpha, d_rho, out=d_ll, info=d_info)
             torch.cuda.synchronize(dev)
         roofline = roofline_leg(obj, args, N, L, G, Gtot, elapsed, run_once)
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu_baseline = cpu_baseline_leg(args, Nb, L, G, delays, d_ll.cpu().numpy())
 
     if rank == 0:
@@ -580,7 +591,7 @@ def main():
             "clock_mhz": gstate["sclk_mhz"], "power_w": gstate["power_w"], "gpu_state": gstate,
             "info_nonzero": info_bad, "posterior_sum": psum,
             "roofline": roofline, "cpu_baseline": cpu_baseline, "shared_prefix_mode": shared,
-            "entry": "device_pointer", "build": gpcc_amd.build_info(),
+            "full": args.full, "entry": "device_pointer", "build": gpcc_amd.build_info(),
         }
         print(json.dumps(out))
     obj.close()

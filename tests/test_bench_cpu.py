@@ -1,4 +1,5 @@
-"""bench.py --dump-outputs: what the timed path computed, written as float64 .npy files under a size bound."""
+"""bench.py --dump-outputs: what the timed path computed, written as float64 .npy files under a size bound; --full: the legs beside
+the headline (roofline pass, CPU baseline) run only when asked for."""
 import os
 
 import numpy as np
@@ -31,3 +32,10 @@ def test_dump_above_the_bound_keeps_the_same_seeded_sample(tmp_path, monkeypatch
     assert np.array_equal(idx, np.load(tmp_path / "b" / "index.npy")) and len(np.unique(idx)) == len(idx) > 0
     for name, a in arrays.items():
         assert np.array_equal(np.load(tmp_path / "a" / (name + ".npy")), a[idx.astype(np.int64)].astype(np.float64))
+
+
+def test_extra_legs_only_with_full():
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and plain.steps == 3 and plain.warmup == 1
+    full = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert full.full and not full.no_roofline and not full.no_cpu_baseline

@@ -9,7 +9,7 @@ for rep in 1 2; do
 for lib in "" /tmp/libgpcc_poly.so; do
   tag=${lib:+poly}; tag=${tag:-table}
   for args in "--steps 3" "--precision fp32 --steps 3" "--n-per-band 55 --grid 12321 --steps 20" "--n-per-band 75 --bands 2 --grid 12321 --steps 20"; do
-    GPCC_HIP_LIB=$lib python bench.py --no-cpu-baseline $args 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$tag', '$args', '|', d['value'], 'evals/s |', d['ms_per_step'], 'ms/step |', r['kernels_ms'])"
+    GPCC_HIP_LIB=$lib python bench.py --full --no-cpu-baseline $args 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$tag', '$args', '|', d['value'], 'evals/s |', d['ms_per_step'], 'ms/step |', r['kernels_ms'])"
   done
 done
 done
