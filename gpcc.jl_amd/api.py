@@ -135,6 +135,31 @@ def mvnormal_logpdf(mu, Sigma, x, device=0):
     return ll.value
 
 
+def logsumexp_rows(values, p):
+    """log sum_m p_m exp(values_m) as gpcc_heldout_mix forms it: one running, max-shifted log-sum-exp over the rows in row order, rows
+    with p_m = 0 skipped; NaN if a row with p_m > 0 is NaN; one row of weight 1 gives its own value bitwise."""
+    mx, s, nan = -np.inf, 0.0, False
+    for x, pm in zip(np.asarray(values, dtype=np.float64), np.asarray(p, dtype=np.float64)):
+        if pm == 0.0:
+            continue
+        if x != x:
+            nan = True
+            continue
+        lx = float(np.log(pm)) + float(x)
+        if lx == -np.inf:
+            continue
+        if s == 0.0:
+            mx, s = lx, 1.0
+        elif lx <= mx:
+            s += float(np.exp(lx - mx))
+        else:
+            s = s * float(np.exp(mx - lx)) + 1.0
+            mx = lx
+    if nan:
+        return float("nan")
+    return -np.inf if s == 0.0 else mx + float(np.log(s))
+
+
 class Objective:
     """The marginal log-likelihood objective(alpha, rho) of gpccfixdelay, bound to one data set and
     living on one GPU -- or, with devices=[...], replicated on several GPUs of this process (gpcc_create_multi:
@@ -449,6 +474,54 @@ class Objective:
         except GpccError as e:
             _raise_reference_error(e)
         return mu, var, ll, info, mix_mu, mix_var
+
+    def heldout_loglik_batch(self, delays, alpha, rho, ttest, ytest, sigmatest, weights=None, fallback=True):
+        """The held-out log-likelihood of the test set (ttest, ytest, sigmatest: lists of L arrays, shared by every row) at M rows
+        (tau, alpha, rho), and its average over the rows with weights -> (heldout[M], loglik[M], info[M], mix or None, refit_mask[M])
+        (gpcc_heldout_loglik_batch).  Row m is predictTest(ttest, ytest, sigmatest) at that row (marginaliseb.jl:311-343); loglik and
+        info are bitwise loglik_grad_batch's, except info = N + j where the j-th pivot of the test block Sigma_pred + JITTER I +
+        diag(sigmatest^2) failed.  mix = log sum p_m exp(heldout_m), p = weights / sum(weights), zero-weight rows skipped.
+        fallback: rows with info > N are recomputed by the reference's rule, the single-row Predictor form (nearestposdef(Sigma;
+        minimumeigenvalue = 1e-6), retried once; :327-341), and flagged in refit_mask; if one of them has p > 0 the mixture is
+        recomputed here from the final rows with the device's row-order log-sum-exp.  Always fp64; a multi-device handle computes on
+        its first device."""
+        if len(ttest) != self.L or len(ytest) != self.L or len(sigmatest) != self.L:
+            raise AssertionError("length(ttest) == length(ytest) == length(sigmatest) == L")
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        Nt, tt = _flatten(ttest)
+        Ny, yt = _flatten(ytest)
+        Ns, st = _flatten(sigmatest)
+        if not (np.array_equal(Nt, Ny) and np.array_equal(Nt, Ns)):
+            raise ValueError("band lengths differ between ttest, ytest and sigmatest")
+        held = np.empty(M, dtype=np.float64)
+        ll = np.empty(M, dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        w = mix = None
+        if weights is not None:
+            w = _d(np.asarray(weights, dtype=np.float64).ravel())
+            if w.shape != (M,):
+                raise ValueError("weights must have M = %d entries" % M)
+            mix = np.empty(1, dtype=np.float64)
+        try:
+            self._chk(_capi.load().gpcc_heldout_loglik_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _ip(Nt), _dp(tt), _dp(yt),
+                                                             _dp(st), _dp(w) if w is not None else None, _dp(held),
+                                                             _dp(mix) if w is not None else None, _dp(ll), _ip(info)))
+        except GpccError as e:
+            _raise_reference_error(e)
+        refit = np.zeros(M, dtype=bool)
+        if fallback:
+            from .fit import Predictor    # (fit imports this module)
+            for m in np.flatnonzero(info > self.N):
+                try:
+                    held[m] = Predictor(self, delays[m], alpha[m], rho[m])(list(ttest), list(ytest), list(sigmatest))
+                except PosDefException:
+                    continue             # the retry failed too: the row stays NaN
+                refit[m] = True
+        mixv = None
+        if w is not None:
+            p = w / np.sum(w)
+            mixv = logsumexp_rows(held, p) if np.any(refit & (p > 0)) else float(mix[0])
+        return held, ll, info, mixv, refit
 
     def posterior_offsets(self, delays, alpha, rho):
         """(mu_postb, Sigma_postb) of marginaliseb.jl:248-252 (the reference wraps them in MvNormal)."""

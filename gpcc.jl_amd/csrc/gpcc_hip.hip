@@ -5,6 +5,7 @@
 #include "gpcc_grad.hip.h"
 #include "gpcc_hess.hip.h"
 #include "gpcc_pred.hip.h"
+#include "gpcc_heldout.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -201,6 +202,13 @@ struct gpcc_handle_s {
     int *d_ptb = nullptr;
     long pred_slots = 0, pred_tp = 0, pw_cap = 0;
     hipEvent_t ev_pmix = nullptr;   // orders the mixture steps of consecutive groups (on different streams) by row
+    // held-out log-likelihood (gpcc_heldout_loglik_batch): allocated on its first call, for held_slots <= workspace slots -- per slot an
+    // augmented workspace of held_nta tile columns (tiles, inv(L_kk), z, w, logdet, Gram, info); the augmented points (3 x held_nta * 128
+    // doubles + ints), the per-row results (hld_cap), the weights and the mixture state
+    double *d_xtile = nullptr, *d_xpts = nullptr, *d_xhld = nullptr, *d_xw = nullptr, *d_xmix = nullptr, *d_xscr = nullptr;
+    int *d_xband = nullptr, *d_xinfo = nullptr, *d_xscri = nullptr;
+    long held_slots = 0, held_ws = 0, held_nta = 0, hld_cap = 0;
+    hipEvent_t ev_hmix = nullptr;   // orders the mixture steps of consecutive groups by row
     double *d_sep = nullptr, *d_seps = nullptr;     // separable factors of the points, the distance scale (GpccCtx::sep, ::seps)
     int *d_sepflag = nullptr;                       // per-tile-row flags (GpccCtx::sepflag)
     int fp32_refine = 1;                            // option "fp32_refine": 0 = no refinement of the quadratic forms
@@ -473,6 +481,8 @@ static void free_workspace(gpcc_handle_t h)
     h->d_hc = h->d_hm = h->d_hu = h->d_hz = h->d_htab = h->d_htr = nullptr; h->hess_slots = h->hess_ws = 0;
     hipFree(h->d_ptt); hipFree(h->d_ptb); hipFree(h->d_ppart); hipFree(h->d_pmu); hipFree(h->d_pvar); hipFree(h->d_pmix);
     h->d_ptt = h->d_ppart = h->d_pmu = h->d_pvar = h->d_pmix = nullptr; h->d_ptb = nullptr; h->pred_slots = h->pred_tp = 0;
+    hipFree(h->d_xtile); hipFree(h->d_xpts); hipFree(h->d_xband); hipFree(h->d_xinfo);
+    h->d_xtile = h->d_xpts = nullptr; h->d_xband = h->d_xinfo = nullptr; h->held_slots = h->held_ws = h->held_nta = 0;
     h->d_chain_words = nullptr; h->d_ximg = h->d_stepval = nullptr; h->d_chain_trace = nullptr; h->chain_streams = 0;
     h->d_tiles = h->d_linv = h->d_z = h->d_w = h->d_logdet = h->d_quad = h->d_kdiag = h->d_cond = h->d_gpart = nullptr;
     h->d_sep = h->d_seps = nullptr;
@@ -499,7 +509,9 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_par); hipFree(h->d_out); hipFree(h->d_oinfo);
     for (auto &ln : h->lanes) ln.release();
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
+    hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
     if (h->ev_pmix) hipEventDestroy(h->ev_pmix);
+    if (h->ev_hmix) hipEventDestroy(h->ev_hmix);
     hipFree(h->d_ocond); hipFree(h->d_fb_idx); hipFree(h->d_fb_par); hipFree(h->d_fb_out); hipFree(h->d_fb_info);
     if (h->fb) gpcc_destroy(h->fb);
     if (h->main_stream) hipStreamDestroy(h->main_stream);
@@ -653,6 +665,7 @@ extern "C" long gpcc_get_option(gpcc_handle_t h, const char *key)
                (h->precision ? 8L * h->Np + 8L * GPCC_MAXRHS * GPCC_MAXRHS * ((long)h->nt * (h->nt + 1) / 2) + 16L : 0L);
     if (!strcmp(key, "hess_bytes_per_slot")) return hess_bytes_per_slot(h);
     if (!strcmp(key, "hess_slots")) return h->hess_slots;
+    if (!strcmp(key, "heldout_slots")) return h->held_slots;   // (0 until gpcc_heldout_loglik_batch has run)
     if (!strcmp(key, "precision")) return h->precision;
     if (!strcmp(key, "fused_solve")) return h->fused_solve;
     if (!strcmp(key, "fused_solve_min")) return h->fused_solve_min;
@@ -2072,6 +2085,250 @@ extern "C" int gpcc_predict_batch(gpcc_handle_t h, int M, const double *delays, 
         HIPCHK(h, hipMemcpyAsync(mix_mu, h->d_pmix + 4 * Tp, sizeof(double) * T, hipMemcpyDeviceToHost, ms));
         HIPCHK(h, hipMemcpyAsync(mix_var, h->d_pmix + 5 * Tp, sizeof(double) * T, hipMemcpyDeviceToHost, ms));
     }
+    HIPCHK(h, hipStreamSynchronize(ms));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Batched held-out log-likelihood and its delay average (gpcc_heldout_loglik_batch; kernels: gpcc_heldout.hip.h).
+// Each row factorises the augmented system [training | test] of DESIGN.md 4.5 completely in a slot of its own, with the
+// launch-per-step kernels of the gradient's part 1 (so its training loglik and info are the gradient's bits); the held-out value
+// comes from the trailing diagonal and w[test].  The buffers are allocated on the first call (ensure_heldout), for as many slots as
+// fit a quarter of the device's memory (at most every workspace slot), and grow with the test points; a handle that never asks
+// holds none of them.
+// ------------------------------------------------------------------------------------------
+static long heldout_bytes_per_slot(long nta)
+{
+    const long Npa = nta * GPCC_TILE;
+    return (long)sizeof(double) * ((nta * (nta + 1) / 2 + 1) * (long)GPCC_TILE_ELEMS + 2 * Npa + 1 + GPCC_MAXRHS * GPCC_MAXRHS) +
+           (long)sizeof(int);
+}
+
+static int ensure_heldout(gpcc_handle_t h, long nta, long M)
+{
+    const long ws = (long)h->ws_streams * h->ws_slots;
+    if (!(h->held_ws == ws && h->held_nta >= nta && h->d_xtile)) {
+        hipFree(h->d_xtile); hipFree(h->d_xpts); hipFree(h->d_xband); hipFree(h->d_xinfo);
+        h->d_xtile = h->d_xpts = nullptr; h->d_xband = h->d_xinfo = nullptr; h->held_slots = h->held_ws = h->held_nta = 0;
+        const long per = heldout_bytes_per_slot(nta), Npa = nta * GPCC_TILE;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) total_b = (size_t)64 << 30;
+        long slots = (long)(0.25 * (double)total_b / (double)per);
+        if (slots > ws) slots = ws;
+        if (slots < 1) slots = 1;
+        HIPCHK(h, hipMalloc(&h->d_xpts, sizeof(double) * 3 * Npa));
+        HIPCHK(h, hipMalloc(&h->d_xband, sizeof(int) * Npa));
+        for (;;) {
+            hipError_t e = hipMalloc(&h->d_xtile, (size_t)(per - (long)sizeof(int)) * slots);
+            if (e == hipSuccess) e = hipMalloc(&h->d_xinfo, sizeof(int) * slots);
+            if (e == hipSuccess) break;
+            (void)hipGetLastError();
+            hipFree(h->d_xtile); hipFree(h->d_xinfo);
+            h->d_xtile = nullptr; h->d_xinfo = nullptr;
+            if (e != hipErrorOutOfMemory || slots <= 1)
+                return fail(h, GPCC_ERR_HIP, "held-out workspace of %ld slots (%ld bytes each, %ld test tile columns): %s", slots, per,
+                            nta - h->nt, hipGetErrorString(e));
+            slots /= 2;
+        }
+        h->held_slots = slots;
+        h->held_ws = ws;
+        h->held_nta = nta;
+        if (slots < ws) {   // a note, not an error
+            char buf[256];
+            snprintf(buf, sizeof buf, "note: the held-out workspace (%ld bytes per slot) fits %ld of the %ld workspace slots; its groups run "
+                     "through %ld slots (results unchanged)", per, slots, ws, slots);
+            h->err = buf;
+        }
+    }
+    if (M > h->hld_cap) {
+        hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xscr); hipFree(h->d_xscri);
+        h->d_xhld = h->d_xw = h->d_xscr = nullptr; h->d_xscri = nullptr; h->hld_cap = 0;
+        HIPCHK(h, hipMalloc(&h->d_xhld, sizeof(double) * M));
+        HIPCHK(h, hipMalloc(&h->d_xw, sizeof(double) * M));
+        HIPCHK(h, hipMalloc(&h->d_xscr, sizeof(double) * M));
+        HIPCHK(h, hipMalloc(&h->d_xscri, sizeof(int) * M));
+        h->hld_cap = M;
+    }
+    if (!h->d_xmix) HIPCHK(h, hipMalloc(&h->d_xmix, sizeof(double) * 4));
+    if (!h->ev_hmix) HIPCHK(h, hipEventCreateWithFlags(&h->ev_hmix, hipEventDisableTiming));
+    return 0;
+}
+
+// one group: assembly of the augmented systems, the left-looking launch-per-step factorisation over all nta tile columns (the first
+// nt exactly as enqueue_grad_inverse runs them: the training loglik and info of the last training step land in g.out_*; the trailing
+// steps run with ct, whose last step writes into the scratch outputs of gt), and the finish
+static int enqueue_heldout_group(gpcc_handle_t h, const GpccCtx &c, const GpccCtx &ct, const GpccGroup &g, const GpccGroup &gt,
+                                 const GpccHeldBuf &hb, hipStream_t s)
+{
+    const int cnt8 = g.spread ? g.cnt : 8 * ((g.cnt + 7) / 8);
+    launch_assemble(h, c, g, s, false, false);
+    for (int k = 0; k < c.nt; ++k) {
+        const bool train = k < c.nt_fact;
+        if (k > 0) {
+            ProfScope pr(h, GPCC_PROF_PANEL_UPDATE, s);
+            gpcc_panel_update<double, false><<<cnt8 * (c.nt - k), GPCC_GEMM_THREADS, GPCC_GEMM_LDS_BYTES, s>>>(c, g, k, k, 0);
+        }
+        {
+            ProfScope pr(h, GPCC_PROF_DIAG, s);
+            if (train) gpcc_diag_factor<double><<<g.cnt, GPCC_DIAG_THREADS, GPCC_DIAG_LDS_BYTES, s>>>(c, g, k);
+            else gpcc_diag_factor<double><<<g.cnt, GPCC_DIAG_THREADS, GPCC_DIAG_LDS_BYTES, s>>>(ct, gt, k);
+        }
+        if (k < c.nt - 1) {
+            ProfScope pr(h, GPCC_PROF_TRSM, s);
+            gpcc_panel_trsm<double><<<cnt8 * (c.nt - k - 1), GPCC_GEMM_THREADS, GPCC_GEMM_LDS_BYTES, s>>>(c, g, k);
+        }
+    }
+    gpcc_heldout_finish<<<g.cnt, GPCC_HELD_THREADS, 0, s>>>(c, g, hb);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int gpcc_heldout_loglik_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                         const int *Ntest, const double *ttest, const double *ytest, const double *sigmatest,
+                                         const double *weights, double *heldout, double *mix_heldout, double *loglik, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (!delays || !alpha || !rho || !Ntest || !ttest || !ytest || !sigmatest || !loglik || !info)
+        return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    if (weights && !mix_heldout) return fail(h, GPCC_ERR_ARGUMENT, "weights given: mix_heldout is required");
+    if (!weights && mix_heldout) return fail(h, GPCC_ERR_ARGUMENT, "mix_heldout needs weights");
+    if (!weights && !heldout) return fail(h, GPCC_ERR_ARGUMENT, "NULL heldout without weights: nothing to return");
+    if (h->is_multi()) {   // device_ids[0], like the gradient
+        const int rc = gpcc_heldout_loglik_batch(primary(h), M, delays, alpha, rho, Ntest, ttest, ytest, sigmatest, weights, heldout,
+                                                 mix_heldout, loglik, info);
+        return rc ? fail(h, rc, "%s", primary(h)->err.c_str()) : 0;
+    }
+    if (h->precision == GPCC_PRECISION_FP32) {   // always fp64: on the handle's fp64 twin
+        int rc = ensure_fb(h, 0);
+        if (rc) return rc;
+        rc = gpcc_heldout_loglik_batch(h->fb, M, delays, alpha, rho, Ntest, ttest, ytest, sigmatest, weights, heldout, mix_heldout,
+                                       loglik, info);
+        return rc ? fail(h, rc, "fp32 handle, held-out log-likelihood in fp64: %s", h->fb->err.c_str()) : 0;
+    }
+    long T = 0;
+    for (int l = 0; l < h->L; ++l) { if (Ntest[l] < 0) return fail(h, GPCC_ERR_ARGUMENT, "negative Ntest"); T += Ntest[l]; }
+    if (T <= 0 || T > 32768) return fail(h, GPCC_ERR_ARGUMENT, "total number of test points %ld outside [1, 32768]", T);
+    // the normalised weights p_m = w_m / sum w (sums in row order), checked before any device work (gpcc_predict_batch's rules)
+    std::vector<double> p;
+    if (weights) {
+        double sw = 0.0;
+        for (int m = 0; m < M; ++m) {
+            if (!std::isfinite(weights[m]) || weights[m] < 0.0)
+                return fail(h, GPCC_ERR_ARGUMENT, "weight %d = %g: weights must be finite and >= 0", m, weights[m]);
+            sw += weights[m];
+        }
+        if (!(sw > 0.0) || !std::isfinite(sw)) return fail(h, GPCC_ERR_ARGUMENT, "the weights sum to %g: need a finite sum > 0", sw);
+        p.resize(M);
+        for (int m = 0; m < M; ++m) p[m] = weights[m] / sw;
+    }
+    if (M == 0) return 0;
+    GPCC_ON_DEVICE(h, h->device);
+    const int nta = h->nt + (int)((T + GPCC_TILE - 1) / GPCC_TILE);
+    const long Npa = (long)nta * GPCC_TILE;
+    int rc = ensure_workspace(h);
+    if (!rc) rc = ensure_heldout(h, nta, M);
+    if (!rc) rc = ensure_staging(h, M);
+    if (rc) return rc;
+    // the augmented points: the handle's (training) points, padding to Np, the test points, padding to Npa
+    std::vector<double> pts(3 * (size_t)Npa, 0.0);
+    std::vector<int> band(Npa, -1);
+    for (int i = 0; i < h->N; ++i) {
+        pts[i] = h->t_host[i];
+        pts[Npa + i] = h->sig2_host[i];
+        pts[2 * (size_t)Npa + i] = h->resid_host[i];
+        band[i] = h->band_host[i];
+    }
+    {
+        long o = 0;
+        for (int l = 0; l < h->L; ++l)
+            for (int n = 0; n < Ntest[l]; ++n, ++o) {
+                const long i = h->Np + o;
+                pts[i] = ttest[o];
+                pts[Npa + i] = sigmatest[o] * sigmatest[o] + 1e-8;      // Sobs* + JITTER (marginaliseb.jl:69, :317)
+                pts[2 * (size_t)Npa + i] = ytest[o] - h->mean_b[l];     // y* - bbar*: z[test] ends as y* - mu_pred
+                band[i] = l;
+            }
+    }
+    const long ML = (long)M * h->L;
+    double *dd = h->d_par, *da = h->d_par + ML, *dr = h->d_par + 2 * ML;
+    hipStream_t ms = h->main_stream;
+    HIPCHK(h, hipMemcpyAsync(dd, delays, sizeof(double) * ML, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(da, alpha, sizeof(double) * ML, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(dr, rho, sizeof(double) * M, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_xpts, pts.data(), sizeof(double) * pts.size(), hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_xband, band.data(), sizeof(int) * Npa, hipMemcpyHostToDevice, ms));
+    if (weights) HIPCHK(h, hipMemcpyAsync(h->d_xw, p.data(), sizeof(double) * M, hipMemcpyHostToDevice, ms));
+    // the augmented context: slot workspace of nta tile columns; the trailing tiles go through the same kernels (woodbury = 0, the literal
+    // fp64 model -- what an fp64 handle's gradient runs too)
+    const long stride = ((long)nta * (nta + 1) / 2) * GPCC_TILE_ELEMS, slots = h->held_slots;
+    GpccCtx c = make_ctx(h);
+    c.t = h->d_xpts; c.sig2 = h->d_xpts + Npa; c.resid = h->d_xpts + 2 * Npa; c.yv = nullptr; c.band = h->d_xband;
+    c.tiles = h->d_xtile;
+    c.linv = h->d_xtile + stride * slots;
+    c.z = (double *)c.linv + GPCC_TILE_ELEMS * slots;
+    c.w = c.z + Npa * slots;
+    c.logdet = c.w + Npa * slots;
+    c.gram = c.logdet + slots;
+    c.info = h->d_xinfo;
+    c.kdiag = nullptr; c.cond = nullptr; c.gpart = nullptr; c.linv_keep = 0;
+    c.sep = nullptr; c.seps = nullptr; c.sepflag = nullptr; c.fold = 0; c.fold_mixed = 0;
+    c.slot_stride = stride; c.Np = (int)Npa; c.nt = nta; c.nt_fact = h->nt;
+    c.nrhs = 1; c.woodbury = 0; c.share_p = 0;
+    c.store_l = 1;   // L22's diagonal is read by the finish
+    if (!h->mb) for (int l = 0; l < GPCC_MAXL; ++l) c.sigma_b[l] = 0.0;
+    GpccCtx ct = c;
+    ct.nt_fact = nta;   // the trailing steps: the last one reports into the scratch outputs
+    GpccHeldBuf hb;
+    hb.hld = h->d_xhld; hb.mix = h->d_xmix; hb.T = (int)T; hb.N = h->N; hb.off = h->Np;
+    const int cs = (int)(slots < h->ws_slots ? slots : h->ws_slots);
+    int S = h->prof ? 1 : (int)(slots / cs);
+    if (S > h->ws_streams) S = h->ws_streams;
+    const int ngroups = (M + cs - 1) / cs, used = ngroups < S ? ngroups : S;
+    HIPCHK(h, hipEventRecord(h->ev_start, ms));
+    for (int s = 0; s < used; ++s) HIPCHK(h, hipStreamWaitEvent(h->str[s], h->ev_start, 0));
+    for (int gi = 0; gi < ngroups && !rc; ++gi) {
+        const int s = gi % S;
+        hipStream_t st = h->str[s];
+        GpccGroup g0;
+        g0.delays = dd; g0.alpha = da; g0.rho = dr;
+        g0.out_loglik = h->d_out; g0.out_info = h->d_oinfo; g0.out_cond = nullptr;
+        g0.first = gi * cs;
+        g0.slot0 = s * cs;
+        g0.cnt = (M - g0.first < cs) ? (M - g0.first) : cs;
+        g0.spread = 0;
+        const GpccGroup g = grad_group(g0);
+        GpccGroup gt = g;
+        gt.out_loglik = h->d_xscr; gt.out_info = h->d_xscri;
+        rc = enqueue_heldout_group(h, c, ct, g, gt, hb, st);
+        if (rc) break;
+        if (weights) {   // after the previous group's mixture step, whichever stream ran it
+            hipError_t e = hipSuccess;
+            if (gi > 0) e = hipStreamWaitEvent(st, h->ev_hmix, 0);
+            if (e == hipSuccess) {
+                gpcc_heldout_mix<<<1, 64, 0, st>>>(g, hb, h->d_xw, gi == 0 ? 1 : 0, gi == ngroups - 1 ? 1 : 0);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipEventRecord(h->ev_hmix, st);
+            if (e != hipSuccess) { rc = fail(h, GPCC_ERR_HIP, "held-out mixture: %s", hipGetErrorString(e)); break; }
+        }
+    }
+    if (rc) {   // nothing may be left running when the error is returned
+        const std::string msg = h->err;
+        for (int s = 0; s < used; ++s) (void)hipStreamSynchronize(h->str[s]);
+        (void)hipGetLastError();
+        h->err = msg;
+        return rc;
+    }
+    for (int s = 0; s < used; ++s) {
+        HIPCHK(h, hipEventRecord(h->ev_done[s], h->str[s]));
+        HIPCHK(h, hipStreamWaitEvent(ms, h->ev_done[s], 0));
+    }
+    HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
+    if (heldout) HIPCHK(h, hipMemcpyAsync(heldout, h->d_xhld, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
+    if (weights) HIPCHK(h, hipMemcpyAsync(mix_heldout, h->d_xmix + 3, sizeof(double), hipMemcpyDeviceToHost, ms));
     HIPCHK(h, hipStreamSynchronize(ms));
     return 0;
 }

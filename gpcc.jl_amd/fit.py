@@ -16,7 +16,7 @@ a + (b - a) * logistic(x), the package's documented purpose; `safewrapper` is ta
 import numpy as np
 
 from . import laplace
-from .api import Objective, PosDefException, mvnormal_logpdf
+from .api import Objective, PosDefException, getprobabilities, mvnormal_logpdf
 from .neldermead import BatchedNelderMead
 
 
@@ -293,8 +293,8 @@ class DelayAveragedPredictor:
       pred(ttest)    ttest = one array / range  -> (mu per band, sigma per band) at those times in every band
       pred(ttest)    ttest = list of L arrays   -> the same per-band lists at each band's own times
     mu = sum p mu_g and sigma = sqrt(max(var, 1e-6)) with var = sum p (var_g + (mu_g - mu)^2), the mixture's mean and variance.
-    There is no joint form: a mixture of Gaussians has no single joint Gaussian to return, so neither a joint covariance nor a test
-    log-likelihood is offered."""
+    There is no joint form: a mixture of Gaussians has no single joint Gaussian to return.  Its held-out density is still well
+    defined: loglik(ttest, ytest, sigmatest) = log sum_g p_g N(ytest; mu_g, Sigma_g) (Objective.heldout_loglik_batch)."""
 
     def __init__(self, objective, delays, alpha, rho, weights):
         self.obj = objective
@@ -319,6 +319,11 @@ class DelayAveragedPredictor:
         return ([mu[off[l]:off[l + 1]] for l in range(L)],
                 [np.sqrt(np.maximum(var[off[l]:off[l + 1]], 1e-6)) for l in range(L)])      # :301-303
 
+    def loglik(self, ttest, ytest, sigmatest):
+        """The mixture's held-out log density log sum_g p_g N(ytest; mu_g, Sigma_g + diag(sigmatest^2)) of the test set (lists of L
+        arrays), every row scored as Predictor(ttest, ytest, sigmatest) scores it (marginaliseb.jl:311-343)."""
+        return self.obj.heldout_loglik_batch(self.delays, self.alpha, self.rho, ttest, ytest, sigmatest, weights=self.weights)[3]
+
 
 def gpcc(tarray, yarray, stdarray, *, kernel, delays, iterations, seed=1, numberofrestarts=1, initialrandom=5,
          rhomin=0.1, rhomax, device=0):
@@ -341,3 +346,116 @@ def singlegp(tobs, yobs, sigmaobs, *, kernel, iterations, seed=1, numberofrestar
     """src/util.jl:95-99: one band, delay [0.0] -- gpccfixdelay([tobs], [yobs], [sigmaobs]; tau = [0.0], ...)."""
     return gpcc([tobs], [yobs], [sigmaobs], kernel=kernel, delays=[0.0], iterations=iterations, seed=seed,
                 numberofrestarts=numberofrestarts, initialrandom=initialrandom, rhomin=rhomin, rhomax=rhomax, device=device)
+
+
+# ------------------------------------------------------------------------------------------
+# Cross-validation (src/UNUSED/performcv.jl)
+# ------------------------------------------------------------------------------------------
+def cvindices(Nl, numberoffolds, seed):
+    """The folds of performcv.jl:59: per band b (1-based) a partition of range(Nl[b-1]) into `numberoffolds` test folds (sorted index
+    arrays) whose sizes differ by at most 1, drawn from numpy.random.default_rng(seed + b) -- the reference's `seedcv + b`.  A band with
+    fewer points than folds leaves some folds empty.  MiscUtil's CVindices and Julia's random stream are not available here, so these
+    folds are this project's own (as the random starts of gpcc_grid_loglik are), not the reference's."""
+    F = int(numberoffolds)
+    if F < 2:
+        raise ValueError("numberoffolds must be >= 2, got %d" % F)
+    out = []
+    for b, n in enumerate(Nl, start=1):
+        perm = np.random.default_rng(int(seed) + b).permutation(int(n))
+        out.append([np.sort(f) for f in np.array_split(perm, F)])
+    return out
+
+
+def _split(tobs, yobs, sobs, folds, f):
+    """(train, test) of fold f: each a triple of per-band lists."""
+    L = len(tobs)
+    tr, te = ([], [], []), ([], [], [])
+    for b in range(L):
+        n = len(tobs[b])
+        test = folds[b][f]
+        train = np.setdiff1d(np.arange(n), test)
+        for k, arr in enumerate((tobs, yobs, sobs)):
+            a = np.asarray(arr[b], dtype=np.float64)
+            tr[k].append(a[train])
+            te[k].append(a[test])
+    return tr, te
+
+
+def _check_folds(tobs, yobs, sobs, folds, F):
+    for b in range(len(tobs)):
+        if not len(tobs[b]) == len(yobs[b]) == len(sobs[b]):
+            raise AssertionError("length(tobs[i]) == length(yobs[i]) == length(σobs[i])")
+        for f in range(F):
+            ntrain = len(tobs[b]) - len(folds[b][f])
+            if ntrain < 2:
+                raise ValueError("fold %d leaves band %d with %d training point(s): the marginalised offset needs at least 2 per band "
+                                 "(sample variance)" % (f + 1, b + 1, ntrain))
+    for f in range(F):
+        if sum(len(folds[b][f]) for b in range(len(tobs))) == 0:
+            raise ValueError("fold %d has no test points in any band" % (f + 1))
+
+
+def performcv(tobs, yobs, σobs, *, delays, kernel, iterations=1, seedcv=1, numberofrestarts=1, initialrandom=1, numberoffolds=5,
+              rhomin=0.1, rhomax=20.0, device=0):
+    """fitness[F] = performcv(tobs, yobs, σobs; delays, kernel, ...) -- src/UNUSED/performcv.jl with its defaults: per fold, gpcc() on
+    the training split (seed = seedcv), then the Predictor's test log-likelihood of the held-out split.  Folds: cvindices(.., seedcv)."""
+    assert len(tobs) == len(yobs) == len(σobs)
+    F = int(numberoffolds)
+    folds = cvindices([len(a) for a in tobs], F, seedcv)
+    _check_folds(tobs, yobs, σobs, folds, F)
+    fitness = np.zeros(F)
+    for f in range(F):
+        (ttr, ytr, str_), (tte, yte, ste) = _split(tobs, yobs, σobs, folds, f)
+        _, pred, _ = gpcc(ttr, ytr, str_, kernel=kernel, delays=delays, numberofrestarts=numberofrestarts, initialrandom=initialrandom,
+                          iterations=iterations, seed=seedcv, rhomin=rhomin, rhomax=rhomax, device=device)
+        fitness[f] = pred(tte, yte, ste)
+        pred.obj.close()
+    return fitness
+
+
+class CVGrid:
+    """Result of performcv_grid: heldout[F, G] and info[F, G] (Objective.heldout_loglik_batch per fold and delay), fits[F] (the folds'
+    GridFits), weights[F, G] (each fold's own delay posterior), mix[F] (the delay-averaged held-out score per fold), cv_score[G] =
+    heldout.sum(0) and probabilities = getprobabilities(cv_score)."""
+
+    def __init__(self, heldout, info, fits, weights, mix, refit):
+        self.heldout, self.info, self.fits, self.weights, self.mix, self.refit = heldout, info, fits, weights, mix, refit
+        self.cv_score = heldout.sum(0)
+        ok = np.isfinite(self.cv_score)
+        self.probabilities = getprobabilities(np.where(ok, self.cv_score, -np.inf)) if ok.any() else np.full_like(self.cv_score, np.nan)
+
+
+def performcv_grid(tobs, yobs, σobs, *, candidatedelays, kernel, iterations=1, seedcv=1, numberofrestarts=1, initialrandom=1,
+                   numberoffolds=5, rhomin=0.1, rhomax=20.0, evidence=None, device=0):
+    """performcv over a whole grid of candidate delays (G, L): per fold ONE Objective on the training split, ONE gpcc_grid fit over all
+    G delays (seed = seedcv, as performcv's gpcc calls) and ONE heldout_loglik_batch over the G rows, weighted by the fold's own delay
+    posterior (getprobabilities(loglikel), or of log_evidence with evidence="laplace") -> CVGrid.  heldout[:, g] is what performcv
+    returns at delay g.  Compare kernels by performcv_grid(...).mix.sum()."""
+    cand = np.ascontiguousarray(np.atleast_2d(candidatedelays), dtype=np.float64)
+    G, L = cand.shape
+    assert L == len(tobs) == len(yobs) == len(σobs)
+    F = int(numberoffolds)
+    folds = cvindices([len(a) for a in tobs], F, seedcv)
+    _check_folds(tobs, yobs, σobs, folds, F)
+    held = np.empty((F, G))
+    info = np.zeros((F, G), dtype=np.int32)
+    wts = np.empty((F, G))
+    mix = np.empty(F)
+    refit = np.zeros((F, G), dtype=bool)
+    fits = []
+    for f in range(F):
+        (ttr, ytr, str_), (tte, yte, ste) = _split(tobs, yobs, σobs, folds, f)
+        with Objective(ttr, ytr, str_, kernel, marginalise_b=True, device=device) as obj:
+            res = gpcc_grid(ttr, ytr, str_, kernel=kernel, candidatedelays=cand, iterations=iterations, seed=seedcv,
+                            numberofrestarts=numberofrestarts, initialrandom=initialrandom, rhomin=rhomin, rhomax=rhomax, objective=obj,
+                            evidence=evidence)
+            score = res.log_evidence if evidence == "laplace" else res.loglikel
+            score = np.where(np.isfinite(score), score, -np.inf)
+            w = getprobabilities(score)
+            a = np.where(np.isfinite(res.alpha), res.alpha, 1.0)   # (a delay without a fit: a placeholder row of weight 0)
+            r = np.where(np.isfinite(res.rho), res.rho, 1.0)
+            held[f], _, info[f], mix[f], refit[f] = obj.heldout_loglik_batch(cand, a, r, tte, yte, ste, weights=w)
+            held[f][~(np.all(np.isfinite(res.alpha), axis=1) & np.isfinite(res.rho))] = np.nan
+            wts[f] = w
+            fits.append(res)
+    return CVGrid(held, info, fits, wts, mix, refit)

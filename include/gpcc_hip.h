@@ -156,7 +156,8 @@ int gpcc_multi_stats(gpcc_handle_t handle, double *compute_ms, double *gather_ms
  *                                     estimates 0; 0 = fp32 tiles on the launch-per-step path ("fp32_chain_count": evaluations so far)
  *
  * Read-only keys of gpcc_get_option: "N", "Np", "precision", "bytes_per_slot", "hess_bytes_per_slot" / "hess_slots" (the Hessian's
- * memory per slot and the slots it holds, 0 before its first call: gpcc_loglik_hess_batch), "share_tiles", "n_devices", "gather_mode",
+ * memory per slot and the slots it holds, 0 before its first call: gpcc_loglik_hess_batch), "heldout_slots" (the slots of the held-out
+ * workspace, 0 before the first gpcc_heldout_loglik_batch), "share_tiles", "n_devices", "gather_mode",
  * "gather_width", "small_n_max" (383), "small_n_active", "small_n_count", "chain_count" (evaluations that took the persistent
  * launch so far), "chain_last_grid" (workgroups of the last one), "fp32_guard_count", "fp32_chain_count", "workspace_streams" / "workspace_slots" (what the workspace really holds: smaller than "streams" /
  * "slots_per_stream" only if the device's memory was short when it was allocated -- then gpcc_last_error carries a note; the
@@ -280,6 +281,34 @@ int gpcc_predict(gpcc_handle_t handle, const double *delays, const double *alpha
 int gpcc_predict_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const int *Ntest,
                        const double *ttest, const double *weights, double *mu_out, double *var_out, double *mix_mu,
                        double *mix_var, double *loglik, int *info);
+
+/* The held-out (test) log-likelihood at M rows (tau, alpha, rho) -- gpcc_predict_batch's row layout -- on one test set shared by every
+ * row (Ntest[l] points per band, flattened in band order in ttest, ytest and sigmatest; 1 <= T = sum Ntest <= 32768; Ntest[l] = 0
+ * allowed), and its average over the rows.  Per row m: heldout[m] is predictTest(ttest, ytest, sigmatest) of
+ * src/gpccfixdelay_marginaliseb.jl:311-325, logpdf(MvNormal(mu_pred, Sigma_pred + JITTER I + diag(sigmatest^2)), ytest) with
+ * JITTER = 1e-8 and gpcc_predict's mu_pred and Sigma_pred (with marginalise_b == 0 the fixed-b model, src/gpccfixdelay.jl).  loglik[m]
+ * and info[m]: the training log-likelihood, bitwise what gpcc_loglik_grad_batch returns, and
+ *   info 0: success;  1 .. N (or < 0): the training matrix failed, as gpcc_loglik_batch reports it -- heldout[m] NaN;
+ *   N + j (1 <= j <= T): the j-th pivot of the test block Sigma_pred + JITTER I + diag(sigmatest^2) is not positive (the case the
+ *   reference catches with PosDefException at :327-341; its nearestposdef retry is host work, left to the caller) -- heldout[m] NaN,
+ *   loglik[m] valid.  A failed row changes no other row.
+ * Mixture (weights != NULL, M entries): p_m = w_m / sum w, mix_heldout = log sum_m p_m exp(heldout_m), a running max-shifted
+ * log-sum-exp over the rows in row order (one row of weight 1 returns its own bits); rows with p_m = 0 are skipped, failed or not; a
+ * failed row with p_m > 0 makes mix_heldout NaN (the call still returns 0).  A negative or non-finite weight, or sum w = 0, returns
+ * GPCC_ERR_ARGUMENT before any device work.  mix_heldout is required exactly when weights are given; heldout may then be NULL
+ * (mixture only: no row is copied back); loglik and info are required.
+ * Path: each row factorises the augmented system [training | test] (the test points from the next tile boundary on,
+ * with sigma*^2 + JITTER on their diagonal and y* - bbar* as their right-hand side) completely, with the launch-per-step tile kernels
+ * of the gradient's factorisation; the trailing diagonal and the whitened test residual give the held-out value.
+ * Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Results are bitwise repeatable and
+ * do not depend on the batch, its grouping or the stream / slot options.  Memory: allocated on the first call and grown with T, an
+ * augmented workspace of nta (nta + 1) / 2 tiles per slot (nta = Np / 128 + ceil(T / 128); about 74 MB at N = 3277, T = 819) for as
+ * many slots as fit a quarter of the device's memory (at most workspace_streams x workspace_slots; fewer: smaller groups, same
+ * results, a note in gpcc_last_error), 28 (Np + 128 ceil(T / 128)) bytes of points and 28 M bytes of per-row state; a handle that
+ * never calls this allocates none of it.  A size whose single slot does not fit returns GPCC_ERR_HIP with a message.  Blocking. */
+int gpcc_heldout_loglik_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const int *Ntest,
+                              const double *ttest, const double *ytest, const double *sigmatest, const double *weights,
+                              double *heldout, double *mix_heldout, double *loglik, int *info);
 
 /* Posterior of the offsets b (src/gpccfixdelay_marginaliseb.jl:248-252): mu_postb[L], Sigma_postb[L x L]
  * (column-major, symmetrised).  The N x N solves (Sobs + K) \ [Q Y] run on the device as an augmented

@@ -145,6 +145,29 @@ function predict_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64
     return mu, var, ll, info, (weights === nothing ? nothing : mm), (weights === nothing ? nothing : mv)
 end
 
+"held-out log-likelihood of the test set (ttest, ytest, σtest: L vectors each, shared by every column) at the columns (τ, α, ρ) of
+delays, alpha (L×M) and rho[M], and its average over the columns with weights (M, or nothing) -> (heldout[M] (predictTest(ttest, ytest,
+σtest), marginaliseb.jl:311-325), ll[M] (bitwise loglik_grad_batch's), info[M] (N + j: the j-th pivot of the test block failed; heldout
+NaN, ll valid), mix (log Σ p exp(heldout), p = weights / sum(weights); nothing without weights)).  The nearestposdef retry of :327-341
+is left to the caller (rows with info > N)."
+function heldout_loglik_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64}, ttest, ytest, σtest;
+                              weights = nothing)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M) && length(ttest) == length(ytest) == length(σtest) == h.L
+    @assert all(length.(ttest) .== length.(ytest) .== length.(σtest))
+    Nt = Cint[length(a) for a in ttest]
+    tt, yt, st = Float64.(reduce(vcat, ttest)), Float64.(reduce(vcat, ytest)), Float64.(reduce(vcat, σtest))
+    held, ll, info = Vector{Float64}(undef, M), Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    w = weights === nothing ? C_NULL : Float64.(weights)
+    mix = weights === nothing ? C_NULL : Vector{Float64}(undef, 1)
+    rc = ccall((:gpcc_heldout_loglik_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, Nt, tt, yt, st, w, held, mix, ll, info)
+    rc == 0 || error("gpcc_heldout_loglik_batch: " * lasterror(h.ptr))
+    return held, ll, info, (weights === nothing ? nothing : mix[1])
+end
+
 "Drop-in body of objective(α, ρ) (gpccfixdelay_marginaliseb.jl:133-141): throws what the Julia code throws."
 function objective(h::Handle, τ, α, ρ)
     ll, info = loglik_batch(h, reshape(Float64.(τ), :, 1), reshape(Float64.(α), :, 1), [Float64(ρ)])
