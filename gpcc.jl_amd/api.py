@@ -523,6 +523,69 @@ class Objective:
             mixv = logsumexp_rows(held, p) if np.any(refit & (p > 0)) else float(mix[0])
         return held, ll, info, mixv, refit
 
+    def sample_batch(self, delays, alpha, rho, ttest, S, seed, weights=None, sigmatest=None, return_noise=False, fallback=True):
+        """Joint posterior draws of the light curves at M rows (tau, alpha, rho) on the test times ttest (a list of L arrays, shared by
+        every row) -> (draws, draw_row, loglik[M], info[M]) and, with return_noise, zeta (gpcc_sample_batch).  A draw of row m is
+        mu_pred + chol(Sigma_pred + JITTER I + diag(sigmatest^2)) zeta with zeta ~ N(0, I_T) (marginaliseb.jl:259-289; sigmatest None:
+        the latent curve, else a replicated observation).  Without weights: draws (M * S, T), draw s of row m at row m * S + s, draw_row
+        its row.  With weights (M): S draws of the mixture, draw_row[s] the row each one used (rows without a draw: loglik NaN, info
+        GPCC_SAMPLE_NOT_DRAWN = -14).  loglik and info of a drawn row are bitwise heldout_loglik_batch's (info = N + j: the j-th pivot
+        of the test block failed).  seed: Philox4x64-10 key (gpcc_amd.rng mirrors it).  fallback: the draws of rows with info > N are
+        redrawn here with the same zeta -- Objective.predict, nearestposdef(Sigma; minimumeigenvalue = 1e-6) (:327-341), a numpy
+        Cholesky --; such rows keep info = N + j with finite draws (that is their flag), and stay NaN if that fails too.  zeta of the
+        fallback: the device's with return_noise, else gpcc_amd.rng's (the same normals within 1e-15).  Always fp64; a multi-device
+        handle computes on its first device."""
+        if len(ttest) != self.L:
+            raise AssertionError("length(ttest) == L")
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        Nt, tt = _flatten(ttest)
+        T = int(Nt.sum())
+        S = int(S)
+        st = None
+        if sigmatest is not None:
+            if len(sigmatest) != self.L:
+                raise AssertionError("length(sigmatest) == L")
+            Ns, st = _flatten(sigmatest)
+            if not np.array_equal(Nt, Ns):
+                raise ValueError("band lengths differ between ttest and sigmatest")
+        w = None
+        if weights is not None:
+            w = _d(np.asarray(weights, dtype=np.float64).ravel())
+            if w.shape != (M,):
+                raise ValueError("weights must have M = %d entries" % M)
+        D = S if w is not None else M * S
+        draws = np.empty((max(D, 0), T), dtype=np.float64)
+        rows = np.empty(max(D, 0), dtype=np.int32)
+        zeta = np.empty((max(D, 0), T), dtype=np.float64) if return_noise else None
+        ll = np.empty(M, dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        try:
+            self._chk(_capi.load().gpcc_sample_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _ip(Nt), _dp(tt),
+                                                     _dp(st) if st is not None else None, _dp(w) if w is not None else None, S,
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, _dp(draws), _ip(rows),
+                                                     _dp(zeta) if zeta is not None else None, _dp(ll), _ip(info)))
+        except GpccError as e:
+            _raise_reference_error(e)
+        if fallback:
+            from . import rng
+            from .fit import nearestposdef    # (fit imports this module)
+            for m in np.flatnonzero(info > self.N):
+                sel = np.flatnonzero(rows == m)
+                mu, Sig = self.predict(delays[m], alpha[m], rho[m], list(ttest))
+                if st is not None:
+                    Sig = Sig + np.diag(st ** 2)
+                try:
+                    Lc = np.linalg.cholesky(nearestposdef(Sig, minimumeigenvalue=1e-6))
+                except np.linalg.LinAlgError:
+                    continue             # the row stays NaN
+                if zeta is not None:
+                    z = zeta[sel]
+                else:
+                    z = rng.normals(seed, T, sel if w is not None else sel - m * S, rng.MIXROW if w is not None else m)
+                draws[sel] = mu[None, :] + z @ Lc.T
+        out = (draws, rows, ll, info)
+        return out + (zeta,) if return_noise else out
+
     def posterior_offsets(self, delays, alpha, rho):
         """(mu_postb, Sigma_postb) of marginaliseb.jl:248-252 (the reference wraps them in MvNormal)."""
         delays, alpha = _d(delays), _d(alpha)

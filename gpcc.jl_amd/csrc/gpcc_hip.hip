@@ -6,6 +6,7 @@
 #include "gpcc_hess.hip.h"
 #include "gpcc_pred.hip.h"
 #include "gpcc_heldout.hip.h"
+#include "gpcc_sample.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -209,6 +210,11 @@ struct gpcc_handle_s {
     int *d_xband = nullptr, *d_xinfo = nullptr, *d_xscri = nullptr;
     long held_slots = 0, held_ws = 0, held_nta = 0, hld_cap = 0;
     hipEvent_t ev_hmix = nullptr;   // orders the mixture steps of consecutive groups by row
+    // joint draws (gpcc_sample_batch): the held-out workspace above, plus the per-slot means (smean_cap doubles), the draws and their
+    // normals (sdraw_cap / szeta_cap doubles), the draw lists (slist_cap ints) and their offsets (soff_cap ints); allocated on first use
+    double *d_smean = nullptr, *d_sdraw = nullptr, *d_szeta = nullptr;
+    int *d_slist = nullptr, *d_soff = nullptr;
+    long smean_cap = 0, sdraw_cap = 0, szeta_cap = 0, slist_cap = 0, soff_cap = 0;
     double *d_sep = nullptr, *d_seps = nullptr;     // separable factors of the points, the distance scale (GpccCtx::sep, ::seps)
     int *d_sepflag = nullptr;                       // per-tile-row flags (GpccCtx::sepflag)
     int fp32_refine = 1;                            // option "fp32_refine": 0 = no refinement of the quadratic forms
@@ -510,6 +516,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     for (auto &ln : h->lanes) ln.release();
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
     hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
+    hipFree(h->d_smean); hipFree(h->d_sdraw); hipFree(h->d_szeta); hipFree(h->d_slist); hipFree(h->d_soff);
     if (h->ev_pmix) hipEventDestroy(h->ev_pmix);
     if (h->ev_hmix) hipEventDestroy(h->ev_hmix);
     hipFree(h->d_ocond); hipFree(h->d_fb_idx); hipFree(h->d_fb_par); hipFree(h->d_fb_out); hipFree(h->d_fb_info);
@@ -2154,6 +2161,55 @@ static int ensure_heldout(gpcc_handle_t h, long nta, long M)
     return 0;
 }
 
+// the augmented points of the held-out system: the handle's (training) points, padding to Np, the test points, padding to Npa.
+// ytest == NULL: test residual 0 (gpcc_sample_batch); sigmatest == NULL: test noise 0, i.e. JITTER alone on the diagonal.
+static void heldout_points(gpcc_handle_t h, long Npa, const int *Ntest, const double *ttest, const double *ytest, const double *sigmatest,
+                           std::vector<double> &pts, std::vector<int> &band)
+{
+    pts.assign(3 * (size_t)Npa, 0.0);
+    band.assign(Npa, -1);
+    for (int i = 0; i < h->N; ++i) {
+        pts[i] = h->t_host[i];
+        pts[Npa + i] = h->sig2_host[i];
+        pts[2 * (size_t)Npa + i] = h->resid_host[i];
+        band[i] = h->band_host[i];
+    }
+    long o = 0;
+    for (int l = 0; l < h->L; ++l)
+        for (int n = 0; n < Ntest[l]; ++n, ++o) {
+            const long i = h->Np + o;
+            const double st = sigmatest ? sigmatest[o] : 0.0;
+            pts[i] = ttest[o];
+            pts[Npa + i] = st * st + 1e-8;                                        // Sobs* + JITTER (marginaliseb.jl:69, :317)
+            pts[2 * (size_t)Npa + i] = ytest ? ytest[o] - h->mean_b[l] : 0.0;     // y* - bbar*: z[test] ends as y* - mu_pred
+            band[i] = l;
+        }
+}
+
+// the augmented context: slot workspace of nta tile columns; the trailing tiles go through the same kernels (woodbury = 0, the literal
+// fp64 model -- what an fp64 handle's gradient runs too)
+static GpccCtx heldout_ctx(gpcc_handle_t h, int nta)
+{
+    const long Npa = (long)nta * GPCC_TILE;
+    const long stride = ((long)nta * (nta + 1) / 2) * GPCC_TILE_ELEMS, slots = h->held_slots;
+    GpccCtx c = make_ctx(h);
+    c.t = h->d_xpts; c.sig2 = h->d_xpts + Npa; c.resid = h->d_xpts + 2 * Npa; c.yv = nullptr; c.band = h->d_xband;
+    c.tiles = h->d_xtile;
+    c.linv = h->d_xtile + stride * slots;
+    c.z = (double *)c.linv + GPCC_TILE_ELEMS * slots;
+    c.w = c.z + Npa * slots;
+    c.logdet = c.w + Npa * slots;
+    c.gram = c.logdet + slots;
+    c.info = h->d_xinfo;
+    c.kdiag = nullptr; c.cond = nullptr; c.gpart = nullptr; c.linv_keep = 0;
+    c.sep = nullptr; c.seps = nullptr; c.sepflag = nullptr; c.fold = 0; c.fold_mixed = 0;
+    c.slot_stride = stride; c.Np = (int)Npa; c.nt = nta; c.nt_fact = h->nt;
+    c.nrhs = 1; c.woodbury = 0; c.share_p = 0;
+    c.store_l = 1;   // L22's diagonal is read by the finish (and L22 by gpcc_sample_tiles)
+    if (!h->mb) for (int l = 0; l < GPCC_MAXL; ++l) c.sigma_b[l] = 0.0;
+    return c;
+}
+
 // one group: assembly of the augmented systems, the left-looking launch-per-step factorisation over all nta tile columns (the first
 // nt exactly as enqueue_grad_inverse runs them: the training loglik and info of the last training step land in g.out_*; the trailing
 // steps run with ct, whose last step writes into the scratch outputs of gt), and the finish
@@ -2231,26 +2287,9 @@ extern "C" int gpcc_heldout_loglik_batch(gpcc_handle_t h, int M, const double *d
     if (!rc) rc = ensure_heldout(h, nta, M);
     if (!rc) rc = ensure_staging(h, M);
     if (rc) return rc;
-    // the augmented points: the handle's (training) points, padding to Np, the test points, padding to Npa
-    std::vector<double> pts(3 * (size_t)Npa, 0.0);
-    std::vector<int> band(Npa, -1);
-    for (int i = 0; i < h->N; ++i) {
-        pts[i] = h->t_host[i];
-        pts[Npa + i] = h->sig2_host[i];
-        pts[2 * (size_t)Npa + i] = h->resid_host[i];
-        band[i] = h->band_host[i];
-    }
-    {
-        long o = 0;
-        for (int l = 0; l < h->L; ++l)
-            for (int n = 0; n < Ntest[l]; ++n, ++o) {
-                const long i = h->Np + o;
-                pts[i] = ttest[o];
-                pts[Npa + i] = sigmatest[o] * sigmatest[o] + 1e-8;      // Sobs* + JITTER (marginaliseb.jl:69, :317)
-                pts[2 * (size_t)Npa + i] = ytest[o] - h->mean_b[l];     // y* - bbar*: z[test] ends as y* - mu_pred
-                band[i] = l;
-            }
-    }
+    std::vector<double> pts;
+    std::vector<int> band;
+    heldout_points(h, Npa, Ntest, ttest, ytest, sigmatest, pts, band);
     const long ML = (long)M * h->L;
     double *dd = h->d_par, *da = h->d_par + ML, *dr = h->d_par + 2 * ML;
     hipStream_t ms = h->main_stream;
@@ -2260,24 +2299,8 @@ extern "C" int gpcc_heldout_loglik_batch(gpcc_handle_t h, int M, const double *d
     HIPCHK(h, hipMemcpyAsync(h->d_xpts, pts.data(), sizeof(double) * pts.size(), hipMemcpyHostToDevice, ms));
     HIPCHK(h, hipMemcpyAsync(h->d_xband, band.data(), sizeof(int) * Npa, hipMemcpyHostToDevice, ms));
     if (weights) HIPCHK(h, hipMemcpyAsync(h->d_xw, p.data(), sizeof(double) * M, hipMemcpyHostToDevice, ms));
-    // the augmented context: slot workspace of nta tile columns; the trailing tiles go through the same kernels (woodbury = 0, the literal
-    // fp64 model -- what an fp64 handle's gradient runs too)
-    const long stride = ((long)nta * (nta + 1) / 2) * GPCC_TILE_ELEMS, slots = h->held_slots;
-    GpccCtx c = make_ctx(h);
-    c.t = h->d_xpts; c.sig2 = h->d_xpts + Npa; c.resid = h->d_xpts + 2 * Npa; c.yv = nullptr; c.band = h->d_xband;
-    c.tiles = h->d_xtile;
-    c.linv = h->d_xtile + stride * slots;
-    c.z = (double *)c.linv + GPCC_TILE_ELEMS * slots;
-    c.w = c.z + Npa * slots;
-    c.logdet = c.w + Npa * slots;
-    c.gram = c.logdet + slots;
-    c.info = h->d_xinfo;
-    c.kdiag = nullptr; c.cond = nullptr; c.gpart = nullptr; c.linv_keep = 0;
-    c.sep = nullptr; c.seps = nullptr; c.sepflag = nullptr; c.fold = 0; c.fold_mixed = 0;
-    c.slot_stride = stride; c.Np = (int)Npa; c.nt = nta; c.nt_fact = h->nt;
-    c.nrhs = 1; c.woodbury = 0; c.share_p = 0;
-    c.store_l = 1;   // L22's diagonal is read by the finish
-    if (!h->mb) for (int l = 0; l < GPCC_MAXL; ++l) c.sigma_b[l] = 0.0;
+    const long slots = h->held_slots;
+    const GpccCtx c = heldout_ctx(h, nta);
     GpccCtx ct = c;
     ct.nt_fact = nta;   // the trailing steps: the last one reports into the scratch outputs
     GpccHeldBuf hb;
@@ -2330,6 +2353,190 @@ extern "C" int gpcc_heldout_loglik_batch(gpcc_handle_t h, int M, const double *d
     if (heldout) HIPCHK(h, hipMemcpyAsync(heldout, h->d_xhld, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
     if (weights) HIPCHK(h, hipMemcpyAsync(mix_heldout, h->d_xmix + 3, sizeof(double), hipMemcpyDeviceToHost, ms));
     HIPCHK(h, hipStreamSynchronize(ms));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Joint posterior draws (gpcc_sample_batch; kernels: gpcc_sample.hip.h, random numbers: gpcc_rng.h).  The host picks
+// the rows of mixture draws, compacts the drawn rows and builds each one's ascending list of draw indices; every drawn row then runs
+// the held-out group unchanged (test residual 0: its loglik and info are the held-out path's bits), the mean kernel and the draw tiles.
+// ------------------------------------------------------------------------------------------
+template <typename T>
+static int grow_buf(gpcc_handle_t h, T **p, long *cap, long n)
+{
+    if (n <= *cap) return 0;
+    hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    HIPCHK(h, hipMalloc(p, sizeof(T) * (size_t)n));
+    *cap = n;
+    return 0;
+}
+
+extern "C" int gpcc_sample_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const int *Ntest,
+                                 const double *ttest, const double *sigmatest, const double *weights, int S, unsigned long long seed,
+                                 double *draws, int *draw_row, double *zeta, double *loglik, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (S < 1) return fail(h, GPCC_ERR_ARGUMENT, "S=%d < 1", S);
+    if (!delays || !alpha || !rho || !Ntest || !ttest || !draws || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    if (weights && !draw_row) return fail(h, GPCC_ERR_ARGUMENT, "weights given: draw_row is required");
+    if (h->is_multi()) {   // device_ids[0], like the gradient
+        const int rc = gpcc_sample_batch(primary(h), M, delays, alpha, rho, Ntest, ttest, sigmatest, weights, S, seed, draws, draw_row,
+                                         zeta, loglik, info);
+        return rc ? fail(h, rc, "%s", primary(h)->err.c_str()) : 0;
+    }
+    if (h->precision == GPCC_PRECISION_FP32) {   // always fp64: on the handle's fp64 twin
+        int rc = ensure_fb(h, 0);
+        if (rc) return rc;
+        rc = gpcc_sample_batch(h->fb, M, delays, alpha, rho, Ntest, ttest, sigmatest, weights, S, seed, draws, draw_row, zeta, loglik,
+                               info);
+        return rc ? fail(h, rc, "fp32 handle, draws in fp64: %s", h->fb->err.c_str()) : 0;
+    }
+    long T = 0;
+    for (int l = 0; l < h->L; ++l) { if (Ntest[l] < 0) return fail(h, GPCC_ERR_ARGUMENT, "negative Ntest"); T += Ntest[l]; }
+    if (T <= 0 || T > 32768) return fail(h, GPCC_ERR_ARGUMENT, "total number of test points %ld outside [1, 32768]", T);
+    const long D = weights ? (long)S : (long)M * S;   // output rows
+    if (D > 0x7fffffffL) return fail(h, GPCC_ERR_ARGUMENT, "M S = %ld draws: at most 2^31 - 1 per call", D);
+    // the cumulative weights c_m (sums in row order), checked before any device work (gpcc_predict_batch's rules)
+    std::vector<double> cw;
+    if (weights) {
+        double sw = 0.0;
+        cw.resize(M);
+        for (int m = 0; m < M; ++m) {
+            if (!std::isfinite(weights[m]) || weights[m] < 0.0)
+                return fail(h, GPCC_ERR_ARGUMENT, "weight %d = %g: weights must be finite and >= 0", m, weights[m]);
+            sw += weights[m];
+            cw[m] = sw;
+        }
+        if (!(sw > 0.0) || !std::isfinite(sw)) return fail(h, GPCC_ERR_ARGUMENT, "the weights sum to %g: need a finite sum > 0", sw);
+    }
+    if (M == 0) return 0;
+    // the row of every draw, the drawn rows (compact, in row order) and each one's ascending draw list
+    std::vector<int> ndraw(M, 0);
+    if (weights) {
+        for (long s = 0; s < D; ++s) {
+            const int m = gpccrng::pick_row(seed, (uint64_t)s, cw.data(), weights, M);
+            draw_row[s] = m;
+            ++ndraw[m];
+        }
+    } else {
+        for (int m = 0; m < M; ++m) ndraw[m] = S;
+        if (draw_row)
+            for (long o = 0; o < D; ++o) draw_row[o] = (int)(o / S);
+    }
+    std::vector<int> rows, cidx(M, -1);
+    for (int m = 0; m < M; ++m) {
+        if (ndraw[m] > 0) { cidx[m] = (int)rows.size(); rows.push_back(m); }
+        else { loglik[m] = __builtin_nan(""); info[m] = GPCC_SAMPLE_NOT_DRAWN; }
+    }
+    const int Mc = (int)rows.size();
+    std::vector<int> doff(Mc + 1, 0), dlist(D);
+    for (int k = 0; k < Mc; ++k) doff[k + 1] = doff[k] + ndraw[rows[k]];
+    if (weights) {
+        std::vector<int> fill(doff.begin(), doff.end() - 1);
+        for (long s = 0; s < D; ++s) dlist[fill[cidx[draw_row[s]]]++] = (int)s;
+    } else {
+        for (long o = 0; o < D; ++o) dlist[o] = (int)(o % S);
+    }
+    const long L = h->L;
+    std::vector<double> cpar((size_t)Mc * (2 * L + 1));
+    for (int k = 0; k < Mc; ++k) {
+        const int m = rows[k];
+        for (long l = 0; l < L; ++l) {
+            cpar[(size_t)k * L + l] = delays[(size_t)m * L + l];
+            cpar[(size_t)Mc * L + (size_t)k * L + l] = alpha[(size_t)m * L + l];
+        }
+        cpar[(size_t)2 * Mc * L + k] = rho[m];
+    }
+    GPCC_ON_DEVICE(h, h->device);
+    const int nta = h->nt + (int)((T + GPCC_TILE - 1) / GPCC_TILE), ntT = nta - h->nt;
+    const long Npa = (long)nta * GPCC_TILE, Tp = (long)ntT * GPCC_TILE;
+    int rc = ensure_workspace(h);
+    if (!rc) rc = ensure_heldout(h, nta, Mc);
+    if (!rc) rc = ensure_staging(h, Mc);
+    if (!rc) rc = grow_buf(h, &h->d_smean, &h->smean_cap, h->held_slots * Tp);
+    if (!rc) rc = grow_buf(h, &h->d_sdraw, &h->sdraw_cap, D * T);
+    if (!rc && zeta) rc = grow_buf(h, &h->d_szeta, &h->szeta_cap, D * T);
+    if (!rc) rc = grow_buf(h, &h->d_slist, &h->slist_cap, D);
+    if (!rc) rc = grow_buf(h, &h->d_soff, &h->soff_cap, (long)Mc + 1);
+    if (rc) return rc;
+    std::vector<double> pts;
+    std::vector<int> band;
+    heldout_points(h, Npa, Ntest, ttest, nullptr, sigmatest, pts, band);
+    const long ML = (long)Mc * L;
+    double *dd = h->d_par, *da = h->d_par + ML, *dr = h->d_par + 2 * ML;
+    hipStream_t ms = h->main_stream;
+    HIPCHK(h, hipMemcpyAsync(h->d_par, cpar.data(), sizeof(double) * cpar.size(), hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_xpts, pts.data(), sizeof(double) * pts.size(), hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_xband, band.data(), sizeof(int) * Npa, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_slist, dlist.data(), sizeof(int) * D, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_soff, doff.data(), sizeof(int) * (Mc + 1), hipMemcpyHostToDevice, ms));
+    const long slots = h->held_slots;
+    const GpccCtx c = heldout_ctx(h, nta);
+    GpccCtx ct = c;
+    ct.nt_fact = nta;   // the trailing steps: the last one reports into the scratch outputs
+    GpccHeldBuf hb;
+    hb.hld = h->d_xhld; hb.mix = h->d_xmix; hb.T = (int)T; hb.N = h->N; hb.off = h->Np;   // (the held-out values: scratch here)
+    GpccSampBuf sb;
+    sb.mean = h->d_smean; sb.draws = h->d_sdraw; sb.zeta = zeta ? h->d_szeta : nullptr;
+    sb.dlist = h->d_slist; sb.doff = h->d_soff; sb.seed = seed;
+    sb.T = (int)T; sb.Tp = (int)Tp; sb.ntT = ntT; sb.ntr = h->nt; sb.S = S; sb.mixture = weights ? 1 : 0; sb.nblk = 1;
+    for (int l = 0; l < GPCC_MAXL; ++l) sb.mean_b[l] = (l < h->L) ? h->mean_b[l] : 0.0;
+    const int cs = (int)(slots < h->ws_slots ? slots : h->ws_slots);
+    int NS = h->prof ? 1 : (int)(slots / cs);
+    if (NS > h->ws_streams) NS = h->ws_streams;
+    const int ngroups = (Mc + cs - 1) / cs, used = ngroups < NS ? ngroups : NS;
+    HIPCHK(h, hipEventRecord(h->ev_start, ms));
+    for (int s = 0; s < used; ++s) HIPCHK(h, hipStreamWaitEvent(h->str[s], h->ev_start, 0));
+    for (int gi = 0; gi < ngroups && !rc; ++gi) {
+        const int s = gi % NS;
+        hipStream_t st = h->str[s];
+        GpccGroup g0;
+        g0.delays = dd; g0.alpha = da; g0.rho = dr;
+        g0.out_loglik = h->d_out; g0.out_info = h->d_oinfo; g0.out_cond = nullptr;
+        g0.first = gi * cs;
+        g0.slot0 = s * cs;
+        g0.cnt = (Mc - g0.first < cs) ? (Mc - g0.first) : cs;
+        g0.spread = 0;
+        const GpccGroup g = grad_group(g0);
+        GpccGroup gt = g;
+        gt.out_loglik = h->d_xscr; gt.out_info = h->d_xscri;
+        rc = enqueue_heldout_group(h, c, ct, g, gt, hb, st);
+        if (rc) break;
+        GpccSampBuf sg = sb;
+        for (int k = g.first; k < g.first + g.cnt; ++k) {
+            const int nb = (doff[k + 1] - doff[k] + GPCC_TILE - 1) / GPCC_TILE;
+            if (nb > sg.nblk) sg.nblk = nb;
+        }
+        gpcc_sample_mean<<<g.cnt * ntT, 512, 0, st>>>(c, g, sg);
+        gpcc_sample_tiles<<<(unsigned)((long)g.cnt * ntT * sg.nblk), 512, 0, st>>>(c, g, sg);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = fail(h, GPCC_ERR_HIP, "draw kernels: %s", hipGetErrorString(e));
+    }
+    if (rc) {   // nothing may be left running when the error is returned
+        const std::string msg = h->err;
+        for (int s = 0; s < used; ++s) (void)hipStreamSynchronize(h->str[s]);
+        (void)hipGetLastError();
+        h->err = msg;
+        return rc;
+    }
+    for (int s = 0; s < used; ++s) {
+        HIPCHK(h, hipEventRecord(h->ev_done[s], h->str[s]));
+        HIPCHK(h, hipStreamWaitEvent(ms, h->ev_done[s], 0));
+    }
+    std::vector<double> cll(Mc);
+    std::vector<int> cinfo(Mc);
+    HIPCHK(h, hipMemcpyAsync(cll.data(), h->d_out, sizeof(double) * Mc, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipMemcpyAsync(cinfo.data(), h->d_oinfo, sizeof(int) * Mc, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipMemcpyAsync(draws, h->d_sdraw, sizeof(double) * D * T, hipMemcpyDeviceToHost, ms));
+    if (zeta) HIPCHK(h, hipMemcpyAsync(zeta, h->d_szeta, sizeof(double) * D * T, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipStreamSynchronize(ms));
+    for (int k = 0; k < Mc; ++k) {
+        loglik[rows[k]] = cll[k];
+        info[rows[k]] = cinfo[k];
+    }
     return 0;
 }
 

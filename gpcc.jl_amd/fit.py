@@ -251,6 +251,18 @@ def _with_evidence(res, obj, cand, engine, evidence, rhomin, rhomax, max_rounds,
     return res
 
 
+def _sample_bands(L, ttest):
+    """ttest as Predictor's call forms take it: a list of L arrays (each band's own times) or one array (the same times in every band)."""
+    if isinstance(ttest, (list, tuple)) and len(ttest) == L and all(np.ndim(a) == 1 for a in ttest):
+        return [np.asarray(a, dtype=np.float64) for a in ttest]
+    return [np.asarray(ttest, dtype=np.float64).ravel()] * L
+
+
+def _split_bands(draws, bands):
+    off = np.concatenate([[0], np.cumsum([len(b) for b in bands])]).astype(int)
+    return [draws[:, off[l]:off[l + 1]] for l in range(len(bands))]
+
+
 class Predictor:
     """The `predictTest` closure returned by gpcc() (marginaliseb.jl:259-343), three call forms:
       pred(ttest)                       ttest = list of L arrays  -> (mu_pred, Sigma_pred), joint    (:259-289)
@@ -284,6 +296,17 @@ class Predictor:
         return ([mu[l * n:(l + 1) * n] for l in range(L)],
                 [np.sqrt(np.maximum(d[l * n:(l + 1) * n], 1e-6)) for l in range(L)])      # :301-303
 
+    def sample(self, ttest, S, seed, sigmatest=None):
+        """S joint draws of the light curves at ttest (Predictor's forms: a list of L arrays or one array for every band) -> per-band
+        arrays (S, Ntest_l): mu_pred + chol(Sigma_pred + diag(sigmatest^2)) zeta, the latent curve without sigmatest (Sigma_pred holds
+        JITTER), a replicated observation with it (Objective.sample_batch, one row)."""
+        bands = _sample_bands(self.obj.L, ttest)
+        st = None if sigmatest is None else _sample_bands(self.obj.L, sigmatest)
+        draws, _, _, info = self.obj.sample_batch(self.delays[None, :], self.alpha[None, :], [self.rho], bands, S, seed, sigmatest=st)
+        if 0 < info[0] <= self.obj.N:
+            raise PosDefException(int(info[0]))
+        return _split_bands(draws, bands)
+
 
 class DelayAveragedPredictor:
     """Light-curve predictions averaged over a posterior of delays: the mixture over the rows (delays[g], alpha[g], rho[g]) with
@@ -293,8 +316,10 @@ class DelayAveragedPredictor:
       pred(ttest)    ttest = one array / range  -> (mu per band, sigma per band) at those times in every band
       pred(ttest)    ttest = list of L arrays   -> the same per-band lists at each band's own times
     mu = sum p mu_g and sigma = sqrt(max(var, 1e-6)) with var = sum p (var_g + (mu_g - mu)^2), the mixture's mean and variance.
-    There is no joint form: a mixture of Gaussians has no single joint Gaussian to return.  Its held-out density is still well
-    defined: loglik(ttest, ytest, sigmatest) = log sum_g p_g N(ytest; mu_g, Sigma_g) (Objective.heldout_loglik_batch)."""
+    A mixture of Gaussians has no single joint Gaussian to return, so its joint uncertainty comes as draws instead:
+    sample(ttest, S, seed) returns S joint draws of the mixture, each from a row picked by the weights (Objective.sample_batch).  Its
+    held-out density is well defined too: loglik(ttest, ytest, sigmatest) = log sum_g p_g N(ytest; mu_g, Sigma_g)
+    (Objective.heldout_loglik_batch)."""
 
     def __init__(self, objective, delays, alpha, rho, weights):
         self.obj = objective
@@ -323,6 +348,15 @@ class DelayAveragedPredictor:
         """The mixture's held-out log density log sum_g p_g N(ytest; mu_g, Sigma_g + diag(sigmatest^2)) of the test set (lists of L
         arrays), every row scored as Predictor(ttest, ytest, sigmatest) scores it (marginaliseb.jl:311-343)."""
         return self.obj.heldout_loglik_batch(self.delays, self.alpha, self.rho, ttest, ytest, sigmatest, weights=self.weights)[3]
+
+    def sample(self, ttest, S, seed, sigmatest=None):
+        """S joint draws of the delay-averaged light curves -> (per-band arrays (S, Ntest_l), row[S]): draw s comes from the row
+        row[s], picked with probability weights[row] / sum(weights), so (self.delays[row[s]], draws[.][s]) are joint (tau, f*)
+        samples.  ttest and sigmatest take Predictor's forms; without sigmatest the latent curves, with it replicated observations."""
+        bands = _sample_bands(self.obj.L, ttest)
+        st = None if sigmatest is None else _sample_bands(self.obj.L, sigmatest)
+        draws, rows, _, _ = self.obj.sample_batch(self.delays, self.alpha, self.rho, bands, S, seed, weights=self.weights, sigmatest=st)
+        return _split_bands(draws, bands), rows
 
 
 def gpcc(tarray, yarray, stdarray, *, kernel, delays, iterations, seed=1, numberofrestarts=1, initialrandom=5,

@@ -310,6 +310,32 @@ int gpcc_heldout_loglik_batch(gpcc_handle_t h, int M, const double *delays, cons
                               const double *ttest, const double *ytest, const double *sigmatest, const double *weights,
                               double *heldout, double *mix_heldout, double *loglik, int *info);
 
+/* Joint posterior draws of the light curves at M rows (tau, alpha, rho) -- gpcc_predict_batch's row layout -- on one test set shared by
+ * every row (Ntest[l] points per band, flattened in band order in ttest; 1 <= T = sum Ntest <= 32768; Ntest[l] = 0 allowed).  One draw
+ * of row m is f* = mu_pred + chol(Sigma_pred + JITTER I + diag(sigmatest^2)) zeta, zeta ~ N(0, I_T), with gpcc_predict's mu_pred and
+ * Sigma_pred (src/gpccfixdelay_marginaliseb.jl:259-289) and JITTER = 1e-8: sigmatest == NULL draws the latent curve, sigmatest (T
+ * entries) a replicated observation.  S >= 1.
+ *   Per-row mode (weights == NULL): draws holds M S rows of T values, draw s of row m at row m S + s; draw_row (NULL or M S entries)
+ *   receives m for each of them.
+ *   Mixture mode (weights != NULL, M entries, rejected as gpcc_predict_batch rejects them): draws holds S rows; draw s uses the row
+ *   draw_row[s] (required) = the first m with u_s c_{M-1} < c_m and w_m > 0, c_m = sum_{k <= m} w_k in row order.
+ * Random numbers (csrc/gpcc_rng.h): Philox4x64-10, key (seed, 0).  Element j of draw s of row m is a Box-Muller normal of counter
+ * (j / 4, s, m, 0) (m = 2^64 - 1 in mixture mode: the noise of a mixture draw does not depend on its row); u_s is word 0 of counter
+ * (s, 0, 2^64 - 1, 1).  zeta (NULL, or the layout of draws) receives the normals each draw used.
+ * Only rows with at least one draw are factorised (every row in per-row mode); the others get loglik NaN and info
+ * GPCC_SAMPLE_NOT_DRAWN.  loglik and info of a factorised row are bitwise gpcc_heldout_loglik_batch's for the same row and test set
+ * (info = N + j: the j-th pivot of the test block failed); a failed row's draws are NaN and change nothing else; the call returns 0.
+ * Path: the held-out path's augmented factorisation with a test residual of 0, then gfx950 kernels: the mean
+ * bbar* + L21 w1 once per row and test tile, and L22 zeta in fp64 MFMA with zeta generated in LDS.  Always fp64 (an fp32 handle on
+ * its fp64 twin); a multi-device handle computes on device_ids[0].  Bitwise repeatable, and independent of the grouping, the stream /
+ * slot options, fp32 vs fp64 handles and S (the first S' draws of a call with S > S' are the draws of a call with S').  Memory: the
+ * held-out workspace (gpcc_heldout_loglik_batch, shared with it), plus 8 T' bytes per held-out slot (T' = 128 ceil(T / 128)), 8 D T
+ * bytes for the draws (D = M S, or S) and as much again for zeta when asked for, 4 D + 4 M bytes of draw lists; a handle that never
+ * samples allocates none of it, and bytes_per_slot is unchanged.  Blocking. */
+int gpcc_sample_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const int *Ntest,
+                      const double *ttest, const double *sigmatest, const double *weights, int S, unsigned long long seed,
+                      double *draws, int *draw_row, double *zeta, double *loglik, int *info);
+
 /* Posterior of the offsets b (src/gpccfixdelay_marginaliseb.jl:248-252): mu_postb[L], Sigma_postb[L x L]
  * (column-major, symmetrised).  The N x N solves (Sobs + K) \ [Q Y] run on the device as an augmented
  * factorisation; only the final L x L inverse is host arithmetic. */
@@ -367,7 +393,8 @@ enum {
     GPCC_LAPLACE_NOT_CONVERGED = -10,   /* the polish did not converge within max_rounds evaluations (or its step collapsed) */
     GPCC_LAPLACE_NOT_MAXIMUM = -11,     /* -Hessian not positive definite at the last point */
     GPCC_LAPLACE_ON_BOUND = -12,        /* the mode lies on the box (gpcc_laplace_evidence: rho = rhomin or rhomax) */
-    GPCC_LAPLACE_BAD_START = -13        /* gpcc_newton_batch: the start was rejected (non-finite value) */
+    GPCC_LAPLACE_BAD_START = -13,       /* gpcc_newton_batch: the start was rejected (non-finite value) */
+    GPCC_SAMPLE_NOT_DRAWN = -14         /* gpcc_sample_batch: the row received no draw of the mixture and was not factorised */
 };
 
 /* The Newton polish of gpcc_laplace_evidence on its own (host only): P independent maximisations of l(u), u in R^n, in lock-step.

@@ -168,6 +168,32 @@ function heldout_loglik_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{
     return held, ll, info, (weights === nothing ? nothing : mix[1])
 end
 
+"joint posterior draws of the light curves on the test times ttest (L vectors, shared by every column) at the columns (τ, α, ρ) of
+delays, alpha (L×M) and rho[M]: f* = μpred + chol(Σpred + JITTER I + diag(σtest²)) ζ (σtest = nothing: the latent curve) ->
+(draws (T × D), draw_row[D], ll[M], info[M], ζ (T × D) or nothing).  weights = nothing: D = M S, draw s of column m in column m S + s;
+weights (M): D = S draws of the mixture, draw_row the 0-based column each used (columns without a draw: ll NaN, info -14).  ll and info
+are heldout_loglik_batch's (info = N + j: the j-th pivot of the test block failed, draws NaN).  seed: the Philox4x64-10 key."
+function sample_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64}, ttest, S::Integer, seed::Integer;
+                      weights = nothing, σtest = nothing, return_noise::Bool = false)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M) && length(ttest) == h.L
+    Nt = Cint[length(a) for a in ttest]
+    tt = Float64.(reduce(vcat, ttest))
+    T = length(tt)
+    st = σtest === nothing ? C_NULL : Float64.(reduce(vcat, σtest))
+    D = weights === nothing ? M * S : S
+    draws, rows = Matrix{Float64}(undef, T, D), Vector{Cint}(undef, D)
+    ζ = return_noise ? Matrix{Float64}(undef, T, D) : C_NULL
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    w = weights === nothing ? C_NULL : Float64.(weights)
+    rc = ccall((:gpcc_sample_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+                Culonglong, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, Nt, tt, st, w, S, UInt64(seed), draws, rows, ζ, ll, info)
+    rc == 0 || error("gpcc_sample_batch: " * lasterror(h.ptr))
+    return draws, rows, ll, info, (return_noise ? ζ : nothing)
+end
+
 "Drop-in body of objective(α, ρ) (gpccfixdelay_marginaliseb.jl:133-141): throws what the Julia code throws."
 function objective(h::Handle, τ, α, ρ)
     ll, info = loglik_batch(h, reshape(Float64.(τ), :, 1), reshape(Float64.(α), :, 1), [Float64(ρ)])
