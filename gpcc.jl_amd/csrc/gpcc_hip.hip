@@ -29,6 +29,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #define GPCC_VERSION_NUMBER 100
@@ -205,10 +206,11 @@ struct gpcc_handle_s {
     hipEvent_t ev_pmix = nullptr;   // orders the mixture steps of consecutive groups (on different streams) by row
     // held-out log-likelihood (gpcc_heldout_loglik_batch): allocated on its first call, for held_slots <= workspace slots -- per slot an
     // augmented workspace of held_nta tile columns (tiles, inv(L_kk), z, w, logdet, Gram, info); the augmented points (3 x held_nta * 128
-    // doubles + ints), the per-row results (hld_cap), the weights and the mixture state
+    // doubles + ints), the per-row results (hld_cap), the weights (xw_cap), the mixture state and the per-row scratch outputs of the
+    // trailing steps (xscr_cap, xscri_cap)
     double *d_xtile = nullptr, *d_xpts = nullptr, *d_xhld = nullptr, *d_xw = nullptr, *d_xmix = nullptr, *d_xscr = nullptr;
     int *d_xband = nullptr, *d_xinfo = nullptr, *d_xscri = nullptr;
-    long held_slots = 0, held_ws = 0, held_nta = 0, hld_cap = 0;
+    long held_slots = 0, held_ws = 0, held_nta = 0, hld_cap = 0, xw_cap = 0, xscr_cap = 0, xscri_cap = 0;
     hipEvent_t ev_hmix = nullptr;   // orders the mixture steps of consecutive groups by row
     // joint draws (gpcc_sample_batch): the held-out workspace above, plus the per-slot means (smean_cap doubles), the draws and their
     // normals (sdraw_cap / szeta_cap doubles), the draw lists (slist_cap ints) and their offsets (soff_cap ints); allocated on first use
@@ -1592,6 +1594,197 @@ extern "C" int gpcc_loglik_batch(gpcc_handle_t h, int M, const double *delays, c
 }
 
 // ------------------------------------------------------------------------------------------
+// Host code shared by the fp64-only batched entry points (gradient, Hessian, predictive, held-out log-likelihood, draws): the routing of
+// multi-device and fp32 handles, the checks of test points and weights, the staging, the buffers that grow on demand, the slot budget
+// of the large per-slot buffers, the kernel-id dispatch, the launch-per-step factorisation and the group driver.
+// ------------------------------------------------------------------------------------------
+
+// an fp64-only call on a handle that does not compute it itself: a multi-device handle runs it on device_ids[0] (like the
+// single-matrix utilities), an fp32 handle on its fp64 twin.  call(o) re-issues the call on handle o; what names the call in the fp32
+// handle's message.  True: the call went elsewhere and rc is its code; false: h computes it.
+template <typename Call>
+static bool route_fp64(gpcc_handle_t h, const char *what, int &rc, Call &&call)
+{
+    if (h->is_multi()) {
+        rc = call(primary(h));
+        if (rc) rc = fail(h, rc, "%s", primary(h)->err.c_str());
+        return true;
+    }
+    if (h->precision != GPCC_PRECISION_FP32) return false;
+    rc = ensure_fb(h, 0);
+    if (!rc) {
+        rc = call(h->fb);
+        if (rc) rc = fail(h, rc, "fp32 handle, %s in fp64: %s", what, h->fb->err.c_str());
+    }
+    return true;
+}
+
+// the test points, checked before any device work: Ntest[l] >= 0, in total T in [1, 32768]
+static int count_test_points(gpcc_handle_t h, const int *Ntest, long &T)
+{
+    T = 0;
+    for (int l = 0; l < h->L; ++l) { if (Ntest[l] < 0) return fail(h, GPCC_ERR_ARGUMENT, "negative Ntest"); T += Ntest[l]; }
+    if (T <= 0 || T > 32768) return fail(h, GPCC_ERR_ARGUMENT, "total number of test points %ld outside [1, 32768]", T);
+    return 0;
+}
+
+// the mixture weights of M rows, checked before any device work: each finite and >= 0, with a finite sum > 0 (summed in row order).
+// p: the normalised weights w_m / sum w, or the cumulative sums; empty without weights.
+static int mixture_weights(gpcc_handle_t h, int M, const double *weights, bool cumulative, std::vector<double> &p)
+{
+    if (!weights) return 0;
+    double sw = 0.0;
+    p.resize(M);
+    for (int m = 0; m < M; ++m) {
+        if (!std::isfinite(weights[m]) || weights[m] < 0.0)
+            return fail(h, GPCC_ERR_ARGUMENT, "weight %d = %g: weights must be finite and >= 0", m, weights[m]);
+        sw += weights[m];
+        p[m] = sw;
+    }
+    if (!(sw > 0.0) || !std::isfinite(sw)) return fail(h, GPCC_ERR_ARGUMENT, "the weights sum to %g: need a finite sum > 0", sw);
+    if (!cumulative)
+        for (int m = 0; m < M; ++m) p[m] = weights[m] / sw;
+    return 0;
+}
+
+// the parameters of M rows -> the staging buffer (ensure_staging) on main_stream: dd = delays (M x L), da = alpha (M x L), dr = rho (M)
+static int stage_params(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, double *&dd, double *&da,
+                        double *&dr)
+{
+    const long ML = (long)M * h->L;
+    dd = h->d_par; da = h->d_par + ML; dr = h->d_par + 2 * ML;
+    HIPCHK(h, hipMemcpyAsync(dd, delays, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(da, alpha, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(dr, rho, sizeof(double) * M, hipMemcpyHostToDevice, h->main_stream));
+    return 0;
+}
+
+// a buffer of at least n elements (*cap: what it holds), reallocated only to grow
+template <typename T>
+static int grow_buf(gpcc_handle_t h, T **p, long *cap, long n)
+{
+    if (n <= *cap) return 0;
+    hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    HIPCHK(h, hipMalloc(p, sizeof(T) * (size_t)n));
+    *cap = n;
+    return 0;
+}
+
+// the slots of a buffer set too large to give every workspace slot one (per bytes each): as many as fit a quarter of the device's
+// memory (of 64 GiB when hipMemGetInfo reports none), at most the workspace's ws slots, at least 1; halved while alloc(slots), which
+// frees what it took when it fails, runs out of memory.  With fewer than ws the groups run through fewer slots -- every evaluation's
+// arithmetic is the same in any group -- and gpcc_last_error carries a note.  what: the set's name in the messages.
+template <typename Alloc>
+static int alloc_slots(gpcc_handle_t h, const char *what, long per, long ws, long &slots, Alloc &&alloc)
+{
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) total_b = (size_t)64 << 30;
+    slots = (long)(0.25 * (double)total_b / (double)per);
+    if (slots > ws) slots = ws;
+    if (slots < 1) slots = 1;
+    for (;;) {
+        const hipError_t e = alloc(slots);
+        if (e == hipSuccess) break;
+        (void)hipGetLastError();
+        if (e != hipErrorOutOfMemory || slots <= 1)
+            return fail(h, GPCC_ERR_HIP, "%s of %ld slots (%ld bytes each): %s", what, slots, per, hipGetErrorString(e));
+        slots /= 2;
+    }
+    if (slots < ws) {   // a note, not an error
+        char buf[256];
+        snprintf(buf, sizeof buf, "note: the %s (%ld bytes per slot) fit %ld of the %ld workspace slots; its groups run through %ld slots "
+                 "(results unchanged)", what, per, slots, ws, slots);
+        h->err = buf;
+    }
+    return 0;
+}
+
+// f(std::integral_constant<int, KID>()) for the covariance kernel kernel_id: the instantiation of a kernel template that a launch takes
+template <typename F>
+static void with_kernel_id(int kernel_id, F &&f)
+{
+    switch (kernel_id) {
+    case 0: f(std::integral_constant<int, 0>()); break;
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    default: f(std::integral_constant<int, 3>()); break;
+    }
+}
+
+// 0, or GPCC_ERR_HIP with what and the error when a launch failed
+static int launch_status(gpcc_handle_t h, const char *what)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail(h, GPCC_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+
+// assembly and the launch-per-step left-looking factorisation (gpcc_panel_update, gpcc_diag_factor, gpcc_panel_trsm) of a group; g: from
+// run_groups.  The diagonal steps k < c.nt_fact run with (c, g), the later ones with (ct, gt): the held-out path's trailing steps,
+// whose last one reports elsewhere.  The gradient passes (c, g) twice.
+static void enqueue_factor_steps(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g, const GpccCtx &ct, const GpccGroup &gt,
+                                 hipStream_t s)
+{
+    const int cnt8 = g.spread ? g.cnt : 8 * ((g.cnt + 7) / 8);
+    launch_assemble(h, c, g, s, false, false);
+    for (int k = 0; k < c.nt; ++k) {
+        if (k > 0) {
+            ProfScope pr(h, GPCC_PROF_PANEL_UPDATE, s);
+            gpcc_panel_update<double, false><<<cnt8 * (c.nt - k), GPCC_GEMM_THREADS, GPCC_GEMM_LDS_BYTES, s>>>(c, g, k, k, 0);
+        }
+        {
+            ProfScope pr(h, GPCC_PROF_DIAG, s);
+            if (k < c.nt_fact) gpcc_diag_factor<double><<<g.cnt, GPCC_DIAG_THREADS, GPCC_DIAG_LDS_BYTES, s>>>(c, g, k);
+            else gpcc_diag_factor<double><<<g.cnt, GPCC_DIAG_THREADS, GPCC_DIAG_LDS_BYTES, s>>>(ct, gt, k);
+        }
+        if (k < c.nt - 1) {
+            ProfScope pr(h, GPCC_PROF_TRSM, s);
+            gpcc_panel_trsm<double><<<cnt8 * (c.nt - k - 1), GPCC_GEMM_THREADS, GPCC_GEMM_LDS_BYTES, s>>>(c, g, k);
+        }
+    }
+}
+
+// M rows, staged at dd, da, dr, in groups of cs = min(budget, ws_slots) evaluations on S = min(budget / cs, ws_streams) streams (one
+// under the profiler): group gi runs on stream gi % S from that stream's first slot.  The streams start after main_stream's work and
+// main_stream waits for every stream used.  body(g, stream, gi, ngroups) enqueues group gi and returns 0 or fail()'s code; the first
+// error ends the loop.
+template <typename Body>
+static int run_groups(gpcc_handle_t h, int M, long budget, const double *dd, const double *da, const double *dr, Body &&body)
+{
+    const int cs = (int)(budget < h->ws_slots ? budget : h->ws_slots);
+    int S = h->prof ? 1 : (int)(budget / cs);
+    if (S > h->ws_streams) S = h->ws_streams;
+    const int ngroups = (M + cs - 1) / cs, used = ngroups < S ? ngroups : S;
+    HIPCHK(h, hipEventRecord(h->ev_start, h->main_stream));
+    for (int s = 0; s < used; ++s) HIPCHK(h, hipStreamWaitEvent(h->str[s], h->ev_start, 0));
+    int rc = 0;
+    for (int gi = 0; gi < ngroups && !rc; ++gi) {
+        const int s = gi % S;
+        GpccGroup g;
+        g.delays = dd; g.alpha = da; g.rho = dr;
+        g.out_loglik = h->d_out; g.out_info = h->d_oinfo; g.out_cond = nullptr;
+        g.first = gi * cs;
+        g.slot0 = s * cs;
+        g.cnt = (M - g.first < cs) ? (M - g.first) : cs;
+        g.spread = (g.cnt < 8) ? 1 : 0;   // the job order of the factorisation (every evaluation's arithmetic is the same either way)
+        rc = body(g, h->str[s], gi, ngroups);
+    }
+    if (rc) {   // nothing may be left running when the error is returned
+        const std::string msg = h->err;
+        for (int s = 0; s < used; ++s) (void)hipStreamSynchronize(h->str[s]);
+        (void)hipGetLastError();
+        h->err = msg;
+        return rc;
+    }
+    for (int s = 0; s < used; ++s) {
+        HIPCHK(h, hipEventRecord(h->ev_done[s], h->str[s]));
+        HIPCHK(h, hipStreamWaitEvent(h->main_stream, h->ev_done[s], 0));
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // Gradient of objective(alpha, rho) (gpcc_loglik_grad_batch; kernels: gpcc_grad.hip.h).  A gradient group always runs
 // the same path, whatever its size: assembly, then the launch-per-step left-looking factorisation (gpcc_panel_update, gpcc_diag_factor,
 // gpcc_panel_trsm) with every inv(L_kk) kept -- no persistent launch, shared prefix, split halves, fold, hybrid tail or small-N family --
@@ -1614,34 +1807,11 @@ static int ensure_grad(gpcc_handle_t h)
     return 0;
 }
 
-// the job order of a gradient group's factorisation (every evaluation's arithmetic is the same either way)
-static GpccGroup grad_group(const GpccGroup &g_in)
-{
-    GpccGroup g = g_in;
-    g.spread = (g.cnt < 8) ? 1 : 0;
-    return g;
-}
-
 // part 1 of a gradient group, shared with the predictive (gpcc_predict_batch): assembly, the launch-per-step factorisation with every
-// inv(L_kk) kept, X = L^-1 over the slot's lower tiles and w = K^-1 r (h->d_gw).  g: from grad_group.
+// inv(L_kk) kept, X = L^-1 over the slot's lower tiles and w = K^-1 r (h->d_gw).  g: from run_groups.
 static void enqueue_grad_inverse(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g, hipStream_t s)
 {
-    const int cnt8 = g.spread ? g.cnt : 8 * ((g.cnt + 7) / 8);
-    launch_assemble(h, c, g, s, false, false);
-    for (int k = 0; k < c.nt; ++k) {
-        if (k > 0) {
-            ProfScope pr(h, GPCC_PROF_PANEL_UPDATE, s);
-            gpcc_panel_update<double, false><<<cnt8 * (c.nt - k), GPCC_GEMM_THREADS, GPCC_GEMM_LDS_BYTES, s>>>(c, g, k, k, 0);
-        }
-        {
-            ProfScope pr(h, GPCC_PROF_DIAG, s);
-            gpcc_diag_factor<double><<<g.cnt, GPCC_DIAG_THREADS, GPCC_DIAG_LDS_BYTES, s>>>(c, g, k);
-        }
-        if (k < c.nt - 1) {
-            ProfScope pr(h, GPCC_PROF_TRSM, s);
-            gpcc_panel_trsm<double><<<cnt8 * (c.nt - k - 1), GPCC_GEMM_THREADS, GPCC_GEMM_LDS_BYTES, s>>>(c, g, k);
-        }
-    }
+    enqueue_factor_steps(h, c, g, c, g, s);
     for (int j = c.nt - 2; j >= 0; --j) {
         const int jobs = g.cnt * (c.nt - 1 - j);
         gpcc_grad_trtri<<<jobs, 512, 0, s>>>(c, g, j, h->d_gscr);
@@ -1650,27 +1820,16 @@ static void enqueue_grad_inverse(gpcc_handle_t h, const GpccCtx &c, const GpccGr
     gpcc_grad_w<<<g.cnt * c.nt, GPCC_TILE, 0, s>>>(c, g, h->d_gw);
 }
 
-// part 2: the fused K^-1 tiles with their derivative sums, and the finish
-static void enqueue_grad_tiles(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g, double *d_grad, hipStream_t s)
+// a gradient group (g: from run_groups): part 1, then the fused K^-1 tiles with their derivative sums, and the finish into h->d_ggrad
+static int enqueue_grad_group(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g, hipStream_t s)
 {
-    const int tiles = g.cnt * (c.nt * (c.nt + 1) / 2);
-    switch (c.kernel_id) {
-    case 0: gpcc_grad_tiles<0><<<tiles, 512, 0, s>>>(c, g, h->d_gw, h->d_gpart3); break;
-    case 1: gpcc_grad_tiles<1><<<tiles, 512, 0, s>>>(c, g, h->d_gw, h->d_gpart3); break;
-    case 2: gpcc_grad_tiles<2><<<tiles, 512, 0, s>>>(c, g, h->d_gw, h->d_gpart3); break;
-    default: gpcc_grad_tiles<3><<<tiles, 512, 0, s>>>(c, g, h->d_gw, h->d_gpart3); break;
-    }
-    gpcc_grad_finish<<<g.cnt, 256, 0, s>>>(c, g, h->d_gpart3, d_grad);
-}
-
-static int enqueue_grad_group(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g_in, double *d_grad, hipStream_t s)
-{
-    const GpccGroup g = grad_group(g_in);
     enqueue_grad_inverse(h, c, g, s);
-    enqueue_grad_tiles(h, c, g, d_grad, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
+    const int tiles = g.cnt * (c.nt * (c.nt + 1) / 2);
+    with_kernel_id(c.kernel_id, [&](auto kid) {
+        gpcc_grad_tiles<decltype(kid)::value><<<tiles, 512, 0, s>>>(c, g, h->d_gw, h->d_gpart3);
+    });
+    gpcc_grad_finish<<<g.cnt, 256, 0, s>>>(c, g, h->d_gpart3, h->d_ggrad);
+    return launch_status(h, "kernel launch failed");
 }
 
 extern "C" int gpcc_loglik_grad_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
@@ -1680,62 +1839,24 @@ extern "C" int gpcc_loglik_grad_batch(gpcc_handle_t h, int M, const double *dela
     if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
     if (M == 0) return 0;
     if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
-    if (h->is_multi()) {   // device_ids[0], like the single-matrix utilities
-        const int rc = gpcc_loglik_grad_batch(primary(h), M, delays, alpha, rho, loglik, grad, info);
-        return rc ? fail(h, rc, "%s", primary(h)->err.c_str()) : 0;
-    }
-    if (h->precision == GPCC_PRECISION_FP32) {   // always fp64: on the handle's fp64 twin
-        int rc = ensure_fb(h, 0);
-        if (rc) return rc;
-        rc = gpcc_loglik_grad_batch(h->fb, M, delays, alpha, rho, loglik, grad, info);
-        return rc ? fail(h, rc, "fp32 handle, gradient in fp64: %s", h->fb->err.c_str()) : 0;
-    }
+    int rc = 0;
+    if (route_fp64(h, "gradient", rc, [&](gpcc_handle_t o) { return gpcc_loglik_grad_batch(o, M, delays, alpha, rho, loglik, grad, info); }))
+        return rc;
     GPCC_ON_DEVICE(h, h->device);
-    int rc = ensure_workspace(h);
+    const long W = 2L * h->L + 1;
+    double *dd, *da, *dr;
+    rc = ensure_workspace(h);
     if (!rc) rc = ensure_grad(h);
     if (!rc) rc = ensure_staging(h, M);
+    if (!rc) rc = grow_buf(h, &h->d_ggrad, &h->ggrad_cap, W * M);
+    if (!rc) rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
     if (rc) return rc;
-    const long W = 2L * h->L + 1;
-    if (M > h->ggrad_cap) {
-        hipFree(h->d_ggrad);
-        h->d_ggrad = nullptr; h->ggrad_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_ggrad, sizeof(double) * W * M));
-        h->ggrad_cap = M;
-    }
-    const long ML = (long)M * h->L;
-    double *dd = h->d_par, *da = h->d_par + ML, *dr = h->d_par + 2 * ML;
-    HIPCHK(h, hipMemcpyAsync(dd, delays, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
-    HIPCHK(h, hipMemcpyAsync(da, alpha, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
-    HIPCHK(h, hipMemcpyAsync(dr, rho, sizeof(double) * M, hipMemcpyHostToDevice, h->main_stream));
     GpccCtx c = make_ctx(h);
     c.linv = h->d_glinv;
     c.linv_keep = 1;
-    const int S = h->prof ? 1 : h->ws_streams, cs = h->ws_slots;
-    const int ngroups = (M + cs - 1) / cs, used = ngroups < S ? ngroups : S;
-    HIPCHK(h, hipEventRecord(h->ev_start, h->main_stream));
-    for (int s = 0; s < used; ++s) HIPCHK(h, hipStreamWaitEvent(h->str[s], h->ev_start, 0));
-    for (int gi = 0; gi < ngroups && !rc; ++gi) {
-        const int s = gi % S;
-        GpccGroup g;
-        g.delays = dd; g.alpha = da; g.rho = dr;
-        g.out_loglik = h->d_out; g.out_info = h->d_oinfo; g.out_cond = nullptr;
-        g.first = gi * cs;
-        g.slot0 = s * cs;
-        g.cnt = (M - g.first < cs) ? (M - g.first) : cs;
-        g.spread = 0;
-        rc = enqueue_grad_group(h, c, g, h->d_ggrad, h->str[s]);
-    }
-    if (rc) {   // nothing may be left running when the error is returned
-        const std::string msg = h->err;
-        for (int s = 0; s < used; ++s) (void)hipStreamSynchronize(h->str[s]);
-        (void)hipGetLastError();
-        h->err = msg;
-        return rc;
-    }
-    for (int s = 0; s < used; ++s) {
-        HIPCHK(h, hipEventRecord(h->ev_done[s], h->str[s]));
-        HIPCHK(h, hipStreamWaitEvent(h->main_stream, h->ev_done[s], 0));
-    }
+    rc = run_groups(h, M, (long)h->ws_streams * h->ws_slots, dd, da, dr,
+                    [&](const GpccGroup &g, hipStream_t s, int, int) { return enqueue_grad_group(h, c, g, s); });
+    if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, h->main_stream));
     HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, h->main_stream));
     HIPCHK(h, hipMemcpyAsync(grad, h->d_ggrad, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
@@ -1754,66 +1875,27 @@ static int ensure_hess(gpcc_handle_t h)
 {
     const long ws = (long)h->ws_streams * h->ws_slots;
     if (h->hess_ws == ws && h->d_hc) return 0;
-    hipFree(h->d_hc); hipFree(h->d_hm); hipFree(h->d_hu); hipFree(h->d_hz); hipFree(h->d_htab); hipFree(h->d_htr);
-    h->d_hc = h->d_hm = h->d_hu = h->d_hz = h->d_htab = h->d_htr = nullptr; h->hess_slots = h->hess_ws = 0;
-    const long per = hess_bytes_per_slot(h), P = 2L * h->L + 1, ntri = (long)h->nt * (h->nt + 1) / 2, NN = (long)h->Np * h->Np;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) total_b = (size_t)64 << 30;
-    long slots = (long)(0.25 * (double)total_b / (double)per);
-    if (slots > ws) slots = ws;
-    if (slots < 1) slots = 1;
-    for (;;) {
-        hipError_t e = hipMalloc(&h->d_hc, sizeof(double) * NN * slots);
-        if (e == hipSuccess) e = hipMalloc(&h->d_hm, sizeof(double) * NN * P * slots);
-        if (e == hipSuccess) e = hipMalloc(&h->d_hu, sizeof(double) * h->Np * P * slots);
-        if (e == hipSuccess) e = hipMalloc(&h->d_hz, sizeof(double) * h->Np * P * slots);
-        if (e == hipSuccess) e = hipMalloc(&h->d_htab, sizeof(double) * ntri * 6 * h->L * h->L * slots);
-        if (e == hipSuccess) e = hipMalloc(&h->d_htr, sizeof(double) * ntri * P * P * slots);
-        if (e == hipSuccess) break;
-        (void)hipGetLastError();
+    auto release = [h] {
         hipFree(h->d_hc); hipFree(h->d_hm); hipFree(h->d_hu); hipFree(h->d_hz); hipFree(h->d_htab); hipFree(h->d_htr);
         h->d_hc = h->d_hm = h->d_hu = h->d_hz = h->d_htab = h->d_htr = nullptr;
-        if (e != hipErrorOutOfMemory || slots <= 1)
-            return fail(h, GPCC_ERR_HIP, "Hessian buffers of %ld slots (%ld bytes each): %s", slots, per, hipGetErrorString(e));
-        slots /= 2;
-    }
+    };
+    release();
+    h->hess_slots = h->hess_ws = 0;
+    const long per = hess_bytes_per_slot(h), P = 2L * h->L + 1, ntri = (long)h->nt * (h->nt + 1) / 2, NN = (long)h->Np * h->Np;
+    long slots = 0;
+    const int rc = alloc_slots(h, "Hessian buffers", per, ws, slots, [&](long n) {
+        hipError_t e = hipMalloc(&h->d_hc, sizeof(double) * NN * n);
+        if (e == hipSuccess) e = hipMalloc(&h->d_hm, sizeof(double) * NN * P * n);
+        if (e == hipSuccess) e = hipMalloc(&h->d_hu, sizeof(double) * h->Np * P * n);
+        if (e == hipSuccess) e = hipMalloc(&h->d_hz, sizeof(double) * h->Np * P * n);
+        if (e == hipSuccess) e = hipMalloc(&h->d_htab, sizeof(double) * ntri * 6 * h->L * h->L * n);
+        if (e == hipSuccess) e = hipMalloc(&h->d_htr, sizeof(double) * ntri * P * P * n);
+        if (e != hipSuccess) release();
+        return e;
+    });
+    if (rc) return rc;
     h->hess_slots = slots;
     h->hess_ws = ws;
-    if (slots < ws) {   // a note, not an error
-        char buf[256];
-        snprintf(buf, sizeof buf, "note: the Hessian's buffers (%ld bytes per slot) fit %ld of the %ld workspace slots; its groups run "
-                 "through %ld slots (results unchanged)", per, slots, ws, slots);
-        h->err = buf;
-    }
-    return 0;
-}
-
-template <int KID>
-static void launch_hess_kernels(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g, const GpccHessBuf &hb, double *d_hess,
-                                double *d_fisher, hipStream_t s)
-{
-    const int ntri = c.nt * (c.nt + 1) / 2;
-    gpcc_hess_ctab<KID><<<g.cnt * ntri, 512, 0, s>>>(c, g, h->d_gw, hb);
-    gpcc_hess_u<KID><<<g.cnt * c.nt, GPCC_TILE, 0, s>>>(c, g, h->d_gw, hb);
-    gpcc_hess_z<<<g.cnt * c.nt, GPCC_TILE, 0, s>>>(c, g, hb);
-    gpcc_hess_gemm<KID><<<(unsigned)((long)g.cnt * hb.Pa * c.nt * c.nt), 512, 0, s>>>(c, g, hb);
-    gpcc_hess_trace<<<g.cnt * ntri, 256, 0, s>>>(c, g, hb);
-    gpcc_hess_finish<<<g.cnt, 512, 0, s>>>(c, g, hb, d_hess, d_fisher);
-}
-
-static int enqueue_hess_group(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g, const GpccHessBuf &hb, double *d_hess,
-                              double *d_fisher, hipStream_t s)
-{
-    int rc = enqueue_grad_group(h, c, g, h->d_ggrad, s);
-    if (rc) return rc;
-    switch (c.kernel_id) {
-    case 0: launch_hess_kernels<0>(h, c, g, hb, d_hess, d_fisher, s); break;
-    case 1: launch_hess_kernels<1>(h, c, g, hb, d_hess, d_fisher, s); break;
-    case 2: launch_hess_kernels<2>(h, c, g, hb, d_hess, d_fisher, s); break;
-    default: launch_hess_kernels<3>(h, c, g, hb, d_hess, d_fisher, s); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
     return 0;
 }
 
@@ -1826,42 +1908,24 @@ static int loglik_hess(gpcc_handle_t h, int hyper, int M, const double *delays, 
     if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
     if (M == 0) return 0;
     if (!delays || !alpha || !rho || !loglik || !grad || !hess || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
-    if (h->is_multi()) {   // device_ids[0], like the gradient
-        const int rc = loglik_hess(primary(h), hyper, M, delays, alpha, rho, loglik, grad, hess, fisher, info);
-        return rc ? fail(h, rc, "%s", primary(h)->err.c_str()) : 0;
-    }
-    if (h->precision == GPCC_PRECISION_FP32) {   // always fp64: on the handle's fp64 twin
-        int rc = ensure_fb(h, 0);
-        if (rc) return rc;
-        rc = loglik_hess(h->fb, hyper, M, delays, alpha, rho, loglik, grad, hess, fisher, info);
-        return rc ? fail(h, rc, "fp32 handle, Hessian in fp64: %s", h->fb->err.c_str()) : 0;
-    }
+    int rc = 0;
+    if (route_fp64(h, "Hessian", rc, [&](gpcc_handle_t o) {
+            return loglik_hess(o, hyper, M, delays, alpha, rho, loglik, grad, hess, fisher, info);
+        }))
+        return rc;
     GPCC_ON_DEVICE(h, h->device);
-    int rc = ensure_workspace(h);
+    const long W = 2L * h->L + 1, W2 = W * W;
+    double *dd, *da, *dr;
+    rc = ensure_workspace(h);
     if (!rc) rc = ensure_grad(h);
     if (!rc) rc = ensure_hess(h);
     if (!rc) rc = ensure_staging(h, M);
+    if (!rc) rc = grow_buf(h, &h->d_ggrad, &h->ggrad_cap, W * M);
+    if (!rc) rc = grow_buf(h, &h->d_hout, &h->hout_cap, 2 * W2 * M);
+    if (!rc) rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
     if (rc) return rc;
-    const long W = 2L * h->L + 1, W2 = W * W;
-    if (M > h->ggrad_cap) {
-        hipFree(h->d_ggrad);
-        h->d_ggrad = nullptr; h->ggrad_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_ggrad, sizeof(double) * W * M));
-        h->ggrad_cap = M;
-    }
-    if (M > h->hout_cap) {
-        hipFree(h->d_hout);
-        h->d_hout = nullptr; h->hout_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_hout, sizeof(double) * 2 * W2 * M));
-        h->hout_cap = M;
-    }
     const long Pa = hyper ? h->L + 1 : W, Pa2 = Pa * Pa;   // the block: a prefix of the same allocation
     double *d_hess = h->d_hout, *d_fisher = h->d_hout + Pa2 * M;
-    const long ML = (long)M * h->L;
-    double *dd = h->d_par, *da = h->d_par + ML, *dr = h->d_par + 2 * ML;
-    HIPCHK(h, hipMemcpyAsync(dd, delays, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
-    HIPCHK(h, hipMemcpyAsync(da, alpha, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
-    HIPCHK(h, hipMemcpyAsync(dr, rho, sizeof(double) * M, hipMemcpyHostToDevice, h->main_stream));
     GpccCtx c = make_ctx(h);
     c.linv = h->d_glinv;
     c.linv_keep = 1;
@@ -1872,34 +1936,22 @@ static int loglik_hess(gpcc_handle_t h, int hyper, int M, const double *delays, 
     hb.off[0] = 0;
     for (int l = 0; l < GPCC_MAXL; ++l) hb.off[l + 1] = hb.off[l] + (l < h->L ? h->Nl[l] : 0);
     // groups of at most hess_slots evaluations, on as many streams as the Hessian's slots hold
-    const int cs = (int)(h->hess_slots < h->ws_slots ? h->hess_slots : h->ws_slots);
-    int S = h->prof ? 1 : (int)(h->hess_slots / cs);
-    if (S > h->ws_streams) S = h->ws_streams;
-    const int ngroups = (M + cs - 1) / cs, used = ngroups < S ? ngroups : S;
-    HIPCHK(h, hipEventRecord(h->ev_start, h->main_stream));
-    for (int s = 0; s < used; ++s) HIPCHK(h, hipStreamWaitEvent(h->str[s], h->ev_start, 0));
-    for (int gi = 0; gi < ngroups && !rc; ++gi) {
-        const int s = gi % S;
-        GpccGroup g;
-        g.delays = dd; g.alpha = da; g.rho = dr;
-        g.out_loglik = h->d_out; g.out_info = h->d_oinfo; g.out_cond = nullptr;
-        g.first = gi * cs;
-        g.slot0 = s * cs;
-        g.cnt = (M - g.first < cs) ? (M - g.first) : cs;
-        g.spread = 0;
-        rc = enqueue_hess_group(h, c, g, hb, d_hess, d_fisher, h->str[s]);
-    }
-    if (rc) {   // nothing may be left running when the error is returned
-        const std::string msg = h->err;
-        for (int s = 0; s < used; ++s) (void)hipStreamSynchronize(h->str[s]);
-        (void)hipGetLastError();
-        h->err = msg;
-        return rc;
-    }
-    for (int s = 0; s < used; ++s) {
-        HIPCHK(h, hipEventRecord(h->ev_done[s], h->str[s]));
-        HIPCHK(h, hipStreamWaitEvent(h->main_stream, h->ev_done[s], 0));
-    }
+    rc = run_groups(h, M, h->hess_slots, dd, da, dr, [&](const GpccGroup &g, hipStream_t s, int, int) {
+        const int r = enqueue_grad_group(h, c, g, s);
+        if (r) return r;
+        const int ntri = c.nt * (c.nt + 1) / 2;
+        with_kernel_id(c.kernel_id, [&](auto kid) {
+            constexpr int KID = decltype(kid)::value;
+            gpcc_hess_ctab<KID><<<g.cnt * ntri, 512, 0, s>>>(c, g, h->d_gw, hb);
+            gpcc_hess_u<KID><<<g.cnt * c.nt, GPCC_TILE, 0, s>>>(c, g, h->d_gw, hb);
+            gpcc_hess_z<<<g.cnt * c.nt, GPCC_TILE, 0, s>>>(c, g, hb);
+            gpcc_hess_gemm<KID><<<(unsigned)((long)g.cnt * hb.Pa * c.nt * c.nt), 512, 0, s>>>(c, g, hb);
+            gpcc_hess_trace<<<g.cnt * ntri, 256, 0, s>>>(c, g, hb);
+            gpcc_hess_finish<<<g.cnt, 512, 0, s>>>(c, g, hb, d_hess, d_fisher);
+        });
+        return launch_status(h, "kernel launch failed");
+    });
+    if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, h->main_stream));
     HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, h->main_stream));
     HIPCHK(h, hipMemcpyAsync(grad, h->d_ggrad, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
@@ -1927,7 +1979,7 @@ extern "C" int gpcc_loglik_hess_hyper_batch(gpcc_handle_t h, int M, const double
 // on the same slots.  The buffers are allocated on the first call (ensure_pred) and grow with the test points; a handle that never
 // predicts holds none of them.
 // ------------------------------------------------------------------------------------------
-static int ensure_pred(gpcc_handle_t h, long Tp, long M)
+static int ensure_pred(gpcc_handle_t h, long Tp)
 {
     const long slots = (long)h->ws_streams * h->ws_slots;
     if (!(h->pred_slots == slots && h->pred_tp >= Tp && h->d_ppart)) {
@@ -1942,20 +1994,8 @@ static int ensure_pred(gpcc_handle_t h, long Tp, long M)
         h->pred_slots = slots;
         h->pred_tp = Tp;
     }
-    if (M > h->pw_cap) {
-        hipFree(h->d_pw);
-        h->d_pw = nullptr; h->pw_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_pw, sizeof(double) * M));
-        h->pw_cap = M;
-    }
     if (!h->ev_pmix) HIPCHK(h, hipEventCreateWithFlags(&h->ev_pmix, hipEventDisableTiming));
     return 0;
-}
-
-template <int KID>
-static void launch_pred_tiles(const GpccCtx &c, const GpccGroup &g, const GpccPredBuf &pb, hipStream_t s)
-{
-    gpcc_pred_tiles<KID><<<(unsigned)((long)g.cnt * c.nt * pb.ntT), 512, 0, s>>>(c, g, pb);
 }
 
 extern "C" int gpcc_predict_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
@@ -1969,40 +2009,23 @@ extern "C" int gpcc_predict_batch(gpcc_handle_t h, int M, const double *delays, 
     if (weights && (!mix_mu || !mix_var)) return fail(h, GPCC_ERR_ARGUMENT, "weights given: mix_mu and mix_var are required");
     if (!weights && (mix_mu || mix_var)) return fail(h, GPCC_ERR_ARGUMENT, "mix_mu and mix_var need weights");
     if (!weights && !mu_out) return fail(h, GPCC_ERR_ARGUMENT, "NULL mu_out / var_out without weights: nothing to return");
-    if (h->is_multi()) {   // device_ids[0], like the gradient
-        const int rc = gpcc_predict_batch(primary(h), M, delays, alpha, rho, Ntest, ttest, weights, mu_out, var_out, mix_mu, mix_var,
-                                          loglik, info);
-        return rc ? fail(h, rc, "%s", primary(h)->err.c_str()) : 0;
-    }
-    if (h->precision == GPCC_PRECISION_FP32) {   // always fp64: on the handle's fp64 twin
-        int rc = ensure_fb(h, 0);
-        if (rc) return rc;
-        rc = gpcc_predict_batch(h->fb, M, delays, alpha, rho, Ntest, ttest, weights, mu_out, var_out, mix_mu, mix_var, loglik, info);
-        return rc ? fail(h, rc, "fp32 handle, predictive in fp64: %s", h->fb->err.c_str()) : 0;
-    }
+    int rc = 0;
+    if (route_fp64(h, "predictive", rc, [&](gpcc_handle_t o) {
+            return gpcc_predict_batch(o, M, delays, alpha, rho, Ntest, ttest, weights, mu_out, var_out, mix_mu, mix_var, loglik, info);
+        }))
+        return rc;
     long T = 0;
-    for (int l = 0; l < h->L; ++l) { if (Ntest[l] < 0) return fail(h, GPCC_ERR_ARGUMENT, "negative Ntest"); T += Ntest[l]; }
-    if (T <= 0 || T > 32768) return fail(h, GPCC_ERR_ARGUMENT, "total number of test points %ld outside [1, 32768]", T);
-    // the normalised weights p_m = w_m / sum w (sums in row order), checked before any device work
-    std::vector<double> p;
-    if (weights) {
-        double sw = 0.0;
-        for (int m = 0; m < M; ++m) {
-            if (!std::isfinite(weights[m]) || weights[m] < 0.0)
-                return fail(h, GPCC_ERR_ARGUMENT, "weight %d = %g: weights must be finite and >= 0", m, weights[m]);
-            sw += weights[m];
-        }
-        if (!(sw > 0.0) || !std::isfinite(sw)) return fail(h, GPCC_ERR_ARGUMENT, "the weights sum to %g: need a finite sum > 0", sw);
-        p.resize(M);
-        for (int m = 0; m < M; ++m) p[m] = weights[m] / sw;
-    }
-    if (M == 0) return 0;
+    std::vector<double> p;   // the normalised weights p_m = w_m / sum w
+    rc = count_test_points(h, Ntest, T);
+    if (!rc) rc = mixture_weights(h, M, weights, false, p);
+    if (rc || M == 0) return rc;
     GPCC_ON_DEVICE(h, h->device);
     const int ntT = (int)((T + GPCC_TILE - 1) / GPCC_TILE);
     const long Tp = (long)ntT * GPCC_TILE;
-    int rc = ensure_workspace(h);
+    rc = ensure_workspace(h);
     if (!rc) rc = ensure_grad(h);
-    if (!rc) rc = ensure_pred(h, Tp, weights ? M : 0);
+    if (!rc) rc = ensure_pred(h, Tp);
+    if (!rc && weights) rc = grow_buf(h, &h->d_pw, &h->pw_cap, M);
     if (!rc) rc = ensure_staging(h, M);
     if (rc) return rc;
     std::vector<double> tt(Tp, 0.0);
@@ -2012,12 +2035,10 @@ extern "C" int gpcc_predict_batch(gpcc_handle_t h, int M, const double *delays, 
         for (int l = 0; l < h->L; ++l)
             for (int n = 0; n < Ntest[l]; ++n, ++o) { tt[o] = ttest[o]; tb[o] = l; }
     }
-    const long ML = (long)M * h->L;
-    double *dd = h->d_par, *da = h->d_par + ML, *dr = h->d_par + 2 * ML;
+    double *dd, *da, *dr;
+    rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
+    if (rc) return rc;
     hipStream_t ms = h->main_stream;
-    HIPCHK(h, hipMemcpyAsync(dd, delays, sizeof(double) * ML, hipMemcpyHostToDevice, ms));
-    HIPCHK(h, hipMemcpyAsync(da, alpha, sizeof(double) * ML, hipMemcpyHostToDevice, ms));
-    HIPCHK(h, hipMemcpyAsync(dr, rho, sizeof(double) * M, hipMemcpyHostToDevice, ms));
     HIPCHK(h, hipMemcpyAsync(h->d_ptt, tt.data(), sizeof(double) * Tp, hipMemcpyHostToDevice, ms));
     HIPCHK(h, hipMemcpyAsync(h->d_ptb, tb.data(), sizeof(int) * Tp, hipMemcpyHostToDevice, ms));
     if (weights) {
@@ -2032,38 +2053,22 @@ extern "C" int gpcc_predict_batch(gpcc_handle_t h, int M, const double *delays, 
     pb.part = h->d_ppart; pb.mu = h->d_pmu; pb.var = h->d_pvar; pb.mix = h->d_pmix;
     pb.T = (int)T; pb.Tp = (int)Tp; pb.ntT = ntT;
     for (int l = 0; l < GPCC_MAXL; ++l) pb.mean_b[l] = (l < h->L) ? h->mean_b[l] : 0.0;
-    const int S = h->prof ? 1 : h->ws_streams, cs = h->ws_slots;
-    const int ngroups = (M + cs - 1) / cs, used = ngroups < S ? ngroups : S;
-    HIPCHK(h, hipEventRecord(h->ev_start, ms));
-    for (int s = 0; s < used; ++s) HIPCHK(h, hipStreamWaitEvent(h->str[s], h->ev_start, 0));
-    for (int gi = 0; gi < ngroups && !rc; ++gi) {
-        const int s = gi % S;
-        hipStream_t st = h->str[s];
-        GpccGroup g0;
-        g0.delays = dd; g0.alpha = da; g0.rho = dr;
-        g0.out_loglik = h->d_out; g0.out_info = h->d_oinfo; g0.out_cond = nullptr;
-        g0.first = gi * cs;
-        g0.slot0 = s * cs;
-        g0.cnt = (M - g0.first < cs) ? (M - g0.first) : cs;
-        g0.spread = 0;
-        const GpccGroup g = grad_group(g0);
+    rc = run_groups(h, M, (long)h->ws_streams * h->ws_slots, dd, da, dr, [&](const GpccGroup &g, hipStream_t st, int gi, int ngroups) {
         enqueue_grad_inverse(h, c, g, st);
-        switch (c.kernel_id) {
-        case 0: launch_pred_tiles<0>(c, g, pb, st); break;
-        case 1: launch_pred_tiles<1>(c, g, pb, st); break;
-        case 2: launch_pred_tiles<2>(c, g, pb, st); break;
-        default: launch_pred_tiles<3>(c, g, pb, st); break;
-        }
+        with_kernel_id(c.kernel_id, [&](auto kid) {
+            gpcc_pred_tiles<decltype(kid)::value><<<(unsigned)((long)g.cnt * c.nt * ntT), 512, 0, st>>>(c, g, pb);
+        });
         gpcc_pred_finish<<<g.cnt * ntT, GPCC_TILE, 0, st>>>(c, g, pb);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { rc = fail(h, GPCC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e)); break; }
+        const int r = launch_status(h, "kernel launch failed");
+        if (r) return r;
+        hipError_t e = hipSuccess;
         if (mu_out) {   // the group's rows (stride Tp on the device, T in the caller's arrays)
             e = hipMemcpy2DAsync(mu_out + (long)g.first * T, sizeof(double) * T, h->d_pmu + (long)g.slot0 * Tp, sizeof(double) * Tp,
                                  sizeof(double) * T, g.cnt, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess)
                 e = hipMemcpy2DAsync(var_out + (long)g.first * T, sizeof(double) * T, h->d_pvar + (long)g.slot0 * Tp, sizeof(double) * Tp,
                                      sizeof(double) * T, g.cnt, hipMemcpyDeviceToHost, st);
-            if (e != hipSuccess) { rc = fail(h, GPCC_ERR_HIP, "predictive rows: %s", hipGetErrorString(e)); break; }
+            if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "predictive rows: %s", hipGetErrorString(e));
         }
         if (weights) {   // after the previous group's mixture step, whichever stream ran it
             if (gi > 0) e = hipStreamWaitEvent(st, h->ev_pmix, 0);
@@ -2072,20 +2077,11 @@ extern "C" int gpcc_predict_batch(gpcc_handle_t h, int M, const double *delays, 
                 e = hipGetLastError();
             }
             if (e == hipSuccess) e = hipEventRecord(h->ev_pmix, st);
-            if (e != hipSuccess) { rc = fail(h, GPCC_ERR_HIP, "predictive mixture: %s", hipGetErrorString(e)); break; }
+            if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "predictive mixture: %s", hipGetErrorString(e));
         }
-    }
-    if (rc) {   // nothing may be left running when the error is returned
-        const std::string msg = h->err;
-        for (int s = 0; s < used; ++s) (void)hipStreamSynchronize(h->str[s]);
-        (void)hipGetLastError();
-        h->err = msg;
-        return rc;
-    }
-    for (int s = 0; s < used; ++s) {
-        HIPCHK(h, hipEventRecord(h->ev_done[s], h->str[s]));
-        HIPCHK(h, hipStreamWaitEvent(ms, h->ev_done[s], 0));
-    }
+        return 0;
+    });
+    if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
     HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
     if (weights) {
@@ -2118,44 +2114,28 @@ static int ensure_heldout(gpcc_handle_t h, long nta, long M)
         hipFree(h->d_xtile); hipFree(h->d_xpts); hipFree(h->d_xband); hipFree(h->d_xinfo);
         h->d_xtile = h->d_xpts = nullptr; h->d_xband = h->d_xinfo = nullptr; h->held_slots = h->held_ws = h->held_nta = 0;
         const long per = heldout_bytes_per_slot(nta), Npa = nta * GPCC_TILE;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) total_b = (size_t)64 << 30;
-        long slots = (long)(0.25 * (double)total_b / (double)per);
-        if (slots > ws) slots = ws;
-        if (slots < 1) slots = 1;
         HIPCHK(h, hipMalloc(&h->d_xpts, sizeof(double) * 3 * Npa));
         HIPCHK(h, hipMalloc(&h->d_xband, sizeof(int) * Npa));
-        for (;;) {
-            hipError_t e = hipMalloc(&h->d_xtile, (size_t)(per - (long)sizeof(int)) * slots);
-            if (e == hipSuccess) e = hipMalloc(&h->d_xinfo, sizeof(int) * slots);
-            if (e == hipSuccess) break;
-            (void)hipGetLastError();
-            hipFree(h->d_xtile); hipFree(h->d_xinfo);
-            h->d_xtile = nullptr; h->d_xinfo = nullptr;
-            if (e != hipErrorOutOfMemory || slots <= 1)
-                return fail(h, GPCC_ERR_HIP, "held-out workspace of %ld slots (%ld bytes each, %ld test tile columns): %s", slots, per,
-                            nta - h->nt, hipGetErrorString(e));
-            slots /= 2;
-        }
+        long slots = 0;
+        const int rc = alloc_slots(h, "held-out buffers", per, ws, slots, [&](long n) {
+            hipError_t e = hipMalloc(&h->d_xtile, (size_t)(per - (long)sizeof(int)) * n);
+            if (e == hipSuccess) e = hipMalloc(&h->d_xinfo, sizeof(int) * n);
+            if (e != hipSuccess) {
+                hipFree(h->d_xtile); hipFree(h->d_xinfo);
+                h->d_xtile = nullptr; h->d_xinfo = nullptr;
+            }
+            return e;
+        });
+        if (rc) return rc;
         h->held_slots = slots;
         h->held_ws = ws;
         h->held_nta = nta;
-        if (slots < ws) {   // a note, not an error
-            char buf[256];
-            snprintf(buf, sizeof buf, "note: the held-out workspace (%ld bytes per slot) fits %ld of the %ld workspace slots; its groups run "
-                     "through %ld slots (results unchanged)", per, slots, ws, slots);
-            h->err = buf;
-        }
     }
-    if (M > h->hld_cap) {
-        hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xscr); hipFree(h->d_xscri);
-        h->d_xhld = h->d_xw = h->d_xscr = nullptr; h->d_xscri = nullptr; h->hld_cap = 0;
-        HIPCHK(h, hipMalloc(&h->d_xhld, sizeof(double) * M));
-        HIPCHK(h, hipMalloc(&h->d_xw, sizeof(double) * M));
-        HIPCHK(h, hipMalloc(&h->d_xscr, sizeof(double) * M));
-        HIPCHK(h, hipMalloc(&h->d_xscri, sizeof(int) * M));
-        h->hld_cap = M;
-    }
+    int rc = grow_buf(h, &h->d_xhld, &h->hld_cap, M);
+    if (!rc) rc = grow_buf(h, &h->d_xw, &h->xw_cap, M);
+    if (!rc) rc = grow_buf(h, &h->d_xscr, &h->xscr_cap, M);
+    if (!rc) rc = grow_buf(h, &h->d_xscri, &h->xscri_cap, M);
+    if (rc) return rc;
     if (!h->d_xmix) HIPCHK(h, hipMalloc(&h->d_xmix, sizeof(double) * 4));
     if (!h->ev_hmix) HIPCHK(h, hipEventCreateWithFlags(&h->ev_hmix, hipEventDisableTiming));
     return 0;
@@ -2210,34 +2190,18 @@ static GpccCtx heldout_ctx(gpcc_handle_t h, int nta)
     return c;
 }
 
-// one group: assembly of the augmented systems, the left-looking launch-per-step factorisation over all nta tile columns (the first
-// nt exactly as enqueue_grad_inverse runs them: the training loglik and info of the last training step land in g.out_*; the trailing
-// steps run with ct, whose last step writes into the scratch outputs of gt), and the finish
-static int enqueue_heldout_group(gpcc_handle_t h, const GpccCtx &c, const GpccCtx &ct, const GpccGroup &g, const GpccGroup &gt,
-                                 const GpccHeldBuf &hb, hipStream_t s)
+// one group (g: from run_groups): assembly of the augmented systems, the left-looking launch-per-step factorisation over all nta tile
+// columns (the first nt exactly as enqueue_grad_inverse runs them: the training loglik and info of the last training step land in
+// g.out_*; the trailing steps run with ct, whose last step writes into the scratch outputs of gt), and the finish
+static int enqueue_heldout_group(gpcc_handle_t h, const GpccCtx &c, const GpccGroup &g, const GpccHeldBuf &hb, hipStream_t s)
 {
-    const int cnt8 = g.spread ? g.cnt : 8 * ((g.cnt + 7) / 8);
-    launch_assemble(h, c, g, s, false, false);
-    for (int k = 0; k < c.nt; ++k) {
-        const bool train = k < c.nt_fact;
-        if (k > 0) {
-            ProfScope pr(h, GPCC_PROF_PANEL_UPDATE, s);
-            gpcc_panel_update<double, false><<<cnt8 * (c.nt - k), GPCC_GEMM_THREADS, GPCC_GEMM_LDS_BYTES, s>>>(c, g, k, k, 0);
-        }
-        {
-            ProfScope pr(h, GPCC_PROF_DIAG, s);
-            if (train) gpcc_diag_factor<double><<<g.cnt, GPCC_DIAG_THREADS, GPCC_DIAG_LDS_BYTES, s>>>(c, g, k);
-            else gpcc_diag_factor<double><<<g.cnt, GPCC_DIAG_THREADS, GPCC_DIAG_LDS_BYTES, s>>>(ct, gt, k);
-        }
-        if (k < c.nt - 1) {
-            ProfScope pr(h, GPCC_PROF_TRSM, s);
-            gpcc_panel_trsm<double><<<cnt8 * (c.nt - k - 1), GPCC_GEMM_THREADS, GPCC_GEMM_LDS_BYTES, s>>>(c, g, k);
-        }
-    }
+    GpccCtx ct = c;
+    ct.nt_fact = c.nt;
+    GpccGroup gt = g;
+    gt.out_loglik = h->d_xscr; gt.out_info = h->d_xscri;
+    enqueue_factor_steps(h, c, g, ct, gt, s);
     gpcc_heldout_finish<<<g.cnt, GPCC_HELD_THREADS, 0, s>>>(c, g, hb);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-    return 0;
+    return launch_status(h, "kernel launch failed");
 }
 
 extern "C" int gpcc_heldout_loglik_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
@@ -2251,103 +2215,50 @@ extern "C" int gpcc_heldout_loglik_batch(gpcc_handle_t h, int M, const double *d
     if (weights && !mix_heldout) return fail(h, GPCC_ERR_ARGUMENT, "weights given: mix_heldout is required");
     if (!weights && mix_heldout) return fail(h, GPCC_ERR_ARGUMENT, "mix_heldout needs weights");
     if (!weights && !heldout) return fail(h, GPCC_ERR_ARGUMENT, "NULL heldout without weights: nothing to return");
-    if (h->is_multi()) {   // device_ids[0], like the gradient
-        const int rc = gpcc_heldout_loglik_batch(primary(h), M, delays, alpha, rho, Ntest, ttest, ytest, sigmatest, weights, heldout,
-                                                 mix_heldout, loglik, info);
-        return rc ? fail(h, rc, "%s", primary(h)->err.c_str()) : 0;
-    }
-    if (h->precision == GPCC_PRECISION_FP32) {   // always fp64: on the handle's fp64 twin
-        int rc = ensure_fb(h, 0);
-        if (rc) return rc;
-        rc = gpcc_heldout_loglik_batch(h->fb, M, delays, alpha, rho, Ntest, ttest, ytest, sigmatest, weights, heldout, mix_heldout,
-                                       loglik, info);
-        return rc ? fail(h, rc, "fp32 handle, held-out log-likelihood in fp64: %s", h->fb->err.c_str()) : 0;
-    }
+    int rc = 0;
+    if (route_fp64(h, "held-out log-likelihood", rc, [&](gpcc_handle_t o) {
+            return gpcc_heldout_loglik_batch(o, M, delays, alpha, rho, Ntest, ttest, ytest, sigmatest, weights, heldout, mix_heldout,
+                                             loglik, info);
+        }))
+        return rc;
     long T = 0;
-    for (int l = 0; l < h->L; ++l) { if (Ntest[l] < 0) return fail(h, GPCC_ERR_ARGUMENT, "negative Ntest"); T += Ntest[l]; }
-    if (T <= 0 || T > 32768) return fail(h, GPCC_ERR_ARGUMENT, "total number of test points %ld outside [1, 32768]", T);
-    // the normalised weights p_m = w_m / sum w (sums in row order), checked before any device work (gpcc_predict_batch's rules)
-    std::vector<double> p;
-    if (weights) {
-        double sw = 0.0;
-        for (int m = 0; m < M; ++m) {
-            if (!std::isfinite(weights[m]) || weights[m] < 0.0)
-                return fail(h, GPCC_ERR_ARGUMENT, "weight %d = %g: weights must be finite and >= 0", m, weights[m]);
-            sw += weights[m];
-        }
-        if (!(sw > 0.0) || !std::isfinite(sw)) return fail(h, GPCC_ERR_ARGUMENT, "the weights sum to %g: need a finite sum > 0", sw);
-        p.resize(M);
-        for (int m = 0; m < M; ++m) p[m] = weights[m] / sw;
-    }
-    if (M == 0) return 0;
+    std::vector<double> p;   // the normalised weights p_m = w_m / sum w
+    rc = count_test_points(h, Ntest, T);
+    if (!rc) rc = mixture_weights(h, M, weights, false, p);
+    if (rc || M == 0) return rc;
     GPCC_ON_DEVICE(h, h->device);
     const int nta = h->nt + (int)((T + GPCC_TILE - 1) / GPCC_TILE);
     const long Npa = (long)nta * GPCC_TILE;
-    int rc = ensure_workspace(h);
+    rc = ensure_workspace(h);
     if (!rc) rc = ensure_heldout(h, nta, M);
     if (!rc) rc = ensure_staging(h, M);
     if (rc) return rc;
     std::vector<double> pts;
     std::vector<int> band;
     heldout_points(h, Npa, Ntest, ttest, ytest, sigmatest, pts, band);
-    const long ML = (long)M * h->L;
-    double *dd = h->d_par, *da = h->d_par + ML, *dr = h->d_par + 2 * ML;
+    double *dd, *da, *dr;
+    rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
+    if (rc) return rc;
     hipStream_t ms = h->main_stream;
-    HIPCHK(h, hipMemcpyAsync(dd, delays, sizeof(double) * ML, hipMemcpyHostToDevice, ms));
-    HIPCHK(h, hipMemcpyAsync(da, alpha, sizeof(double) * ML, hipMemcpyHostToDevice, ms));
-    HIPCHK(h, hipMemcpyAsync(dr, rho, sizeof(double) * M, hipMemcpyHostToDevice, ms));
     HIPCHK(h, hipMemcpyAsync(h->d_xpts, pts.data(), sizeof(double) * pts.size(), hipMemcpyHostToDevice, ms));
     HIPCHK(h, hipMemcpyAsync(h->d_xband, band.data(), sizeof(int) * Npa, hipMemcpyHostToDevice, ms));
     if (weights) HIPCHK(h, hipMemcpyAsync(h->d_xw, p.data(), sizeof(double) * M, hipMemcpyHostToDevice, ms));
-    const long slots = h->held_slots;
     const GpccCtx c = heldout_ctx(h, nta);
-    GpccCtx ct = c;
-    ct.nt_fact = nta;   // the trailing steps: the last one reports into the scratch outputs
     GpccHeldBuf hb;
     hb.hld = h->d_xhld; hb.mix = h->d_xmix; hb.T = (int)T; hb.N = h->N; hb.off = h->Np;
-    const int cs = (int)(slots < h->ws_slots ? slots : h->ws_slots);
-    int S = h->prof ? 1 : (int)(slots / cs);
-    if (S > h->ws_streams) S = h->ws_streams;
-    const int ngroups = (M + cs - 1) / cs, used = ngroups < S ? ngroups : S;
-    HIPCHK(h, hipEventRecord(h->ev_start, ms));
-    for (int s = 0; s < used; ++s) HIPCHK(h, hipStreamWaitEvent(h->str[s], h->ev_start, 0));
-    for (int gi = 0; gi < ngroups && !rc; ++gi) {
-        const int s = gi % S;
-        hipStream_t st = h->str[s];
-        GpccGroup g0;
-        g0.delays = dd; g0.alpha = da; g0.rho = dr;
-        g0.out_loglik = h->d_out; g0.out_info = h->d_oinfo; g0.out_cond = nullptr;
-        g0.first = gi * cs;
-        g0.slot0 = s * cs;
-        g0.cnt = (M - g0.first < cs) ? (M - g0.first) : cs;
-        g0.spread = 0;
-        const GpccGroup g = grad_group(g0);
-        GpccGroup gt = g;
-        gt.out_loglik = h->d_xscr; gt.out_info = h->d_xscri;
-        rc = enqueue_heldout_group(h, c, ct, g, gt, hb, st);
-        if (rc) break;
-        if (weights) {   // after the previous group's mixture step, whichever stream ran it
-            hipError_t e = hipSuccess;
-            if (gi > 0) e = hipStreamWaitEvent(st, h->ev_hmix, 0);
-            if (e == hipSuccess) {
-                gpcc_heldout_mix<<<1, 64, 0, st>>>(g, hb, h->d_xw, gi == 0 ? 1 : 0, gi == ngroups - 1 ? 1 : 0);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipEventRecord(h->ev_hmix, st);
-            if (e != hipSuccess) { rc = fail(h, GPCC_ERR_HIP, "held-out mixture: %s", hipGetErrorString(e)); break; }
+    rc = run_groups(h, M, h->held_slots, dd, da, dr, [&](const GpccGroup &g, hipStream_t st, int gi, int ngroups) {
+        const int r = enqueue_heldout_group(h, c, g, hb, st);
+        if (r || !weights) return r;
+        hipError_t e = hipSuccess;   // after the previous group's mixture step, whichever stream ran it
+        if (gi > 0) e = hipStreamWaitEvent(st, h->ev_hmix, 0);
+        if (e == hipSuccess) {
+            gpcc_heldout_mix<<<1, 64, 0, st>>>(g, hb, h->d_xw, gi == 0 ? 1 : 0, gi == ngroups - 1 ? 1 : 0);
+            e = hipGetLastError();
         }
-    }
-    if (rc) {   // nothing may be left running when the error is returned
-        const std::string msg = h->err;
-        for (int s = 0; s < used; ++s) (void)hipStreamSynchronize(h->str[s]);
-        (void)hipGetLastError();
-        h->err = msg;
-        return rc;
-    }
-    for (int s = 0; s < used; ++s) {
-        HIPCHK(h, hipEventRecord(h->ev_done[s], h->str[s]));
-        HIPCHK(h, hipStreamWaitEvent(ms, h->ev_done[s], 0));
-    }
+        if (e == hipSuccess) e = hipEventRecord(h->ev_hmix, st);
+        return e == hipSuccess ? 0 : fail(h, GPCC_ERR_HIP, "held-out mixture: %s", hipGetErrorString(e));
+    });
+    if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
     HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
     if (heldout) HIPCHK(h, hipMemcpyAsync(heldout, h->d_xhld, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
@@ -2361,18 +2272,6 @@ extern "C" int gpcc_heldout_loglik_batch(gpcc_handle_t h, int M, const double *d
 // the rows of mixture draws, compacts the drawn rows and builds each one's ascending list of draw indices; every drawn row then runs
 // the held-out group unchanged (test residual 0: its loglik and info are the held-out path's bits), the mean kernel and the draw tiles.
 // ------------------------------------------------------------------------------------------
-template <typename T>
-static int grow_buf(gpcc_handle_t h, T **p, long *cap, long n)
-{
-    if (n <= *cap) return 0;
-    hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HIPCHK(h, hipMalloc(p, sizeof(T) * (size_t)n));
-    *cap = n;
-    return 0;
-}
-
 extern "C" int gpcc_sample_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const int *Ntest,
                                  const double *ttest, const double *sigmatest, const double *weights, int S, unsigned long long seed,
                                  double *draws, int *draw_row, double *zeta, double *loglik, int *info)
@@ -2382,37 +2281,20 @@ extern "C" int gpcc_sample_batch(gpcc_handle_t h, int M, const double *delays, c
     if (S < 1) return fail(h, GPCC_ERR_ARGUMENT, "S=%d < 1", S);
     if (!delays || !alpha || !rho || !Ntest || !ttest || !draws || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
     if (weights && !draw_row) return fail(h, GPCC_ERR_ARGUMENT, "weights given: draw_row is required");
-    if (h->is_multi()) {   // device_ids[0], like the gradient
-        const int rc = gpcc_sample_batch(primary(h), M, delays, alpha, rho, Ntest, ttest, sigmatest, weights, S, seed, draws, draw_row,
-                                         zeta, loglik, info);
-        return rc ? fail(h, rc, "%s", primary(h)->err.c_str()) : 0;
-    }
-    if (h->precision == GPCC_PRECISION_FP32) {   // always fp64: on the handle's fp64 twin
-        int rc = ensure_fb(h, 0);
-        if (rc) return rc;
-        rc = gpcc_sample_batch(h->fb, M, delays, alpha, rho, Ntest, ttest, sigmatest, weights, S, seed, draws, draw_row, zeta, loglik,
-                               info);
-        return rc ? fail(h, rc, "fp32 handle, draws in fp64: %s", h->fb->err.c_str()) : 0;
-    }
+    int rc = 0;
+    if (route_fp64(h, "draws", rc, [&](gpcc_handle_t o) {
+            return gpcc_sample_batch(o, M, delays, alpha, rho, Ntest, ttest, sigmatest, weights, S, seed, draws, draw_row, zeta, loglik,
+                                     info);
+        }))
+        return rc;
     long T = 0;
-    for (int l = 0; l < h->L; ++l) { if (Ntest[l] < 0) return fail(h, GPCC_ERR_ARGUMENT, "negative Ntest"); T += Ntest[l]; }
-    if (T <= 0 || T > 32768) return fail(h, GPCC_ERR_ARGUMENT, "total number of test points %ld outside [1, 32768]", T);
+    rc = count_test_points(h, Ntest, T);
+    if (rc) return rc;
     const long D = weights ? (long)S : (long)M * S;   // output rows
     if (D > 0x7fffffffL) return fail(h, GPCC_ERR_ARGUMENT, "M S = %ld draws: at most 2^31 - 1 per call", D);
-    // the cumulative weights c_m (sums in row order), checked before any device work (gpcc_predict_batch's rules)
-    std::vector<double> cw;
-    if (weights) {
-        double sw = 0.0;
-        cw.resize(M);
-        for (int m = 0; m < M; ++m) {
-            if (!std::isfinite(weights[m]) || weights[m] < 0.0)
-                return fail(h, GPCC_ERR_ARGUMENT, "weight %d = %g: weights must be finite and >= 0", m, weights[m]);
-            sw += weights[m];
-            cw[m] = sw;
-        }
-        if (!(sw > 0.0) || !std::isfinite(sw)) return fail(h, GPCC_ERR_ARGUMENT, "the weights sum to %g: need a finite sum > 0", sw);
-    }
-    if (M == 0) return 0;
+    std::vector<double> cw;   // the cumulative weights c_m
+    rc = mixture_weights(h, M, weights, true, cw);
+    if (rc || M == 0) return rc;
     // the row of every draw, the drawn rows (compact, in row order) and each one's ascending draw list
     std::vector<int> ndraw(M, 0);
     if (weights) {
@@ -2453,7 +2335,7 @@ extern "C" int gpcc_sample_batch(gpcc_handle_t h, int M, const double *delays, c
     GPCC_ON_DEVICE(h, h->device);
     const int nta = h->nt + (int)((T + GPCC_TILE - 1) / GPCC_TILE), ntT = nta - h->nt;
     const long Npa = (long)nta * GPCC_TILE, Tp = (long)ntT * GPCC_TILE;
-    int rc = ensure_workspace(h);
+    rc = ensure_workspace(h);
     if (!rc) rc = ensure_heldout(h, nta, Mc);
     if (!rc) rc = ensure_staging(h, Mc);
     if (!rc) rc = grow_buf(h, &h->d_smean, &h->smean_cap, h->held_slots * Tp);
@@ -2473,10 +2355,7 @@ extern "C" int gpcc_sample_batch(gpcc_handle_t h, int M, const double *delays, c
     HIPCHK(h, hipMemcpyAsync(h->d_xband, band.data(), sizeof(int) * Npa, hipMemcpyHostToDevice, ms));
     HIPCHK(h, hipMemcpyAsync(h->d_slist, dlist.data(), sizeof(int) * D, hipMemcpyHostToDevice, ms));
     HIPCHK(h, hipMemcpyAsync(h->d_soff, doff.data(), sizeof(int) * (Mc + 1), hipMemcpyHostToDevice, ms));
-    const long slots = h->held_slots;
     const GpccCtx c = heldout_ctx(h, nta);
-    GpccCtx ct = c;
-    ct.nt_fact = nta;   // the trailing steps: the last one reports into the scratch outputs
     GpccHeldBuf hb;
     hb.hld = h->d_xhld; hb.mix = h->d_xmix; hb.T = (int)T; hb.N = h->N; hb.off = h->Np;   // (the held-out values: scratch here)
     GpccSampBuf sb;
@@ -2484,27 +2363,9 @@ extern "C" int gpcc_sample_batch(gpcc_handle_t h, int M, const double *delays, c
     sb.dlist = h->d_slist; sb.doff = h->d_soff; sb.seed = seed;
     sb.T = (int)T; sb.Tp = (int)Tp; sb.ntT = ntT; sb.ntr = h->nt; sb.S = S; sb.mixture = weights ? 1 : 0; sb.nblk = 1;
     for (int l = 0; l < GPCC_MAXL; ++l) sb.mean_b[l] = (l < h->L) ? h->mean_b[l] : 0.0;
-    const int cs = (int)(slots < h->ws_slots ? slots : h->ws_slots);
-    int NS = h->prof ? 1 : (int)(slots / cs);
-    if (NS > h->ws_streams) NS = h->ws_streams;
-    const int ngroups = (Mc + cs - 1) / cs, used = ngroups < NS ? ngroups : NS;
-    HIPCHK(h, hipEventRecord(h->ev_start, ms));
-    for (int s = 0; s < used; ++s) HIPCHK(h, hipStreamWaitEvent(h->str[s], h->ev_start, 0));
-    for (int gi = 0; gi < ngroups && !rc; ++gi) {
-        const int s = gi % NS;
-        hipStream_t st = h->str[s];
-        GpccGroup g0;
-        g0.delays = dd; g0.alpha = da; g0.rho = dr;
-        g0.out_loglik = h->d_out; g0.out_info = h->d_oinfo; g0.out_cond = nullptr;
-        g0.first = gi * cs;
-        g0.slot0 = s * cs;
-        g0.cnt = (Mc - g0.first < cs) ? (Mc - g0.first) : cs;
-        g0.spread = 0;
-        const GpccGroup g = grad_group(g0);
-        GpccGroup gt = g;
-        gt.out_loglik = h->d_xscr; gt.out_info = h->d_xscri;
-        rc = enqueue_heldout_group(h, c, ct, g, gt, hb, st);
-        if (rc) break;
+    rc = run_groups(h, Mc, h->held_slots, dd, da, dr, [&](const GpccGroup &g, hipStream_t st, int, int) {
+        const int r = enqueue_heldout_group(h, c, g, hb, st);
+        if (r) return r;
         GpccSampBuf sg = sb;
         for (int k = g.first; k < g.first + g.cnt; ++k) {
             const int nb = (doff[k + 1] - doff[k] + GPCC_TILE - 1) / GPCC_TILE;
@@ -2512,20 +2373,9 @@ extern "C" int gpcc_sample_batch(gpcc_handle_t h, int M, const double *delays, c
         }
         gpcc_sample_mean<<<g.cnt * ntT, 512, 0, st>>>(c, g, sg);
         gpcc_sample_tiles<<<(unsigned)((long)g.cnt * ntT * sg.nblk), 512, 0, st>>>(c, g, sg);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = fail(h, GPCC_ERR_HIP, "draw kernels: %s", hipGetErrorString(e));
-    }
-    if (rc) {   // nothing may be left running when the error is returned
-        const std::string msg = h->err;
-        for (int s = 0; s < used; ++s) (void)hipStreamSynchronize(h->str[s]);
-        (void)hipGetLastError();
-        h->err = msg;
-        return rc;
-    }
-    for (int s = 0; s < used; ++s) {
-        HIPCHK(h, hipEventRecord(h->ev_done[s], h->str[s]));
-        HIPCHK(h, hipStreamWaitEvent(ms, h->ev_done[s], 0));
-    }
+        return launch_status(h, "draw kernels");
+    });
+    if (rc) return rc;
     std::vector<double> cll(Mc);
     std::vector<int> cinfo(Mc);
     HIPCHK(h, hipMemcpyAsync(cll.data(), h->d_out, sizeof(double) * Mc, hipMemcpyDeviceToHost, ms));

@@ -100,9 +100,11 @@ def test_repeatable_across_batches_slots_and_precision():
         three = obj3.heldout_loglik_batch(delays, alpha, rho, *ts)
     with gpcc_amd.Objective(*data, gpcc_amd.matern32, precision="fp32") as o32:
         f32 = o32.heldout_loglik_batch(delays, alpha, rho, *ts)
+    with gpcc_amd.Objective(*data, gpcc_amd.matern32, devices=[0, 0]) as om:
+        multi = om.heldout_loglik_batch(delays, alpha, rho, *ts)
     assert (full[2] == 0).all() and np.array_equal(full[1], gl) and np.array_equal(full[2], gi)
     for k in range(3):
-        for other in (again, eight, three, f32):
+        for other in (again, eight, three, f32, multi):
             assert np.array_equal(full[k], other[k]), k
         assert np.array_equal(full[k][:7], seven[k]), k
         for i, one in zip((0, 6, 39), ones):

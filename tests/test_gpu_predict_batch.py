@@ -203,8 +203,11 @@ def test_fp32_handle_runs_the_fp64_twin():
         r64 = o64.predict_batch(delays, alpha, rho, ttest, weights=w)
     with gpcc_amd.Objective(*data, gpcc_amd.rbf, precision="fp32") as o32:
         r32 = o32.predict_batch(delays, alpha, rho, ttest, weights=w)
-    for a, b in zip(r64, r32):
-        assert np.array_equal(a, b)
+    with gpcc_amd.Objective(*data, gpcc_amd.rbf, devices=[0, 0]) as om:
+        rm = om.predict_batch(delays, alpha, rho, ttest, weights=w)
+    for other in (r32, rm):
+        for a, b in zip(r64, other):
+            assert np.array_equal(a, b)
 
 
 @pytest.mark.parametrize("N", [4095, 4096])

@@ -98,10 +98,12 @@ def test_invariance():
         three = obj3.sample_batch(delays, alpha, rho, tt, S, seed, sigmatest=st)
     with gpcc_amd.Objective(*data, gpcc_amd.matern32, precision="fp32") as o32:
         f32 = o32.sample_batch(delays, alpha, rho, tt, S, seed, sigmatest=st)
+    with gpcc_amd.Objective(*data, gpcc_amd.matern32, devices=[0, 0]) as om:
+        multi = om.sample_batch(delays, alpha, rho, tt, S, seed, sigmatest=st)
     assert (full[3] == 0).all() and np.isfinite(full[0]).all()
     assert np.array_equal(full[2], held[1]) and np.array_equal(full[3], held[2])
     for k in range(4):
-        for other in (again, eight, three, f32):
+        for other in (again, eight, three, f32, multi):
             assert np.array_equal(full[k], other[k]), k
         assert np.array_equal(full[k][:7 * S], seven[k]) if k < 2 else np.array_equal(full[k][:7], seven[k]), k
     for i in (0, 6, 39):
