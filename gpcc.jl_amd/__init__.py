@@ -3,7 +3,7 @@
 Public surface mirrors the reference for this path: the kernel tokens OU / rbf / matern32 /
 matern52, delayedCovariance, getprobabilities, and Objective (the objective(alpha, rho) closure
 of gpccfixdelay) -- all backed by csrc/libgpcc_hip.so through the C ABI of include/gpcc_hip.h."""
-from . import synthetic  # noqa: F401
+from . import markov, synthetic  # noqa: F401
 from ._capi import GpccError  # noqa: F401
 from .api import (KERNELS, OU, Kernel, Objective, PosDefException, build_info, delayedCovariance,  # noqa: F401
                   getprobabilities, matern32, matern52, mvnormal_logpdf, rbf, selftest)

@@ -42,6 +42,8 @@ SIGNATURES = {
     "gpcc_get_conditioning": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p]),
     "gpcc_loglik_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                          c_double_p, c_int_p]),
+    "gpcc_loglik_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
+                                                c_double_p, c_int_p]),
     "gpcc_loglik_grad_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                               c_double_p, c_double_p, c_int_p]),
     "gpcc_loglik_hess_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,

@@ -291,6 +291,16 @@ class Objective:
         self._chk(_capi.load().gpcc_loglik_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _ip(info)))
         return ll, info
 
+    def loglik_markov_batch(self, delays, alpha, rho):
+        """The same objective in linear time (gpcc_loglik_markov_batch: a Kalman filter over the observations merged by shifted time;
+        OU, matern32 and matern52 only) -> (loglik[M], info[M]).  info as loglik_batch, a positive value being the merged position of
+        the first predictive variance that is not positive.  rbf, or marginalise_b with more than 4 bands: GpccError (unsupported)."""
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        ll = np.empty(M, dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        self._chk(_capi.load().gpcc_loglik_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _ip(info)))
+        return ll, info
+
     def __call__(self, alpha, rho, delays):
         """objective(alpha, rho) for one delay vector, raising what the reference raises."""
         ll, info = self.loglik_batch([delays], [alpha], [rho])

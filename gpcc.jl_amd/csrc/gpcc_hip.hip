@@ -7,6 +7,7 @@
 #include "gpcc_pred.hip.h"
 #include "gpcc_heldout.hip.h"
 #include "gpcc_sample.hip.h"
+#include "gpcc_markov.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -15,6 +16,7 @@
 
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -32,7 +34,7 @@
 #include <type_traits>
 #include <vector>
 
-#define GPCC_VERSION_NUMBER 100
+#define GPCC_VERSION_NUMBER 101
 #define GPCC_MAX_STREAMS 8
 
 static thread_local std::string g_err;
@@ -217,6 +219,13 @@ struct gpcc_handle_s {
     double *d_smean = nullptr, *d_sdraw = nullptr, *d_szeta = nullptr;
     int *d_slist = nullptr, *d_soff = nullptr;
     long smean_cap = 0, sdraw_cap = 0, szeta_cap = 0, slist_cap = 0, soff_cap = 0;
+    // linear-time log-likelihood (gpcc_loglik_markov_batch): built on its first call -- the light curves with every band sorted by time
+    // (t | r | sigma^2: 3 N doubles) and the permutation that sorted them; none of the N^2 workspace
+    double *d_mk = nullptr;
+    std::vector<int> mk_perm;
+    int mk_cus = 0;
+    std::atomic<long> markov_count{0};   // evaluations that took it so far ("markov_count")
+    int fit_markov = 0;                  // option "fit_markov": gpcc_grid_loglik's optimiser rounds are gpcc_loglik_markov_batch calls
     double *d_sep = nullptr, *d_seps = nullptr;     // separable factors of the points, the distance scale (GpccCtx::sep, ::seps)
     int *d_sepflag = nullptr;                       // per-tile-row flags (GpccCtx::sepflag)
     int fp32_refine = 1;                            // option "fp32_refine": 0 = no refinement of the quadratic forms
@@ -516,6 +525,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_t); hipFree(h->d_sig2); hipFree(h->d_resid); hipFree(h->d_band); hipFree(h->d_yv);
     hipFree(h->d_par); hipFree(h->d_out); hipFree(h->d_oinfo);
     for (auto &ln : h->lanes) ln.release();
+    hipFree(h->d_mk);
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
     hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
     hipFree(h->d_smean); hipFree(h->d_sdraw); hipFree(h->d_szeta); hipFree(h->d_slist); hipFree(h->d_soff);
@@ -610,6 +620,13 @@ extern "C" int gpcc_set_option(gpcc_handle_t h, const char *key, long v)
         h->hybrid_mall_mb = (int)v;
     } else if (!strcmp(key, "fit_speculate")) {
         h->fit_speculate = v != 0;
+    } else if (!strcmp(key, "fit_markov")) {
+        if (v != 0 && h->kernel_id == GPCC_KERNEL_RBF)
+            return fail(h, GPCC_ERR_UNSUPPORTED, "fit_markov: the rbf kernel is not Markov (OU, matern32, matern52 are); its fit stays dense");
+        if (v != 0 && h->mb && h->L > GPCC_MARKOV_MAX_OFFSETS)
+            return fail(h, GPCC_ERR_UNSUPPORTED, "fit_markov: marginalise_b with L=%d bands (the filter keeps at most %d offset states)", h->L,
+                        GPCC_MARKOV_MAX_OFFSETS);
+        h->fit_markov = v != 0;
     } else if (!strcmp(key, "fit_device_unpack")) {
         h->fit_device_unpack = v != 0;
     } else if (!strcmp(key, "fit_threads")) {
@@ -689,6 +706,8 @@ extern "C" long gpcc_get_option(gpcc_handle_t h, const char *key)
     if (!strcmp(key, "split_small")) return h->split_small;
     if (!strcmp(key, "fit_speculate")) return h->fit_speculate;
     if (!strcmp(key, "fit_device_unpack")) return h->fit_device_unpack;
+    if (!strcmp(key, "fit_markov")) return h->fit_markov;
+    if (!strcmp(key, "markov_count")) return h->markov_count;
     if (!strcmp(key, "fit_threads")) return h->fit_threads;
     if (!strcmp(key, "small_n_max")) return GPCC_SMALLW_MAXN;
     if (!strcmp(key, "small_wide_max")) return h->small_wide_max;
@@ -1865,6 +1884,94 @@ extern "C" int gpcc_loglik_grad_batch(gpcc_handle_t h, int M, const double *dela
 }
 
 // ------------------------------------------------------------------------------------------
+// The exact linear-time log-likelihood of the Markov kernels (gpcc_loglik_markov_batch; kernel: gpcc_markov.hip.h): a
+// Kalman filter over the observations merged by shifted time, one lane per evaluation, one launch per call.  It needs the light
+// curves with every band sorted by time (built here on the first call) and the staging buffers, nothing of the N^2 workspace.
+// ------------------------------------------------------------------------------------------
+static int ensure_markov(gpcc_handle_t h)
+{
+    if (h->d_mk) return 0;
+    const long N = h->N;
+    std::vector<double> pts(3 * N);
+    h->mk_perm.resize(N);
+    long off = 0;
+    for (int l = 0; l < h->L; ++l) {   // stable: points of equal time keep the caller's order (the likelihood does not depend on it)
+        int *perm = h->mk_perm.data() + off;
+        for (int i = 0; i < h->Nl[l]; ++i) perm[i] = (int)(off + i);
+        std::stable_sort(perm, perm + h->Nl[l], [&](int x, int y) { return h->t_host[x] < h->t_host[y]; });
+        off += h->Nl[l];
+    }
+    for (long i = 0; i < N; ++i) {
+        pts[i] = h->t_host[h->mk_perm[i]];
+        pts[N + i] = h->resid_host[h->mk_perm[i]];
+        pts[2 * N + i] = h->sig2_host[h->mk_perm[i]];
+    }
+    int cus = 0;
+    HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    h->mk_cus = cus > 0 ? cus : 1;
+    HIPCHK(h, gpcc_markov_configure());
+    double *d = nullptr;
+    HIPCHK(h, hipMalloc(&d, sizeof(double) * 3 * N));
+    const hipError_t e = hipMemcpy(d, pts.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(d);
+        return fail(h, GPCC_ERR_HIP, "uploading the sorted light curves failed: %s", hipGetErrorString(e));
+    }
+    h->d_mk = d;
+    return 0;
+}
+
+extern "C" int gpcc_loglik_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                        double *loglik, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (M == 0) return 0;
+    if (!delays || !alpha || !rho || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    {
+        const gpcc_handle_t p = primary(h);
+        if (p->kernel_id == GPCC_KERNEL_RBF)
+            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_markov_batch: the rbf kernel is not Markov (OU, matern32 and matern52 are); "
+                                                 "use gpcc_loglik_batch");
+        if (p->mb && p->L > GPCC_MARKOV_MAX_OFFSETS)
+            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_markov_batch: marginalise_b with L=%d bands (the filter keeps at most %d offset "
+                                                 "states); use gpcc_loglik_batch", p->L, GPCC_MARKOV_MAX_OFFSETS);
+    }
+    int rc = 0;
+    if (route_fp64(h, "linear-time log-likelihood", rc,
+                   [&](gpcc_handle_t o) { return gpcc_loglik_markov_batch(o, M, delays, alpha, rho, loglik, info); }))
+        return rc;
+    GPCC_ON_DEVICE(h, h->device);
+    double *dd, *da, *dr;
+    rc = ensure_markov(h);
+    if (!rc) rc = ensure_staging(h, M);
+    if (!rc) rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
+    if (rc) return rc;
+    GpccMarkovArgs a;
+    a.pts = h->d_mk; a.delays = dd; a.alpha = da; a.rho = dr;
+    a.out_loglik = h->d_out; a.out_info = h->d_oinfo;
+    a.M = M; a.L = h->L; a.N = h->N;
+    a.off[0] = 0;
+    for (int l = 0; l < GPCC_MARKOV_MAXL; ++l) a.off[l + 1] = a.off[l] + (l < h->L ? h->Nl[l] : 0);
+    const int noff = h->mb ? h->L : 0;
+    for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) a.sigma_b[l] = l < noff ? h->sigma_b[l] : 0.0;
+    // one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy of the light curves
+    // beyond; the light curves go to LDS when they fit beside the lanes' cursors
+    const long waves = ((long)M + 63) / 64;
+    const int wpb = waves <= h->mk_cus ? 1 : (waves <= 2L * h->mk_cus ? 2 : 4), threads = 64 * wpb;
+    a.stage = gpcc_markov_lds_bytes(h->N, h->L, threads, true) <= GPCC_MARKOV_LDS_MAX ? 1 : 0;
+    const size_t lds = gpcc_markov_lds_bytes(h->N, h->L, threads, a.stage != 0);
+    const int p = h->kernel_id == GPCC_KERNEL_OU ? 1 : (h->kernel_id == GPCC_KERNEL_MATERN32 ? 2 : 3);
+    const hipError_t e = gpcc_markov_launch(p, noff, a, (int)((waves + wpb - 1) / wpb), threads, lds, h->main_stream);
+    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_eval: %s", hipGetErrorString(e));
+    HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, h->main_stream));
+    HIPCHK(h, hipStreamSynchronize(h->main_stream));
+    h->markov_count += M;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // Hessian and Fisher information of objective(alpha, rho) (gpcc_loglik_hess_batch; kernels: gpcc_hess.hip.h).  A Hessian
 // group first runs the gradient group unchanged (enqueue_grad_group: loglik and grad are the gradient path's bits), then the curvature
 // kernels on the same slots.  Its buffers are allocated on the first call (ensure_hess), for as many slots as fit a quarter of the
@@ -2948,7 +3055,8 @@ int fit_eval(void *vctx, long K, const long *pidx, const double *X, double *f)
         for (int l = 0; l < L; ++l) e.delays[i * L + l] = e.cand[((e.p0 + pidx[i]) / e.R) * L + l];
     int rc = gpcc_unpack_params((int)K, L, X, e.rhomin, e.rhomax, e.alpha.data(), e.rho.data());
     if (rc) return rc;
-    rc = gpcc_loglik_batch(e.h, (int)K, e.delays.data(), e.alpha.data(), e.rho.data(), e.ll.data(), e.info.data());
+    rc = e.h->fit_markov ? gpcc_loglik_markov_batch(e.h, (int)K, e.delays.data(), e.alpha.data(), e.rho.data(), e.ll.data(), e.info.data())
+                         : gpcc_loglik_batch(e.h, (int)K, e.delays.data(), e.alpha.data(), e.rho.data(), e.ll.data(), e.info.data());
     if (rc) return rc;
     for (long i = 0; i < K; ++i)   // safewrapper(negativeobjective), :149-153: a failed evaluation is +Inf
         f[i] = e.info[i] == 0 ? -e.ll[i] : std::numeric_limits<double>::infinity();
@@ -2984,7 +3092,7 @@ extern "C" int gpcc_grid_loglik(gpcc_handle_t h, int G, const double *delays, in
         return multi_grid_loglik(h, G, delays, iterations, R, C, rhomin, rhomax, cands.data(), loglik_out, alpha_out, rho_out, info_out,
                                  iterations_out, stats_out);
     FitEval ev{h, delays, R, L, rhomin, rhomax, {}, {}, {}, {}, {}};
-    const bool small_fit = small_path(h);
+    const bool small_fit = small_path(h) && !h->fit_markov;   // (option "fit_markov": every round is one gpcc_markov_eval launch)
     if (small_fit && h->fit_device_unpack) {   // the candidate-delay table lives on the device for the duration of the fit
         GPCC_ON_DEVICE(h, h->device);
         if ((long)G * L > h->cand_cap) {

@@ -1,0 +1,228 @@
+// gpcc_markov.hip.h -- the exact linear-time log-likelihood of the Markov kernels (OU, Matern-3/2, Matern-5/2) for gfx950:
+// gpcc_loglik_markov_batch of include/gpcc_hip.h; gpcc.jl_amd/markov.py is the same algorithm in numpy.
+//
+// f with one of these kernels is a stationary Gauss-Markov process of state dimension P = 1, 2, 3 (f, f', f''), so with all
+// observations merged in the order of their shifted times s = t - tau_band, K = alpha alpha' k(s - s') + Sobs (+ B) is the covariance
+// of a linear-Gaussian state-space model and logpdf(MvNormal(bbar, K), Y) is the sum of the Kalman filter's one-step predictive
+// log-densities: O(N P^2) work and O(1) memory per evaluation, nothing approximated.  The marginalised offsets b_l are NOFF = L
+// more states that never move (prior variance 100 var(y_l)); more than GPCC_MARKOV_MAX_OFFSETS = 4 of them do not fit a lane's
+// registers: gpcc_loglik_markov_batch returns GPCC_ERR_UNSUPPORTED for marginalise_b with L > 4 (without marginalise_b any L <= 8).
+//
+// ONE LANE PER EVALUATION.  The filter is N dependent steps of ~100-300 fp64 operations; nothing inside one evaluation is worth a
+// wave.  A lane keeps the mean (P + NOFF) and the upper triangle of the covariance ((P + NOFF)(P + NOFF + 1) / 2 doubles, 7 + 28 at
+// most) in registers -- every loop over the state is unrolled by the template parameters, every index a constant, the observed
+// band's offset column chosen by selects -- and walks an L-way merge of the bands (each sorted by time once, on the host): L
+// cursors, the head of each band, tau and alpha per band live in LDS, [band][thread] (a lane indexes them by its own band).  The
+// light curves (t, r = y - mean, sigma^2: 24 bytes per point) are the same for every lane; they are staged in LDS when they fit
+// beside that (N <= ~6500) and read from global memory through the caches otherwise -- one code path, `pts` points to either.
+// A workgroup is one wave while the batch has no more waves than the chip has CUs (a 1024-delay grid spreads over 16 CUs), two or
+// four waves sharing one staged copy beyond.  Lanes beyond M compute row M - 1 again and store nothing.  No atomics, no
+// communication between lanes: a lane's result depends on its own (tau, alpha, rho) only, so results are bitwise the same for any M,
+// any row order and any launch shape.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#define GPCC_MARKOV_MAX_OFFSETS 4
+#define GPCC_MARKOV_MAXL 8
+#define GPCC_MARKOV_LDS_MAX (156 * 1024)   /* of the CU's 160 KiB */
+#define GPCC_MARKOV_LANE_BYTES 28          /* per lane and band: head, tau, alpha (doubles) and the cursor (int) */
+
+struct GpccMarkovArgs {
+    const double *pts;                     // t[N] | r[N] | sigma^2[N], bands one after the other, each sorted by t
+    const double *delays, *alpha, *rho;    // M x L, M x L, M
+    double *out_loglik;
+    int *out_info;
+    int M, L, N, stage;                    // stage: copy pts to LDS first
+    int off[GPCC_MARKOV_MAXL + 1];         // band l holds points off[l] .. off[l + 1] - 1
+    double sigma_b[GPCC_MARKOV_MAX_OFFSETS];
+};
+
+// dynamic LDS of a workgroup of `threads` lanes
+static inline size_t gpcc_markov_lds_bytes(int N, int L, int threads, bool stage)
+{
+    return (stage ? (size_t)24 * N : 0) + (size_t)GPCC_MARKOV_LANE_BYTES * L * threads;
+}
+
+// element (i, j) of a symmetric matrix kept in its upper triangle (constant indices after unrolling)
+#define GPCC_MK_SYM(Q, i, j) ((i) <= (j) ? Q[i][j] : Q[j][i])
+
+template <int P, int NOFF>
+__global__ void __launch_bounds__(256) gpcc_markov_eval(const GpccMarkovArgs a)
+{
+    constexpr int NS = P + NOFF;
+    extern __shared__ __attribute__((aligned(16))) double gpcc_mk_lds[];
+    const int tid = threadIdx.x, nthr = blockDim.x, L = a.L, N = a.N;
+    double *shead = gpcc_mk_lds + (a.stage ? 3L * N : 0);
+    double *stau = shead + L * nthr, *salpha = stau + L * nthr;
+    int *scur = (int *)(salpha + L * nthr);
+    if (a.stage)
+        for (int i = tid; i < 3 * N; i += nthr) gpcc_mk_lds[i] = a.pts[i];
+    const double *pts = a.stage ? (const double *)gpcc_mk_lds : a.pts;
+
+    const long row = (long)blockIdx.x * nthr + tid;
+    const bool valid = row < a.M;
+    const long m_ = valid ? row : a.M - 1;
+    const double rho = a.rho[m_];
+    int info = 0;   // the reference's argument checks (delayedCovariance.jl:3, :5-7), as gpcc_loglik_batch reports them
+    for (int l = 0; l < L; ++l) {
+        const double al = a.alpha[m_ * L + l];
+        if (!(al > 0.0)) info = -1;
+        salpha[l * nthr + tid] = al;
+        stau[l * nthr + tid] = a.delays[m_ * L + l];
+    }
+    if (info == 0 && rho <= 0.0) info = -2;
+    __syncthreads();
+    for (int l = 0; l < L; ++l) {
+        scur[l * nthr + tid] = a.off[l];
+        shead[l * nthr + tid] = pts[a.off[l]] - stau[l * nthr + tid];
+    }
+
+    const double lam = (P == 1 ? 1.0 : (P == 2 ? 1.7320508075688772 : 2.23606797749979)) / rho;
+    const double lam2 = lam * lam;
+    double Q[P][P];   // Pinf
+#pragma unroll
+    for (int i = 0; i < P; ++i)
+#pragma unroll
+        for (int j = 0; j < P; ++j) Q[i][j] = 0.0;
+    Q[0][0] = 1.0;
+    if constexpr (P == 2) Q[1][1] = lam2;
+    if constexpr (P == 3) {
+        Q[0][2] = Q[2][0] = -lam2 / 3.0;
+        Q[1][1] = lam2 / 3.0;
+        Q[2][2] = lam2 * lam2;
+    }
+    double mu[NS], C[NS][NS];   // C: upper triangle used
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        mu[i] = 0.0;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) C[i][j] = (i < P && j < P) ? Q[i][j] : 0.0;
+    }
+#pragma unroll
+    for (int c = 0; c < NOFF; ++c) C[P + c][P + c] = a.sigma_b[c];
+
+    double ll = 0.0, sprev = 0.0;
+    for (int j = 0; j < N; ++j) {
+        // merge: the band whose head has the smallest shifted time, the lowest band on ties
+        int b = -1;
+        double s = 0.0;
+        for (int l = 0; l < L; ++l) {
+            const double sl = shead[l * nthr + tid];
+            const bool live = scur[l * nthr + tid] < a.off[l + 1];
+            const bool take = live && (b < 0 || sl < s);
+            b = take ? l : b;
+            s = take ? sl : s;
+        }
+        const int i = scur[b * nthr + tid];
+        const double r = pts[N + i], s2 = pts[2 * N + i], al = salpha[b * nthr + tid];
+        scur[b * nthr + tid] = i + 1;
+        if (i + 1 < a.off[b + 1]) shead[b * nthr + tid] = pts[i + 1] - stau[b * nthr + tid];
+        const double d = (j == 0) ? 0.0 : s - sprev;
+        sprev = s;
+
+        // A = expm(F d)
+        const double e = exp(-lam * d), x = lam * d;
+        double A[P][P];
+        if constexpr (P == 1) {
+            A[0][0] = e;
+        } else if constexpr (P == 2) {
+            A[0][0] = e * (1.0 + x);
+            A[0][1] = e * d;
+            A[1][0] = -e * lam2 * d;
+            A[1][1] = e * (1.0 - x);
+        } else {
+            A[0][0] = e * (1.0 + x + 0.5 * x * x);
+            A[0][1] = e * d * (1.0 + x);
+            A[0][2] = e * 0.5 * d * d;
+            A[1][0] = -e * 0.5 * lam2 * lam * d * d;
+            A[1][1] = e * (1.0 + x - x * x);
+            A[1][2] = e * d * (1.0 - 0.5 * x);
+            A[2][0] = e * lam2 * x * (0.5 * x - 1.0);
+            A[2][1] = e * lam * x * (x - 3.0);
+            A[2][2] = e * (1.0 - 2.0 * x + 0.5 * x * x);
+        }
+        // predict: m <- A m, C_xx <- A (C_xx - Pinf) A' + Pinf, C_xb <- A C_xb
+        {
+            double t1[P], D[P][P], T[P][P];
+#pragma unroll
+            for (int i2 = 0; i2 < P; ++i2) {
+                double acc = 0.0;
+#pragma unroll
+                for (int k = 0; k < P; ++k) acc += A[i2][k] * mu[k];
+                t1[i2] = acc;
+            }
+#pragma unroll
+            for (int i2 = 0; i2 < P; ++i2) mu[i2] = t1[i2];
+#pragma unroll
+            for (int i2 = 0; i2 < P; ++i2)
+#pragma unroll
+                for (int k = 0; k < P; ++k) D[i2][k] = GPCC_MK_SYM(C, i2, k) - Q[i2][k];
+#pragma unroll
+            for (int i2 = 0; i2 < P; ++i2)
+#pragma unroll
+                for (int k = 0; k < P; ++k) {
+                    double acc = 0.0;
+#pragma unroll
+                    for (int q = 0; q < P; ++q) acc += A[i2][q] * D[q][k];
+                    T[i2][k] = acc;
+                }
+#pragma unroll
+            for (int i2 = 0; i2 < P; ++i2)
+#pragma unroll
+                for (int k = i2; k < P; ++k) {
+                    double acc = Q[i2][k];
+#pragma unroll
+                    for (int q = 0; q < P; ++q) acc += T[i2][q] * A[k][q];
+                    C[i2][k] = acc;
+                }
+#pragma unroll
+            for (int c = 0; c < NOFF; ++c) {
+#pragma unroll
+                for (int i2 = 0; i2 < P; ++i2) {
+                    double acc = 0.0;
+#pragma unroll
+                    for (int k = 0; k < P; ++k) acc += A[i2][k] * C[k][P + c];
+                    t1[i2] = acc;
+                }
+#pragma unroll
+                for (int i2 = 0; i2 < P; ++i2) C[i2][P + c] = t1[i2];
+            }
+        }
+        // update with h = alpha_b e_1 + e_{P + b}
+        double Ph[NS];
+#pragma unroll
+        for (int i2 = 0; i2 < NS; ++i2) {
+            double acc = al * GPCC_MK_SYM(C, i2, 0);
+#pragma unroll
+            for (int c = 0; c < NOFF; ++c) acc += (b == c) ? GPCC_MK_SYM(C, i2, P + c) : 0.0;
+            Ph[i2] = acc;
+        }
+        double S = al * Ph[0] + s2, hm = al * mu[0];
+#pragma unroll
+        for (int c = 0; c < NOFF; ++c) {
+            S += (b == c) ? Ph[P + c] : 0.0;
+            hm += (b == c) ? mu[P + c] : 0.0;
+        }
+        const bool ok = S > 0.0 && S < __builtin_inf();
+        info = (info == 0 && !ok) ? j + 1 : info;   // first predictive variance that is not positive and finite
+        const double inv = 1.0 / S, eps = r - hm;
+        ll -= 0.5 * (1.8378770664093453 + log(S) + eps * eps * inv);
+        const double g = eps * inv;
+#pragma unroll
+        for (int i2 = 0; i2 < NS; ++i2) {
+            mu[i2] += Ph[i2] * g;
+            const double ki = Ph[i2] * inv;
+#pragma unroll
+            for (int k = i2; k < NS; ++k) C[i2][k] -= ki * Ph[k];
+        }
+    }
+    if (valid) {
+        a.out_loglik[row] = info ? __builtin_nan("") : ll;
+        a.out_info[row] = info;
+    }
+}
+
+// the launch of instantiation (p, noff) (gpcc_markov_inst.hip: its own object) and the LDS limit of all of them on the current device
+hipError_t gpcc_markov_launch(int p, int noff, const GpccMarkovArgs &a, int blocks, int threads, size_t lds, hipStream_t s);
+hipError_t gpcc_markov_configure();

@@ -157,7 +157,7 @@ class GridFit:
 
 def gpcc_grid(tarray, yarray, stdarray, *, kernel, candidatedelays, iterations, seed=1, numberofrestarts=1,
               initialrandom=5, rhomin=0.1, rhomax=20.0, objective=None, device=0, marginalise_b=True, engine=None,
-              unpack=None, evidence=None, laplace_rounds=50, laplace_g_tol=1e-6):
+              unpack=None, evidence=None, laplace_rounds=50, laplace_g_tol=1e-6, solver="dense"):
     """Fits the GPCC model for each row of candidatedelays (G, L): the README's
     `map(delay -> gpcc(...; delays = [0; delay])[1], candidatedelays)` as one lock-step batch.
 
@@ -166,11 +166,18 @@ def gpcc_grid(tarray, yarray, stdarray, *, kernel, candidatedelays, iterations, 
     objective is injected): the same algorithm in numpy (neldermead.py) over objective.loglik_batch; `unpack`
     may replace the numpy parameter transforms (api.unpack_params = the library's own).
 
+    solver "dense" (default): every optimiser round is a batch of dense Cholesky factorisations (loglik_batch).  solver "markov": the
+    rounds evaluate the same likelihood in linear time (loglik_markov_batch: OU, matern32, matern52; option "fit_markov" of the native
+    engine) -- the values agree with the dense ones to rounding, so the fit follows the same trajectory up to that; rbf, or more than 4
+    bands with marginalise_b, raise.  The evidence and every prediction stay dense.
+
     evidence "laplace": after the fit, the Laplace-marginalised evidence over alpha and rho at every delay, from the fitted
     (alpha, rho) (Objective.laplace_evidence with the native engine, laplace.laplace_evidence otherwise) -> GridFit.log_evidence,
     .hyper_cov, .laplace_info, .laplace_rounds.  None (default): the profile likelihood only, as before."""
     if evidence not in (None, "laplace"):
         raise ValueError("evidence must be None or 'laplace', got %r" % (evidence,))
+    if solver not in ("dense", "markov"):
+        raise ValueError("solver must be 'dense' or 'markov', got %r" % (solver,))
     cand = np.ascontiguousarray(np.atleast_2d(candidatedelays), dtype=np.float64)
     G, L = cand.shape
     assert L == len(tarray) == len(yarray) == len(stdarray)          # marginaliseb.jl:78
@@ -195,9 +202,14 @@ def gpcc_grid(tarray, yarray, stdarray, *, kernel, candidatedelays, iterations, 
         if engine is None:
             engine = "native" if isinstance(obj, Objective) else "python"
         if engine == "native":
-            ll, alpha, rho, info, its, (f_calls, rounds) = obj.grid_loglik(
-                cand, iterations, numberofrestarts=R, initialrandom=initialrandom, rhomin=rhomin, rhomax=rhomax,
-                seed=seed, init_params=cands)
+            before = obj.get_option("fit_markov")
+            obj.set_option("fit_markov", int(solver == "markov"))
+            try:
+                ll, alpha, rho, info, its, (f_calls, rounds) = obj.grid_loglik(
+                    cand, iterations, numberofrestarts=R, initialrandom=initialrandom, rhomin=rhomin, rhomax=rhomax,
+                    seed=seed, init_params=cands)
+            finally:
+                obj.set_option("fit_markov", before)
             return _with_evidence(GridFit(ll, alpha, rho, f_calls, rounds, its.astype(np.int64)), obj, cand, engine, evidence,
                                   rhomin, rhomax, laplace_rounds, laplace_g_tol)
 
@@ -207,7 +219,7 @@ def gpcc_grid(tarray, yarray, stdarray, *, kernel, candidatedelays, iterations, 
             else:
                 alpha = makepositive(X[:, :L]) + 1e-8                    # makeα, :112
                 rho = transformbetween(X[:, L], rhomin, rhomax)          # makeρ, :114
-            ll, info = obj.loglik_batch(cand[pidx // R], alpha, rho)
+            ll, info = (obj.loglik_markov_batch if solver == "markov" else obj.loglik_batch)(cand[pidx // R], alpha, rho)
             return np.where(info == 0, -ll, np.inf)                      # safewrapper(negativeobjective), :149-153
 
         # argmin over the random candidates (:209)
@@ -360,16 +372,16 @@ class DelayAveragedPredictor:
 
 
 def gpcc(tarray, yarray, stdarray, *, kernel, delays, iterations, seed=1, numberofrestarts=1, initialrandom=5,
-         rhomin=0.1, rhomax, device=0):
+         rhomin=0.1, rhomax, device=0, solver="dense"):
     """loglikel, pred, (alpha, postb, rho) = gpcc(tarray, yarray, stdarray; kernel, delays, iterations, ...)
     -- src/gpccfixdelay_marginaliseb.jl:46-53.  postb is returned as (mu_postb, Sigma_postb), the
-    parameters of the reference's MvNormal (:252)."""
+    parameters of the reference's MvNormal (:252).  solver: gpcc_grid's (the fit's likelihood evaluations; postb and pred are dense)."""
     delays = np.asarray(delays, dtype=np.float64)
     assert len(delays) == len(tarray) == len(yarray) == len(stdarray)              # :78
     obj = Objective(tarray, yarray, stdarray, kernel, marginalise_b=True, device=device)
     res = gpcc_grid(tarray, yarray, stdarray, kernel=kernel, candidatedelays=delays[None, :], iterations=iterations,
                     seed=seed, numberofrestarts=numberofrestarts, initialrandom=initialrandom, rhomin=rhomin,
-                    rhomax=rhomax, objective=obj)
+                    rhomax=rhomax, objective=obj, solver=solver)
     alpha, rho = res.alpha[0], float(res.rho[0])
     postb = obj.posterior_offsets(delays, alpha, rho)
     return float(res.loglikel[0]), Predictor(obj, delays, alpha, rho), (alpha, postb, rho)
@@ -460,11 +472,12 @@ class CVGrid:
 
 
 def performcv_grid(tobs, yobs, σobs, *, candidatedelays, kernel, iterations=1, seedcv=1, numberofrestarts=1, initialrandom=1,
-                   numberoffolds=5, rhomin=0.1, rhomax=20.0, evidence=None, device=0):
+                   numberoffolds=5, rhomin=0.1, rhomax=20.0, evidence=None, device=0, solver="dense"):
     """performcv over a whole grid of candidate delays (G, L): per fold ONE Objective on the training split, ONE gpcc_grid fit over all
     G delays (seed = seedcv, as performcv's gpcc calls) and ONE heldout_loglik_batch over the G rows, weighted by the fold's own delay
     posterior (getprobabilities(loglikel), or of log_evidence with evidence="laplace") -> CVGrid.  heldout[:, g] is what performcv
-    returns at delay g.  Compare kernels by performcv_grid(...).mix.sum()."""
+    returns at delay g.  Compare kernels by performcv_grid(...).mix.sum().  solver: gpcc_grid's (the folds' fits; the held-out scores are
+    dense)."""
     cand = np.ascontiguousarray(np.atleast_2d(candidatedelays), dtype=np.float64)
     G, L = cand.shape
     assert L == len(tobs) == len(yobs) == len(σobs)
@@ -482,7 +495,7 @@ def performcv_grid(tobs, yobs, σobs, *, candidatedelays, kernel, iterations=1, 
         with Objective(ttr, ytr, str_, kernel, marginalise_b=True, device=device) as obj:
             res = gpcc_grid(ttr, ytr, str_, kernel=kernel, candidatedelays=cand, iterations=iterations, seed=seedcv,
                             numberofrestarts=numberofrestarts, initialrandom=initialrandom, rhomin=rhomin, rhomax=rhomax, objective=obj,
-                            evidence=evidence)
+                            evidence=evidence, solver=solver)
             score = res.log_evidence if evidence == "laplace" else res.loglikel
             score = np.where(np.isfinite(score), score, -np.inf)
             w = getprobabilities(score)

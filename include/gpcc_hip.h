@@ -147,6 +147,8 @@ int gpcc_multi_stats(gpcc_handle_t handle, double *compute_ms, double *gather_ms
  *   fit_device_unpack        1        gpcc_grid_loglik, small-N path: the kernel unpacks the optimiser's vectors itself
  *   fit_speculate            1        ... latency-bound rounds evaluate all four candidate points of an iteration at once
  *   fit_threads              0        ... host threads (slices) of a large fit; 0 = by size
+ *   fit_markov               0        gpcc_grid_loglik: 1 = every optimiser round is one gpcc_loglik_markov_batch (OU, Matern kernels; the
+ *                                     same likelihood evaluated in linear time, so the fit's trajectory agrees to rounding, not bitwise)
  *   fp32_refine              1        fp32 handles: fp64 refinement of the quadratic forms
  *   fp32_guard               1        fp32 handles: evaluations whose pivot ratios exceed the limits are repeated in fp64
  *   fp32_assemble            1        fp32 handles: tiles inside one band pair are evaluated in fp32
@@ -192,6 +194,27 @@ int gpcc_get_conditioning(gpcc_handle_t handle, int M, double *out);
  * (README.md:172-174, :202-206, :231).  Blocking; caller-allocated outputs. */
 int gpcc_loglik_batch(gpcc_handle_t handle, int M, const double *delays, const double *alpha,
                       const double *rho, double *loglik, int *info);
+
+/* The same objective(alpha, rho) for M independent (tau, alpha, rho) in LINEAR time, for the kernels that are covariances of a Markov
+ * process: OU, Matern-3/2 and Matern-5/2 (state dimension p = 1, 2, 3).  With all observations merged in the order of their shifted
+ * times t - tau_band, K = delayedCovariance + Sobs (+ B) is the covariance of a linear-Gaussian state-space model, and
+ * logpdf(MvNormal(bbar, K), Y) is exactly the sum of the Kalman filter's one-step predictive log-densities: O(N p^2) work and O(1)
+ * memory per evaluation instead of N^3 / 3 and N^2; nothing is approximated, only the order of the arithmetic differs (agreement with
+ * gpcc_loglik_batch: DESIGN.md 4.15).  The marginalised offsets b are L more (constant) states.
+ *   Layout, argument checks and info codes of gpcc_loglik_batch (-1: some alpha <= 0, -2: rho <= 0; a refused row never touches the
+ *   others); info[m] = j > 0: the predictive variance of the j-th observation IN MERGED ORDER was not positive and finite (the
+ *   PosDefException of the dense path; possible only with sigma = 0 points or non-finite parameters), loglik[m] = NaN.
+ *   GPCC_ERR_UNSUPPORTED: an rbf handle (not Markov), or marginalise_b with more than 4 bands (the offset states a lane keeps in
+ *   registers; without marginalise_b any L <= GPCC_MAX_BANDS) -- use gpcc_loglik_batch there.
+ * Path: one launch of the kernel gpcc_markov_eval, csrc/gpcc_markov.hip.h: one lane per evaluation, the light curves staged in LDS when they fit
+ * (N <= ~6500).  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  A row's result
+ * depends on that row only: bitwise the same for any M, row order and option.  Memory: the light curves with every band sorted by time
+ * (3 N doubles, built on the first call) and 8 M (2L + 2) bytes of staging; NONE of the N^2 workspace -- a handle that only ever calls
+ * this entry never allocates it.  Option "fit_markov" (default 0): 1 makes every optimiser round of gpcc_grid_loglik one call of this
+ * entry instead of a gpcc_loglik_batch (GPCC_ERR_UNSUPPORTED where this entry is); read-only "markov_count": evaluations so far.
+ * Gradient, Hessian and predictions stay on the dense path.  Blocking. */
+int gpcc_loglik_markov_batch(gpcc_handle_t handle, int M, const double *delays, const double *alpha, const double *rho,
+                             double *loglik, int *info);
 
 /* objective(alpha, rho) and its gradient for M independent (tau, alpha, rho): loglik[M], info[M] as gpcc_loglik_batch;
  * grad: M rows of 2L+1 doubles [d/d alpha_1..alpha_L, d/d rho, d/d tau_1..tau_L] in the reference's (constrained)

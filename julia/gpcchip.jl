@@ -58,6 +58,20 @@ function loglik_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}
     return ll, info
 end
 
+"objective for M triples in LINEAR time (gpcc_loglik_markov_batch: a Kalman filter over the observations merged by shifted time; OU,
+matern32, matern52 -- the same value as loglik_batch to rounding, DESIGN 4.15).  info as loglik_batch; a positive value is the merged
+position of the first predictive variance that is not positive.  Errors for rbf and for marginalise_b with more than 4 bands."
+function loglik_markov_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    rc = ccall((:gpcc_loglik_markov_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, ll, info)
+    rc == 0 || error("gpcc_loglik_markov_batch: " * lasterror(h.ptr))
+    return ll, info
+end
+
 "objective and its gradient for M triples: (ll[M], grad (2L+1)×M, info[M]); a column of grad is [∂/∂α_1..α_L, ∂/∂ρ, ∂/∂τ_1..τ_L]
 in the constrained parameters, NaN where info != 0.  The reference has no gradient: this is the derivative of objective(α, ρ)."
 function loglik_grad_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
