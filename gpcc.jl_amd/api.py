@@ -301,6 +301,81 @@ class Objective:
         self._chk(_capi.load().gpcc_loglik_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _ip(info)))
         return ll, info
 
+    def predict_markov_batch(self, delays, alpha, rho, ttest, weights=None):
+        """predict_batch in linear time (gpcc_predict_markov_batch: two Kalman filters and a combine per row, O(N + T); OU, matern32 and
+        matern52 only) -> (mu[M, T], var[M, T], loglik[M], info[M], mix_mu[T], mix_var[T]), what predict_batch returns.  ttest need not
+        be sorted.  loglik and info are bitwise loglik_markov_batch's, except info = N + j where the combine of test point j failed;
+        failed rows are NaN.  rbf, or marginalise_b with more than 4 bands: GpccError (unsupported)."""
+        if len(ttest) != self.L:
+            raise AssertionError("length(ttest) == L")
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        Nt, tt = _flatten(ttest)
+        T = int(Nt.sum())
+        mu = np.empty((M, T), dtype=np.float64)
+        var = np.empty((M, T), dtype=np.float64)
+        ll = np.empty(M, dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        w = mix_mu = mix_var = None
+        if weights is not None:
+            w = _d(np.asarray(weights, dtype=np.float64).ravel())
+            if w.shape != (M,):
+                raise ValueError("weights must have M = %d entries" % M)
+            mix_mu = np.empty(T, dtype=np.float64)
+            mix_var = np.empty(T, dtype=np.float64)
+        try:
+            self._chk(_capi.load().gpcc_predict_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _ip(Nt), _dp(tt),
+                                                             _dp(w) if w is not None else None, _dp(mu), _dp(var),
+                                                             _dp(mix_mu) if w is not None else None,
+                                                             _dp(mix_var) if w is not None else None, _dp(ll), _ip(info)))
+        except GpccError as e:
+            _raise_reference_error(e)
+        return mu, var, ll, info, mix_mu, mix_var
+
+    def heldout_loglik_markov_batch(self, delays, alpha, rho, ttest, ytest, sigmatest, weights=None):
+        """heldout_loglik_batch in linear time (gpcc_heldout_loglik_markov_batch: loglik(training U test) - loglik(training), two
+        filters per row) -> (heldout[M], loglik[M], info[M], mix or None).  loglik and info are bitwise loglik_markov_batch's, except
+        info = N + j where the predictive variance of test point j was not positive and finite (heldout NaN; there is no test block
+        to repair, hence no fallback and no refit mask).  mix = log sum p_m exp(heldout_m), p = weights / sum(weights)."""
+        if len(ttest) != self.L or len(ytest) != self.L or len(sigmatest) != self.L:
+            raise AssertionError("length(ttest) == length(ytest) == length(sigmatest) == L")
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        Nt, tt = _flatten(ttest)
+        Ny, yt = _flatten(ytest)
+        Ns, st = _flatten(sigmatest)
+        if not (np.array_equal(Nt, Ny) and np.array_equal(Nt, Ns)):
+            raise ValueError("band lengths differ between ttest, ytest and sigmatest")
+        held = np.empty(M, dtype=np.float64)
+        ll = np.empty(M, dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        w = mix = None
+        if weights is not None:
+            w = _d(np.asarray(weights, dtype=np.float64).ravel())
+            if w.shape != (M,):
+                raise ValueError("weights must have M = %d entries" % M)
+            mix = np.empty(1, dtype=np.float64)
+        try:
+            self._chk(_capi.load().gpcc_heldout_loglik_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _ip(Nt), _dp(tt),
+                                                                    _dp(yt), _dp(st), _dp(w) if w is not None else None, _dp(held),
+                                                                    _dp(mix) if w is not None else None, _dp(ll), _ip(info)))
+        except GpccError as e:
+            _raise_reference_error(e)
+        return held, ll, info, (float(mix[0]) if w is not None else None)
+
+    def posterior_offsets_markov_batch(self, delays, alpha, rho):
+        """posterior_offsets at M rows in linear time (gpcc_posterior_offsets_markov_batch: the offset block of the filter's final
+        state) -> (mu_postb[M, L], Sigma_postb[M, L, L], loglik[M], info[M]); rows with info != 0 are NaN."""
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        mu = np.empty((M, self.L), dtype=np.float64)
+        Sig = np.empty((M, self.L, self.L), dtype=np.float64)
+        ll = np.empty(M, dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        try:
+            self._chk(_capi.load().gpcc_posterior_offsets_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(mu), _dp(Sig),
+                                                                       _dp(ll), _ip(info)))
+        except GpccError as e:
+            _raise_reference_error(e)
+        return mu, Sig, ll, info
+
     def __call__(self, alpha, rho, delays):
         """objective(alpha, rho) for one delay vector, raising what the reference raises."""
         ll, info = self.loglik_batch([delays], [alpha], [rho])

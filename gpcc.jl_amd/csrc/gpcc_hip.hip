@@ -8,6 +8,7 @@
 #include "gpcc_heldout.hip.h"
 #include "gpcc_sample.hip.h"
 #include "gpcc_markov.hip.h"
+#include "gpcc_markov_pred.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -226,6 +227,16 @@ struct gpcc_handle_s {
     int mk_cus = 0;
     std::atomic<long> markov_count{0};   // evaluations that took it so far ("markov_count")
     int fit_markov = 0;                  // option "fit_markov": gpcc_grid_loglik's optimiser rounds are gpcc_loglik_markov_batch calls
+    // linear-time predictions, held-out log-likelihoods and offsets' posterior (gpcc_predict_markov_batch and its siblings): allocated
+    // on first use and grown on demand -- the sorted test points (mkt_cap doubles) with their bands and positions (mkti_cap ints), the
+    // tap scratch of a chunk of rows (mktap_cap doubles, at most GPCC_MKP_TAP_BYTES unless one row needs more), the chunk's mu and var
+    // (mkrow_cap doubles each), the mixture state (mkmix_cap), the weights (mkw_cap), the per-row results of the second lane and the
+    // final states (mkaux_cap doubles, mkauxi_cap ints)
+    double *d_mkt = nullptr, *d_mktap = nullptr, *d_mkmu = nullptr, *d_mkvar = nullptr, *d_mkmix = nullptr, *d_mkw = nullptr, *d_mkaux = nullptr;
+    int *d_mkti = nullptr, *d_mkauxi = nullptr;
+    long mkt_cap = 0, mkti_cap = 0, mktap_cap = 0, mkmu_cap = 0, mkvar_cap = 0, mkmix_cap = 0, mkw_cap = 0, mkaux_cap = 0, mkauxi_cap = 0;
+    int mkp_configured = 0;
+    int markov_chunk_rows = 0;           // option "markov_chunk_rows": rows per chunk of gpcc_predict_markov_batch (0: by the scratch budget)
     double *d_sep = nullptr, *d_seps = nullptr;     // separable factors of the points, the distance scale (GpccCtx::sep, ::seps)
     int *d_sepflag = nullptr;                       // per-tile-row flags (GpccCtx::sepflag)
     int fp32_refine = 1;                            // option "fp32_refine": 0 = no refinement of the quadratic forms
@@ -526,6 +537,8 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_par); hipFree(h->d_out); hipFree(h->d_oinfo);
     for (auto &ln : h->lanes) ln.release();
     hipFree(h->d_mk);
+    hipFree(h->d_mkt); hipFree(h->d_mktap); hipFree(h->d_mkmu); hipFree(h->d_mkvar); hipFree(h->d_mkmix); hipFree(h->d_mkw);
+    hipFree(h->d_mkaux); hipFree(h->d_mkti); hipFree(h->d_mkauxi);
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
     hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
     hipFree(h->d_smean); hipFree(h->d_sdraw); hipFree(h->d_szeta); hipFree(h->d_slist); hipFree(h->d_soff);
@@ -627,6 +640,9 @@ extern "C" int gpcc_set_option(gpcc_handle_t h, const char *key, long v)
             return fail(h, GPCC_ERR_UNSUPPORTED, "fit_markov: marginalise_b with L=%d bands (the filter keeps at most %d offset states)", h->L,
                         GPCC_MARKOV_MAX_OFFSETS);
         h->fit_markov = v != 0;
+    } else if (!strcmp(key, "markov_chunk_rows")) {
+        if (v < 0) return fail(h, GPCC_ERR_ARGUMENT, "markov_chunk_rows must be >= 0");
+        h->markov_chunk_rows = (int)v;
     } else if (!strcmp(key, "fit_device_unpack")) {
         h->fit_device_unpack = v != 0;
     } else if (!strcmp(key, "fit_threads")) {
@@ -708,6 +724,8 @@ extern "C" long gpcc_get_option(gpcc_handle_t h, const char *key)
     if (!strcmp(key, "fit_device_unpack")) return h->fit_device_unpack;
     if (!strcmp(key, "fit_markov")) return h->fit_markov;
     if (!strcmp(key, "markov_count")) return h->markov_count;
+    if (!strcmp(key, "markov_chunk_rows")) return h->markov_chunk_rows;
+    if (!strcmp(key, "markov_tap_bytes")) return 8 * h->mktap_cap;
     if (!strcmp(key, "fit_threads")) return h->fit_threads;
     if (!strcmp(key, "small_n_max")) return GPCC_SMALLW_MAXN;
     if (!strcmp(key, "small_wide_max")) return h->small_wide_max;
@@ -1968,6 +1986,288 @@ extern "C" int gpcc_loglik_markov_batch(gpcc_handle_t h, int M, const double *de
     HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, h->main_stream));
     HIPCHK(h, hipStreamSynchronize(h->main_stream));
     h->markov_count += M;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Linear-time predictions, held-out log-likelihoods and the offsets' posterior of the Markov kernels (gpcc_predict_markov_batch,
+// gpcc_heldout_loglik_markov_batch, gpcc_posterior_offsets_markov_batch; kernels: gpcc_markov_pred.hip.h).  They need
+// what gpcc_loglik_markov_batch needs (the sorted light curves, the staging buffers) plus the buffers grown below, nothing of the N^2
+// workspace.  Everything runs on main_stream.
+// ------------------------------------------------------------------------------------------
+#define GPCC_MKP_TAP_BYTES ((long)128 << 20)   /* the tap scratch of a chunk of rows (a single row may need more: T = 32768, n = 7) */
+
+// the refusals of gpcc_loglik_markov_batch, under the caller's name
+static int markov_refusals(gpcc_handle_t h, const char *who, const char *dense)
+{
+    const gpcc_handle_t p = primary(h);
+    if (p->kernel_id == GPCC_KERNEL_RBF)
+        return fail(h, GPCC_ERR_UNSUPPORTED, "%s: the rbf kernel is not Markov (OU, matern32 and matern52 are); use %s", who, dense);
+    if (p->mb && p->L > GPCC_MARKOV_MAX_OFFSETS)
+        return fail(h, GPCC_ERR_UNSUPPORTED, "%s: marginalise_b with L=%d bands (the filter keeps at most %d offset states); use %s", who,
+                    p->L, GPCC_MARKOV_MAX_OFFSETS, dense);
+    return 0;
+}
+
+// the test points with every band sorted by time (stably): tt = the sorted times, order[j] = the position in the caller's flattened
+// arrays of sorted point j, band[j] its band, toff the bands' offsets
+static void markov_sort_tests(gpcc_handle_t h, const int *Ntest, const double *ttest, long T, std::vector<int> &order, std::vector<int> &band,
+                              int *toff)
+{
+    order.resize(T);
+    band.resize(T);
+    long o = 0;
+    toff[0] = 0;
+    for (int l = 0; l < GPCC_MARKOV_MAXL; ++l) {
+        const int n = l < h->L ? Ntest[l] : 0;
+        for (int i = 0; i < n; ++i) { order[o + i] = (int)(o + i); band[o + i] = l; }
+        std::stable_sort(order.begin() + o, order.begin() + o + n, [&](int x, int y) { return ttest[x] < ttest[y]; });
+        o += n;
+        toff[l + 1] = (int)o;
+    }
+}
+
+// the arguments every launch of gpcc_markov_taps shares, and the launch shape of `rows` rows x ny lanes
+static int markov_pred_common(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, const int *toff, long T,
+                              GpccMarkovPredArgs &a)
+{
+    if (!h->mkp_configured) {
+        HIPCHK(h, gpcc_mkp_configure());
+        h->mkp_configured = 1;
+    }
+    a.pts = h->d_mk; a.tpts = h->d_mkt; a.delays = dd; a.alpha = da; a.rho = dr;
+    a.out_loglik = h->d_out; a.out_info = h->d_oinfo;
+    a.tap = nullptr; a.ll2 = nullptr; a.info2 = nullptr; a.at2 = nullptr; a.fin = nullptr;
+    a.M = M; a.L = h->L; a.N = h->N; a.T = (int)T; a.stage = 0;
+    a.row0 = 0; a.rows = M; a.mstride = M;
+    a.off[0] = 0;
+    for (int l = 0; l < GPCC_MARKOV_MAXL; ++l) a.off[l + 1] = a.off[l] + (l < h->L ? h->Nl[l] : 0);
+    for (int l = 0; l <= GPCC_MARKOV_MAXL; ++l) a.toff[l] = toff ? toff[l] : 0;
+    const int noff = h->mb ? h->L : 0;
+    for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) a.sigma_b[l] = l < noff ? h->sigma_b[l] : 0.0;
+    return 0;
+}
+
+static int markov_pred_launch(gpcc_handle_t h, int mode, GpccMarkovPredArgs &a, int ny)
+{
+    // one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy beyond (as gpcc_markov_eval)
+    const long waves = (((long)a.rows + 63) / 64) * ny;
+    const int wpb = waves <= h->mk_cus ? 1 : (waves <= 2L * h->mk_cus ? 2 : 4), threads = 64 * wpb;
+    const int tw = mode == GPCC_MKP_TAP ? 1 : 3;
+    a.stage = gpcc_mkp_lds_bytes(a.N, a.T, tw, a.L, threads, true) <= GPCC_MARKOV_LDS_MAX ? 1 : 0;
+    const size_t lds = gpcc_mkp_lds_bytes(a.N, a.T, tw, a.L, threads, a.stage != 0);
+    if (lds > GPCC_MARKOV_LDS_MAX) return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_markov_taps: %zu bytes of LDS", lds);
+    const int p = h->kernel_id == GPCC_KERNEL_OU ? 1 : (h->kernel_id == GPCC_KERNEL_MATERN32 ? 2 : 3);
+    const hipError_t e = gpcc_mkp_launch_taps(mode, p, h->mb ? h->L : 0, a, (a.rows + threads - 1) / threads, ny, threads, lds, h->main_stream);
+    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_taps: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                         const int *Ntest, const double *ttest, const double *weights, double *mu_out, double *var_out,
+                                         double *mix_mu, double *mix_var, double *loglik, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (!delays || !alpha || !rho || !Ntest || !ttest || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    if ((mu_out == nullptr) != (var_out == nullptr)) return fail(h, GPCC_ERR_ARGUMENT, "mu_out and var_out are both given or both NULL");
+    if (weights && (!mix_mu || !mix_var)) return fail(h, GPCC_ERR_ARGUMENT, "weights given: mix_mu and mix_var are required");
+    if (!weights && (mix_mu || mix_var)) return fail(h, GPCC_ERR_ARGUMENT, "mix_mu and mix_var need weights");
+    if (!weights && !mu_out) return fail(h, GPCC_ERR_ARGUMENT, "NULL mu_out / var_out without weights: nothing to return");
+    int rc = markov_refusals(h, "gpcc_predict_markov_batch", "gpcc_predict_batch");
+    if (rc) return rc;
+    if (route_fp64(h, "linear-time predictive", rc, [&](gpcc_handle_t o) {
+            return gpcc_predict_markov_batch(o, M, delays, alpha, rho, Ntest, ttest, weights, mu_out, var_out, mix_mu, mix_var, loglik, info);
+        }))
+        return rc;
+    long T = 0;
+    std::vector<double> p;   // the normalised weights p_m = w_m / sum w
+    rc = count_test_points(h, Ntest, T);
+    if (!rc) rc = mixture_weights(h, M, weights, false, p);
+    if (rc || M == 0) return rc;
+    GPCC_ON_DEVICE(h, h->device);
+    const int pdim = h->kernel_id == GPCC_KERNEL_OU ? 1 : (h->kernel_id == GPCC_KERNEL_MATERN32 ? 2 : 3), noff = h->mb ? h->L : 0;
+    const long ns = pdim + noff, nrec = ns + ns * (ns + 1) / 2;
+    // rows per chunk: what the scratch budget holds (whole waves when it holds one), or the option
+    long chunk = GPCC_MKP_TAP_BYTES / (2 * T * nrec * 8);
+    if (chunk >= 64) chunk -= chunk % 64;
+    if (h->markov_chunk_rows > 0) chunk = h->markov_chunk_rows;
+    if (chunk < 1) chunk = 1;
+    if (chunk > M) chunk = M;
+    std::vector<int> order, band;
+    int toff[GPCC_MARKOV_MAXL + 1];
+    markov_sort_tests(h, Ntest, ttest, T, order, band, toff);
+    std::vector<double> tt(T);
+    std::vector<int> ti(2 * T);
+    for (long j = 0; j < T; ++j) { tt[j] = ttest[order[j]]; ti[j] = band[j]; ti[T + j] = order[j]; }
+    rc = ensure_markov(h);
+    if (!rc) rc = ensure_staging(h, M);
+    if (!rc) rc = grow_buf(h, &h->d_mkt, &h->mkt_cap, T);
+    if (!rc) rc = grow_buf(h, &h->d_mkti, &h->mkti_cap, 2 * T);
+    if (!rc) rc = grow_buf(h, &h->d_mktap, &h->mktap_cap, 2 * T * nrec * chunk);
+    if (!rc) rc = grow_buf(h, &h->d_mkmu, &h->mkmu_cap, chunk * T);
+    if (!rc) rc = grow_buf(h, &h->d_mkvar, &h->mkvar_cap, chunk * T);
+    if (!rc && weights) rc = grow_buf(h, &h->d_mkmix, &h->mkmix_cap, 6 * T);
+    if (!rc && weights) rc = grow_buf(h, &h->d_mkw, &h->mkw_cap, M);
+    if (rc) return rc;
+    double *dd, *da, *dr;
+    rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
+    if (rc) return rc;
+    hipStream_t ms = h->main_stream;
+    HIPCHK(h, hipMemcpyAsync(h->d_mkt, tt.data(), sizeof(double) * T, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_mkti, ti.data(), sizeof(int) * 2 * T, hipMemcpyHostToDevice, ms));
+    if (weights) {
+        HIPCHK(h, hipMemcpyAsync(h->d_mkw, p.data(), sizeof(double) * M, hipMemcpyHostToDevice, ms));
+        HIPCHK(h, hipMemsetAsync(h->d_mkmix, 0, sizeof(double) * 4 * T, ms));
+    }
+    GpccMarkovPredArgs a;
+    rc = markov_pred_common(h, M, dd, da, dr, toff, T, a);
+    if (rc) return rc;
+    a.tap = h->d_mktap;
+    GpccMarkovCombineArgs c;
+    c.tap = h->d_mktap; c.alpha = da; c.rho = dr; c.tband = h->d_mkti; c.tperm = h->d_mkti + T; c.mu = h->d_mkmu; c.var = h->d_mkvar;
+    c.L = h->L; c.T = (int)T;
+    for (int l = 0; l < GPCC_MARKOV_MAXL; ++l) c.mean_b[l] = l < h->L ? h->mean_b[l] : 0.0;
+    for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) c.sigma_b[l] = a.sigma_b[l];
+    for (long row0 = 0; row0 < M; row0 += chunk) {
+        const int rows = (int)(M - row0 < chunk ? M - row0 : chunk);
+        a.row0 = c.row0 = (int)row0;
+        a.rows = c.rows = rows;
+        a.mstride = c.mstride = (int)chunk;
+        rc = markov_pred_launch(h, GPCC_MKP_TAP, a, 2);
+        if (rc) return rc;
+        hipError_t e = gpcc_mkp_launch_combine(pdim, noff, c, ms);
+        if (e == hipSuccess) e = gpcc_mkp_launch_rowinfo(h->d_mkmu, h->d_mkvar, h->d_oinfo, h->N, (int)T, (int)row0, rows, ms);
+        if (e == hipSuccess && weights)
+            e = gpcc_mkp_launch_mix(h->d_mkmu, h->d_mkvar, h->d_mkw, h->d_mkmix, (int)T, (int)row0, rows, row0 + rows == M ? 1 : 0, ms);
+        if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "linear-time predictive: %s", hipGetErrorString(e));
+        if (mu_out) {
+            HIPCHK(h, hipMemcpyAsync(mu_out + row0 * T, h->d_mkmu, sizeof(double) * rows * T, hipMemcpyDeviceToHost, ms));
+            HIPCHK(h, hipMemcpyAsync(var_out + row0 * T, h->d_mkvar, sizeof(double) * rows * T, hipMemcpyDeviceToHost, ms));
+        }
+    }
+    HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
+    if (weights) {
+        HIPCHK(h, hipMemcpyAsync(mix_mu, h->d_mkmix + 4 * T, sizeof(double) * T, hipMemcpyDeviceToHost, ms));
+        HIPCHK(h, hipMemcpyAsync(mix_var, h->d_mkmix + 5 * T, sizeof(double) * T, hipMemcpyDeviceToHost, ms));
+    }
+    HIPCHK(h, hipStreamSynchronize(ms));
+    return 0;
+}
+
+extern "C" int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                                const int *Ntest, const double *ttest, const double *ytest, const double *sigmatest,
+                                                const double *weights, double *heldout, double *mix_heldout, double *loglik, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (!delays || !alpha || !rho || !Ntest || !ttest || !ytest || !sigmatest || !loglik || !info)
+        return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    if (weights && !mix_heldout) return fail(h, GPCC_ERR_ARGUMENT, "weights given: mix_heldout is required");
+    if (!weights && mix_heldout) return fail(h, GPCC_ERR_ARGUMENT, "mix_heldout needs weights");
+    if (!weights && !heldout) return fail(h, GPCC_ERR_ARGUMENT, "NULL heldout without weights: nothing to return");
+    int rc = markov_refusals(h, "gpcc_heldout_loglik_markov_batch", "gpcc_heldout_loglik_batch");
+    if (rc) return rc;
+    if (route_fp64(h, "linear-time held-out log-likelihood", rc, [&](gpcc_handle_t o) {
+            return gpcc_heldout_loglik_markov_batch(o, M, delays, alpha, rho, Ntest, ttest, ytest, sigmatest, weights, heldout, mix_heldout,
+                                                    loglik, info);
+        }))
+        return rc;
+    long T = 0;
+    std::vector<double> p;
+    rc = count_test_points(h, Ntest, T);
+    if (!rc) rc = mixture_weights(h, M, weights, false, p);
+    if (rc || M == 0) return rc;
+    GPCC_ON_DEVICE(h, h->device);
+    std::vector<int> order, band;
+    int toff[GPCC_MARKOV_MAXL + 1];
+    markov_sort_tests(h, Ntest, ttest, T, order, band, toff);
+    std::vector<double> tp(3 * T);   // t | y* - mean(y_band of the training data) | sigma*^2 + JITTER
+    for (long j = 0; j < T; ++j) {
+        const int o = order[j];
+        tp[j] = ttest[o];
+        tp[T + j] = ytest[o] - h->mean_b[band[j]];
+        tp[2 * T + j] = sigmatest[o] * sigmatest[o] + GPCC_MKP_JITTER;
+    }
+    rc = ensure_markov(h);
+    if (!rc) rc = ensure_staging(h, M);
+    if (!rc) rc = grow_buf(h, &h->d_mkt, &h->mkt_cap, 3 * T);
+    if (!rc) rc = grow_buf(h, &h->d_mkti, &h->mkti_cap, T);
+    if (!rc) rc = grow_buf(h, &h->d_mkaux, &h->mkaux_cap, 2L * M + 4);
+    if (!rc) rc = grow_buf(h, &h->d_mkauxi, &h->mkauxi_cap, 2L * M);
+    if (!rc && weights) rc = grow_buf(h, &h->d_mkw, &h->mkw_cap, M);
+    if (rc) return rc;
+    double *dd, *da, *dr;
+    rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
+    if (rc) return rc;
+    hipStream_t ms = h->main_stream;
+    HIPCHK(h, hipMemcpyAsync(h->d_mkt, tp.data(), sizeof(double) * 3 * T, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_mkti, order.data(), sizeof(int) * T, hipMemcpyHostToDevice, ms));
+    if (weights) HIPCHK(h, hipMemcpyAsync(h->d_mkw, p.data(), sizeof(double) * M, hipMemcpyHostToDevice, ms));
+    GpccMarkovPredArgs a;
+    rc = markov_pred_common(h, M, dd, da, dr, toff, T, a);
+    if (rc) return rc;
+    double *d_held = h->d_mkaux + M, *d_mix = h->d_mkaux + 2L * M;
+    a.ll2 = h->d_mkaux; a.info2 = h->d_mkauxi; a.at2 = h->d_mkauxi + M;
+    rc = markov_pred_launch(h, GPCC_MKP_UPDATE, a, 2);
+    if (rc) return rc;
+    const hipError_t e = gpcc_mkp_launch_heldout_finish(h->d_out, h->d_oinfo, a.ll2, a.info2, a.at2, h->d_mkti, d_held,
+                                                        weights ? h->d_mkw : nullptr, d_mix, h->N, M, ms);
+    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "linear-time held-out log-likelihood: %s", hipGetErrorString(e));
+    if (heldout) HIPCHK(h, hipMemcpyAsync(heldout, d_held, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
+    if (weights) HIPCHK(h, hipMemcpyAsync(mix_heldout, d_mix + 3, sizeof(double), hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipStreamSynchronize(ms));
+    return 0;
+}
+
+extern "C" int gpcc_posterior_offsets_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                                   double *mu_b_out, double *Sigma_b_out, double *loglik, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (!delays || !alpha || !rho || !mu_b_out || !Sigma_b_out || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    if (!primary(h)->mb) return fail(h, GPCC_ERR_ARGUMENT, "the fixed-b variant (gpccfixdelay.jl) has no posterior over offsets");
+    int rc = markov_refusals(h, "gpcc_posterior_offsets_markov_batch", "gpcc_posterior_offsets");
+    if (rc) return rc;
+    if (route_fp64(h, "linear-time posterior of the offsets", rc, [&](gpcc_handle_t o) {
+            return gpcc_posterior_offsets_markov_batch(o, M, delays, alpha, rho, mu_b_out, Sigma_b_out, loglik, info);
+        }))
+        return rc;
+    if (M == 0) return 0;
+    GPCC_ON_DEVICE(h, h->device);
+    const int L = h->L, nfin = L + L * (L + 1) / 2;
+    rc = ensure_markov(h);
+    if (!rc) rc = ensure_staging(h, M);
+    if (!rc) rc = grow_buf(h, &h->d_mkaux, &h->mkaux_cap, (long)nfin * M);
+    if (!rc) rc = grow_buf(h, &h->d_mkt, &h->mkt_cap, 3);   // (no test points: the kernel reads none, the pointer must exist)
+    if (rc) return rc;
+    double *dd, *da, *dr;
+    rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
+    if (rc) return rc;
+    GpccMarkovPredArgs a;
+    rc = markov_pred_common(h, M, dd, da, dr, nullptr, 0, a);
+    if (rc) return rc;
+    a.fin = h->d_mkaux;
+    rc = markov_pred_launch(h, GPCC_MKP_UPDATE, a, 1);
+    if (rc) return rc;
+    hipStream_t ms = h->main_stream;
+    std::vector<double> fin((size_t)nfin * M);
+    HIPCHK(h, hipMemcpyAsync(fin.data(), h->d_mkaux, sizeof(double) * nfin * M, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipStreamSynchronize(ms));
+    for (long m = 0; m < M; ++m) {
+        double *mu = mu_b_out + m * L, *S = Sigma_b_out + m * L * L;
+        const bool bad = info[m] != 0;
+        int c = 0;
+        for (int i = 0; i < L; ++i) mu[i] = bad ? NAN : fin[(size_t)(c++) * M + m] + h->mean_b[i];
+        c = L;
+        for (int i = 0; i < L; ++i)
+            for (int k = i; k < L; ++k) S[i * L + k] = S[k * L + i] = bad ? NAN : fin[(size_t)(c++) * M + m];
+    }
     return 0;
 }
 

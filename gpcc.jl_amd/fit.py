@@ -280,14 +280,35 @@ class Predictor:
       pred(ttest)                       ttest = list of L arrays  -> (mu_pred, Sigma_pred), joint    (:259-289)
       pred(ttest)                       ttest = one array / range -> (mu per band, sigma per band)   (:293-307)
       pred(ttest, ytest, sigmatest)     lists of L arrays         -> test log-likelihood             (:311-343)
-    All linear algebra runs on the device (Objective.predict / mvnormal_logpdf)."""
+    All linear algebra runs on the device (Objective.predict / mvnormal_logpdf).
+    solver "dense" (default): every form factorises the N x N matrix.  solver "markov" (OU, matern32, matern52): the per-band form and
+    the three-argument form run in linear time (Objective.predict_markov_batch / heldout_loglik_markov_batch, one row; a test point
+    whose combine or predictive variance fails raises PosDefException, there being no test block for nearestposdef to repair); the
+    JOINT form (Sigma_pred is T x T) and sample() stay dense."""
 
-    def __init__(self, objective, delays, alpha, rho):
+    def __init__(self, objective, delays, alpha, rho, solver="dense"):
+        if solver not in ("dense", "markov"):
+            raise ValueError("solver must be 'dense' or 'markov', got %r" % (solver,))
         self.obj, self.delays, self.alpha, self.rho = objective, np.array(delays, float), np.array(alpha, float), float(rho)
+        self.solver = solver
 
     def __call__(self, ttest, ytest=None, sigmatest=None):
         L = self.obj.L
         joint = isinstance(ttest, (list, tuple)) and len(ttest) == L and all(np.ndim(a) == 1 for a in ttest)
+        if self.solver == "markov" and ytest is not None:
+            held, _, info, _ = self.obj.heldout_loglik_markov_batch(self.delays[None, :], self.alpha[None, :], [self.rho], list(ttest),
+                                                                    list(ytest), list(sigmatest))
+            if info[0] > 0:
+                raise PosDefException(int(info[0]))
+            return float(held[0])
+        if self.solver == "markov" and not joint:
+            tt = np.asarray(ttest, dtype=np.float64).ravel()
+            n = len(tt)
+            mu, var, _, info, _, _ = self.obj.predict_markov_batch(self.delays[None, :], self.alpha[None, :], [self.rho], [tt] * L)
+            if info[0] > 0:
+                raise PosDefException(int(info[0]))
+            return ([mu[0, l * n:(l + 1) * n] for l in range(L)],
+                    [np.sqrt(np.maximum(var[0, l * n:(l + 1) * n], 1e-6)) for l in range(L)])      # :301-303
         if ytest is not None:
             mu, Sig = self.obj.predict(self.delays, self.alpha, self.rho, ttest)
             s2 = np.concatenate([np.asarray(a, dtype=np.float64) for a in sigmatest]) ** 2
@@ -331,10 +352,15 @@ class DelayAveragedPredictor:
     A mixture of Gaussians has no single joint Gaussian to return, so its joint uncertainty comes as draws instead:
     sample(ttest, S, seed) returns S joint draws of the mixture, each from a row picked by the weights (Objective.sample_batch).  Its
     held-out density is well defined too: loglik(ttest, ytest, sigmatest) = log sum_g p_g N(ytest; mu_g, Sigma_g)
-    (Objective.heldout_loglik_batch)."""
+    (Objective.heldout_loglik_batch).
+    solver "markov" (OU, matern32, matern52): __call__ and loglik run in linear time (Objective.predict_markov_batch /
+    heldout_loglik_markov_batch); sample() stays dense."""
 
-    def __init__(self, objective, delays, alpha, rho, weights):
+    def __init__(self, objective, delays, alpha, rho, weights, solver="dense"):
+        if solver not in ("dense", "markov"):
+            raise ValueError("solver must be 'dense' or 'markov', got %r" % (solver,))
         self.obj = objective
+        self.solver = solver
         self.delays = np.atleast_2d(np.asarray(delays, dtype=np.float64))
         self.alpha = np.atleast_2d(np.asarray(alpha, dtype=np.float64))
         self.rho = np.atleast_1d(np.asarray(rho, dtype=np.float64))
@@ -351,7 +377,8 @@ class DelayAveragedPredictor:
             bands = [np.asarray(a, dtype=np.float64) for a in ttest]
         else:
             bands = [np.asarray(ttest, dtype=np.float64).ravel()] * L
-        _, _, _, _, mu, var = self.obj.predict_batch(self.delays, self.alpha, self.rho, bands, weights=self.weights)
+        predict = self.obj.predict_markov_batch if self.solver == "markov" else self.obj.predict_batch
+        _, _, _, _, mu, var = predict(self.delays, self.alpha, self.rho, bands, weights=self.weights)
         off = np.concatenate([[0], np.cumsum([len(b) for b in bands])])
         return ([mu[off[l]:off[l + 1]] for l in range(L)],
                 [np.sqrt(np.maximum(var[off[l]:off[l + 1]], 1e-6)) for l in range(L)])      # :301-303
@@ -359,6 +386,8 @@ class DelayAveragedPredictor:
     def loglik(self, ttest, ytest, sigmatest):
         """The mixture's held-out log density log sum_g p_g N(ytest; mu_g, Sigma_g + diag(sigmatest^2)) of the test set (lists of L
         arrays), every row scored as Predictor(ttest, ytest, sigmatest) scores it (marginaliseb.jl:311-343)."""
+        if self.solver == "markov":
+            return self.obj.heldout_loglik_markov_batch(self.delays, self.alpha, self.rho, ttest, ytest, sigmatest, weights=self.weights)[3]
         return self.obj.heldout_loglik_batch(self.delays, self.alpha, self.rho, ttest, ytest, sigmatest, weights=self.weights)[3]
 
     def sample(self, ttest, S, seed, sigmatest=None):
@@ -375,7 +404,8 @@ def gpcc(tarray, yarray, stdarray, *, kernel, delays, iterations, seed=1, number
          rhomin=0.1, rhomax, device=0, solver="dense"):
     """loglikel, pred, (alpha, postb, rho) = gpcc(tarray, yarray, stdarray; kernel, delays, iterations, ...)
     -- src/gpccfixdelay_marginaliseb.jl:46-53.  postb is returned as (mu_postb, Sigma_postb), the
-    parameters of the reference's MvNormal (:252).  solver: gpcc_grid's (the fit's likelihood evaluations; postb and pred are dense)."""
+    parameters of the reference's MvNormal (:252).  solver: gpcc_grid's; with "markov" the fit, postb (the filter's final state) and the
+    returned Predictor's per-band and held-out forms are all linear-time (its joint form and sample() stay dense)."""
     delays = np.asarray(delays, dtype=np.float64)
     assert len(delays) == len(tarray) == len(yarray) == len(stdarray)              # :78
     obj = Objective(tarray, yarray, stdarray, kernel, marginalise_b=True, device=device)
@@ -383,8 +413,14 @@ def gpcc(tarray, yarray, stdarray, *, kernel, delays, iterations, seed=1, number
                     seed=seed, numberofrestarts=numberofrestarts, initialrandom=initialrandom, rhomin=rhomin,
                     rhomax=rhomax, objective=obj, solver=solver)
     alpha, rho = res.alpha[0], float(res.rho[0])
-    postb = obj.posterior_offsets(delays, alpha, rho)
-    return float(res.loglikel[0]), Predictor(obj, delays, alpha, rho), (alpha, postb, rho)
+    if solver == "markov":
+        mu_b, Sig_b, _, info = obj.posterior_offsets_markov_batch(delays[None, :], alpha[None, :], [rho])
+        if info[0] > 0:
+            raise PosDefException(int(info[0]))
+        postb = (mu_b[0], Sig_b[0])
+    else:
+        postb = obj.posterior_offsets(delays, alpha, rho)
+    return float(res.loglikel[0]), Predictor(obj, delays, alpha, rho, solver=solver), (alpha, postb, rho)
 
 
 def singlegp(tobs, yobs, sigmaobs, *, kernel, iterations, seed=1, numberofrestarts=1, initialrandom=5, rhomin=0.1,
@@ -476,8 +512,8 @@ def performcv_grid(tobs, yobs, σobs, *, candidatedelays, kernel, iterations=1, 
     """performcv over a whole grid of candidate delays (G, L): per fold ONE Objective on the training split, ONE gpcc_grid fit over all
     G delays (seed = seedcv, as performcv's gpcc calls) and ONE heldout_loglik_batch over the G rows, weighted by the fold's own delay
     posterior (getprobabilities(loglikel), or of log_evidence with evidence="laplace") -> CVGrid.  heldout[:, g] is what performcv
-    returns at delay g.  Compare kernels by performcv_grid(...).mix.sum().  solver: gpcc_grid's (the folds' fits; the held-out scores are
-    dense)."""
+    returns at delay g.  Compare kernels by performcv_grid(...).mix.sum().  solver: gpcc_grid's; with "markov" the folds' fits AND their
+    held-out scores are linear-time (heldout_loglik_markov_batch: no nearestposdef retry, refit stays False)."""
     cand = np.ascontiguousarray(np.atleast_2d(candidatedelays), dtype=np.float64)
     G, L = cand.shape
     assert L == len(tobs) == len(yobs) == len(σobs)
@@ -501,7 +537,10 @@ def performcv_grid(tobs, yobs, σobs, *, candidatedelays, kernel, iterations=1, 
             w = getprobabilities(score)
             a = np.where(np.isfinite(res.alpha), res.alpha, 1.0)   # (a delay without a fit: a placeholder row of weight 0)
             r = np.where(np.isfinite(res.rho), res.rho, 1.0)
-            held[f], _, info[f], mix[f], refit[f] = obj.heldout_loglik_batch(cand, a, r, tte, yte, ste, weights=w)
+            if solver == "markov":
+                held[f], _, info[f], mix[f] = obj.heldout_loglik_markov_batch(cand, a, r, tte, yte, ste, weights=w)
+            else:
+                held[f], _, info[f], mix[f], refit[f] = obj.heldout_loglik_batch(cand, a, r, tte, yte, ste, weights=w)
             held[f][~(np.all(np.isfinite(res.alpha), axis=1) & np.isfinite(res.rho))] = np.nan
             wts[f] = w
             fits.append(res)

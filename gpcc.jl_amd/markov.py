@@ -179,9 +179,236 @@ def loglik_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginali
     return np.array([o[0] for o in out]), np.array([o[1] for o in out], dtype=np.int32)
 
 
+JITTER = 1e-8   # added to every predictive variance and to sigma*^2 of a held-out point (gpcc_predict_batch's constant)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Linear-time predictions, held-out log-likelihoods and the offsets' posterior (csrc/gpcc_markov_pred.hip.h), the same
+# algorithm in numpy.
+#
+#   predict   two filters and a combine.  The process is stationary, so reversed in time it is the same process with the odd
+#             derivative negated: the identical filter over the points in DESCENDING shifted time with lags |d|, its state mapped by
+#             D = diag(1, -1, 1)[:p] (+) I.  For a test point at s* = t* - tau_band: (m_f, P_f) = the forward filter after the training
+#             points with s <= s*, propagated to s*; (m_b, P_b) = the backward filter after those with s > s*, propagated to s* (a
+#             training point that ties with the test point is on the forward side only).  With P0 = blockdiag(Pinf, diag Sigma_b):
+#             P_s = (P_f^-1 + P_b^-1 - P0^-1)^-1, m_s = P_s (P_f^-1 m_f + P_b^-1 m_b), mu* = h'm_s + mean(y_band), var* = h'P_s h +
+#             JITTER; everything scaled by diag(P0)^-1/2 before the inversions.  The propagation works on a copy: the filter's own
+#             chain is not split at test points, so the training log-likelihood is loglik()'s.
+#   heldout   log p(y* | Y) = loglik(training U test) - loglik(training): the test points enter as observations with variance
+#             sigma*^2 + JITTER and residual y* - mean(y_band of the TRAINING data); the offsets' priors from the training data.
+#   postb     the offset block of the forward filter's final state: mu = m[p:] + mean(y_band), Sigma = P[p:, p:].
+# ----------------------------------------------------------------------------------------------------------------------------------
+def _prior(name, rho, p, n, vb):
+    P0 = np.zeros((n, n))
+    P0[:p, :p] = stationary(name, rho)
+    for l in range(n - p):
+        P0[p + l, p + l] = vb[l]
+    return P0
+
+
+def _propagate(name, m, P, Pinf, d, rho, p):
+    A = transition(name, d, rho)
+    m = m.copy()
+    P = P.copy()
+    m[:p] = A @ m[:p]
+    P[:p, :p] = A @ (P[:p, :p] - Pinf) @ A.T + Pinf
+    P[:p, p:] = A @ P[:p, p:]
+    P[p:, :p] = P[:p, p:].T
+    return m, P
+
+
+def _pass(name, train, tests, alpha, rho, p, n, vb, reverse=False, tests_update=False, ties_first=False):
+    """One filter over the training observations `train` [(s, band, position, r, sigma^2)] and the test points `tests` [(s, band, index,
+    r, sigma^2)].  reverse: descending s.  tests_update: the test points are observations too (held-out union) -- otherwise each is
+    tapped: the state after the training points before it, propagated to it, kept in taps[index] (unflipped).  Ties in s: training
+    points before test points going forward (or with ties_first), test points first going backward.
+    -> (loglik, info, final mean, final covariance, taps, index of the test point at which info was set or -1)."""
+    sg = -1.0 if reverse else 1.0
+    tr_kind = 0 if (not reverse or ties_first or tests_update) else 1
+    ev = [(sg * s, tr_kind, b, sg * i, True, r, s2, i) for (s, b, i, r, s2) in train]
+    ev += [(sg * s, 1 - tr_kind if not tests_update else 1, b, sg * i, False, r, s2, i) for (s, b, i, r, s2) in tests]
+    ev.sort(key=lambda e: e[:4])
+    Pinf = stationary(name, rho)
+    P = _prior(name, rho, p, n, vb)
+    m = np.zeros(n)
+    ll, info, at, sprev, step, taps = 0.0, 0, -1, None, 0, {}
+    for (key, _, b, _, is_train, r, s2, i) in ev:
+        d = 0.0 if sprev is None else key - sprev
+        if not is_train and not tests_update:
+            taps[i] = _propagate(name, m, P, Pinf, d, rho, p)
+            continue
+        sprev = key
+        step += 1
+        m, P = _propagate(name, m, P, Pinf, d, rho, p)
+        h = np.zeros(n)
+        h[0] = alpha[b]
+        if n > p:
+            h[p + b] = 1.0
+        Ph = P @ h
+        S = h @ Ph + s2
+        if not (S > 0.0 and math.isfinite(S)):
+            if info == 0:
+                info, at = step, (-1 if is_train else i)
+            return math.nan, info, m, P, taps, at
+        eps = r - h @ m
+        ll -= 0.5 * (LOG2PI + math.log(S) + eps * eps / S)
+        m = m + Ph * (eps / S)
+        P = P - np.outer(Ph, Ph) / S
+        P = 0.5 * (P + P.T)
+    return ll, info, m, P, taps, at
+
+
+def _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b):
+    name = _name(kernel)
+    L = len(tarray)
+    delays = np.asarray(delays, np.float64).reshape(L)
+    alpha = np.asarray(alpha, np.float64).reshape(L)
+    rho = float(rho)
+    if marginalise_b and L > MAX_OFFSET_BANDS:
+        raise ValueError("marginalise_b with %d bands: the linear-time solver keeps at most %d offset states" % (L, MAX_OFFSET_BANDS))
+    code = -1 if not np.all(alpha > 0.0) else (-2 if rho <= 0.0 else 0)
+    ts, rs, s2, vb = prepare(tarray, yarray, stdarray, marginalise_b)
+    means = np.array([np.asarray(y, np.float64).sum() / len(y) for y in yarray])
+    p = _ORDER[name]
+    n = p + (L if marginalise_b else 0)
+    train = [(ts[l][i] - delays[l], l, i, rs[l][i], s2[l][i]) for l in range(L) for i in range(len(ts[l]))]
+    return name, L, delays, alpha, rho, code, vb, means, p, n, train
+
+
+def _spd_inverse(A):
+    """inv(A) by Cholesky; None where a pivot is not positive and finite."""
+    n = len(A)
+    Lc = np.zeros((n, n))
+    for j in range(n):
+        d = A[j, j] - Lc[j, :j] @ Lc[j, :j]
+        if not (d > 0.0 and math.isfinite(d)):
+            return None
+        Lc[j, j] = math.sqrt(d)
+        for i in range(j + 1, n):
+            Lc[i, j] = (A[i, j] - Lc[i, :j] @ Lc[j, :j]) / Lc[j, j]
+    Li = np.linalg.solve(Lc, np.eye(n))
+    return Li.T @ Li
+
+
+def predict(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, marginalise_b=True, _slip=None):
+    """(mu[T], var[T], loglik, info) of one (tau, alpha, rho) at the test times ttest (a list of L arrays, any order; T = their total,
+    flattened in band order): predictTest's per-band mean and variance (JITTER included) by two filters and a combine, and the training
+    log-likelihood.  info: loglik()'s codes for the training filter (mu and var NaN then), else N + j for the first test point j
+    (1-based, flattened order) whose combine meets a pivot that is not positive and finite (mu and var NaN), else 0.
+    _slip (tests only): "no_flip" (D left out on the backward side), "tie_both" (a training point that ties with a test point used on
+    both sides), "no_prior" (-P0^-1 dropped), "no_jitter"."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b)
+    tests, band_of = [], []
+    for l in range(L):
+        for v in np.asarray(ttest[l], np.float64).reshape(-1):
+            tests.append((v - delays[l], l, len(tests), 0.0, 0.0))
+            band_of.append(l)
+    T, N = len(tests), len(train)
+    nan = np.full(T, math.nan)
+    if code:
+        return nan, nan.copy(), math.nan, code
+    ll, info, _, _, fw, _ = _pass(name, train, tests, alpha, rho, p, n, vb)
+    if info:
+        return nan, nan.copy(), math.nan, info
+    _, _, _, _, bw, _ = _pass(name, train, tests, alpha, rho, p, n, vb, reverse=True, ties_first=(_slip == "tie_both"))
+    P0 = _prior(name, rho, p, n, vb)
+    sc = 1.0 / np.sqrt(np.diag(P0))
+    I0 = np.linalg.inv(sc[:, None] * P0 * sc[None, :])
+    D = np.ones(n)
+    if p >= 2 and _slip != "no_flip":
+        D[1] = -1.0
+    mu, var = np.empty(T), np.empty(T)
+    for j in range(T):
+        mf, Pf = fw[j]
+        mb, Pb = bw[j]
+        mb, Pb = D * mb, D[:, None] * Pb * D[None, :]
+        If = _spd_inverse(sc[:, None] * Pf * sc[None, :])
+        Ib = _spd_inverse(sc[:, None] * Pb * sc[None, :])
+        Ps = None
+        if If is not None and Ib is not None:
+            Ps = _spd_inverse(If + Ib - (0.0 if _slip == "no_prior" else I0))
+        if Ps is None:
+            return nan, nan.copy(), ll, N + j + 1
+        ms = Ps @ (If @ (sc * mf) + Ib @ (sc * mb))
+        h = np.zeros(n)
+        h[0] = alpha[band_of[j]]
+        if n > p:
+            h[p + band_of[j]] = 1.0
+        h = h / sc
+        mu[j] = h @ ms + means[band_of[j]]
+        var[j] = h @ Ps @ h + (0.0 if _slip == "no_jitter" else JITTER)
+    return mu, var, ll, 0
+
+
+def heldout(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, ytest, sigmatest, marginalise_b=True, _slip=None):
+    """(heldout, loglik, info) of one (tau, alpha, rho): log p(ytest | training) = loglik(training U test) - loglik(training), the
+    reference's predictTest(ttest, ytest, sigmatest).  info: loglik()'s codes for the training filter, else N + j for the first test
+    point j (1-based, flattened band order) whose predictive variance in the union filter is not positive and finite (heldout NaN).
+    _slip (tests only): "no_jitter", "test_mean" (test residuals centred on the test set's own band means)."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b)
+    if code:
+        return math.nan, math.nan, code
+    jit = 0.0 if _slip == "no_jitter" else JITTER
+    tests = []
+    for l in range(L):
+        tt, yt, st = (np.asarray(a[l], np.float64).reshape(-1) for a in (ttest, ytest, sigmatest))
+        centre = (yt.sum() / len(yt) if len(yt) else 0.0) if _slip == "test_mean" else means[l]
+        for v, yv, sv in zip(tt, yt, st):
+            tests.append((v - delays[l], l, len(tests), yv - centre, sv * sv + jit))
+    ll, info, _, _, _, _ = _pass(name, train, [], alpha, rho, p, n, vb)
+    if info:
+        return math.nan, math.nan, info
+    lu, uinfo, _, _, _, at = _pass(name, train, tests, alpha, rho, p, n, vb, tests_update=True)
+    if uinfo:
+        return math.nan, ll, len(train) + max(at, 0) + 1
+    return lu - ll, ll, 0
+
+
+def posterior_offsets(kernel, tarray, yarray, stdarray, delays, alpha, rho):
+    """(mu_postb[L], Sigma_postb[L, L], loglik, info) of one (tau, alpha, rho) with marginalised offsets: the offset block of the
+    forward filter's final state (marginaliseb.jl:244-250), NaN where the training filter fails."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, True)
+    if code:
+        return np.full(L, math.nan), np.full((L, L), math.nan), math.nan, code
+    ll, info, m, P, _, _ = _pass(name, train, [], alpha, rho, p, n, vb)
+    if info:
+        return np.full(L, math.nan), np.full((L, L), math.nan), math.nan, info
+    return m[p:] + means, P[p:, p:].copy(), ll, 0
+
+
+def mix_moments(mu, var, weights):
+    """The device's mixture over rows (gpcc_predict_batch's semantics): p = w / sum w, a running weighted mean and sum of squared
+    deviations in row order; zero-weight rows skipped."""
+    w = np.asarray(weights, np.float64)
+    p = w / np.sum(w)
+    T = np.shape(mu)[1]
+    W, mean, S, V = np.zeros(T), np.zeros(T), np.zeros(T), np.zeros(T)
+    for m_ in range(len(p)):
+        if p[m_] == 0.0:
+            continue
+        W = W + p[m_]
+        d = mu[m_] - mean
+        mean = mean + (p[m_] / W) * d
+        S = S + p[m_] * d * (mu[m_] - mean)
+        V = V + p[m_] * var[m_]
+    return mean, (V + S) / W
+
+
+def mix_logsumexp(values, weights):
+    """log sum p_m exp(values_m), p = w / sum w, zero-weight rows skipped; NaN if a row with weight is NaN."""
+    w = np.asarray(weights, np.float64)
+    p = w / np.sum(w)
+    keep = p > 0
+    x = np.log(p[keep]) + np.asarray(values, np.float64)[keep]
+    if np.any(np.isnan(x)):
+        return math.nan
+    mx = np.max(x)
+    return float(mx + math.log(np.sum(np.exp(x - mx)))) if np.isfinite(mx) else float(mx)
+
+
 class MarkovObjective:
-    """The CPU mirror with the two methods gpcc_grid's `engine="python"` fit calls (loglik_batch and loglik_markov_batch are the same
-    filter here): gpcc_grid(..., objective=MarkovObjective(...), solver="markov") fits without a GPU."""
+    """The CPU mirror with the methods gpcc_grid's `engine="python"` fit and the Markov predictors call (loglik_batch and
+    loglik_markov_batch are the same filter here): gpcc_grid(..., objective=MarkovObjective(...), solver="markov") fits without a GPU."""
 
     def __init__(self, tarray, yarray, stdarray, kernel, marginalise_b=True):
         self.data = (tarray, yarray, stdarray)
@@ -191,6 +418,38 @@ class MarkovObjective:
         return loglik_batch(self.kernel, *self.data, delays, alpha, rho, self.marginalise_b)
 
     loglik_batch = loglik_markov_batch
+
+    def _rows(self, delays, alpha, rho):
+        delays = np.asarray(delays, np.float64).reshape(-1, self.L)
+        alpha = np.asarray(alpha, np.float64).reshape(-1, self.L)
+        rho = np.asarray(rho, np.float64).reshape(-1)
+        return delays, alpha, rho
+
+    def predict_markov_batch(self, delays, alpha, rho, ttest, weights=None):
+        """Objective.predict_markov_batch's result: (mu[M, T], var[M, T], loglik[M], info[M], mix_mu, mix_var)."""
+        delays, alpha, rho = self._rows(delays, alpha, rho)
+        out = [predict(self.kernel, *self.data, delays[i], alpha[i], rho[i], ttest, self.marginalise_b) for i in range(len(rho))]
+        mu, var = np.array([o[0] for o in out]), np.array([o[1] for o in out])
+        mix = mix_moments(mu, var, weights) if weights is not None else (None, None)
+        return mu, var, np.array([o[2] for o in out]), np.array([o[3] for o in out], dtype=np.int32), mix[0], mix[1]
+
+    def heldout_loglik_markov_batch(self, delays, alpha, rho, ttest, ytest, sigmatest, weights=None):
+        """Objective.heldout_loglik_markov_batch's result: (heldout[M], loglik[M], info[M], mix or None)."""
+        delays, alpha, rho = self._rows(delays, alpha, rho)
+        out = [heldout(self.kernel, *self.data, delays[i], alpha[i], rho[i], ttest, ytest, sigmatest, self.marginalise_b)
+               for i in range(len(rho))]
+        held = np.array([o[0] for o in out])
+        mix = mix_logsumexp(held, weights) if weights is not None else None
+        return held, np.array([o[1] for o in out]), np.array([o[2] for o in out], dtype=np.int32), mix
+
+    def posterior_offsets_markov_batch(self, delays, alpha, rho):
+        """Objective.posterior_offsets_markov_batch's result: (mu_b[M, L], Sigma_b[M, L, L], loglik[M], info[M])."""
+        if not self.marginalise_b:
+            raise ValueError("posterior_offsets needs marginalise_b")
+        delays, alpha, rho = self._rows(delays, alpha, rho)
+        out = [posterior_offsets(self.kernel, *self.data, delays[i], alpha[i], rho[i]) for i in range(len(rho))]
+        return (np.array([o[0] for o in out]), np.array([o[1] for o in out]), np.array([o[2] for o in out]),
+                np.array([o[3] for o in out], dtype=np.int32))
 
     def close(self):
         pass

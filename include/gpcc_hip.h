@@ -149,6 +149,8 @@ int gpcc_multi_stats(gpcc_handle_t handle, double *compute_ms, double *gather_ms
  *   fit_threads              0        ... host threads (slices) of a large fit; 0 = by size
  *   fit_markov               0        gpcc_grid_loglik: 1 = every optimiser round is one gpcc_loglik_markov_batch (OU, Matern kernels; the
  *                                     same likelihood evaluated in linear time, so the fit's trajectory agrees to rounding, not bitwise)
+ *   markov_chunk_rows        0        gpcc_predict_markov_batch: rows per chunk of its tap scratch; 0 = what fits 128 MiB (results do not
+ *                                     depend on it)
  *   fp32_refine              1        fp32 handles: fp64 refinement of the quadratic forms
  *   fp32_guard               1        fp32 handles: evaluations whose pivot ratios exceed the limits are repeated in fp64
  *   fp32_assemble            1        fp32 handles: tiles inside one band pair are evaluated in fp32
@@ -163,7 +165,7 @@ int gpcc_multi_stats(gpcc_handle_t handle, double *compute_ms, double *gather_ms
  * "gather_width", "small_n_max" (383), "small_n_active", "small_n_count", "chain_count" (evaluations that took the persistent
  * launch so far), "chain_last_grid" (workgroups of the last one), "fp32_guard_count", "fp32_chain_count", "workspace_streams" / "workspace_slots" (what the workspace really holds: smaller than "streams" /
  * "slots_per_stream" only if the device's memory was short when it was allocated -- then gpcc_last_error carries a note; the
- * options themselves are never rewritten). */
+ * options themselves are never rewritten); "markov_tap_bytes" (the tap scratch of gpcc_predict_markov_batch, 0 before its first call). */
 int gpcc_set_option(gpcc_handle_t handle, const char *key, long value);
 long gpcc_get_option(gpcc_handle_t handle, const char *key);
 
@@ -212,9 +214,50 @@ int gpcc_loglik_batch(gpcc_handle_t handle, int M, const double *delays, const d
  * (3 N doubles, built on the first call) and 8 M (2L + 2) bytes of staging; NONE of the N^2 workspace -- a handle that only ever calls
  * this entry never allocates it.  Option "fit_markov" (default 0): 1 makes every optimiser round of gpcc_grid_loglik one call of this
  * entry instead of a gpcc_loglik_batch (GPCC_ERR_UNSUPPORTED where this entry is); read-only "markov_count": evaluations so far.
- * Gradient, Hessian and predictions stay on the dense path.  Blocking. */
+ * Predictions, held-out scores and the offsets' posterior in linear time: the three entries below; gradient and Hessian stay dense.
+ * Blocking. */
 int gpcc_loglik_markov_batch(gpcc_handle_t handle, int M, const double *delays, const double *alpha, const double *rho,
                              double *loglik, int *info);
+
+/* The three post-fit products of the Markov kernels in linear time, O(N + T) per row, from the same state-space model as
+ * gpcc_loglik_markov_batch (kernels: csrc/gpcc_markov_pred.hip.h); nothing is approximated, only the order of the
+ * arithmetic differs from the dense entries.  Argument lists, NULL rules, weight checks (GPCC_ERR_ARGUMENT before any device work),
+ * 1 <= T <= 32768 with Ntest[l] = 0 allowed and the mixtures' semantics are those of gpcc_predict_batch and
+ * gpcc_heldout_loglik_batch; the refusals are gpcc_loglik_markov_batch's (GPCC_ERR_UNSUPPORTED: rbf; marginalise_b with L > 4).  The
+ * test times need not be sorted (each band is sorted on the host, results come back in the caller's order).  loglik[m], and info[m]
+ * where the training filter fails (-1, -2, 1 .. N), are bitwise gpcc_loglik_markov_batch's for that row.  A row's bits do not depend on
+ * M, the chunking, the row order or the launch shape.  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on
+ * device_ids[0].  Blocking.
+ *
+ * gpcc_predict_markov_batch: gpcc_predict_batch's mu_out / var_out (M x T; predictTest's per-band mean and variance, JITTER = 1e-8
+ *   included) by two filters and a combine: one lane per (row, direction) walks the training points merged with the test points in
+ *   ascending / descending shifted time and stores, for every test point, a copy of its state propagated to that point (the backward
+ *   state mapped by D = diag(1, -1, 1), the time reversal of a stationary process); one lane per (row, test point) then forms
+ *   P_s = (P_f^-1 + P_b^-1 - P0^-1)^-1, m_s = P_s (P_f^-1 m_f + P_b^-1 m_b), mu* = h'm_s + mean(y_band), var* = h'P_s h + JITTER.  A
+ *   training point that ties with a test point in shifted time counts on the forward side only.  info[m] = N + j (1 <= j <= T, the
+ *   caller's flattened order): the combine of test point j met a pivot that is not positive and finite -- row m of mu_out and var_out
+ *   is NaN, loglik[m] valid, no other row touched.
+ *   Memory, allocated on the first call and grown on demand: gpcc_loglik_markov_batch's, plus 16 T bytes of test points, the tap
+ *   scratch 16 T (n + n (n + 1) / 2) bytes per row of a chunk (n = p + L offsets <= 7: at most 560 T), the chunk being the rows that
+ *   fit 128 MiB (whole waves of 64 when it holds one; at least one row, whatever it needs; option "markov_chunk_rows" > 0 sets it;
+ *   read-only "markov_tap_bytes": its size), 16 T bytes per row of the chunk for mu and var, and with weights 48 T + 8 M bytes.
+ * gpcc_heldout_loglik_markov_batch: heldout[m] = loglik(training U test) - loglik(training), two lanes per row of one launch, the test
+ *   points entering the first as observations with variance sigmatest^2 + JITTER and residual ytest - mean(y_band of the training
+ *   data); equal to gpcc_heldout_loglik_batch's logpdf.  info[m] = N + j: the predictive variance of test point j (the caller's
+ *   order) in the union filter was not positive and finite (or that of a training point after it) -- heldout[m] NaN, loglik[m] valid.
+ *   There is no nearestposdef retry here (there is no test block to repair).  Memory: 28 T bytes of test points and 28 M + 32 bytes.
+ * gpcc_posterior_offsets_markov_batch: mu_b_out (M x L) and Sigma_b_out (M x L x L, symmetric) of gpcc_posterior_offsets at every row:
+ *   the offset block of the forward filter's final state, mu = m[p:] + mean(y_band), Sigma = P[p:, p:]; NaN where info[m] != 0.
+ *   marginalise_b == 0: GPCC_ERR_ARGUMENT, as gpcc_posterior_offsets.  Memory: 8 M (L + L (L + 1) / 2) bytes.
+ * A handle that never calls these allocates none of it, and none of them allocates the N^2 workspace. */
+int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const int *Ntest,
+                              const double *ttest, const double *weights, double *mu_out, double *var_out, double *mix_mu,
+                              double *mix_var, double *loglik, int *info);
+int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                     const int *Ntest, const double *ttest, const double *ytest, const double *sigmatest,
+                                     const double *weights, double *heldout, double *mix_heldout, double *loglik, int *info);
+int gpcc_posterior_offsets_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                        double *mu_b_out, double *Sigma_b_out, double *loglik, int *info);
 
 /* objective(alpha, rho) and its gradient for M independent (tau, alpha, rho): loglik[M], info[M] as gpcc_loglik_batch;
  * grad: M rows of 2L+1 doubles [d/d alpha_1..alpha_L, d/d rho, d/d tau_1..tau_L] in the reference's (constrained)

@@ -72,6 +72,66 @@ function loglik_markov_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{F
     return ll, info
 end
 
+"predict_batch in LINEAR time (gpcc_predict_markov_batch: two Kalman filters and a combine per row, DESIGN 4.16; OU, matern32, matern52):
+(mu T×M, var T×M, ll[M], info[M]) and, with weights, (mix_mu[T], mix_var[T]) -- what predict_batch returns, to rounding.  ttest: a
+vector of L vectors, any order.  info = N + j: the combine of test point j failed (that column NaN)."
+function predict_markov_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64},
+                              ttest::Vector{Vector{Float64}}; weights::Union{Nothing,Vector{Float64}} = nothing)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M) && length(ttest) == h.L
+    Nt, tt = Cint.(length.(ttest)), reduce(vcat, ttest)
+    T = length(tt)
+    mu, var = Matrix{Float64}(undef, T, M), Matrix{Float64}(undef, T, M)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    mm, mv = Vector{Float64}(undef, T), Vector{Float64}(undef, T)
+    w = weights === nothing ? C_NULL : pointer(weights)
+    GC.@preserve weights begin
+        rc = ccall((:gpcc_predict_markov_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                    Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+                   h.ptr, M, delays, alpha, rho, Nt, tt, w, mu, var, weights === nothing ? C_NULL : pointer(mm),
+                   weights === nothing ? C_NULL : pointer(mv), ll, info)
+    end
+    rc == 0 || error("gpcc_predict_markov_batch: " * lasterror(h.ptr))
+    return mu, var, ll, info, (weights === nothing ? nothing : (mm, mv))
+end
+
+"heldout_loglik_batch in LINEAR time (gpcc_heldout_loglik_markov_batch: loglik(training ∪ test) − loglik(training), two filters per
+row): (heldout[M], ll[M], info[M], mix or nothing).  info = N + j: the predictive variance of test point j was not positive and finite."
+function heldout_loglik_markov_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64},
+                                     ttest::Vector{Vector{Float64}}, ytest::Vector{Vector{Float64}}, sigmatest::Vector{Vector{Float64}};
+                                     weights::Union{Nothing,Vector{Float64}} = nothing)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M) && length(ttest) == length(ytest) == length(sigmatest) == h.L
+    @assert length.(ttest) == length.(ytest) == length.(sigmatest)
+    Nt, tt, yt, st = Cint.(length.(ttest)), reduce(vcat, ttest), reduce(vcat, ytest), reduce(vcat, sigmatest)
+    held, ll, info = Vector{Float64}(undef, M), Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    mix = Vector{Float64}(undef, 1)
+    GC.@preserve weights begin
+        rc = ccall((:gpcc_heldout_loglik_markov_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                    Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+                   h.ptr, M, delays, alpha, rho, Nt, tt, yt, st, weights === nothing ? C_NULL : pointer(weights), held,
+                   weights === nothing ? C_NULL : pointer(mix), ll, info)
+    end
+    rc == 0 || error("gpcc_heldout_loglik_markov_batch: " * lasterror(h.ptr))
+    return held, ll, info, (weights === nothing ? nothing : mix[1])
+end
+
+"posterior_offsets at M rows in LINEAR time (gpcc_posterior_offsets_markov_batch: the offset block of the filter's final state):
+(mu_postb L×M, Sigma_postb L×L×M, ll[M], info[M]); columns with info != 0 are NaN.  Needs marginalise_b."
+function posterior_offsets_markov_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    mu, Sig = Matrix{Float64}(undef, h.L, M), Array{Float64,3}(undef, h.L, h.L, M)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    rc = ccall((:gpcc_posterior_offsets_markov_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, mu, Sig, ll, info)
+    rc == 0 || error("gpcc_posterior_offsets_markov_batch: " * lasterror(h.ptr))
+    return mu, Sig, ll, info
+end
+
 "objective and its gradient for M triples: (ll[M], grad (2L+1)×M, info[M]); a column of grad is [∂/∂α_1..α_L, ∂/∂ρ, ∂/∂τ_1..τ_L]
 in the constrained parameters, NaN where info != 0.  The reference has no gradient: this is the derivative of objective(α, ρ)."
 function loglik_grad_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
