@@ -1905,6 +1905,7 @@ extern "C" int gpcc_loglik_grad_batch(gpcc_handle_t h, int M, const double *dela
 // The exact linear-time log-likelihood of the Markov kernels (gpcc_loglik_markov_batch; kernel: gpcc_markov.hip.h): a
 // Kalman filter over the observations merged by shifted time, one lane per evaluation, one launch per call.  It needs the light
 // curves with every band sorted by time (built here on the first call) and the staging buffers, nothing of the N^2 workspace.
+// The rules all four linear-time entries follow (refusals, <P, NOFF>, prologue and tail, common arguments, launch shape) are here, once.
 // ------------------------------------------------------------------------------------------
 static int ensure_markov(gpcc_handle_t h)
 {
@@ -1939,6 +1940,72 @@ static int ensure_markov(gpcc_handle_t h)
     return 0;
 }
 
+// the refusals of every linear-time entry, under the caller's name (dense: the entry that takes what this one cannot)
+static int markov_refusals(gpcc_handle_t h, const char *who, const char *dense)
+{
+    const gpcc_handle_t p = primary(h);
+    if (p->kernel_id == GPCC_KERNEL_RBF)
+        return fail(h, GPCC_ERR_UNSUPPORTED, "%s: the rbf kernel is not Markov (OU, matern32 and matern52 are); use %s", who, dense);
+    if (p->mb && p->L > GPCC_MARKOV_MAX_OFFSETS)
+        return fail(h, GPCC_ERR_UNSUPPORTED, "%s: marginalise_b with L=%d bands (the filter keeps at most %d offset states); use %s", who,
+                    p->L, GPCC_MARKOV_MAX_OFFSETS, dense);
+    return 0;
+}
+
+// the instantiation <P, NOFF> of a handle's filter: the states of the process and the offset states
+struct MarkovDims { int p, noff; };
+static MarkovDims markov_dims(gpcc_handle_t h)
+{
+    return {h->kernel_id == GPCC_KERNEL_OU ? 1 : (h->kernel_id == GPCC_KERNEL_MATERN32 ? 2 : 3), h->mb ? h->L : 0};
+}
+
+// what every linear-time entry does first on its device: the sorted light curves, the staging buffers, the entry's own buffers (grow()
+// returns 0 or fail()'s code) and the M rows staged at dd, da, dr
+template <typename Grow>
+static int markov_begin(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, double *&dd, double *&da,
+                        double *&dr, Grow &&grow)
+{
+    int rc = ensure_markov(h);
+    if (!rc) rc = ensure_staging(h, M);
+    if (!rc) rc = grow();
+    if (!rc) rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
+    return rc;
+}
+
+// ... and last: the filter's loglik and info of the M rows to the caller, after whatever else main_stream holds
+static int markov_finish(gpcc_handle_t h, int M, double *loglik, int *info)
+{
+    HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, h->main_stream));
+    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, h->main_stream));
+    HIPCHK(h, hipStreamSynchronize(h->main_stream));
+    return 0;
+}
+
+// the arguments gpcc_markov_eval and gpcc_markov_taps share (ARGS: GpccMarkovArgs or GpccMarkovPredArgs); the launch sets stage
+template <typename ARGS>
+static void markov_fill_args(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, ARGS &a)
+{
+    a.pts = h->d_mk; a.delays = dd; a.alpha = da; a.rho = dr;
+    a.out_loglik = h->d_out; a.out_info = h->d_oinfo;
+    a.M = M; a.L = h->L; a.N = h->N; a.stage = 0;
+    a.off[0] = 0;
+    for (int l = 0; l < GPCC_MARKOV_MAXL; ++l) a.off[l + 1] = a.off[l] + (l < h->L ? h->Nl[l] : 0);
+    const int noff = markov_dims(h).noff;
+    for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) a.sigma_b[l] = l < noff ? h->sigma_b[l] : 0.0;
+}
+
+// the launch shape of `waves` waves of lanes: one wave per workgroup while the chip has a CU for every wave, two or four waves sharing
+// one staged copy beyond; the light curves (and test points) go to LDS when they fit beside the lanes' cursors.  lds_bytes(threads,
+// stage): the kernel's dynamic LDS.  -> threads per workgroup
+template <typename LdsBytes>
+static int markov_launch_shape(gpcc_handle_t h, long waves, LdsBytes &&lds_bytes, int &stage, size_t &lds)
+{
+    const int wpb = waves <= h->mk_cus ? 1 : (waves <= 2L * h->mk_cus ? 2 : 4), threads = 64 * wpb;
+    stage = lds_bytes(threads, true) <= GPCC_MARKOV_LDS_MAX ? 1 : 0;
+    lds = lds_bytes(threads, stage != 0);
+    return threads;
+}
+
 extern "C" int gpcc_loglik_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                         double *loglik, int *info)
 {
@@ -1946,45 +2013,25 @@ extern "C" int gpcc_loglik_markov_batch(gpcc_handle_t h, int M, const double *de
     if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
     if (M == 0) return 0;
     if (!delays || !alpha || !rho || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
-    {
-        const gpcc_handle_t p = primary(h);
-        if (p->kernel_id == GPCC_KERNEL_RBF)
-            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_markov_batch: the rbf kernel is not Markov (OU, matern32 and matern52 are); "
-                                                 "use gpcc_loglik_batch");
-        if (p->mb && p->L > GPCC_MARKOV_MAX_OFFSETS)
-            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_markov_batch: marginalise_b with L=%d bands (the filter keeps at most %d offset "
-                                                 "states); use gpcc_loglik_batch", p->L, GPCC_MARKOV_MAX_OFFSETS);
-    }
-    int rc = 0;
+    int rc = markov_refusals(h, "gpcc_loglik_markov_batch", "gpcc_loglik_batch");
+    if (rc) return rc;
     if (route_fp64(h, "linear-time log-likelihood", rc,
                    [&](gpcc_handle_t o) { return gpcc_loglik_markov_batch(o, M, delays, alpha, rho, loglik, info); }))
         return rc;
     GPCC_ON_DEVICE(h, h->device);
     double *dd, *da, *dr;
-    rc = ensure_markov(h);
-    if (!rc) rc = ensure_staging(h, M);
-    if (!rc) rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [] { return 0; });
     if (rc) return rc;
     GpccMarkovArgs a;
-    a.pts = h->d_mk; a.delays = dd; a.alpha = da; a.rho = dr;
-    a.out_loglik = h->d_out; a.out_info = h->d_oinfo;
-    a.M = M; a.L = h->L; a.N = h->N;
-    a.off[0] = 0;
-    for (int l = 0; l < GPCC_MARKOV_MAXL; ++l) a.off[l + 1] = a.off[l] + (l < h->L ? h->Nl[l] : 0);
-    const int noff = h->mb ? h->L : 0;
-    for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) a.sigma_b[l] = l < noff ? h->sigma_b[l] : 0.0;
-    // one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy of the light curves
-    // beyond; the light curves go to LDS when they fit beside the lanes' cursors
-    const long waves = ((long)M + 63) / 64;
-    const int wpb = waves <= h->mk_cus ? 1 : (waves <= 2L * h->mk_cus ? 2 : 4), threads = 64 * wpb;
-    a.stage = gpcc_markov_lds_bytes(h->N, h->L, threads, true) <= GPCC_MARKOV_LDS_MAX ? 1 : 0;
-    const size_t lds = gpcc_markov_lds_bytes(h->N, h->L, threads, a.stage != 0);
-    const int p = h->kernel_id == GPCC_KERNEL_OU ? 1 : (h->kernel_id == GPCC_KERNEL_MATERN32 ? 2 : 3);
-    const hipError_t e = gpcc_markov_launch(p, noff, a, (int)((waves + wpb - 1) / wpb), threads, lds, h->main_stream);
+    markov_fill_args(h, M, dd, da, dr, a);
+    size_t lds;
+    const int threads = markov_launch_shape(h, ((long)M + 63) / 64,
+                                            [&](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }, a.stage, lds);
+    const MarkovDims d = markov_dims(h);
+    const hipError_t e = gpcc_markov_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), threads, lds, h->main_stream);
     if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_eval: %s", hipGetErrorString(e));
-    HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, h->main_stream));
-    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, h->main_stream));
-    HIPCHK(h, hipStreamSynchronize(h->main_stream));
+    rc = markov_finish(h, M, loglik, info);
+    if (rc) return rc;
     h->markov_count += M;
     return 0;
 }
@@ -1996,18 +2043,6 @@ extern "C" int gpcc_loglik_markov_batch(gpcc_handle_t h, int M, const double *de
 // workspace.  Everything runs on main_stream.
 // ------------------------------------------------------------------------------------------
 #define GPCC_MKP_TAP_BYTES ((long)128 << 20)   /* the tap scratch of a chunk of rows (a single row may need more: T = 32768, n = 7) */
-
-// the refusals of gpcc_loglik_markov_batch, under the caller's name
-static int markov_refusals(gpcc_handle_t h, const char *who, const char *dense)
-{
-    const gpcc_handle_t p = primary(h);
-    if (p->kernel_id == GPCC_KERNEL_RBF)
-        return fail(h, GPCC_ERR_UNSUPPORTED, "%s: the rbf kernel is not Markov (OU, matern32 and matern52 are); use %s", who, dense);
-    if (p->mb && p->L > GPCC_MARKOV_MAX_OFFSETS)
-        return fail(h, GPCC_ERR_UNSUPPORTED, "%s: marginalise_b with L=%d bands (the filter keeps at most %d offset states); use %s", who,
-                    p->L, GPCC_MARKOV_MAX_OFFSETS, dense);
-    return 0;
-}
 
 // the test points with every band sorted by time (stably): tt = the sorted times, order[j] = the position in the caller's flattened
 // arrays of sorted point j, band[j] its band, toff the bands' offsets
@@ -2027,7 +2062,8 @@ static void markov_sort_tests(gpcc_handle_t h, const int *Ntest, const double *t
     }
 }
 
-// the arguments every launch of gpcc_markov_taps shares, and the launch shape of `rows` rows x ny lanes
+// the arguments every launch of gpcc_markov_taps shares: the filter's, the test points (toff: their bands' offsets, or NULL for none)
+// and one chunk of all M rows
 static int markov_pred_common(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, const int *toff, long T,
                               GpccMarkovPredArgs &a)
 {
@@ -2035,30 +2071,24 @@ static int markov_pred_common(gpcc_handle_t h, int M, const double *dd, const do
         HIPCHK(h, gpcc_mkp_configure());
         h->mkp_configured = 1;
     }
-    a.pts = h->d_mk; a.tpts = h->d_mkt; a.delays = dd; a.alpha = da; a.rho = dr;
-    a.out_loglik = h->d_out; a.out_info = h->d_oinfo;
+    markov_fill_args(h, M, dd, da, dr, a);
+    a.tpts = h->d_mkt; a.T = (int)T;
     a.tap = nullptr; a.ll2 = nullptr; a.info2 = nullptr; a.at2 = nullptr; a.fin = nullptr;
-    a.M = M; a.L = h->L; a.N = h->N; a.T = (int)T; a.stage = 0;
     a.row0 = 0; a.rows = M; a.mstride = M;
-    a.off[0] = 0;
-    for (int l = 0; l < GPCC_MARKOV_MAXL; ++l) a.off[l + 1] = a.off[l] + (l < h->L ? h->Nl[l] : 0);
     for (int l = 0; l <= GPCC_MARKOV_MAXL; ++l) a.toff[l] = toff ? toff[l] : 0;
-    const int noff = h->mb ? h->L : 0;
-    for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) a.sigma_b[l] = l < noff ? h->sigma_b[l] : 0.0;
     return 0;
 }
 
+// `rows` rows x ny lanes of gpcc_markov_taps
 static int markov_pred_launch(gpcc_handle_t h, int mode, GpccMarkovPredArgs &a, int ny)
 {
-    // one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy beyond (as gpcc_markov_eval)
-    const long waves = (((long)a.rows + 63) / 64) * ny;
-    const int wpb = waves <= h->mk_cus ? 1 : (waves <= 2L * h->mk_cus ? 2 : 4), threads = 64 * wpb;
     const int tw = mode == GPCC_MKP_TAP ? 1 : 3;
-    a.stage = gpcc_mkp_lds_bytes(a.N, a.T, tw, a.L, threads, true) <= GPCC_MARKOV_LDS_MAX ? 1 : 0;
-    const size_t lds = gpcc_mkp_lds_bytes(a.N, a.T, tw, a.L, threads, a.stage != 0);
+    size_t lds;
+    const int threads = markov_launch_shape(h, (((long)a.rows + 63) / 64) * ny,
+                                            [&](int thr, bool st) { return gpcc_mkp_lds_bytes(a.N, a.T, tw, a.L, thr, st); }, a.stage, lds);
     if (lds > GPCC_MARKOV_LDS_MAX) return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_markov_taps: %zu bytes of LDS", lds);
-    const int p = h->kernel_id == GPCC_KERNEL_OU ? 1 : (h->kernel_id == GPCC_KERNEL_MATERN32 ? 2 : 3);
-    const hipError_t e = gpcc_mkp_launch_taps(mode, p, h->mb ? h->L : 0, a, (a.rows + threads - 1) / threads, ny, threads, lds, h->main_stream);
+    const MarkovDims d = markov_dims(h);
+    const hipError_t e = gpcc_mkp_launch_taps(mode, d.p, d.noff, a, (a.rows + threads - 1) / threads, ny, threads, lds, h->main_stream);
     if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_taps: %s", hipGetErrorString(e));
     return 0;
 }
@@ -2086,8 +2116,8 @@ extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *d
     if (!rc) rc = mixture_weights(h, M, weights, false, p);
     if (rc || M == 0) return rc;
     GPCC_ON_DEVICE(h, h->device);
-    const int pdim = h->kernel_id == GPCC_KERNEL_OU ? 1 : (h->kernel_id == GPCC_KERNEL_MATERN32 ? 2 : 3), noff = h->mb ? h->L : 0;
-    const long ns = pdim + noff, nrec = ns + ns * (ns + 1) / 2;
+    const MarkovDims d = markov_dims(h);
+    const long ns = d.p + d.noff, nrec = ns + ns * (ns + 1) / 2;
     // rows per chunk: what the scratch budget holds (whole waves when it holds one), or the option
     long chunk = GPCC_MKP_TAP_BYTES / (2 * T * nrec * 8);
     if (chunk >= 64) chunk -= chunk % 64;
@@ -2100,18 +2130,17 @@ extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *d
     std::vector<double> tt(T);
     std::vector<int> ti(2 * T);
     for (long j = 0; j < T; ++j) { tt[j] = ttest[order[j]]; ti[j] = band[j]; ti[T + j] = order[j]; }
-    rc = ensure_markov(h);
-    if (!rc) rc = ensure_staging(h, M);
-    if (!rc) rc = grow_buf(h, &h->d_mkt, &h->mkt_cap, T);
-    if (!rc) rc = grow_buf(h, &h->d_mkti, &h->mkti_cap, 2 * T);
-    if (!rc) rc = grow_buf(h, &h->d_mktap, &h->mktap_cap, 2 * T * nrec * chunk);
-    if (!rc) rc = grow_buf(h, &h->d_mkmu, &h->mkmu_cap, chunk * T);
-    if (!rc) rc = grow_buf(h, &h->d_mkvar, &h->mkvar_cap, chunk * T);
-    if (!rc && weights) rc = grow_buf(h, &h->d_mkmix, &h->mkmix_cap, 6 * T);
-    if (!rc && weights) rc = grow_buf(h, &h->d_mkw, &h->mkw_cap, M);
-    if (rc) return rc;
     double *dd, *da, *dr;
-    rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
+        int g = grow_buf(h, &h->d_mkt, &h->mkt_cap, T);
+        if (!g) g = grow_buf(h, &h->d_mkti, &h->mkti_cap, 2 * T);
+        if (!g) g = grow_buf(h, &h->d_mktap, &h->mktap_cap, 2 * T * nrec * chunk);
+        if (!g) g = grow_buf(h, &h->d_mkmu, &h->mkmu_cap, chunk * T);
+        if (!g) g = grow_buf(h, &h->d_mkvar, &h->mkvar_cap, chunk * T);
+        if (!g && weights) g = grow_buf(h, &h->d_mkmix, &h->mkmix_cap, 6 * T);
+        if (!g && weights) g = grow_buf(h, &h->d_mkw, &h->mkw_cap, M);
+        return g;
+    });
     if (rc) return rc;
     hipStream_t ms = h->main_stream;
     HIPCHK(h, hipMemcpyAsync(h->d_mkt, tt.data(), sizeof(double) * T, hipMemcpyHostToDevice, ms));
@@ -2136,7 +2165,7 @@ extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *d
         a.mstride = c.mstride = (int)chunk;
         rc = markov_pred_launch(h, GPCC_MKP_TAP, a, 2);
         if (rc) return rc;
-        hipError_t e = gpcc_mkp_launch_combine(pdim, noff, c, ms);
+        hipError_t e = gpcc_mkp_launch_combine(d.p, d.noff, c, ms);
         if (e == hipSuccess) e = gpcc_mkp_launch_rowinfo(h->d_mkmu, h->d_mkvar, h->d_oinfo, h->N, (int)T, (int)row0, rows, ms);
         if (e == hipSuccess && weights)
             e = gpcc_mkp_launch_mix(h->d_mkmu, h->d_mkvar, h->d_mkw, h->d_mkmix, (int)T, (int)row0, rows, row0 + rows == M ? 1 : 0, ms);
@@ -2146,14 +2175,11 @@ extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *d
             HIPCHK(h, hipMemcpyAsync(var_out + row0 * T, h->d_mkvar, sizeof(double) * rows * T, hipMemcpyDeviceToHost, ms));
         }
     }
-    HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
-    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
     if (weights) {
         HIPCHK(h, hipMemcpyAsync(mix_mu, h->d_mkmix + 4 * T, sizeof(double) * T, hipMemcpyDeviceToHost, ms));
         HIPCHK(h, hipMemcpyAsync(mix_var, h->d_mkmix + 5 * T, sizeof(double) * T, hipMemcpyDeviceToHost, ms));
     }
-    HIPCHK(h, hipStreamSynchronize(ms));
-    return 0;
+    return markov_finish(h, M, loglik, info);
 }
 
 extern "C" int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
@@ -2190,16 +2216,15 @@ extern "C" int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const do
         tp[T + j] = ytest[o] - h->mean_b[band[j]];
         tp[2 * T + j] = sigmatest[o] * sigmatest[o] + GPCC_MKP_JITTER;
     }
-    rc = ensure_markov(h);
-    if (!rc) rc = ensure_staging(h, M);
-    if (!rc) rc = grow_buf(h, &h->d_mkt, &h->mkt_cap, 3 * T);
-    if (!rc) rc = grow_buf(h, &h->d_mkti, &h->mkti_cap, T);
-    if (!rc) rc = grow_buf(h, &h->d_mkaux, &h->mkaux_cap, 2L * M + 4);
-    if (!rc) rc = grow_buf(h, &h->d_mkauxi, &h->mkauxi_cap, 2L * M);
-    if (!rc && weights) rc = grow_buf(h, &h->d_mkw, &h->mkw_cap, M);
-    if (rc) return rc;
     double *dd, *da, *dr;
-    rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
+        int g = grow_buf(h, &h->d_mkt, &h->mkt_cap, 3 * T);
+        if (!g) g = grow_buf(h, &h->d_mkti, &h->mkti_cap, T);
+        if (!g) g = grow_buf(h, &h->d_mkaux, &h->mkaux_cap, 2L * M + 4);
+        if (!g) g = grow_buf(h, &h->d_mkauxi, &h->mkauxi_cap, 2L * M);
+        if (!g && weights) g = grow_buf(h, &h->d_mkw, &h->mkw_cap, M);
+        return g;
+    });
     if (rc) return rc;
     hipStream_t ms = h->main_stream;
     HIPCHK(h, hipMemcpyAsync(h->d_mkt, tp.data(), sizeof(double) * 3 * T, hipMemcpyHostToDevice, ms));
@@ -2216,11 +2241,8 @@ extern "C" int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const do
                                                         weights ? h->d_mkw : nullptr, d_mix, h->N, M, ms);
     if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "linear-time held-out log-likelihood: %s", hipGetErrorString(e));
     if (heldout) HIPCHK(h, hipMemcpyAsync(heldout, d_held, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
-    HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
-    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
     if (weights) HIPCHK(h, hipMemcpyAsync(mix_heldout, d_mix + 3, sizeof(double), hipMemcpyDeviceToHost, ms));
-    HIPCHK(h, hipStreamSynchronize(ms));
-    return 0;
+    return markov_finish(h, M, loglik, info);
 }
 
 extern "C" int gpcc_posterior_offsets_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
@@ -2239,13 +2261,11 @@ extern "C" int gpcc_posterior_offsets_markov_batch(gpcc_handle_t h, int M, const
     if (M == 0) return 0;
     GPCC_ON_DEVICE(h, h->device);
     const int L = h->L, nfin = L + L * (L + 1) / 2;
-    rc = ensure_markov(h);
-    if (!rc) rc = ensure_staging(h, M);
-    if (!rc) rc = grow_buf(h, &h->d_mkaux, &h->mkaux_cap, (long)nfin * M);
-    if (!rc) rc = grow_buf(h, &h->d_mkt, &h->mkt_cap, 3);   // (no test points: the kernel reads none, the pointer must exist)
-    if (rc) return rc;
     double *dd, *da, *dr;
-    rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
+        const int g = grow_buf(h, &h->d_mkaux, &h->mkaux_cap, (long)nfin * M);
+        return g ? g : grow_buf(h, &h->d_mkt, &h->mkt_cap, 3);   // (no test points: the kernel reads none, the pointer must exist)
+    });
     if (rc) return rc;
     GpccMarkovPredArgs a;
     rc = markov_pred_common(h, M, dd, da, dr, nullptr, 0, a);
@@ -2253,12 +2273,10 @@ extern "C" int gpcc_posterior_offsets_markov_batch(gpcc_handle_t h, int M, const
     a.fin = h->d_mkaux;
     rc = markov_pred_launch(h, GPCC_MKP_UPDATE, a, 1);
     if (rc) return rc;
-    hipStream_t ms = h->main_stream;
     std::vector<double> fin((size_t)nfin * M);
-    HIPCHK(h, hipMemcpyAsync(fin.data(), h->d_mkaux, sizeof(double) * nfin * M, hipMemcpyDeviceToHost, ms));
-    HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
-    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
-    HIPCHK(h, hipStreamSynchronize(ms));
+    HIPCHK(h, hipMemcpyAsync(fin.data(), h->d_mkaux, sizeof(double) * nfin * M, hipMemcpyDeviceToHost, h->main_stream));
+    rc = markov_finish(h, M, loglik, info);
+    if (rc) return rc;
     for (long m = 0; m < M; ++m) {
         double *mu = mu_b_out + m * L, *S = Sigma_b_out + m * L * L;
         const bool bad = info[m] != 0;

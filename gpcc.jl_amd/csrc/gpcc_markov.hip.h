@@ -1,5 +1,7 @@
 // gpcc_markov.hip.h -- the exact linear-time log-likelihood of the Markov kernels (OU, Matern-3/2, Matern-5/2) for gfx950:
-// gpcc_loglik_markov_batch of include/gpcc_hip.h; gpcc.jl_amd/markov.py is the same algorithm in numpy.
+// gpcc_loglik_markov_batch of include/gpcc_hip.h; gpcc.jl_amd/markov.py is the same algorithm in numpy.  This file owns
+// the Kalman filter itself (gpcc_mk_init, gpcc_mk_transition, gpcc_mk_propagate, gpcc_mk_update): gpcc_markov_eval below and
+// gpcc_markov_taps of gpcc_markov_pred.hip.h are two walks over the data around the one step.
 //
 // f with one of these kernels is a stationary Gauss-Markov process of state dimension P = 1, 2, 3 (f, f', f''), so with all
 // observations merged in the order of their shifted times s = t - tau_band, K = alpha alpha' k(s - s') + Sobs (+ B) is the covariance
@@ -47,6 +49,172 @@ static inline size_t gpcc_markov_lds_bytes(int N, int L, int threads, bool stage
 // element (i, j) of a symmetric matrix kept in its upper triangle (constant indices after unrolling)
 #define GPCC_MK_SYM(Q, i, j) ((i) <= (j) ? Q[i][j] : Q[j][i])
 
+// ---- the filter, shared by gpcc_markov_eval and gpcc_markov_taps (gpcc_markov_pred.hip.h).  Everything is __forceinline__ and takes its
+// arrays by reference, so that after unrolling they stay in registers; the compiler's FMA contraction of these statements, in this
+// order, decides the bits of every entry point ----
+
+// lambda: 1/rho (OU), sqrt3/rho (Matern-3/2), sqrt5/rho (Matern-5/2)
+template <int P>
+__device__ __forceinline__ double gpcc_mk_rate(double rho)
+{
+    return (P == 1 ? 1.0 : (P == 2 ? 1.7320508075688772 : 2.23606797749979)) / rho;
+}
+
+// the rate and the prior state: lam, lam2 = lam^2, Q = Pinf, mu = 0, C = blockdiag(Pinf, diag sigma_b) (C: upper triangle used)
+template <int P, int NOFF>
+__device__ __forceinline__ void gpcc_mk_init(double rho, const double (&sigma_b)[GPCC_MARKOV_MAX_OFFSETS], double &lam, double &lam2,
+                                             double (&Q)[P][P], double (&mu)[P + NOFF], double (&C)[P + NOFF][P + NOFF])
+{
+    constexpr int NS = P + NOFF;
+    lam = gpcc_mk_rate<P>(rho);
+    lam2 = lam * lam;
+#pragma unroll
+    for (int i = 0; i < P; ++i)
+#pragma unroll
+        for (int j = 0; j < P; ++j) Q[i][j] = 0.0;
+    Q[0][0] = 1.0;
+    if constexpr (P == 2) Q[1][1] = lam2;
+    if constexpr (P == 3) {
+        Q[0][2] = Q[2][0] = -lam2 / 3.0;
+        Q[1][1] = lam2 / 3.0;
+        Q[2][2] = lam2 * lam2;
+    }
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        mu[i] = 0.0;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) C[i][j] = (i < P && j < P) ? Q[i][j] : 0.0;
+    }
+#pragma unroll
+    for (int c = 0; c < NOFF; ++c) C[P + c][P + c] = sigma_b[c];
+}
+
+// a lane's row m: alpha and tau to LDS, [band][thread], and the reference's argument checks (delayedCovariance.jl:3, :5-7) as
+// gpcc_loglik_batch reports them: -1 (some alpha <= 0), -2 (rho <= 0), else 0.  ARGS: GpccMarkovArgs or GpccMarkovPredArgs
+template <class ARGS>
+__device__ __forceinline__ int gpcc_mk_load_row(const ARGS &a, long m, double rho, double *stau, double *salpha, int nthr, int tid)
+{
+    int info = 0;
+    for (int l = 0; l < a.L; ++l) {
+        const double al = a.alpha[m * a.L + l];
+        if (!(al > 0.0)) info = -1;
+        salpha[l * nthr + tid] = al;
+        stau[l * nthr + tid] = a.delays[m * a.L + l];
+    }
+    if (info == 0 && rho <= 0.0) info = -2;
+    return info;
+}
+
+// A = expm(F d)
+template <int P>
+__device__ __forceinline__ void gpcc_mk_transition(double lam, double lam2, double d, double (&A)[P][P])
+{
+    const double e = exp(-lam * d), x = lam * d;
+    if constexpr (P == 1) {
+        A[0][0] = e;
+    } else if constexpr (P == 2) {
+        A[0][0] = e * (1.0 + x);
+        A[0][1] = e * d;
+        A[1][0] = -e * lam2 * d;
+        A[1][1] = e * (1.0 - x);
+    } else {
+        A[0][0] = e * (1.0 + x + 0.5 * x * x);
+        A[0][1] = e * d * (1.0 + x);
+        A[0][2] = e * 0.5 * d * d;
+        A[1][0] = -e * 0.5 * lam2 * lam * d * d;
+        A[1][1] = e * (1.0 + x - x * x);
+        A[1][2] = e * d * (1.0 - 0.5 * x);
+        A[2][0] = e * lam2 * x * (0.5 * x - 1.0);
+        A[2][1] = e * lam * x * (x - 3.0);
+        A[2][2] = e * (1.0 - 2.0 * x + 0.5 * x * x);
+    }
+}
+
+// predict: m <- A m, C_xx <- A (C_xx - Pinf) A' + Pinf, C_xb <- A C_xb
+template <int P, int NOFF>
+__device__ __forceinline__ void gpcc_mk_propagate(const double (&A)[P][P], const double (&Q)[P][P], double (&mu)[P + NOFF],
+                                                  double (&C)[P + NOFF][P + NOFF])
+{
+    double t1[P], D[P][P], T[P][P];
+#pragma unroll
+    for (int i2 = 0; i2 < P; ++i2) {
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < P; ++k) acc += A[i2][k] * mu[k];
+        t1[i2] = acc;
+    }
+#pragma unroll
+    for (int i2 = 0; i2 < P; ++i2) mu[i2] = t1[i2];
+#pragma unroll
+    for (int i2 = 0; i2 < P; ++i2)
+#pragma unroll
+        for (int k = 0; k < P; ++k) D[i2][k] = GPCC_MK_SYM(C, i2, k) - Q[i2][k];
+#pragma unroll
+    for (int i2 = 0; i2 < P; ++i2)
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            double acc = 0.0;
+#pragma unroll
+            for (int q = 0; q < P; ++q) acc += A[i2][q] * D[q][k];
+            T[i2][k] = acc;
+        }
+#pragma unroll
+    for (int i2 = 0; i2 < P; ++i2)
+#pragma unroll
+        for (int k = i2; k < P; ++k) {
+            double acc = Q[i2][k];
+#pragma unroll
+            for (int q = 0; q < P; ++q) acc += T[i2][q] * A[k][q];
+            C[i2][k] = acc;
+        }
+#pragma unroll
+    for (int c = 0; c < NOFF; ++c) {
+#pragma unroll
+        for (int i2 = 0; i2 < P; ++i2) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < P; ++k) acc += A[i2][k] * C[k][P + c];
+            t1[i2] = acc;
+        }
+#pragma unroll
+        for (int i2 = 0; i2 < P; ++i2) C[i2][P + c] = t1[i2];
+    }
+}
+
+// update with h = alpha_b e_1 + e_{P + b}; false: the predictive variance is not positive and finite
+template <int P, int NOFF>
+__device__ __forceinline__ bool gpcc_mk_update(int b, double al, double r, double s2, double (&mu)[P + NOFF],
+                                               double (&C)[P + NOFF][P + NOFF], double &ll)
+{
+    constexpr int NS = P + NOFF;
+    double Ph[NS];
+#pragma unroll
+    for (int i2 = 0; i2 < NS; ++i2) {
+        double acc = al * GPCC_MK_SYM(C, i2, 0);
+#pragma unroll
+        for (int c = 0; c < NOFF; ++c) acc += (b == c) ? GPCC_MK_SYM(C, i2, P + c) : 0.0;
+        Ph[i2] = acc;
+    }
+    double S = al * Ph[0] + s2, hm = al * mu[0];
+#pragma unroll
+    for (int c = 0; c < NOFF; ++c) {
+        S += (b == c) ? Ph[P + c] : 0.0;
+        hm += (b == c) ? mu[P + c] : 0.0;
+    }
+    const bool ok = S > 0.0 && S < __builtin_inf();
+    const double inv = 1.0 / S, eps = r - hm;
+    ll -= 0.5 * (1.8378770664093453 + log(S) + eps * eps * inv);
+    const double g = eps * inv;
+#pragma unroll
+    for (int i2 = 0; i2 < NS; ++i2) {
+        mu[i2] += Ph[i2] * g;
+        const double ki = Ph[i2] * inv;
+#pragma unroll
+        for (int k = i2; k < NS; ++k) C[i2][k] -= ki * Ph[k];
+    }
+    return ok;
+}
+
 template <int P, int NOFF>
 __global__ void __launch_bounds__(256) gpcc_markov_eval(const GpccMarkovArgs a)
 {
@@ -64,43 +232,15 @@ __global__ void __launch_bounds__(256) gpcc_markov_eval(const GpccMarkovArgs a)
     const bool valid = row < a.M;
     const long m_ = valid ? row : a.M - 1;
     const double rho = a.rho[m_];
-    int info = 0;   // the reference's argument checks (delayedCovariance.jl:3, :5-7), as gpcc_loglik_batch reports them
-    for (int l = 0; l < L; ++l) {
-        const double al = a.alpha[m_ * L + l];
-        if (!(al > 0.0)) info = -1;
-        salpha[l * nthr + tid] = al;
-        stau[l * nthr + tid] = a.delays[m_ * L + l];
-    }
-    if (info == 0 && rho <= 0.0) info = -2;
+    int info = gpcc_mk_load_row(a, m_, rho, stau, salpha, nthr, tid);
     __syncthreads();
     for (int l = 0; l < L; ++l) {
         scur[l * nthr + tid] = a.off[l];
         shead[l * nthr + tid] = pts[a.off[l]] - stau[l * nthr + tid];
     }
 
-    const double lam = (P == 1 ? 1.0 : (P == 2 ? 1.7320508075688772 : 2.23606797749979)) / rho;
-    const double lam2 = lam * lam;
-    double Q[P][P];   // Pinf
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-#pragma unroll
-        for (int j = 0; j < P; ++j) Q[i][j] = 0.0;
-    Q[0][0] = 1.0;
-    if constexpr (P == 2) Q[1][1] = lam2;
-    if constexpr (P == 3) {
-        Q[0][2] = Q[2][0] = -lam2 / 3.0;
-        Q[1][1] = lam2 / 3.0;
-        Q[2][2] = lam2 * lam2;
-    }
-    double mu[NS], C[NS][NS];   // C: upper triangle used
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        mu[i] = 0.0;
-#pragma unroll
-        for (int j = 0; j < NS; ++j) C[i][j] = (i < P && j < P) ? Q[i][j] : 0.0;
-    }
-#pragma unroll
-    for (int c = 0; c < NOFF; ++c) C[P + c][P + c] = a.sigma_b[c];
+    double lam, lam2, Q[P][P], mu[NS], C[NS][NS];
+    gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
 
     double ll = 0.0, sprev = 0.0;
     for (int j = 0; j < N; ++j) {
@@ -121,107 +261,21 @@ __global__ void __launch_bounds__(256) gpcc_markov_eval(const GpccMarkovArgs a)
         const double d = (j == 0) ? 0.0 : s - sprev;
         sprev = s;
 
-        // A = expm(F d)
-        const double e = exp(-lam * d), x = lam * d;
         double A[P][P];
-        if constexpr (P == 1) {
-            A[0][0] = e;
-        } else if constexpr (P == 2) {
-            A[0][0] = e * (1.0 + x);
-            A[0][1] = e * d;
-            A[1][0] = -e * lam2 * d;
-            A[1][1] = e * (1.0 - x);
-        } else {
-            A[0][0] = e * (1.0 + x + 0.5 * x * x);
-            A[0][1] = e * d * (1.0 + x);
-            A[0][2] = e * 0.5 * d * d;
-            A[1][0] = -e * 0.5 * lam2 * lam * d * d;
-            A[1][1] = e * (1.0 + x - x * x);
-            A[1][2] = e * d * (1.0 - 0.5 * x);
-            A[2][0] = e * lam2 * x * (0.5 * x - 1.0);
-            A[2][1] = e * lam * x * (x - 3.0);
-            A[2][2] = e * (1.0 - 2.0 * x + 0.5 * x * x);
-        }
-        // predict: m <- A m, C_xx <- A (C_xx - Pinf) A' + Pinf, C_xb <- A C_xb
-        {
-            double t1[P], D[P][P], T[P][P];
-#pragma unroll
-            for (int i2 = 0; i2 < P; ++i2) {
-                double acc = 0.0;
-#pragma unroll
-                for (int k = 0; k < P; ++k) acc += A[i2][k] * mu[k];
-                t1[i2] = acc;
-            }
-#pragma unroll
-            for (int i2 = 0; i2 < P; ++i2) mu[i2] = t1[i2];
-#pragma unroll
-            for (int i2 = 0; i2 < P; ++i2)
-#pragma unroll
-                for (int k = 0; k < P; ++k) D[i2][k] = GPCC_MK_SYM(C, i2, k) - Q[i2][k];
-#pragma unroll
-            for (int i2 = 0; i2 < P; ++i2)
-#pragma unroll
-                for (int k = 0; k < P; ++k) {
-                    double acc = 0.0;
-#pragma unroll
-                    for (int q = 0; q < P; ++q) acc += A[i2][q] * D[q][k];
-                    T[i2][k] = acc;
-                }
-#pragma unroll
-            for (int i2 = 0; i2 < P; ++i2)
-#pragma unroll
-                for (int k = i2; k < P; ++k) {
-                    double acc = Q[i2][k];
-#pragma unroll
-                    for (int q = 0; q < P; ++q) acc += T[i2][q] * A[k][q];
-                    C[i2][k] = acc;
-                }
-#pragma unroll
-            for (int c = 0; c < NOFF; ++c) {
-#pragma unroll
-                for (int i2 = 0; i2 < P; ++i2) {
-                    double acc = 0.0;
-#pragma unroll
-                    for (int k = 0; k < P; ++k) acc += A[i2][k] * C[k][P + c];
-                    t1[i2] = acc;
-                }
-#pragma unroll
-                for (int i2 = 0; i2 < P; ++i2) C[i2][P + c] = t1[i2];
-            }
-        }
-        // update with h = alpha_b e_1 + e_{P + b}
-        double Ph[NS];
-#pragma unroll
-        for (int i2 = 0; i2 < NS; ++i2) {
-            double acc = al * GPCC_MK_SYM(C, i2, 0);
-#pragma unroll
-            for (int c = 0; c < NOFF; ++c) acc += (b == c) ? GPCC_MK_SYM(C, i2, P + c) : 0.0;
-            Ph[i2] = acc;
-        }
-        double S = al * Ph[0] + s2, hm = al * mu[0];
-#pragma unroll
-        for (int c = 0; c < NOFF; ++c) {
-            S += (b == c) ? Ph[P + c] : 0.0;
-            hm += (b == c) ? mu[P + c] : 0.0;
-        }
-        const bool ok = S > 0.0 && S < __builtin_inf();
+        gpcc_mk_transition<P>(lam, lam2, d, A);
+        gpcc_mk_propagate<P, NOFF>(A, Q, mu, C);
+        const bool ok = gpcc_mk_update<P, NOFF>(b, al, r, s2, mu, C, ll);
         info = (info == 0 && !ok) ? j + 1 : info;   // first predictive variance that is not positive and finite
-        const double inv = 1.0 / S, eps = r - hm;
-        ll -= 0.5 * (1.8378770664093453 + log(S) + eps * eps * inv);
-        const double g = eps * inv;
-#pragma unroll
-        for (int i2 = 0; i2 < NS; ++i2) {
-            mu[i2] += Ph[i2] * g;
-            const double ki = Ph[i2] * inv;
-#pragma unroll
-            for (int k = i2; k < NS; ++k) C[i2][k] -= ki * Ph[k];
-        }
     }
     if (valid) {
         a.out_loglik[row] = info ? __builtin_nan("") : ll;
         a.out_info[row] = info;
     }
 }
+
+// the instantiations (P, NOFF) of every kernel of the filter, here and in gpcc_markov_pred.hip.h
+#define GPCC_MK_EACH(F) \
+    F(1, 0) F(1, 1) F(1, 2) F(1, 3) F(1, 4) F(2, 0) F(2, 1) F(2, 2) F(2, 3) F(2, 4) F(3, 0) F(3, 1) F(3, 2) F(3, 3) F(3, 4)
 
 // the launch of instantiation (p, noff) (gpcc_markov_inst.hip: its own object) and the LDS limit of all of them on the current device
 hipError_t gpcc_markov_launch(int p, int noff, const GpccMarkovArgs &a, int blocks, int threads, size_t lds, hipStream_t s);

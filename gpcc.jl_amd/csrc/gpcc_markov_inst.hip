@@ -2,9 +2,6 @@
 // states) and their launch, as an object of their own (gpcc.jl_amd/build.py compiles the objects side by side).
 #include "gpcc_markov.hip.h"
 
-#define GPCC_MK_EACH(F) \
-    F(1, 0) F(1, 1) F(1, 2) F(1, 3) F(1, 4) F(2, 0) F(2, 1) F(2, 2) F(2, 3) F(2, 4) F(3, 0) F(3, 1) F(3, 2) F(3, 3) F(3, 4)
-
 hipError_t gpcc_markov_launch(int p, int noff, const GpccMarkovArgs &a, int blocks, int threads, size_t lds, hipStream_t s)
 {
 #define GPCC_MK_CASE(PP, NN)                                                              \

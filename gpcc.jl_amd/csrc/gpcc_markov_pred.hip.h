@@ -1,10 +1,11 @@
 // gpcc_markov_pred.hip.h -- linear-time predictions, held-out log-likelihoods and the offsets' posterior of the Markov kernels (OU,
 // Matern-3/2, Matern-5/2) for gfx950: gpcc_predict_markov_batch, gpcc_heldout_loglik_markov_batch and
 // gpcc_posterior_offsets_markov_batch of include/gpcc_hip.h; gpcc.jl_amd/markov.py (predict, heldout,
-// posterior_offsets) is the same algorithm in numpy.  The state-space model is gpcc_markov.hip.h's; nothing is approximated.
+// posterior_offsets) is the same algorithm in numpy.  The state-space model and the filter's step (gpcc_mk_*) are gpcc_markov.hip.h's;
+// nothing is approximated.
 //
 // gpcc_markov_taps<P, NOFF, MODE>: ONE LANE PER (ROW, blockIdx.y).  The filter of gpcc_markov_eval with the same register-resident
-// state and the same arithmetic, walking a 2L-way merge: L training streams that update the state and L test streams.
+// state and the same functions, walking a 2L-way merge: L training streams that update the state and L test streams.
 //   MODE = GPCC_MKP_TAP     blockIdx.y = 0: the forward filter (ascending shifted time); 1: the backward filter (descending shifted
 //                           time, lags |d|; the process reversed in time is the same process with f' negated, which the combine
 //                           applies).  A test point is tapped: a COPY of the state is propagated to it and stored to the scratch
@@ -29,6 +30,8 @@
 #define GPCC_MKP_LANE_BYTES 40             /* per lane and band: two heads, tau, alpha (doubles) and two cursors (ints) */
 #define GPCC_MKP_JITTER 1e-8
 
+// GpccMarkovArgs' fields under the same names (the host fills both through one template) and what the test points add.  Not derived from
+// it: the kernel-argument layout that gives moves the register allocation of gpcc_markov_taps<.., GPCC_MKP_UPDATE>
 struct GpccMarkovPredArgs {
     const double *pts;                     // t[N] | r[N] | sigma^2[N], as GpccMarkovArgs
     const double *tpts;                    // test points, each band sorted by time: t[T] (TAP), t[T] | r[T] | sigma^2 + JITTER [T] (UPDATE)
@@ -58,117 +61,6 @@ static inline size_t gpcc_mkp_lds_bytes(int N, int T, int tw, int L, int threads
     return (stage ? (size_t)24 * N + (size_t)8 * tw * T : 0) + (size_t)GPCC_MKP_LANE_BYTES * L * threads;
 }
 
-// ---- the filter's step: the arithmetic of gpcc_markov_eval, statement by statement.  A copy, so that gpcc_markov_eval itself stays the
-// code that produced its bits so far; the tests hold lane 0 of every mode bitwise to it, so the two cannot drift apart unnoticed ----
-template <int P>
-__device__ __forceinline__ void gpcc_mk_transition(double lam, double lam2, double d, double (&A)[P][P])
-{
-    const double e = exp(-lam * d), x = lam * d;
-    if constexpr (P == 1) {
-        A[0][0] = e;
-    } else if constexpr (P == 2) {
-        A[0][0] = e * (1.0 + x);
-        A[0][1] = e * d;
-        A[1][0] = -e * lam2 * d;
-        A[1][1] = e * (1.0 - x);
-    } else {
-        A[0][0] = e * (1.0 + x + 0.5 * x * x);
-        A[0][1] = e * d * (1.0 + x);
-        A[0][2] = e * 0.5 * d * d;
-        A[1][0] = -e * 0.5 * lam2 * lam * d * d;
-        A[1][1] = e * (1.0 + x - x * x);
-        A[1][2] = e * d * (1.0 - 0.5 * x);
-        A[2][0] = e * lam2 * x * (0.5 * x - 1.0);
-        A[2][1] = e * lam * x * (x - 3.0);
-        A[2][2] = e * (1.0 - 2.0 * x + 0.5 * x * x);
-    }
-}
-
-// predict: m <- A m, C_xx <- A (C_xx - Pinf) A' + Pinf, C_xb <- A C_xb
-template <int P, int NOFF>
-__device__ __forceinline__ void gpcc_mk_propagate(const double (&A)[P][P], const double (&Q)[P][P], double (&mu)[P + NOFF],
-                                                  double (&C)[P + NOFF][P + NOFF])
-{
-    double t1[P], D[P][P], T[P][P];
-#pragma unroll
-    for (int i2 = 0; i2 < P; ++i2) {
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < P; ++k) acc += A[i2][k] * mu[k];
-        t1[i2] = acc;
-    }
-#pragma unroll
-    for (int i2 = 0; i2 < P; ++i2) mu[i2] = t1[i2];
-#pragma unroll
-    for (int i2 = 0; i2 < P; ++i2)
-#pragma unroll
-        for (int k = 0; k < P; ++k) D[i2][k] = GPCC_MK_SYM(C, i2, k) - Q[i2][k];
-#pragma unroll
-    for (int i2 = 0; i2 < P; ++i2)
-#pragma unroll
-        for (int k = 0; k < P; ++k) {
-            double acc = 0.0;
-#pragma unroll
-            for (int q = 0; q < P; ++q) acc += A[i2][q] * D[q][k];
-            T[i2][k] = acc;
-        }
-#pragma unroll
-    for (int i2 = 0; i2 < P; ++i2)
-#pragma unroll
-        for (int k = i2; k < P; ++k) {
-            double acc = Q[i2][k];
-#pragma unroll
-            for (int q = 0; q < P; ++q) acc += T[i2][q] * A[k][q];
-            C[i2][k] = acc;
-        }
-#pragma unroll
-    for (int c = 0; c < NOFF; ++c) {
-#pragma unroll
-        for (int i2 = 0; i2 < P; ++i2) {
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < P; ++k) acc += A[i2][k] * C[k][P + c];
-            t1[i2] = acc;
-        }
-#pragma unroll
-        for (int i2 = 0; i2 < P; ++i2) C[i2][P + c] = t1[i2];
-    }
-}
-
-// update with h = alpha_b e_1 + e_{P + b}; false: the predictive variance is not positive and finite
-template <int P, int NOFF>
-__device__ __forceinline__ bool gpcc_mk_update(int b, double al, double r, double s2, double (&mu)[P + NOFF],
-                                               double (&C)[P + NOFF][P + NOFF], double &ll)
-{
-    constexpr int NS = P + NOFF;
-    double Ph[NS];
-#pragma unroll
-    for (int i2 = 0; i2 < NS; ++i2) {
-        double acc = al * GPCC_MK_SYM(C, i2, 0);
-#pragma unroll
-        for (int c = 0; c < NOFF; ++c) acc += (b == c) ? GPCC_MK_SYM(C, i2, P + c) : 0.0;
-        Ph[i2] = acc;
-    }
-    double S = al * Ph[0] + s2, hm = al * mu[0];
-#pragma unroll
-    for (int c = 0; c < NOFF; ++c) {
-        S += (b == c) ? Ph[P + c] : 0.0;
-        hm += (b == c) ? mu[P + c] : 0.0;
-    }
-    const bool ok = S > 0.0 && S < __builtin_inf();
-    const double inv = 1.0 / S, eps = r - hm;
-    ll -= 0.5 * (1.8378770664093453 + log(S) + eps * eps * inv);
-    const double g = eps * inv;
-#pragma unroll
-    for (int i2 = 0; i2 < NS; ++i2) {
-        mu[i2] += Ph[i2] * g;
-        const double ki = Ph[i2] * inv;
-#pragma unroll
-        for (int k = i2; k < NS; ++k) C[i2][k] -= ki * Ph[k];
-    }
-    return ok;
-}
-
 template <int P, int NOFF, int MODE>
 __global__ void __launch_bounds__(256) gpcc_markov_taps(const GpccMarkovPredArgs a)
 {
@@ -193,14 +85,7 @@ __global__ void __launch_bounds__(256) gpcc_markov_taps(const GpccMarkovPredArgs
     const bool valid = lrow < a.rows;
     const long m_ = a.row0 + (valid ? lrow : a.rows - 1);
     const double rho = a.rho[m_];
-    int info = 0;
-    for (int l = 0; l < L; ++l) {
-        const double al = a.alpha[m_ * L + l];
-        if (!(al > 0.0)) info = -1;
-        salpha[l * nthr + tid] = al;
-        stau[l * nthr + tid] = a.delays[m_ * L + l];
-    }
-    if (info == 0 && rho <= 0.0) info = -2;
+    int info = gpcc_mk_load_row(a, m_, rho, stau, salpha, nthr, tid);
     __syncthreads();
     const int step = rev ? -1 : 1;
     for (int l = 0; l < L; ++l) {
@@ -216,29 +101,8 @@ __global__ void __launch_bounds__(256) gpcc_markov_taps(const GpccMarkovPredArgs
         }
     }
 
-    const double lam = (P == 1 ? 1.0 : (P == 2 ? 1.7320508075688772 : 2.23606797749979)) / rho;
-    const double lam2 = lam * lam;
-    double Q[P][P];   // Pinf
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-#pragma unroll
-        for (int j = 0; j < P; ++j) Q[i][j] = 0.0;
-    Q[0][0] = 1.0;
-    if constexpr (P == 2) Q[1][1] = lam2;
-    if constexpr (P == 3) {
-        Q[0][2] = Q[2][0] = -lam2 / 3.0;
-        Q[1][1] = lam2 / 3.0;
-        Q[2][2] = lam2 * lam2;
-    }
-    double mu[NS], C[NS][NS];   // C: upper triangle used
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        mu[i] = 0.0;
-#pragma unroll
-        for (int j = 0; j < NS; ++j) C[i][j] = (i < P && j < P) ? Q[i][j] : 0.0;
-    }
-#pragma unroll
-    for (int c = 0; c < NOFF; ++c) C[P + c][P + c] = a.sigma_b[c];
+    double lam, lam2, Q[P][P], mu[NS], C[NS][NS];
+    gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
 
     double ll = 0.0, sprev = 0.0;
     int jt = 0, at = 0;         // jt: updates so far
@@ -315,7 +179,7 @@ __global__ void __launch_bounds__(256) gpcc_markov_taps(const GpccMarkovPredArgs
             r = pts[N + i];
             s2 = pts[2 * N + i];
         }
-        // one filter step, gpcc_markov_eval's
+        // one filter step, as in gpcc_markov_eval
         const double al = salpha[band * nthr + tid];
         const double d = (jt == 0) ? 0.0 : key - sprev;
         sprev = key;
@@ -401,7 +265,7 @@ __global__ void __launch_bounds__(64) gpcc_markov_combine(const GpccMarkovCombin
     const long row = a.row0 + lrow;
     const int qb = a.tband[tj];
     const double rho = a.rho[row], al = a.alpha[row * a.L + qb];
-    const double lam = (P == 1 ? 1.0 : (P == 2 ? 1.7320508075688772 : 2.23606797749979)) / rho;
+    const double lam = gpcc_mk_rate<P>(rho);
     // sc = diag(P0)^-1/2; sgn = D, the time reversal of the backward state
     double sc[NS], sgn[NS];
 #pragma unroll

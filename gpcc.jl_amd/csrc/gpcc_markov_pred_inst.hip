@@ -3,9 +3,6 @@
 // own (gpcc.jl_amd/build.py compiles the objects side by side).
 #include "gpcc_markov_pred.hip.h"
 
-#define GPCC_MKP_EACH(F) \
-    F(1, 0) F(1, 1) F(1, 2) F(1, 3) F(1, 4) F(2, 0) F(2, 1) F(2, 2) F(2, 3) F(2, 4) F(3, 0) F(3, 1) F(3, 2) F(3, 3) F(3, 4)
-
 hipError_t gpcc_mkp_launch_taps(int mode, int p, int noff, const GpccMarkovPredArgs &a, int blocks, int ny, int threads, size_t lds,
                                 hipStream_t s)
 {
@@ -17,7 +14,7 @@ hipError_t gpcc_mkp_launch_taps(int mode, int p, int noff, const GpccMarkovPredA
             gpcc_markov_taps<PP, NN, GPCC_MKP_UPDATE><<<dim3(blocks, ny), dim3(threads), lds, s>>>(a);               \
         return hipGetLastError();                                                                                    \
     }
-    GPCC_MKP_EACH(GPCC_MKP_CASE)
+    GPCC_MK_EACH(GPCC_MKP_CASE)
 #undef GPCC_MKP_CASE
     return hipErrorInvalidValue;
 }
@@ -29,7 +26,7 @@ hipError_t gpcc_mkp_launch_combine(int p, int noff, const GpccMarkovCombineArgs 
         gpcc_markov_combine<PP, NN><<<dim3((a.rows + 63) / 64, a.T), dim3(64), 0, s>>>(a);                           \
         return hipGetLastError();                                                                                    \
     }
-    GPCC_MKP_EACH(GPCC_MKP_CASE)
+    GPCC_MK_EACH(GPCC_MKP_CASE)
 #undef GPCC_MKP_CASE
     return hipErrorInvalidValue;
 }
@@ -46,7 +43,7 @@ hipError_t gpcc_mkp_configure()
                                     hipFuncAttributeMaxDynamicSharedMemorySize, GPCC_MARKOV_LDS_MAX);                                \
         if (e != hipSuccess) return e;                                                                                               \
     }
-    GPCC_MKP_EACH(GPCC_MKP_ATTR)
+    GPCC_MK_EACH(GPCC_MKP_ATTR)
 #undef GPCC_MKP_ATTR
     return hipSuccess;
 }

@@ -110,63 +110,14 @@ def loglik(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=T
     _slip (tests only) injects one mistake an implementation can make: "order" (two neighbours of the merged order swapped where
     their shifted times differ: one negative lag), "no_q" (P <- A P A' without the process noise), "var_n" (offset prior 100 var with n
     instead of n - 1), "no_offset" (h without the offset entry)."""
-    name = _name(kernel)
-    L = len(tarray)
-    delays = np.asarray(delays, np.float64).reshape(L)
-    alpha = np.asarray(alpha, np.float64).reshape(L)
-    rho = float(rho)
-    if not np.all(alpha > 0.0):
-        return math.nan, -1
-    if rho <= 0.0:
-        return math.nan, -2
-    if marginalise_b and L > MAX_OFFSET_BANDS:
-        raise ValueError("marginalise_b with %d bands: the linear-time solver keeps at most %d offset states" % (L, MAX_OFFSET_BANDS))
-    ts, rs, s2, vb = prepare(tarray, yarray, stdarray, marginalise_b)
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b,
+                                                                       codes_first=True)
+    if code:
+        return math.nan, code
     if _slip == "var_n":
-        vb = vb * np.array([(len(t) - 1.0) / len(t) for t in ts])
-    p = _ORDER[name]
-    n = p + (L if marginalise_b else 0)
-    Pinf = stationary(name, rho)
-    P = np.zeros((n, n))
-    P[:p, :p] = Pinf
-    for l in range(n - p):
-        P[p + l, p + l] = vb[l]
-    m = np.zeros(n)
-    seq = merge_order(ts, delays)
-    if _slip == "order":
-        for j in range(len(seq) // 2, len(seq) - 1):
-            (b0, i0), (b1, i1) = seq[j], seq[j + 1]
-            if ts[b0][i0] - delays[b0] != ts[b1][i1] - delays[b1]:
-                seq[j], seq[j + 1] = seq[j + 1], seq[j]
-                break
-    ll = 0.0
-    sprev = None
-    for j, (b, i) in enumerate(seq):
-        s = ts[b][i] - delays[b]
-        d = 0.0 if sprev is None else s - sprev
-        sprev = s
-        A = transition(name, d, rho)
-        m[:p] = A @ m[:p]
-        if _slip == "no_q":
-            P[:p, :p] = A @ P[:p, :p] @ A.T
-        else:
-            P[:p, :p] = A @ (P[:p, :p] - Pinf) @ A.T + Pinf
-        P[:p, p:] = A @ P[:p, p:]
-        P[p:, :p] = P[:p, p:].T
-        h = np.zeros(n)
-        h[0] = alpha[b]
-        if n > p and _slip != "no_offset":
-            h[p + b] = 1.0
-        Ph = P @ h
-        S = h @ Ph + s2[b][i]
-        if not (S > 0.0 and math.isfinite(S)):
-            return math.nan, j + 1
-        eps = rs[b][i] - h @ m
-        ll -= 0.5 * (LOG2PI + math.log(S) + eps * eps / S)
-        m += Ph * (eps / S)
-        P -= np.outer(Ph, Ph) / S
-        P = 0.5 * (P + P.T)
-    return ll, 0
+        vb = vb * np.array([(len(t) - 1.0) / len(t) for t in tarray])
+    ll, info, _, _, _, _ = _pass(name, train, [], alpha, rho, p, n, vb, slip=_slip)
+    return ll, info
 
 
 def loglik_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True):
@@ -197,6 +148,8 @@ JITTER = 1e-8   # added to every predictive variance and to sigma*^2 of a held-o
 #   heldout   log p(y* | Y) = loglik(training U test) - loglik(training): the test points enter as observations with variance
 #             sigma*^2 + JITTER and residual y* - mean(y_band of the TRAINING data); the offsets' priors from the training data.
 #   postb     the offset block of the forward filter's final state: mu = m[p:] + mean(y_band), Sigma = P[p:, p:].
+#
+# _setup, _prior, _propagate and _pass are the module's one filter: loglik() above is _setup + _pass over the training points alone.
 # ----------------------------------------------------------------------------------------------------------------------------------
 def _prior(name, rho, p, n, vb):
     P0 = np.zeros((n, n))
@@ -206,28 +159,35 @@ def _prior(name, rho, p, n, vb):
     return P0
 
 
-def _propagate(name, m, P, Pinf, d, rho, p):
+def _propagate(name, m, P, Pinf, d, rho, p, no_q=False):
+    """The state (m, P) a lag d later, on copies: m <- A m, P_xx <- A (P_xx - Pinf) A' + Pinf, P_xb <- A P_xb."""
     A = transition(name, d, rho)
     m = m.copy()
     P = P.copy()
     m[:p] = A @ m[:p]
-    P[:p, :p] = A @ (P[:p, :p] - Pinf) @ A.T + Pinf
+    P[:p, :p] = A @ P[:p, :p] @ A.T if no_q else A @ (P[:p, :p] - Pinf) @ A.T + Pinf
     P[:p, p:] = A @ P[:p, p:]
     P[p:, :p] = P[:p, p:].T
     return m, P
 
 
-def _pass(name, train, tests, alpha, rho, p, n, vb, reverse=False, tests_update=False, ties_first=False):
+def _pass(name, train, tests, alpha, rho, p, n, vb, reverse=False, tests_update=False, ties_first=False, slip=None):
     """One filter over the training observations `train` [(s, band, position, r, sigma^2)] and the test points `tests` [(s, band, index,
     r, sigma^2)].  reverse: descending s.  tests_update: the test points are observations too (held-out union) -- otherwise each is
     tapped: the state after the training points before it, propagated to it, kept in taps[index] (unflipped).  Ties in s: training
-    points before test points going forward (or with ties_first), test points first going backward.
+    points before test points going forward (or with ties_first), test points first going backward.  Among themselves the training
+    points come by shifted time, then band, then position in the band: merge_order()'s order, which the device walks.  slip: loglik()'s.
     -> (loglik, info, final mean, final covariance, taps, index of the test point at which info was set or -1)."""
     sg = -1.0 if reverse else 1.0
     tr_kind = 0 if (not reverse or ties_first or tests_update) else 1
     ev = [(sg * s, tr_kind, b, sg * i, True, r, s2, i) for (s, b, i, r, s2) in train]
     ev += [(sg * s, 1 - tr_kind if not tests_update else 1, b, sg * i, False, r, s2, i) for (s, b, i, r, s2) in tests]
     ev.sort(key=lambda e: e[:4])
+    if slip == "order":
+        for j in range(len(ev) // 2, len(ev) - 1):
+            if ev[j][0] != ev[j + 1][0]:
+                ev[j], ev[j + 1] = ev[j + 1], ev[j]
+                break
     Pinf = stationary(name, rho)
     P = _prior(name, rho, p, n, vb)
     m = np.zeros(n)
@@ -239,10 +199,10 @@ def _pass(name, train, tests, alpha, rho, p, n, vb, reverse=False, tests_update=
             continue
         sprev = key
         step += 1
-        m, P = _propagate(name, m, P, Pinf, d, rho, p)
+        m, P = _propagate(name, m, P, Pinf, d, rho, p, no_q=(slip == "no_q"))
         h = np.zeros(n)
         h[0] = alpha[b]
-        if n > p:
+        if n > p and slip != "no_offset":
             h[p + b] = 1.0
         Ph = P @ h
         S = h @ Ph + s2
@@ -258,15 +218,17 @@ def _pass(name, train, tests, alpha, rho, p, n, vb, reverse=False, tests_update=
     return ll, info, m, P, taps, at
 
 
-def _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b):
+def _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b, codes_first=False):
+    """The arguments as arrays, the argument code (-1: some alpha <= 0, -2: rho <= 0, else 0), what prepare() gives and the training
+    observations for _pass.  More offset states than the device keeps raise, except (codes_first: loglik's precedence) beside a code."""
     name = _name(kernel)
     L = len(tarray)
     delays = np.asarray(delays, np.float64).reshape(L)
     alpha = np.asarray(alpha, np.float64).reshape(L)
     rho = float(rho)
-    if marginalise_b and L > MAX_OFFSET_BANDS:
-        raise ValueError("marginalise_b with %d bands: the linear-time solver keeps at most %d offset states" % (L, MAX_OFFSET_BANDS))
     code = -1 if not np.all(alpha > 0.0) else (-2 if rho <= 0.0 else 0)
+    if marginalise_b and L > MAX_OFFSET_BANDS and not (codes_first and code):
+        raise ValueError("marginalise_b with %d bands: the linear-time solver keeps at most %d offset states" % (L, MAX_OFFSET_BANDS))
     ts, rs, s2, vb = prepare(tarray, yarray, stdarray, marginalise_b)
     means = np.array([np.asarray(y, np.float64).sum() / len(y) for y in yarray])
     p = _ORDER[name]
