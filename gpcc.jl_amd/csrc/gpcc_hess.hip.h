@@ -235,16 +235,22 @@ __global__ __launch_bounds__(GPCC_TILE) void gpcc_hess_u(GpccCtx c, GpccGroup g,
         for (int qq = 0; qq < GPCC_MAXL; ++qq)
             if (qq == qb) { Uk[qq] = sk; Ur[qq] = sr; Us[qq] = ss; }
     }
-    double ak = 0.0, ar = 0.0, as = 0.0;   // sum_q alpha_q U[q]
+    // sum_q alpha_q U[q]; for k_s over the other bands only: in tau_p's row the own band's term, alpha_p Us[p], cancels exactly, so it
+    // is never added (added and subtracted it leaves its rounding behind: a tau row that is not 0 where D_tau is identically 0)
+    double ak = 0.0, ar = 0.0, as = 0.0;
 #pragma unroll
     for (int qq = 0; qq < GPCC_MAXL; ++qq)
-        if (qq < L) { ak = fma(al[qq], Uk[qq], ak); ar = fma(al[qq], Ur[qq], ar); as = fma(al[qq], Us[qq], as); }
+        if (qq < L) {
+            ak = fma(al[qq], Uk[qq], ak);
+            ar = fma(al[qq], Ur[qq], ar);
+            if (qq != p) as = fma(al[qq], Us[qq], as);
+        }
     const double ap = al[p];
 #pragma unroll
     for (int l = 0; l < GPCC_MAXL; ++l)
         if (l < L) {
             U[(long)l * c.Np + i] = ((p == l) ? ak : 0.0) + ap * Uk[l];                             // alpha_l
-            if (L + 1 + l < hb.Pa) U[(long)(L + 1 + l) * c.Np + i] = ap * (al[l] * Us[l] - ((p == l) ? as : 0.0));   // tau_l
+            if (L + 1 + l < hb.Pa) U[(long)(L + 1 + l) * c.Np + i] = (p == l) ? -(ap * as) : ap * (al[l] * Us[l]);   // tau_l
         }
     U[(long)L * c.Np + i] = ap * ar;                                                              // rho
 }
@@ -461,7 +467,12 @@ static __global__ __launch_bounds__(512) void gpcc_hess_finish(GpccCtx c, GpccGr
         for (int p = 0; p < L; ++p) s += alpha[p] * asum(3, p);
         t1 = 0.5 * s;
     } else if (k1 == 1) t1 = -alpha[n] * asum(4, n);                                                     // rho, tau_l
-    else t1 = ((l == n) ? alpha[l] * asum(5, l) : 0.0) - alpha[l] * alpha[n] * tab(5, l, n);             // tau_l, tau_m
+    else if (l == n) {                                                                                   // tau_l, tau_l: the own band's
+        double s = 0.0;                                                                                  // SS_ll cancels exactly and is
+        for (int pq = 0; pq < L; ++pq)                                                                   // never added
+            if (pq != l) s += alpha[pq] * tab(5, l, pq);
+        t1 = alpha[l] * s;
+    } else t1 = -(alpha[l] * alpha[n] * tab(5, l, n));                                                   // tau_l, tau_m
     const double hv = t1 - s2[tid] + s3[tid];
     H[th * Pa + ph] = H[ph * Pa + th] = hv;
     F[th * Pa + ph] = F[ph * Pa + th] = s3[tid];

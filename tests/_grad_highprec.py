@@ -81,13 +81,13 @@ def _tri_inv(C):
     return X
 
 
-def cholesky_inverse(K):
-    """Blocked (right-looking by block column) Cholesky K = C C' and X = C^-1 -> (C, X, info); info as LAPACK potrf."""
+def cholesky_inverse(K, nb=NB):
+    """Blocked (right-looking by block column, blocks of nb) Cholesky K = C C' and X = C^-1 -> (C, X, info); info as LAPACK potrf."""
     N = K.shape[0]
     C = np.zeros_like(K)
     X = np.zeros_like(K)
-    for k in range(0, N, NB):
-        e = min(k + NB, N)
+    for k in range(0, N, nb):
+        e = min(k + nb, N)
         A = K[k:e, k:e] - C[k:e, :k] @ C[k:e, :k].T
         Ckk, info = _chol_unblocked(A, k)
         if info:
@@ -97,24 +97,24 @@ def cholesky_inverse(K):
         X[k:e, k:e] = Xkk
         if e < N:
             C[e:, k:e] = (K[e:, k:e] - C[e:, :k] @ C[k:e, :k].T) @ Xkk.T
-    for k in range(NB, N, NB):            # block row k of X: X_k,<k = -X_kk C_k,<k X_<k,<k (X_<k,<k lower triangular)
-        e = min(k + NB, N)
+    for k in range(nb, N, nb):            # block row k of X: X_k,<k = -X_kk C_k,<k X_<k,<k (X_<k,<k lower triangular)
+        e = min(k + nb, N)
         T = np.empty((e - k, k), dtype=K.dtype)
-        for j in range(0, k, NB):
-            T[:, j:j + NB] = C[k:e, j:k] @ X[j:k, j:j + NB]
+        for j in range(0, k, nb):
+            T[:, j:j + nb] = C[k:e, j:k] @ X[j:k, j:j + nb]
         X[k:e, :k] = -X[k:e, k:e] @ T
     return C, X, 0
 
 
-def inverse_from_factor(X):
+def inverse_from_factor(X, nb=NB):
     """K^-1 = X' X for X = C^-1 lower triangular: the lower blocks (rows of X from the block's row on), mirrored."""
     N = X.shape[0]
     Kinv = np.empty_like(X)
-    for i in range(0, N, NB):
-        for j in range(0, i + 1, NB):
-            B = X[i:, i:i + NB].T @ X[i:, j:j + NB]
-            Kinv[i:i + NB, j:j + NB] = B
-            Kinv[j:j + NB, i:i + NB] = B.T
+    for i in range(0, N, nb):
+        for j in range(0, i + 1, nb):
+            B = X[i:, i:i + nb].T @ X[i:, j:j + nb]
+            Kinv[i:i + nb, j:j + nb] = B
+            Kinv[j:j + nb, i:i + nb] = B.T
     return Kinv
 
 
