@@ -399,6 +399,19 @@ class Objective:
                                                       _ip(info)))
         return ll, grad, info
 
+    def loglik_grad_markov_batch(self, delays, alpha, rho):
+        """loglik_grad_batch in linear time (gpcc_loglik_grad_markov_batch: the Kalman filter's forward sensitivities, one lane per
+        (row, parameter); OU, matern32 and matern52 only) -> (loglik[M], grad[M, 2L+1], info[M]).  loglik and info are bitwise
+        loglik_markov_batch's; a row of grad is NaN where info != 0.  rbf, or marginalise_b with more than 4 bands: GpccError
+        (unsupported)."""
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        ll = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, 2 * self.L + 1), dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        self._chk(_capi.load().gpcc_loglik_grad_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _dp(grad),
+                                                             _ip(info)))
+        return ll, grad, info
+
     def loglik_hess_batch(self, delays, alpha, rho):
         """objective, gradient, Hessian and expected (Fisher) information for M (tau, alpha, rho) triples -> (loglik[M],
         grad[M, P], hess[M, P, P], fisher[M, P, P], info[M]), P = 2L+1 in a gradient row's order [alpha_1..alpha_L, rho,
@@ -457,10 +470,13 @@ class Objective:
                                                      _dp(cov), _ip(info), _ip(rounds), stats))
         return ll, alpha, rho, logz, cov, info, rounds, (int(stats[0]), int(stats[1]))
 
-    def value_and_grad(self, alpha, rho, delays):
+    def value_and_grad(self, alpha, rho, delays, solver="dense"):
         """(objective(alpha, rho), gradient) for one delay vector: the gradient is a dict {"alpha": (L,), "rho": float,
-        "delays": (L,)}; raises what __call__ raises."""
-        ll, grad, info = self.loglik_grad_batch([delays], [alpha], [rho])
+        "delays": (L,)}; raises what __call__ raises.  solver "dense" (default): loglik_grad_batch; "markov": the same in linear time
+        (loglik_grad_markov_batch; OU, matern32, matern52)."""
+        if solver not in ("dense", "markov"):
+            raise ValueError("solver must be 'dense' or 'markov', got %r" % (solver,))
+        ll, grad, info = (self.loglik_grad_markov_batch if solver == "markov" else self.loglik_grad_batch)([delays], [alpha], [rho])
         if info[0] == -1:
             raise AssertionError("all(scale .> 0)")
         if info[0] == -2:

@@ -9,6 +9,7 @@
 #include "gpcc_sample.hip.h"
 #include "gpcc_markov.hip.h"
 #include "gpcc_markov_pred.hip.h"
+#include "gpcc_markov_grad.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -236,6 +237,10 @@ struct gpcc_handle_s {
     int *d_mkti = nullptr, *d_mkauxi = nullptr;
     long mkt_cap = 0, mkti_cap = 0, mktap_cap = 0, mkmu_cap = 0, mkvar_cap = 0, mkmix_cap = 0, mkw_cap = 0, mkaux_cap = 0, mkauxi_cap = 0;
     int mkp_configured = 0;
+    // linear-time gradient (gpcc_loglik_grad_markov_batch): the per-slot results [slots][M] and the rows [M][2L + 1], grown on demand
+    double *d_mkgs = nullptr, *d_mkgr = nullptr;
+    long mkgs_cap = 0, mkgr_cap = 0;
+    int mkg_configured = 0;
     int markov_chunk_rows = 0;           // option "markov_chunk_rows": rows per chunk of gpcc_predict_markov_batch (0: by the scratch budget)
     double *d_sep = nullptr, *d_seps = nullptr;     // separable factors of the points, the distance scale (GpccCtx::sep, ::seps)
     int *d_sepflag = nullptr;                       // per-tile-row flags (GpccCtx::sepflag)
@@ -539,6 +544,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_mk);
     hipFree(h->d_mkt); hipFree(h->d_mktap); hipFree(h->d_mkmu); hipFree(h->d_mkvar); hipFree(h->d_mkmix); hipFree(h->d_mkw);
     hipFree(h->d_mkaux); hipFree(h->d_mkti); hipFree(h->d_mkauxi);
+    hipFree(h->d_mkgs); hipFree(h->d_mkgr);
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
     hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
     hipFree(h->d_smean); hipFree(h->d_sdraw); hipFree(h->d_szeta); hipFree(h->d_slist); hipFree(h->d_soff);
@@ -2006,6 +2012,20 @@ static int markov_launch_shape(gpcc_handle_t h, long waves, LdsBytes &&lds_bytes
     return threads;
 }
 
+// gpcc_markov_eval over the M staged rows: loglik and info left in d_out / d_oinfo
+static int markov_eval_launch(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr)
+{
+    GpccMarkovArgs a;
+    markov_fill_args(h, M, dd, da, dr, a);
+    size_t lds;
+    const int threads = markov_launch_shape(h, ((long)M + 63) / 64,
+                                            [&](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }, a.stage, lds);
+    const MarkovDims d = markov_dims(h);
+    const hipError_t e = gpcc_markov_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), threads, lds, h->main_stream);
+    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_eval: %s", hipGetErrorString(e));
+    return 0;
+}
+
 extern "C" int gpcc_loglik_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                         double *loglik, int *info)
 {
@@ -2022,14 +2042,8 @@ extern "C" int gpcc_loglik_markov_batch(gpcc_handle_t h, int M, const double *de
     double *dd, *da, *dr;
     rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [] { return 0; });
     if (rc) return rc;
-    GpccMarkovArgs a;
-    markov_fill_args(h, M, dd, da, dr, a);
-    size_t lds;
-    const int threads = markov_launch_shape(h, ((long)M + 63) / 64,
-                                            [&](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }, a.stage, lds);
-    const MarkovDims d = markov_dims(h);
-    const hipError_t e = gpcc_markov_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), threads, lds, h->main_stream);
-    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_eval: %s", hipGetErrorString(e));
+    rc = markov_eval_launch(h, M, dd, da, dr);
+    if (rc) return rc;
     rc = markov_finish(h, M, loglik, info);
     if (rc) return rc;
     h->markov_count += M;
@@ -2287,6 +2301,51 @@ extern "C" int gpcc_posterior_offsets_markov_batch(gpcc_handle_t h, int M, const
             for (int k = i; k < L; ++k) S[i * L + k] = S[k * L + i] = bad ? NAN : fin[(size_t)(c++) * M + m];
     }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The linear-time gradient of the Markov kernels (gpcc_loglik_grad_markov_batch; kernel: gpcc_markov_grad.hip.h): the
+// filter's forward sensitivities, one lane per (row, parameter slot).  Value and info come from a gpcc_markov_eval launch of the same
+// call (bitwise gpcc_loglik_markov_batch's by construction); it needs what that entry needs plus the slots and the rows.
+// ------------------------------------------------------------------------------------------
+extern "C" int gpcc_loglik_grad_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                             double *loglik, double *grad, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (M == 0) return 0;
+    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    int rc = markov_refusals(h, "gpcc_loglik_grad_markov_batch", "gpcc_loglik_grad_batch");
+    if (rc) return rc;
+    if (route_fp64(h, "linear-time gradient", rc,
+                   [&](gpcc_handle_t o) { return gpcc_loglik_grad_markov_batch(o, M, delays, alpha, rho, loglik, grad, info); }))
+        return rc;
+    GPCC_ON_DEVICE(h, h->device);
+    const MarkovDims d = markov_dims(h);
+    const int W = 2 * h->L + 1, twice = d.p == 1, slots = gpcc_markov_grad_slots(h->L, twice != 0);
+    double *dd, *da, *dr;
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
+        const int g = grow_buf(h, &h->d_mkgs, &h->mkgs_cap, (long)slots * M);
+        return g ? g : grow_buf(h, &h->d_mkgr, &h->mkgr_cap, (long)W * M);
+    });
+    if (rc) return rc;
+    if (!h->mkg_configured) {
+        HIPCHK(h, gpcc_markov_grad_configure());
+        h->mkg_configured = 1;
+    }
+    rc = markov_eval_launch(h, M, dd, da, dr);
+    if (rc) return rc;
+    GpccMarkovGradArgs a;
+    markov_fill_args(h, M, dd, da, dr, a);
+    a.slot = h->d_mkgs; a.grad = h->d_mkgr; a.twice = twice;
+    size_t lds;
+    const int threads = markov_launch_shape(h, (((long)M + 63) / 64) * slots,
+                                            [&](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }, a.stage, lds);
+    const hipError_t e = gpcc_markov_grad_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), slots, threads, lds,
+                                                 h->main_stream);
+    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_grad: %s", hipGetErrorString(e));
+    HIPCHK(h, hipMemcpyAsync(grad, h->d_mkgr, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
+    return markov_finish(h, M, loglik, info);
 }
 
 // ------------------------------------------------------------------------------------------

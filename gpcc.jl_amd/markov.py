@@ -130,6 +130,163 @@ def loglik_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginali
     return np.array([o[0] for o in out]), np.array([o[1] for o in out], dtype=np.int32)
 
 
+# ----------------------------------------------------------------------------------------------------------------------------------
+# The gradient in linear time (csrc/gpcc_markov_grad.hip.h), the same algorithm in numpy: the filter's forward
+# sensitivities.  For one parameter theta the tangents (dm, dP) = d(m, P)/d theta are carried beside (m, P):
+#
+#   alpha_l   enters through h only: dh = e_1 on the observations of band l
+#   rho       through lambda (d lambda / d rho = -lambda / rho): dA = dA/drho, dPinf = dPinf/drho, the prior's dP_xx = dPinf
+#   tau_l     through the lags only: with the merged order fixed d_i = s_i - s_(i-1), d d_i / d tau_l = -[band_i = l] + [band_(i-1) = l]
+#             (0 at the first point), and dA/dd = F A, F = companion()
+#   step      dm <- dA m + A dm,  dP_xx <- dA D A' + A dD A' + A D dA' + dPinf  (D = P_xx - Pinf, dD = dP_xx - dPinf),
+#             dP_xb <- dA P_xb + A dP_xb
+#   update    Ph = P h, dPh = dP h + P dh, dS = 2 dh'Ph + h'dP h, deps = -dh'm - h'dm:
+#             dloglik -= (dS / S + 2 eps deps / S - eps^2 dS / S^2) / 2,  then the tangents of m += Ph eps / S and P -= Ph Ph' / S
+#
+# Ties in shifted time: the merged order is piecewise constant in tau, so this is a one-sided derivative at an exact tie of two bands.
+# The Matern kernels are C^1 there.  OU has a kink, and the dense gradient takes dk/ds(0) = 0, the mean of the one-sided derivatives;
+# the trace formula is linear in dK, so that mean is (tangent with band l first among tied points + tangent with band l last) / 2,
+# the other bands keeping the lowest-band-first rule: OU runs two passes per tau_l.  _grad_pass is the tangent-carrying sibling of
+# _pass over the training points; value and info are loglik()'s.
+# ----------------------------------------------------------------------------------------------------------------------------------
+def companion(kernel, rho):
+    """F, the companion matrix of (lambda + d/dt)^p: A(d) = expm(F d), dA/dd = F A."""
+    name = _name(kernel)
+    lam = rate(name, rho)
+    if name == "OU":
+        return np.array([[-lam]])
+    if name == "matern32":
+        return np.array([[0.0, 1.0], [-lam * lam, -2.0 * lam]])
+    return np.array([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [-lam ** 3, -3.0 * lam * lam, -3.0 * lam]])
+
+
+def transition_drho(kernel, d, rho):
+    """dA(d)/drho = (dA/dlambda) (-lambda / rho), in closed form per kernel."""
+    name = _name(kernel)
+    lam = rate(name, rho)
+    x = lam * d
+    e = math.exp(-x) * (-lam / rho)
+    if name == "OU":
+        return np.array([[-e * d]])
+    if name == "matern32":
+        return e * np.array([[-d * x, -d * d], [x * (x - 2.0), d * (x - 2.0)]])
+    q = 3.0 * x - 3.0 - 0.5 * x * x
+    return e * np.array([[-0.5 * d * x * x, -d * d * x, -0.5 * d ** 3],
+                         [0.5 * x * x * (x - 3.0), d * x * (x - 3.0), 0.5 * d * d * (x - 3.0)],
+                         [lam * x * q, x * (6.0 * x - 6.0 - x * x), d * q]])
+
+
+def stationary_drho(kernel, rho):
+    """dPinf/drho: Matern-3/2 dPinf_22/dlambda = 2 lambda; Matern-5/2 dkappa/dlambda = 2 lambda / 3, d lambda^4 / dlambda = 4 lambda^3."""
+    name = _name(kernel)
+    lam = rate(name, rho)
+    dl = -lam / rho
+    if name == "OU":
+        return np.array([[0.0]])
+    if name == "matern32":
+        return np.array([[0.0, 0.0], [0.0, 2.0 * lam * dl]])
+    dk = 2.0 * lam / 3.0 * dl
+    return np.array([[0.0, 0.0, -dk], [0.0, dk, 0.0], [-dk, 0.0, 4.0 * lam ** 3 * dl]])
+
+
+def _grad_pass(name, train, alpha, rho, p, n, vb, kind, band=-1, rank=None, slip=None):
+    """d loglik / d theta by the tangent recursion over the training observations.  kind: "alpha" (of band `band`), "rho", "tau" (of
+    band `band`).  rank: the rank of `band` among points that tie in shifted time (-1: first, L: last; None: its index, merge_order()'s
+    rule).  slip: loglik_grad()'s."""
+    ev = sorted(train, key=lambda e: (e[0], rank if (rank is not None and e[1] == band) else e[1], e[2]))
+    Pinf = stationary(name, rho)
+    dPinf = stationary_drho(name, rho) if (kind == "rho" and slip != "no_dpinf") else np.zeros((p, p))
+    F = companion(name, rho)
+    P = _prior(name, rho, p, n, vb)
+    dP = np.zeros((n, n))
+    dP[:p, :p] = dPinf
+    m, dm = np.zeros(n), np.zeros(n)
+    dll, sprev, bprev = 0.0, None, -1
+    for (s, b, _, r, s2) in ev:
+        d = 0.0 if sprev is None else s - sprev
+        A = transition(name, d, rho)
+        if kind == "rho":
+            dA = transition_drho(name, d, rho)
+        elif kind == "tau" and sprev is not None:
+            dd = -float(b == band) + (0.0 if slip == "tau_one_lag" else float(bprev == band))
+            dA = dd * (F @ A)
+        else:
+            dA = np.zeros((p, p))
+        sprev, bprev = s, b
+        D, dD = P[:p, :p] - Pinf, dP[:p, :p] - dPinf
+        dm[:p] = dA @ m[:p] + A @ dm[:p]
+        dP[:p, :p] = dA @ D @ A.T + A @ dD @ A.T + A @ D @ dA.T + dPinf
+        dP[:p, p:] = dA @ P[:p, p:] + A @ dP[:p, p:]
+        dP[p:, :p] = dP[:p, p:].T
+        m[:p] = A @ m[:p]
+        P[:p, :p] = A @ D @ A.T + Pinf
+        P[:p, p:] = A @ P[:p, p:]
+        P[p:, :p] = P[:p, p:].T
+        h, dh = np.zeros(n), np.zeros(n)
+        h[0] = alpha[b]
+        if n > p:
+            h[p + b] = 1.0
+        if kind == "alpha" and b == band and slip != "no_dh":
+            dh[0] = 1.0
+        Ph = P @ h
+        dPh = dP @ h + P @ dh
+        S = h @ Ph + s2
+        if not (S > 0.0 and math.isfinite(S)):
+            return math.nan
+        dS = dh @ Ph + h @ dPh
+        eps = r - h @ m
+        deps = -(dh @ m) - h @ dm
+        g = eps / S
+        dg = (deps - g * dS) / S
+        dll -= 0.5 * (dS / S + 2.0 * g * deps - g * g * dS)
+        dm = dm + dPh * g + Ph * dg
+        m = m + Ph * g
+        dP = dP - (np.outer(dPh, Ph) + np.outer(Ph, dPh)) / S + np.outer(Ph, Ph) * (dS / (S * S))
+        P = P - np.outer(Ph, Ph) / S
+        P = 0.5 * (P + P.T)
+        dP = 0.5 * (dP + dP.T)
+    return dll
+
+
+def loglik_grad(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True, _slip=None):
+    """(loglik, grad[2L+1], info) of one (tau, alpha, rho): loglik() and its gradient [d/dalpha_1..alpha_L, d/drho, d/dtau_1..tau_L] by
+    the filter's forward sensitivities, Objective.loglik_grad_markov_batch's row.  grad is NaN where info != 0.
+    _slip (tests only) injects one mistake: "one_sided" (OU without the mean of the two tie orders), "no_dpinf" (dPinf left out of the
+    prior and the step), "tau_one_lag" (only the lag before a point of band l is differentiated, not the one after), "no_dh" (the
+    dh terms left out)."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b,
+                                                                       codes_first=True)
+    nan = np.full(2 * L + 1, math.nan)
+    if code:
+        return math.nan, nan, code
+    ll, info, _, _, _, _ = _pass(name, train, [], alpha, rho, p, n, vb)
+    if info:
+        return math.nan, nan, info
+    grad = np.empty(2 * L + 1)
+    for l in range(L):
+        grad[l] = _grad_pass(name, train, alpha, rho, p, n, vb, "alpha", l, slip=_slip)
+    grad[L] = _grad_pass(name, train, alpha, rho, p, n, vb, "rho", slip=_slip)
+    for l in range(L):
+        if name == "OU" and _slip != "one_sided":
+            first = _grad_pass(name, train, alpha, rho, p, n, vb, "tau", l, rank=-1, slip=_slip)
+            last = _grad_pass(name, train, alpha, rho, p, n, vb, "tau", l, rank=L, slip=_slip)
+            grad[L + 1 + l] = 0.5 * (first + last)
+        else:
+            grad[L + 1 + l] = _grad_pass(name, train, alpha, rho, p, n, vb, "tau", l, slip=_slip)
+    return ll, grad, 0
+
+
+def loglik_grad_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True):
+    """loglik_grad over M rows -> (loglik[M], grad[M, 2L+1], info[M]): Objective.loglik_grad_markov_batch's shape."""
+    L = len(tarray)
+    delays = np.asarray(delays, np.float64).reshape(-1, L)
+    alpha = np.asarray(alpha, np.float64).reshape(-1, L)
+    rho = np.asarray(rho, np.float64).reshape(-1)
+    out = [loglik_grad(kernel, tarray, yarray, stdarray, delays[i], alpha[i], rho[i], marginalise_b) for i in range(len(rho))]
+    return (np.array([o[0] for o in out]), np.array([o[1] for o in out]).reshape(-1, 2 * L + 1),
+            np.array([o[2] for o in out], dtype=np.int32))
+
+
 JITTER = 1e-8   # added to every predictive variance and to sigma*^2 of a held-out point (gpcc_predict_batch's constant)
 
 

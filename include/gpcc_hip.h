@@ -214,7 +214,8 @@ int gpcc_loglik_batch(gpcc_handle_t handle, int M, const double *delays, const d
  * (3 N doubles, built on the first call) and 8 M (2L + 2) bytes of staging; NONE of the N^2 workspace -- a handle that only ever calls
  * this entry never allocates it.  Option "fit_markov" (default 0): 1 makes every optimiser round of gpcc_grid_loglik one call of this
  * entry instead of a gpcc_loglik_batch (GPCC_ERR_UNSUPPORTED where this entry is); read-only "markov_count": evaluations so far.
- * Predictions, held-out scores and the offsets' posterior in linear time: the three entries below; gradient and Hessian stay dense.
+ * Predictions, held-out scores and the offsets' posterior in linear time: the three entries below; the gradient in linear time:
+ * gpcc_loglik_grad_markov_batch after them; the Hessian stays dense.
  * Blocking. */
 int gpcc_loglik_markov_batch(gpcc_handle_t handle, int M, const double *delays, const double *alpha, const double *rho,
                              double *loglik, int *info);
@@ -258,6 +259,25 @@ int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const double *delay
                                      const double *weights, double *heldout, double *mix_heldout, double *loglik, int *info);
 int gpcc_posterior_offsets_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                         double *mu_b_out, double *Sigma_b_out, double *loglik, int *info);
+
+/* objective(alpha, rho) and its gradient in LINEAR time for the Markov kernels (OU, Matern-3/2, Matern-5/2), exact: the forward
+ * sensitivities of the Kalman filter of gpcc_loglik_markov_batch -- the recursion carried for (d mean / d theta, d covariance / d theta)
+ * beside (mean, covariance), O(N p^2) work and O(1) memory per parameter (kernel: csrc/gpcc_markov_grad.hip.h).
+ *   Layout of gpcc_loglik_grad_batch: grad is M rows of 2L+1 doubles [d/d alpha_1..alpha_L, d/d rho, d/d tau_1..tau_L] in the
+ *   reference's (constrained) parameters; a row is NaN where info != 0.  The conventions are the dense entry's: at an exact tie of two
+ *   bands in shifted time the OU kernel's d/d tau is the mean of the one-sided derivatives (dk/ds at 0 taken as 0), computed as the
+ *   mean of two filters that place the band first and last among the tied points; the Matern kernels are differentiable there.
+ *   Refusals, argument checks, info codes and memory behaviour of gpcc_loglik_markov_batch: GPCC_ERR_UNSUPPORTED for rbf and for
+ *   marginalise_b with more than 4 bands -- use gpcc_loglik_grad_batch there; -1 / -2 rows never touch the others; info[m] = j > 0 is
+ *   the merged position of the first predictive variance that is not positive and finite.  loglik[m] and info[m] are bitwise
+ *   gpcc_loglik_markov_batch's for that row (they come from a launch of its kernel inside the same call).
+ * Path: one lane per (row, parameter slot) -- L alpha slots, one rho slot, L tau slots (OU: 2L) -- in one launch, then a small kernel
+ * that writes the rows.  A row's bits depend on that row alone: no atomics, the same bits for any M, row order, option and handle
+ * flavour.  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Memory: what
+ * gpcc_loglik_markov_batch needs, plus 8 M bytes per slot and 8 M (2L + 1) bytes for the rows, grown on demand; NONE of the N^2
+ * workspace.  Blocking. */
+int gpcc_loglik_grad_markov_batch(gpcc_handle_t handle, int M, const double *delays, const double *alpha, const double *rho,
+                                  double *loglik, double *grad, int *info);
 
 /* objective(alpha, rho) and its gradient for M independent (tau, alpha, rho): loglik[M], info[M] as gpcc_loglik_batch;
  * grad: M rows of 2L+1 doubles [d/d alpha_1..alpha_L, d/d rho, d/d tau_1..tau_L] in the reference's (constrained)

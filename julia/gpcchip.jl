@@ -146,6 +146,21 @@ function loglik_grad_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Flo
     return ll, grad, info
 end
 
+"loglik_grad_batch in LINEAR time (gpcc_loglik_grad_markov_batch: the Kalman filter's forward sensitivities, one lane per (row,
+parameter), DESIGN 4.17; OU, matern32, matern52): (ll[M], grad (2L+1)×M, info[M]).  ll and info are bitwise loglik_markov_batch's; a
+column of grad is NaN where info != 0.  Errors for rbf and for marginalise_b with more than 4 bands."
+function loglik_grad_markov(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    grad = Matrix{Float64}(undef, 2h.L + 1, M)                            # column-major (2L+1)×M == row-major M×(2L+1)
+    rc = ccall((:gpcc_loglik_grad_markov_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, ll, grad, info)
+    rc == 0 || error("gpcc_loglik_grad_markov_batch: " * lasterror(h.ptr))
+    return ll, grad, info
+end
+
 "objective, gradient, Hessian and expected (Fisher) information for M triples: (ll[M], grad (2L+1)×M, hess and fisher
 (2L+1)×(2L+1)×M, info[M]) in [α_1..α_L, ρ, τ_1..τ_L] order, symmetric blocks, NaN where info != 0; fisher = 1/2 tr(K⁻¹D_iK⁻¹D_j)."
 function loglik_hess_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
