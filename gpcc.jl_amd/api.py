@@ -443,13 +443,43 @@ class Objective:
                                                             _dp(hess), _dp(fisher), _ip(info)))
         return ll, grad, hess, fisher, info
 
-    def laplace_evidence(self, delays, alpha0, rho0, rhomin=0.1, rhomax=20.0, max_rounds=50, g_tol=1e-6):
+    def loglik_hess_hyper_markov_batch(self, delays, alpha, rho):
+        """The hyper-parameter block of the Hessian in linear time (gpcc_loglik_hess_hyper_markov_batch: the Kalman filter's second-order
+        forward sensitivities, one lane per (row, pair of parameters); OU, matern32 and matern52 only) -> (loglik[M], grad[M, 2L+1],
+        hess[M, L+1, L+1], info[M]).  loglik, grad and info are bitwise loglik_grad_markov_batch's; hess is bitwise symmetric and NaN where
+        info != 0.  No Fisher information and no rows of tau in linear time: loglik_hess_hyper_batch and loglik_hess_batch have them.
+        rbf, or marginalise_b with more than 4 bands: GpccError (unsupported)."""
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        P, n = 2 * self.L + 1, self.L + 1
+        ll = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, P), dtype=np.float64)
+        hess = np.empty((M, n, n), dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        self._chk(_capi.load().gpcc_loglik_hess_hyper_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _dp(grad),
+                                                                   _dp(hess), _ip(info)))
+        return ll, grad, hess, info
+
+    def laplace_evidence(self, delays, alpha0, rho0, rhomin=0.1, rhomax=20.0, max_rounds=50, g_tol=1e-6, solver="dense"):
         """The Laplace-marginalised evidence over alpha and rho per row of delays (G, L), from (alpha0[G, L], rho0[G]) (usually
         grid_loglik's output) -> (loglik[G], alpha[G, L], rho[G], log_evidence[G], cov[G, L+1, L+1], info[G], rounds[G],
         (evaluations, batches)).  Prior log-uniform in alpha and in rho on [rhomin, rhomax]: log_evidence is log Z(tau) up to one
         additive constant shared by all delays (getprobabilities(log_evidence) is the delay posterior).  cov: the posterior
         covariance of u = (log alpha, log rho).  info: 0, laplace.NOT_CONVERGED / NOT_MAXIMUM / ON_BOUND (NaN log_evidence), or
-        the device's code of a start it could not evaluate."""
+        the device's code of a start it could not evaluate.  solver "dense" (default): every Newton round is one
+        loglik_hess_hyper_batch; "markov": one loglik_hess_hyper_markov_batch (option "laplace_markov", set around the call and
+        restored; OU, matern32, matern52 -- DESIGN.md 4.18)."""
+        if solver not in ("dense", "markov"):
+            raise ValueError("solver must be 'dense' or 'markov', got %r" % (solver,))
+        if solver == "markov":
+            before = self.get_option("laplace_markov")
+            self.set_option("laplace_markov", 1)
+            try:
+                return self._laplace_evidence(delays, alpha0, rho0, rhomin, rhomax, max_rounds, g_tol)
+            finally:
+                self.set_option("laplace_markov", before)
+        return self._laplace_evidence(delays, alpha0, rho0, rhomin, rhomax, max_rounds, g_tol)
+
+    def _laplace_evidence(self, delays, alpha0, rho0, rhomin, rhomax, max_rounds, g_tol):
         cand = np.ascontiguousarray(np.atleast_2d(delays), dtype=np.float64)
         G = cand.shape[0]
         if cand.shape[1] != self.L:

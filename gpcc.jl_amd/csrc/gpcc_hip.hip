@@ -10,6 +10,7 @@
 #include "gpcc_markov.hip.h"
 #include "gpcc_markov_pred.hip.h"
 #include "gpcc_markov_grad.hip.h"
+#include "gpcc_markov_hess.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -241,6 +242,11 @@ struct gpcc_handle_s {
     double *d_mkgs = nullptr, *d_mkgr = nullptr;
     long mkgs_cap = 0, mkgr_cap = 0;
     int mkg_configured = 0;
+    // linear-time Hessian block (gpcc_loglik_hess_hyper_markov_batch): the per-pair results [pair slots][M] and the blocks [M][(L + 1)^2]
+    double *d_mkhs = nullptr, *d_mkhb = nullptr;
+    long mkhs_cap = 0, mkhb_cap = 0;
+    int mkh_configured = 0;
+    int laplace_markov = 0;              // option "laplace_markov": gpcc_laplace_evidence's rounds are gpcc_loglik_hess_hyper_markov_batch calls
     int markov_chunk_rows = 0;           // option "markov_chunk_rows": rows per chunk of gpcc_predict_markov_batch (0: by the scratch budget)
     double *d_sep = nullptr, *d_seps = nullptr;     // separable factors of the points, the distance scale (GpccCtx::sep, ::seps)
     int *d_sepflag = nullptr;                       // per-tile-row flags (GpccCtx::sepflag)
@@ -545,6 +551,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_mkt); hipFree(h->d_mktap); hipFree(h->d_mkmu); hipFree(h->d_mkvar); hipFree(h->d_mkmix); hipFree(h->d_mkw);
     hipFree(h->d_mkaux); hipFree(h->d_mkti); hipFree(h->d_mkauxi);
     hipFree(h->d_mkgs); hipFree(h->d_mkgr);
+    hipFree(h->d_mkhs); hipFree(h->d_mkhb);
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
     hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
     hipFree(h->d_smean); hipFree(h->d_sdraw); hipFree(h->d_szeta); hipFree(h->d_slist); hipFree(h->d_soff);
@@ -639,13 +646,18 @@ extern "C" int gpcc_set_option(gpcc_handle_t h, const char *key, long v)
         h->hybrid_mall_mb = (int)v;
     } else if (!strcmp(key, "fit_speculate")) {
         h->fit_speculate = v != 0;
-    } else if (!strcmp(key, "fit_markov")) {
+    } else if (!strcmp(key, "fit_markov") || !strcmp(key, "laplace_markov")) {   // (one set of refusals for both)
+        const bool fit = !strcmp(key, "fit_markov");
+        const char *what = fit ? "fit" : "evidence";
         if (v != 0 && h->kernel_id == GPCC_KERNEL_RBF)
-            return fail(h, GPCC_ERR_UNSUPPORTED, "fit_markov: the rbf kernel is not Markov (OU, matern32, matern52 are); its fit stays dense");
+            return fail(h, GPCC_ERR_UNSUPPORTED, "%s: the rbf kernel is not Markov (OU, matern32, matern52 are); its %s stays dense", key, what);
         if (v != 0 && h->mb && h->L > GPCC_MARKOV_MAX_OFFSETS)
-            return fail(h, GPCC_ERR_UNSUPPORTED, "fit_markov: marginalise_b with L=%d bands (the filter keeps at most %d offset states)", h->L,
+            return fail(h, GPCC_ERR_UNSUPPORTED, "%s: marginalise_b with L=%d bands (the filter keeps at most %d offset states)", key, h->L,
                         GPCC_MARKOV_MAX_OFFSETS);
-        h->fit_markov = v != 0;
+        if (v != 0 && !fit && !gpcc_markov_hess_shipped(h->kernel_id == GPCC_KERNEL_OU ? 1 : (h->kernel_id == GPCC_KERNEL_MATERN32 ? 2 : 3), h->mb ? h->L : 0))
+            return fail(h, GPCC_ERR_UNSUPPORTED, "laplace_markov: the linear-time Hessian block of this kernel with %d offset states does not ship; "
+                        "its evidence stays dense", h->L);
+        (fit ? h->fit_markov : h->laplace_markov) = v != 0;
     } else if (!strcmp(key, "markov_chunk_rows")) {
         if (v < 0) return fail(h, GPCC_ERR_ARGUMENT, "markov_chunk_rows must be >= 0");
         h->markov_chunk_rows = (int)v;
@@ -729,6 +741,7 @@ extern "C" long gpcc_get_option(gpcc_handle_t h, const char *key)
     if (!strcmp(key, "fit_speculate")) return h->fit_speculate;
     if (!strcmp(key, "fit_device_unpack")) return h->fit_device_unpack;
     if (!strcmp(key, "fit_markov")) return h->fit_markov;
+    if (!strcmp(key, "laplace_markov")) return h->laplace_markov;
     if (!strcmp(key, "markov_count")) return h->markov_count;
     if (!strcmp(key, "markov_chunk_rows")) return h->markov_chunk_rows;
     if (!strcmp(key, "markov_tap_bytes")) return 8 * h->mktap_cap;
@@ -2308,6 +2321,38 @@ extern "C" int gpcc_posterior_offsets_markov_batch(gpcc_handle_t h, int M, const
 // filter's forward sensitivities, one lane per (row, parameter slot).  Value and info come from a gpcc_markov_eval launch of the same
 // call (bitwise gpcc_loglik_markov_batch's by construction); it needs what that entry needs plus the slots and the rows.
 // ------------------------------------------------------------------------------------------
+// the gradient's buffers for M rows, and its launches over the M staged rows: gpcc_markov_eval (loglik and info left in d_out / d_oinfo),
+// gpcc_markov_grad and its finish kernel, the rows copied to `grad` behind them.  gpcc_loglik_hess_hyper_markov_batch shares both
+static int markov_grad_grow(gpcc_handle_t h, int M)
+{
+    const int slots = gpcc_markov_grad_slots(h->L, markov_dims(h).p == 1);
+    const int g = grow_buf(h, &h->d_mkgs, &h->mkgs_cap, (long)slots * M);
+    return g ? g : grow_buf(h, &h->d_mkgr, &h->mkgr_cap, (long)(2 * h->L + 1) * M);
+}
+
+static int markov_grad_enqueue(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, double *grad)
+{
+    const MarkovDims d = markov_dims(h);
+    const int W = 2 * h->L + 1, twice = d.p == 1, slots = gpcc_markov_grad_slots(h->L, twice != 0);
+    if (!h->mkg_configured) {
+        HIPCHK(h, gpcc_markov_grad_configure());
+        h->mkg_configured = 1;
+    }
+    int rc = markov_eval_launch(h, M, dd, da, dr);
+    if (rc) return rc;
+    GpccMarkovGradArgs a;
+    markov_fill_args(h, M, dd, da, dr, a);
+    a.slot = h->d_mkgs; a.grad = h->d_mkgr; a.twice = twice;
+    size_t lds;
+    const int threads = markov_launch_shape(h, (((long)M + 63) / 64) * slots,
+                                            [&](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }, a.stage, lds);
+    const hipError_t e = gpcc_markov_grad_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), slots, threads, lds,
+                                                 h->main_stream);
+    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_grad: %s", hipGetErrorString(e));
+    HIPCHK(h, hipMemcpyAsync(grad, h->d_mkgr, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
+    return 0;
+}
+
 extern "C" int gpcc_loglik_grad_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                              double *loglik, double *grad, int *info)
 {
@@ -2321,30 +2366,66 @@ extern "C" int gpcc_loglik_grad_markov_batch(gpcc_handle_t h, int M, const doubl
                    [&](gpcc_handle_t o) { return gpcc_loglik_grad_markov_batch(o, M, delays, alpha, rho, loglik, grad, info); }))
         return rc;
     GPCC_ON_DEVICE(h, h->device);
+    double *dd, *da, *dr;
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] { return markov_grad_grow(h, M); });
+    if (rc) return rc;
+    rc = markov_grad_enqueue(h, M, dd, da, dr, grad);
+    if (rc) return rc;
+    return markov_finish(h, M, loglik, info);
+}
+
+// ------------------------------------------------------------------------------------------
+// The linear-time (alpha, rho) block of the Hessian of the Markov kernels (gpcc_loglik_hess_hyper_markov_batch; kernel:
+// gpcc_markov_hess.hip.h): the filter's second-order forward sensitivities, one lane per (row, pair slot).  Value, info
+// and gradient come from the gradient entry's launches inside the same call (bitwise gpcc_loglik_grad_markov_batch's by construction);
+// it needs what that entry needs plus the pair slots and the blocks, nothing of the N^2 workspace.
+// ------------------------------------------------------------------------------------------
+extern "C" int gpcc_loglik_hess_hyper_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                                   double *loglik, double *grad, double *hess, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (M == 0) return 0;
+    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    int rc = markov_refusals(h, "gpcc_loglik_hess_hyper_markov_batch", "gpcc_loglik_hess_hyper_batch");
+    if (rc) return rc;
+    {
+        const MarkovDims d = markov_dims(primary(h));
+        if (!gpcc_markov_hess_shipped(d.p, d.noff))
+            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_hess_hyper_markov_batch: the instantiation <%d, %d> (states of the process, "
+                        "offset states) needs scratch memory and does not ship; use gpcc_loglik_hess_hyper_batch", d.p, d.noff);
+    }
+    if (route_fp64(h, "linear-time Hessian block", rc,
+                   [&](gpcc_handle_t o) { return gpcc_loglik_hess_hyper_markov_batch(o, M, delays, alpha, rho, loglik, grad, hess, info); }))
+        return rc;
+    GPCC_ON_DEVICE(h, h->device);
     const MarkovDims d = markov_dims(h);
-    const int W = 2 * h->L + 1, twice = d.p == 1, slots = gpcc_markov_grad_slots(h->L, twice != 0);
+    const int n = h->L + 1, slots = gpcc_markov_hess_slots(h->L);
     double *dd, *da, *dr;
     rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
-        const int g = grow_buf(h, &h->d_mkgs, &h->mkgs_cap, (long)slots * M);
-        return g ? g : grow_buf(h, &h->d_mkgr, &h->mkgr_cap, (long)W * M);
+        int g = markov_grad_grow(h, M);
+        if (!g && hess) g = grow_buf(h, &h->d_mkhs, &h->mkhs_cap, (long)slots * M);
+        return (g || !hess) ? g : grow_buf(h, &h->d_mkhb, &h->mkhb_cap, (long)n * n * M);
     });
     if (rc) return rc;
-    if (!h->mkg_configured) {
-        HIPCHK(h, gpcc_markov_grad_configure());
-        h->mkg_configured = 1;
-    }
-    rc = markov_eval_launch(h, M, dd, da, dr);
+    rc = markov_grad_enqueue(h, M, dd, da, dr, grad);
     if (rc) return rc;
-    GpccMarkovGradArgs a;
-    markov_fill_args(h, M, dd, da, dr, a);
-    a.slot = h->d_mkgs; a.grad = h->d_mkgr; a.twice = twice;
-    size_t lds;
-    const int threads = markov_launch_shape(h, (((long)M + 63) / 64) * slots,
-                                            [&](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }, a.stage, lds);
-    const hipError_t e = gpcc_markov_grad_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), slots, threads, lds,
-                                                 h->main_stream);
-    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_grad: %s", hipGetErrorString(e));
-    HIPCHK(h, hipMemcpyAsync(grad, h->d_mkgr, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
+    if (hess) {
+        if (!h->mkh_configured) {
+            HIPCHK(h, gpcc_markov_hess_configure());
+            h->mkh_configured = 1;
+        }
+        GpccMarkovHessArgs a;
+        markov_fill_args(h, M, dd, da, dr, a);
+        a.slot = h->d_mkhs; a.hess = h->d_mkhb;
+        size_t lds;
+        const int threads = markov_launch_shape(h, (((long)M + 63) / 64) * slots,
+                                                [&](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }, a.stage, lds);
+        const hipError_t e = gpcc_markov_hess_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), slots, threads, lds,
+                                                     h->main_stream);
+        if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_hess: %s", hipGetErrorString(e));
+        HIPCHK(h, hipMemcpyAsync(hess, h->d_mkhb, sizeof(double) * n * n * M, hipMemcpyDeviceToHost, h->main_stream));
+    }
     return markov_finish(h, M, loglik, info);
 }
 
@@ -3328,8 +3409,11 @@ int laplace_eval(void *vctx, long K, const long *pidx, const double *U, double *
         }
         e.r[i] = std::exp(U[i * n + L]);
     }
-    const int rc = gpcc_loglik_hess_hyper_batch(e.h, (int)K, e.d.data(), e.a.data(), e.r.data(), e.ll.data(), e.grad.data(), e.hess.data(),
-                                                nullptr, e.inf.data());
+    const int rc = primary(e.h)->laplace_markov
+                       ? gpcc_loglik_hess_hyper_markov_batch(e.h, (int)K, e.d.data(), e.a.data(), e.r.data(), e.ll.data(), e.grad.data(),
+                                                             e.hess.data(), e.inf.data())
+                       : gpcc_loglik_hess_hyper_batch(e.h, (int)K, e.d.data(), e.a.data(), e.r.data(), e.ll.data(), e.grad.data(), e.hess.data(),
+                                                      nullptr, e.inf.data());
     if (rc) return rc;
     double theta[GPCC_MAXL + 1];
     for (long i = 0; i < K; ++i) {

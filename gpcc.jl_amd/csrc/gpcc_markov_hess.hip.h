@@ -1,0 +1,399 @@
+// gpcc_markov_hess.hip.h -- the exact linear-time (alpha, rho) block of the Hessian of the log-likelihood of the Markov kernels (OU,
+// Matern-3/2, Matern-5/2) for gfx950: gpcc_loglik_hess_hyper_markov_batch of include/gpcc_hip.h; gpcc.jl_amd/markov.py
+// (loglik_hess_hyper) is the same algorithm in numpy.  The filter's step (gpcc_mk_*) is gpcc_markov.hip.h's and the first-order
+// tangents (gpcc_mkg_*) are gpcc_markov_grad.hip.h's; nothing is approximated.
+//
+// SECOND-ORDER FORWARD SENSITIVITY.  For a pair (a, b) of theta = (alpha_1..alpha_L, rho) four sets are carried through the filter: the
+// state (mu, C), its tangents by a and by b, and the second tangent (mu_ab, C_ab); the log-likelihood's second tangent is summed as
+// the value is.  For alpha and rho the merged order is fixed and no kink is crossed, so there is no tie convention.
+//   rho rho  d/drho = (-lambda / rho) d/dlambda, so d2/drho2 = (lambda / rho)^2 d2/dlambda2 + (2 lambda / rho^2) d/dlambda, for A and Pinf
+//            in closed form per kernel (gpcc_mkh_d2transition_rate, gpcc_mkh_d2stationary); the prior's second tangent is Pinf_rhorho
+//   step     the product rule on the gradient's step, written with the gradient's own tangent step:
+//              alpha alpha  (mu_ab, C_ab) moves as an alpha tangent does (A only)
+//              alpha rho    (mu_ab, C_ab) is the rho tangent of the "state" (mu_a, C_a), whose stationary part is zero
+//              rho rho      the rho tangent step with (A_rhorho, Pinf_rhorho) in place of (A_rho, Pinf_rho), plus the cross terms
+//                           2 A_rho mu_rho, 2 A_rho D A_rho' + 2 (A_rho D_rho A' + A D_rho A_rho'), 2 A_rho C_rho,xb  (gpcc_mkh_cross)
+//   update   h_a = e_1 on the observations of band a, h_ab = 0:  (Ph)_a = C_a h + C h_a,  (Ph)_ab = C_ab h + C_a h_b + C_b h_a,
+//            S_a = h_a'Ph + h'(Ph)_a,  S_ab = h_a'(Ph)_b + h_b'(Ph)_a + h'(Ph)_ab,  eps_a = -h_a'mu - h'mu_a,
+//            eps_ab = -h_a'mu_b - h_b'mu_a - h'mu_ab,  g = eps / S, g_a = (eps_a - g S_a) / S, g_ab = (eps_ab - g_a S_b - g_b S_a - g S_ab) / S:
+//            ll_ab -= (S_ab / S - S_a S_b / S^2 + 2 eps_a eps_b / S + 2 g eps_ab - 2 g (eps_a S_b + eps_b S_a) / S - g^2 S_ab
+//                      + 2 g^2 S_a S_b / S) / 2,  then the second tangents of mu += Ph g and C -= k Ph', k = Ph / S
+//
+// NOT HERE.  The Fisher information (its expectation needs another recursion) and the rows of tau (OU's second-order tie convention
+// is not a mean of two filter orders) stay with gpcc_loglik_hess_batch / gpcc_loglik_hess_hyper_batch.
+//
+// gpcc_markov_hess<P, NOFF>: ONE LANE PER (ROW, PAIR SLOT), a <= b, the slot being blockIdx.y: (L + 1)(L + 2) / 2 slots in the order
+// (0,0), (0,1), .., (0,L), (1,1), ..  A workgroup is uniform in its pair, and the walk is a template on the kind of pair: an
+// alpha alpha lane forms no tangent of A, an alpha rho lane A_rho, the rho rho lane A_rho and A_rhorho; a diagonal pair carries three
+// sets, the others four.  State and tangents are register-resident (4 (n + n (n + 1) / 2) = 140 doubles at n = 7, in the unified
+// 512-register file at one wave per SIMD); cursors, heads, tau and alpha in LDS, [band][thread], the light curves staged in LDS when
+// they fit, exactly as in gpcc_markov_eval (gpcc_markov_lds_bytes).  The primal recursion is the one filter step of gpcc_markov.hip.h.
+// Per-slot results go to slot[slot][row]; gpcc_markov_hess_finish writes every pair to both halves of the row's (L+1) x (L+1) block
+// (bitwise symmetric), NaN where info != 0.  Lanes beyond M compute row M - 1 again and store nothing.  No atomics: a row's bits depend
+// on the row alone.
+#pragma once
+#include "gpcc_markov_grad.hip.h"
+
+#define GPCC_MKH_AA_DIAG 0   /* (alpha_l, alpha_l) */
+#define GPCC_MKH_AA_OFF 1    /* (alpha_l, alpha_m), l < m */
+#define GPCC_MKH_AR 2        /* (alpha_l, rho) */
+#define GPCC_MKH_RR 3        /* (rho, rho) */
+
+// GpccMarkovArgs' fields under the same names (the host fills them through one template), the slots and the blocks
+struct GpccMarkovHessArgs {
+    const double *pts;
+    const double *delays, *alpha, *rho;
+    double *out_loglik;                    // gpcc_markov_eval's, of the same call: read by the finish kernel only
+    int *out_info;
+    double *slot;                          // [slots][M]
+    double *hess;                          // [M][L + 1][L + 1]
+    int M, L, N, stage;
+    int off[GPCC_MARKOV_MAXL + 1];
+    double sigma_b[GPCC_MARKOV_MAX_OFFSETS];
+};
+
+static inline int gpcc_markov_hess_slots(int L) { return (L + 1) * (L + 2) / 2; }
+
+// Add = c2 d2A/dlambda2, in closed form per kernel (e = exp(-lambda d), x = lambda d)
+template <int P>
+__device__ __forceinline__ void gpcc_mkh_d2transition_rate(double lam, double d, double c2, double (&Add)[P][P])
+{
+    const double x = lam * d, e = exp(-x) * c2, d2 = d * d;
+    if constexpr (P == 1) {
+        Add[0][0] = e * d2;
+    } else if constexpr (P == 2) {
+        Add[0][0] = e * d2 * (x - 1.0);
+        Add[0][1] = e * d2 * d;
+        Add[1][0] = e * d * (4.0 * x - 2.0 - x * x);
+        Add[1][1] = e * d2 * (3.0 - x);
+    } else {
+        Add[0][0] = e * d2 * x * (0.5 * x - 1.0);
+        Add[0][1] = e * d2 * d * (x - 1.0);
+        Add[0][2] = 0.5 * e * d2 * d2;
+        Add[1][0] = 0.5 * e * d * x * (6.0 * x - 6.0 - x * x);
+        Add[1][1] = e * d2 * (5.0 * x - 3.0 - x * x);
+        Add[1][2] = 0.5 * e * d2 * d * (4.0 - x);
+        Add[2][0] = e * x * (0.5 * x * x * x - 5.0 * x * x + 12.0 * x - 6.0);
+        Add[2][1] = e * d * (x * x * x - 9.0 * x * x + 18.0 * x - 6.0);
+        Add[2][2] = e * d2 * (0.5 * x * x - 4.0 * x + 6.0);
+    }
+}
+
+// Qdd = c2 d2Pinf/dlambda2
+template <int P>
+__device__ __forceinline__ void gpcc_mkh_d2stationary(double lam2, double c2, double (&Qdd)[P][P])
+{
+#pragma unroll
+    for (int i = 0; i < P; ++i)
+#pragma unroll
+        for (int j = 0; j < P; ++j) Qdd[i][j] = 0.0;
+    if constexpr (P == 2) Qdd[1][1] = 2.0 * c2;
+    if constexpr (P == 3) {
+        Qdd[0][2] = Qdd[2][0] = -(2.0 / 3.0) * c2;
+        Qdd[1][1] = (2.0 / 3.0) * c2;
+        Qdd[2][2] = 12.0 * lam2 * c2;
+    }
+}
+
+// the cross terms of the (rho, rho) step, from the state and the rho tangent BEFORE their propagation:
+// mu_ab += 2 Ad dmu,  C_ab,xx += 2 Ad D Ad' + 2 (Ad dD A' + A dD Ad'),  C_ab,xb += 2 Ad dC_xb   (D = C_xx - Q, dD = dC_xx - Qd)
+template <int P, int NOFF>
+__device__ __forceinline__ void gpcc_mkh_cross(const double (&A)[P][P], const double (&Ad)[P][P], const double (&Q)[P][P],
+                                               const double (&Qd)[P][P], const double (&C)[P + NOFF][P + NOFF],
+                                               const double (&dmu)[P + NOFF], const double (&dC)[P + NOFF][P + NOFF],
+                                               double (&mu2)[P + NOFF], double (&C2)[P + NOFF][P + NOFF])
+{
+    double T[P][P], U[P][P], W[P][P];
+#pragma unroll
+    for (int i2 = 0; i2 < P; ++i2) {
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < P; ++k) acc += Ad[i2][k] * dmu[k];
+        mu2[i2] += 2.0 * acc;
+    }
+#pragma unroll
+    for (int i2 = 0; i2 < P; ++i2)
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            double acc = 0.0, acu = 0.0;
+#pragma unroll
+            for (int q = 0; q < P; ++q) {
+                acc += Ad[i2][q] * (GPCC_MK_SYM(dC, q, k) - Qd[q][k]);
+                acu += Ad[i2][q] * (GPCC_MK_SYM(C, q, k) - Q[q][k]);
+            }
+            T[i2][k] = acc;
+            U[i2][k] = acu;
+        }
+#pragma unroll
+    for (int i2 = 0; i2 < P; ++i2)
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            double acc = 0.0;
+#pragma unroll
+            for (int q = 0; q < P; ++q) acc += T[i2][q] * A[k][q];
+            W[i2][k] = acc;
+        }
+#pragma unroll
+    for (int i2 = 0; i2 < P; ++i2)
+#pragma unroll
+        for (int k = i2; k < P; ++k) {
+            double acc = 0.0;
+#pragma unroll
+            for (int q = 0; q < P; ++q) acc += U[i2][q] * Ad[k][q];
+            C2[i2][k] += 2.0 * (acc + W[i2][k] + W[k][i2]);
+        }
+#pragma unroll
+    for (int c = 0; c < NOFF; ++c)
+#pragma unroll
+        for (int i2 = 0; i2 < P; ++i2) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < P; ++k) acc += Ad[i2][k] * dC[k][P + c];
+            C2[i2][P + c] += 2.0 * acc;
+        }
+}
+
+// the second tangent of gpcc_mk_update, from the state and the two tangents BEFORE it (after the propagation).  ha, hb: this
+// observation's h moves with the pair's first / second parameter (an alpha of its band).  A diagonal pair passes its tangent twice
+template <int P, int NOFF>
+__device__ __forceinline__ void gpcc_mkh_update(int b, double al, bool ha, bool hb, double r, double s2, const double (&mu)[P + NOFF],
+                                                const double (&C)[P + NOFF][P + NOFF], const double (&mua)[P + NOFF],
+                                                const double (&Ca)[P + NOFF][P + NOFF], const double (&mub)[P + NOFF],
+                                                const double (&Cb)[P + NOFF][P + NOFF], double (&muab)[P + NOFF],
+                                                double (&Cab)[P + NOFF][P + NOFF], double &hll)
+{
+    constexpr int NS = P + NOFF;
+    double Ph[NS], Pha[NS], Phb[NS], Phab[NS];
+#pragma unroll
+    for (int i2 = 0; i2 < NS; ++i2) {
+        const double c0 = GPCC_MK_SYM(C, i2, 0), a0 = GPCC_MK_SYM(Ca, i2, 0), b0 = GPCC_MK_SYM(Cb, i2, 0);
+        double acc = al * c0, acca = al * a0, accb = al * b0, accab = al * GPCC_MK_SYM(Cab, i2, 0);
+#pragma unroll
+        for (int c = 0; c < NOFF; ++c) {
+            acc += (b == c) ? GPCC_MK_SYM(C, i2, P + c) : 0.0;
+            acca += (b == c) ? GPCC_MK_SYM(Ca, i2, P + c) : 0.0;
+            accb += (b == c) ? GPCC_MK_SYM(Cb, i2, P + c) : 0.0;
+            accab += (b == c) ? GPCC_MK_SYM(Cab, i2, P + c) : 0.0;
+        }
+        Ph[i2] = acc;
+        Pha[i2] = acca + (ha ? c0 : 0.0);
+        Phb[i2] = accb + (hb ? c0 : 0.0);
+        Phab[i2] = accab + (hb ? a0 : 0.0) + (ha ? b0 : 0.0);
+    }
+    double S = al * Ph[0] + s2, Sa = al * Pha[0], Sb = al * Phb[0], Sab = al * Phab[0];
+    double hm = al * mu[0], hma = al * mua[0], hmb = al * mub[0], hmab = al * muab[0];
+#pragma unroll
+    for (int c = 0; c < NOFF; ++c) {
+        S += (b == c) ? Ph[P + c] : 0.0;
+        Sa += (b == c) ? Pha[P + c] : 0.0;
+        Sb += (b == c) ? Phb[P + c] : 0.0;
+        Sab += (b == c) ? Phab[P + c] : 0.0;
+        hm += (b == c) ? mu[P + c] : 0.0;
+        hma += (b == c) ? mua[P + c] : 0.0;
+        hmb += (b == c) ? mub[P + c] : 0.0;
+        hmab += (b == c) ? muab[P + c] : 0.0;
+    }
+    Sa += ha ? Ph[0] : 0.0;
+    Sb += hb ? Ph[0] : 0.0;
+    Sab += (ha ? Phb[0] : 0.0) + (hb ? Pha[0] : 0.0);
+    const double ea = -(hma + (ha ? mu[0] : 0.0)), eb = -(hmb + (hb ? mu[0] : 0.0));
+    const double eab = -(hmab + (ha ? mub[0] : 0.0) + (hb ? mua[0] : 0.0));
+    const double inv = 1.0 / S, g = (r - hm) * inv, ga = (ea - g * Sa) * inv, gb = (eb - g * Sb) * inv;
+    const double gab = (eab - ga * Sb - gb * Sa - g * Sab) * inv;
+    hll -= 0.5 * (Sab * inv - Sa * Sb * inv * inv + 2.0 * ea * eb * inv + 2.0 * g * eab - 2.0 * g * inv * (ea * Sb + eb * Sa) - g * g * Sab
+                  + 2.0 * g * g * Sa * Sb * inv);
+    const double inv2 = inv * inv;
+#pragma unroll
+    for (int i2 = 0; i2 < NS; ++i2) {
+        muab[i2] += Phab[i2] * g + Pha[i2] * gb + Phb[i2] * ga + Ph[i2] * gab;
+        const double ki = Ph[i2] * inv, kai = Pha[i2] * inv - ki * inv * Sa, kbi = Phb[i2] * inv - ki * inv * Sb;
+        const double kabi = Phab[i2] * inv - (Pha[i2] * Sb + Phb[i2] * Sa) * inv2 - ki * inv * Sab + 2.0 * ki * inv2 * Sa * Sb;
+#pragma unroll
+        for (int k = i2; k < NS; ++k) Cab[i2][k] -= kabi * Ph[k] + kai * Phb[k] + kbi * Pha[k] + ki * Phab[k];
+    }
+}
+
+// one lane's walk over the merged observations for the pair (pa, pb) of kind PAIR (pa, pb: the bands of its alphas)
+template <int P, int NOFF, int PAIR>
+__device__ __forceinline__ double gpcc_mkh_walk(const GpccMarkovHessArgs &a, const double *pts, double *shead, const double *stau,
+                                                const double *salpha, int *scur, double rho, int pa, int pb, int nthr, int tid)
+{
+    constexpr int NS = P + NOFF;
+    constexpr bool DIAG = PAIR == GPCC_MKH_AA_DIAG || PAIR == GPCC_MKH_RR;
+    constexpr bool RHO = PAIR == GPCC_MKH_AR || PAIR == GPCC_MKH_RR;      // some tangent of A is formed
+    constexpr int KA = PAIR == GPCC_MKH_RR ? GPCC_MKG_RHO : GPCC_MKG_ALPHA, KB = RHO ? GPCC_MKG_RHO : GPCC_MKG_ALPHA;
+    const int L = a.L, N = a.N;
+    double lam, lam2, Q[P][P], mu[NS], C[NS][NS];
+    gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
+    // Pinf_rho, Pinf_rhorho = (lambda / rho)^2 d2Pinf/dlambda2 - (2 / rho) Pinf_rho, and a zero block
+    double Qr[P][P], Qrr[P][P], Z[P][P];
+    const double dlam = -lam / rho, c2 = dlam * dlam, c1 = -2.0 / rho;
+    gpcc_mkg_dstationary<P>(lam, lam2, RHO ? dlam : 0.0, Qr);
+    gpcc_mkh_d2stationary<P>(lam2, PAIR == GPCC_MKH_RR ? c2 : 0.0, Qrr);
+#pragma unroll
+    for (int i = 0; i < P; ++i)
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            Qrr[i][j] += (PAIR == GPCC_MKH_RR) ? c1 * Qr[i][j] : 0.0;
+            Z[i][j] = 0.0;
+        }
+    // the tangents: zero, except the prior state's by rho (Pinf_rho) and by (rho, rho) (Pinf_rhorho).  A diagonal pair has one tangent
+    // (mub, Cb name it again; its own storage is then never touched)
+    double mua[NS], Ca[NS][NS], mub_[NS], Cb_[NS][NS], muab[NS], Cab[NS][NS];
+    double(&mub)[NS] = DIAG ? mua : mub_;
+    double(&Cb)[NS][NS] = DIAG ? Ca : Cb_;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        mua[i] = muab[i] = 0.0;
+        if constexpr (!DIAG) mub[i] = 0.0;
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const bool xx = i < P && j < P;
+            Ca[i][j] = (KA == GPCC_MKG_RHO && xx) ? Qr[i < P ? i : 0][j < P ? j : 0] : 0.0;
+            if constexpr (!DIAG) Cb[i][j] = (KB == GPCC_MKG_RHO && xx) ? Qr[i < P ? i : 0][j < P ? j : 0] : 0.0;
+            Cab[i][j] = (PAIR == GPCC_MKH_RR && xx) ? Qrr[i < P ? i : 0][j < P ? j : 0] : 0.0;
+        }
+    }
+
+    double ll = 0.0, dll = 0.0, hll = 0.0, sprev = 0.0;
+    for (int j = 0; j < N; ++j) {
+        // merge: the band whose head has the smallest shifted time, the lowest band on ties (gpcc_markov_eval's order)
+        int b = -1;
+        double s = 0.0;
+        for (int l = 0; l < L; ++l) {
+            const double sl = shead[l * nthr + tid];
+            const bool live = scur[l * nthr + tid] < a.off[l + 1];
+            const bool take = live && (b < 0 || sl < s);
+            b = take ? l : b;
+            s = take ? sl : s;
+        }
+        const int i = scur[b * nthr + tid];
+        const double r = pts[N + i], s2 = pts[2 * N + i], al = salpha[b * nthr + tid];
+        scur[b * nthr + tid] = i + 1;
+        if (i + 1 < a.off[b + 1]) shead[b * nthr + tid] = pts[i + 1] - stau[b * nthr + tid];
+        const double d = (j == 0) ? 0.0 : s - sprev;
+        sprev = s;
+
+        double A[P][P], Ar[P][P], Arr[P][P];
+        gpcc_mk_transition<P>(lam, lam2, d, A);
+        if constexpr (RHO) gpcc_mkg_dtransition_rate<P>(lam, lam2, d, dlam, Ar);
+        if constexpr (PAIR == GPCC_MKH_RR) {
+            gpcc_mkh_d2transition_rate<P>(lam, d, c2, Arr);
+#pragma unroll
+            for (int i2 = 0; i2 < P; ++i2)
+#pragma unroll
+                for (int k = 0; k < P; ++k) Arr[i2][k] += c1 * Ar[i2][k];
+        }
+        // the step: the second tangent from the state and the tangents before it, then the tangents, then the state
+        if constexpr (PAIR == GPCC_MKH_RR) {
+            gpcc_mkg_propagate<P, NOFF, GPCC_MKG_RHO>(A, Arr, true, Q, Qrr, mu, C, muab, Cab);
+            gpcc_mkh_cross<P, NOFF>(A, Ar, Q, Qr, C, mua, Ca, muab, Cab);
+        } else if constexpr (PAIR == GPCC_MKH_AR) {
+            gpcc_mkg_propagate<P, NOFF, GPCC_MKG_RHO>(A, Ar, true, Z, Z, mua, Ca, muab, Cab);
+        } else {
+            gpcc_mkg_propagate<P, NOFF, GPCC_MKG_ALPHA>(A, Z, false, Q, Z, mu, C, muab, Cab);
+        }
+        gpcc_mkg_propagate<P, NOFF, KA>(A, Ar, KA == GPCC_MKG_RHO, Q, Qr, mu, C, mua, Ca);
+        if constexpr (!DIAG) gpcc_mkg_propagate<P, NOFF, KB>(A, Ar, KB == GPCC_MKG_RHO, Q, Qr, mu, C, mub, Cb);
+        gpcc_mk_propagate<P, NOFF>(A, Q, mu, C);
+        // the update, in the same order
+        const bool ha = KA == GPCC_MKG_ALPHA && b == pa, hb = KB == GPCC_MKG_ALPHA && b == pb;
+        gpcc_mkh_update<P, NOFF>(b, al, ha, hb, r, s2, mu, C, mua, Ca, mub, Cb, muab, Cab, hll);
+        gpcc_mkg_update<P, NOFF, KA>(b, al, ha, r, s2, mu, C, mua, Ca, dll);
+        if constexpr (!DIAG) gpcc_mkg_update<P, NOFF, KB>(b, al, hb, r, s2, mu, C, mub, Cb, dll);
+        gpcc_mk_update<P, NOFF>(b, al, r, s2, mu, C, ll);
+    }
+    return hll;
+}
+
+template <int P, int NOFF>
+__global__ void __launch_bounds__(256) gpcc_markov_hess(const GpccMarkovHessArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double gpcc_mkh_lds[];
+    const int tid = threadIdx.x, nthr = blockDim.x, L = a.L, N = a.N;
+    double *shead = gpcc_mkh_lds + (a.stage ? 3L * N : 0);
+    double *stau = shead + L * nthr, *salpha = stau + L * nthr;
+    int *scur = (int *)(salpha + L * nthr);
+    if (a.stage)
+        for (int i = tid; i < 3 * N; i += nthr) gpcc_mkh_lds[i] = a.pts[i];
+    const double *pts = a.stage ? (const double *)gpcc_mkh_lds : a.pts;
+
+    const long row = (long)blockIdx.x * nthr + tid;
+    const bool valid = row < a.M;
+    const long m_ = valid ? row : a.M - 1;
+    const double rho = a.rho[m_];
+    gpcc_mk_load_row(a, m_, rho, stau, salpha, nthr, tid);
+    __syncthreads();
+    for (int l = 0; l < L; ++l) {
+        scur[l * nthr + tid] = a.off[l];
+        shead[l * nthr + tid] = pts[a.off[l]] - stau[l * nthr + tid];
+    }
+
+    // the pair of this workgroup (uniform): slot -> (pa, pb), pa <= pb, rows of the upper triangle one after the other
+    const int slot = blockIdx.y;
+    int pa = 0, rest = slot;
+    while (rest >= L + 1 - pa) {
+        rest -= L + 1 - pa;
+        ++pa;
+    }
+    const int pb = pa + rest;
+    double hll;
+    if (pa == L)
+        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_RR>(a, pts, shead, stau, salpha, scur, rho, -1, -1, nthr, tid);
+    else if (pb == L)
+        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AR>(a, pts, shead, stau, salpha, scur, rho, pa, -1, nthr, tid);
+    else if (pa == pb)
+        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AA_DIAG>(a, pts, shead, stau, salpha, scur, rho, pa, pa, nthr, tid);
+    else
+        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AA_OFF>(a, pts, shead, stau, salpha, scur, rho, pa, pb, nthr, tid);
+    if (valid) a.slot[(long)slot * a.M + row] = hll;
+}
+
+// ---- the instantiations that ship, per P (gpcc_markov_hess_inst.hip: one object per P).  One that the compiler cannot keep out of
+// scratch memory does not ship (tools/kernel_resources.py; the table is in DESIGN.md 4.18 and profiles/markov/kernel_resources_hess.log):
+// gpcc_loglik_hess_hyper_markov_batch returns GPCC_ERR_UNSUPPORTED for it and names the dense entry.  At present that is <3, 4> alone:
+// Matern-5/2 with four bands and marginalised offsets ----
+#define GPCC_MKH_EACH_P1(F) F(1, 0) F(1, 1) F(1, 2) F(1, 3) F(1, 4)
+#define GPCC_MKH_EACH_P2(F) F(2, 0) F(2, 1) F(2, 2) F(2, 3) F(2, 4)
+#define GPCC_MKH_EACH_P3(F) F(3, 0) F(3, 1) F(3, 2) F(3, 3)   /* <3, 4>: 512 registers and 28 bytes of scratch */
+
+static inline bool gpcc_markov_hess_shipped(int p, int noff)
+{
+#define GPCC_MKH_IS(PP, NN) \
+    if (p == PP && noff == NN) return true;
+    GPCC_MKH_EACH_P1(GPCC_MKH_IS) GPCC_MKH_EACH_P2(GPCC_MKH_IS) GPCC_MKH_EACH_P3(GPCC_MKH_IS)
+#undef GPCC_MKH_IS
+    return false;
+}
+
+// per P: the launch of gpcc_markov_hess<P, noff> on the grid (blocks, slots), and the LDS limit of its instantiations on the current device
+template <int P>
+hipError_t gpcc_markov_hess_launch_p(int noff, const GpccMarkovHessArgs &a, int blocks, int slots, int threads, size_t lds, hipStream_t s);
+template <int P>
+hipError_t gpcc_markov_hess_configure_p();
+template <> hipError_t gpcc_markov_hess_launch_p<1>(int, const GpccMarkovHessArgs &, int, int, int, size_t, hipStream_t);
+template <> hipError_t gpcc_markov_hess_launch_p<2>(int, const GpccMarkovHessArgs &, int, int, int, size_t, hipStream_t);
+template <> hipError_t gpcc_markov_hess_launch_p<3>(int, const GpccMarkovHessArgs &, int, int, int, size_t, hipStream_t);
+template <> hipError_t gpcc_markov_hess_configure_p<1>();
+template <> hipError_t gpcc_markov_hess_configure_p<2>();
+template <> hipError_t gpcc_markov_hess_configure_p<3>();
+// the finish kernel over the M rows
+hipError_t gpcc_markov_hess_finish_launch(const GpccMarkovHessArgs &a, hipStream_t s);
+
+static inline hipError_t gpcc_markov_hess_configure()
+{
+    hipError_t e = gpcc_markov_hess_configure_p<1>();
+    if (e == hipSuccess) e = gpcc_markov_hess_configure_p<2>();
+    if (e == hipSuccess) e = gpcc_markov_hess_configure_p<3>();
+    return e;
+}
+
+// gpcc_markov_hess<p, noff> on the grid (blocks, slots), then the finish kernel
+static inline hipError_t gpcc_markov_hess_launch(int p, int noff, const GpccMarkovHessArgs &a, int blocks, int slots, int threads, size_t lds,
+                                                 hipStream_t s)
+{
+    const hipError_t e = p == 1   ? gpcc_markov_hess_launch_p<1>(noff, a, blocks, slots, threads, lds, s)
+                         : p == 2 ? gpcc_markov_hess_launch_p<2>(noff, a, blocks, slots, threads, lds, s)
+                                  : gpcc_markov_hess_launch_p<3>(noff, a, blocks, slots, threads, lds, s);
+    return e != hipSuccess ? e : gpcc_markov_hess_finish_launch(a, s);
+}

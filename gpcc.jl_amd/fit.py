@@ -157,7 +157,7 @@ class GridFit:
 
 def gpcc_grid(tarray, yarray, stdarray, *, kernel, candidatedelays, iterations, seed=1, numberofrestarts=1,
               initialrandom=5, rhomin=0.1, rhomax=20.0, objective=None, device=0, marginalise_b=True, engine=None,
-              unpack=None, evidence=None, laplace_rounds=50, laplace_g_tol=1e-6, solver="dense"):
+              unpack=None, evidence=None, laplace_rounds=50, laplace_g_tol=1e-6, solver="dense", evidence_solver=None):
     """Fits the GPCC model for each row of candidatedelays (G, L): the README's
     `map(delay -> gpcc(...; delays = [0; delay])[1], candidatedelays)` as one lock-step batch.
 
@@ -169,11 +169,16 @@ def gpcc_grid(tarray, yarray, stdarray, *, kernel, candidatedelays, iterations, 
     solver "dense" (default): every optimiser round is a batch of dense Cholesky factorisations (loglik_batch).  solver "markov": the
     rounds evaluate the same likelihood in linear time (loglik_markov_batch: OU, matern32, matern52; option "fit_markov" of the native
     engine) -- the values agree with the dense ones to rounding, so the fit follows the same trajectory up to that; rbf, or more than 4
-    bands with marginalise_b, raise.  The evidence and every prediction stay dense.
+    bands with marginalise_b, raise.  Every prediction stays dense, and so does the evidence unless evidence_solver says otherwise.
 
     evidence "laplace": after the fit, the Laplace-marginalised evidence over alpha and rho at every delay, from the fitted
     (alpha, rho) (Objective.laplace_evidence with the native engine, laplace.laplace_evidence otherwise) -> GridFit.log_evidence,
-    .hyper_cov, .laplace_info, .laplace_rounds.  None (default): the profile likelihood only, as before."""
+    .hyper_cov, .laplace_info, .laplace_rounds.  None (default): the profile likelihood only, as before.  evidence_solver None
+    (default) or "dense": the Newton rounds of the evidence take the dense Hessian block whatever `solver` is; "markov": the block in
+    linear time (loglik_hess_hyper_markov_batch; the same kernels and limits as solver "markov")."""
+    if evidence_solver not in (None, "dense", "markov"):
+        raise ValueError("evidence_solver must be None, 'dense' or 'markov', got %r" % (evidence_solver,))
+    esolver = evidence_solver or "dense"
     if evidence not in (None, "laplace"):
         raise ValueError("evidence must be None or 'laplace', got %r" % (evidence,))
     if solver not in ("dense", "markov"):
@@ -211,7 +216,7 @@ def gpcc_grid(tarray, yarray, stdarray, *, kernel, candidatedelays, iterations, 
             finally:
                 obj.set_option("fit_markov", before)
             return _with_evidence(GridFit(ll, alpha, rho, f_calls, rounds, its.astype(np.int64)), obj, cand, engine, evidence,
-                                  rhomin, rhomax, laplace_rounds, laplace_g_tol)
+                                  rhomin, rhomax, laplace_rounds, laplace_g_tol, esolver)
 
         def negobj(pidx, X):
             if unpack is not None:
@@ -237,13 +242,13 @@ def gpcc_grid(tarray, yarray, stdarray, *, kernel, candidatedelays, iterations, 
                         (makepositive(xsel[:, :L]) + 1e-8, transformbetween(xsel[:, L], rhomin, rhomax)))
         return _with_evidence(GridFit(-fmin[np.arange(G), pick], a_sel, r_sel, nm.f_calls + P * initialrandom, nm.rounds + 1,
                                       nm.iterations_done.reshape(G, R)[np.arange(G), pick]), obj, cand, engine, evidence,
-                              rhomin, rhomax, laplace_rounds, laplace_g_tol)
+                              rhomin, rhomax, laplace_rounds, laplace_g_tol, esolver)
     finally:
         if own:
             obj.close()
 
 
-def _with_evidence(res, obj, cand, engine, evidence, rhomin, rhomax, max_rounds, g_tol):
+def _with_evidence(res, obj, cand, engine, evidence, rhomin, rhomax, max_rounds, g_tol, solver="dense"):
     if evidence is None:
         return res
     ok = np.all(np.isfinite(res.alpha), axis=1) & np.isfinite(res.rho) & np.all(res.alpha > 0, axis=1) & (res.rho > 0)
@@ -252,10 +257,10 @@ def _with_evidence(res, obj, cand, engine, evidence, rhomin, rhomax, max_rounds,
     r0 = np.where(ok, res.rho, np.sqrt(rhomin * rhomax))
     if engine == "native":
         _, _, _, logz, cov, info, rounds, _ = obj.laplace_evidence(cand, a0, r0, rhomin=rhomin, rhomax=rhomax, max_rounds=max_rounds,
-                                                                   g_tol=g_tol)
+                                                                   g_tol=g_tol, solver=solver)
     else:
         _, _, _, logz, cov, info, rounds = laplace.laplace_evidence(obj, cand, a0, r0, rhomin=rhomin, rhomax=rhomax,
-                                                                    max_rounds=max_rounds, g_tol=g_tol)
+                                                                    max_rounds=max_rounds, g_tol=g_tol, solver=solver)
     info = np.where(ok, info, laplace.BAD_START).astype(np.int32)
     res.log_evidence = np.where(ok, logz, np.nan)
     res.hyper_cov = np.where(ok[:, None, None], cov, np.nan).reshape(G, n, n)

@@ -240,10 +240,13 @@ class BatchedNewton:
                 np.array(self.info, dtype=np.int32), np.array(self.rounds, dtype=np.int32))
 
 
-def laplace_evidence(objective, delays, alpha0, rho0, rhomin=0.1, rhomax=20.0, max_rounds=50, g_tol=1e-6):
+def laplace_evidence(objective, delays, alpha0, rho0, rhomin=0.1, rhomax=20.0, max_rounds=50, g_tol=1e-6, solver="dense"):
     """The numpy mirror of gpcc_laplace_evidence over any objective with loglik_hess_hyper_batch(delays, alpha, rho) -> (loglik,
     grad, hess[M, L+1, L+1], fisher, info) (Objective's, or a CPU witness) -> (loglik, alpha, rho, log_evidence, cov, info, rounds).
-    Same steps as the C++ polish (bitwise, given bitwise the same objective values)."""
+    Same steps as the C++ polish (bitwise, given bitwise the same objective values).  solver "markov": the rounds call the objective's
+    loglik_hess_hyper_markov_batch -> (loglik, grad, hess, info), the block in linear time (Objective's, or markov.MarkovObjective's)."""
+    if solver not in ("dense", "markov"):
+        raise ValueError("solver must be 'dense' or 'markov', got %r" % (solver,))
     delays = np.ascontiguousarray(np.atleast_2d(delays), dtype=np.float64)
     G, L = delays.shape
     alpha0 = np.asarray(alpha0, dtype=np.float64).reshape(G, L)
@@ -258,7 +261,10 @@ def laplace_evidence(objective, delays, alpha0, rho0, rhomin=0.1, rhomax=20.0, m
     def fb(pidx, U):
         a = np.array([[math.exp(float(U[i, l])) for l in range(L)] for i in range(len(pidx))]).reshape(len(pidx), L)
         r = np.array([math.exp(float(U[i, L])) for i in range(len(pidx))])
-        ll, grad, hess, _, info = objective.loglik_hess_hyper_batch(delays[pidx], a, r)
+        if solver == "markov":
+            ll, grad, hess, info = objective.loglik_hess_hyper_markov_batch(delays[pidx], a, r)
+        else:
+            ll, grad, hess, _, info = objective.loglik_hess_hyper_batch(delays[pidx], a, r)
         if first[0]:
             start_info[pidx] = info
             first[0] = False

@@ -287,6 +287,183 @@ def loglik_grad_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marg
             np.array([o[2] for o in out], dtype=np.int32))
 
 
+# ----------------------------------------------------------------------------------------------------------------------------------
+# The (alpha, rho) block of the Hessian in linear time (csrc/gpcc_markov_hess.hip.h), the same algorithm in numpy: the
+# filter's second-order forward sensitivities.  For a pair (a, b) of theta = (alpha_1..alpha_L, rho) four sets are carried: (m, P),
+# (m_a, P_a), (m_b, P_b), (m_ab, P_ab).  For alpha and rho the merged order is fixed and no kink is crossed: no tie convention.
+#
+#   rho rho   d/drho = (-lambda / rho) d/dlambda, so d2/drho2 = (lambda / rho)^2 d2/dlambda2 + (2 lambda / rho^2) d/dlambda:
+#             transition_d2rho and stationary_d2rho in closed form per kernel; the prior's second tangent is Pinf_ab
+#   step      the product rule on _grad_pass's step: m_ab <- A_ab m + A_a m_b + A_b m_a + A m_ab, the nine terms of A D A' (D = P_xx - Pinf)
+#             plus Pinf_ab, P_xb as m.  A_a = 0 for an alpha; A_ab and Pinf_ab are nonzero for (rho, rho) only
+#   update    h_a = e_1 on the observations of band a, h_ab = 0:
+#             (Ph)_a = P_a h + P h_a,  (Ph)_ab = P_ab h + P_a h_b + P_b h_a,  S_a = h_a'Ph + h'(Ph)_a,
+#             S_ab = h_a'(Ph)_b + h_b'(Ph)_a + h'(Ph)_ab,  eps_a = -h_a'm - h'm_a,  eps_ab = -h_a'm_b - h_b'm_a - h'm_ab,
+#             g = eps / S, g_a = (eps_a - g S_a) / S, g_ab = (eps_ab - g_a S_b - g_b S_a - g S_ab) / S:
+#             l_ab -= (S_ab / S - S_a S_b / S^2 + 2 eps_a eps_b / S + 2 g eps_ab - 2 g (eps_a S_b + eps_b S_a) / S - g^2 S_ab
+#                      + 2 g^2 S_a S_b / S) / 2,
+#             then the second tangents of m += Ph g and P -= k Ph', k = Ph / S
+#
+# The Fisher information is not offered in linear time (its expectation needs another recursion), nor the rows of tau (OU's
+# second-order tie convention is not a mean of two filter orders): both stay with the dense Hessian.
+# ----------------------------------------------------------------------------------------------------------------------------------
+def transition_d2lambda(kernel, d, rho):
+    """d2A(d)/dlambda2, in closed form per kernel."""
+    name = _name(kernel)
+    lam = rate(name, rho)
+    x = lam * d
+    e = math.exp(-x)
+    if name == "OU":
+        return np.array([[e * d * d]])
+    if name == "matern32":
+        return e * np.array([[d * d * (x - 1.0), d ** 3], [d * (4.0 * x - 2.0 - x * x), d * d * (3.0 - x)]])
+    return e * np.array([[d * d * x * (0.5 * x - 1.0), d ** 3 * (x - 1.0), 0.5 * d ** 4],
+                         [0.5 * d * x * (6.0 * x - 6.0 - x * x), d * d * (5.0 * x - 3.0 - x * x), 0.5 * d ** 3 * (4.0 - x)],
+                         [x * (0.5 * x ** 3 - 5.0 * x * x + 12.0 * x - 6.0), d * (x ** 3 - 9.0 * x * x + 18.0 * x - 6.0),
+                          d * d * (0.5 * x * x - 4.0 * x + 6.0)]])
+
+
+def stationary_d2lambda(kernel, rho):
+    """d2Pinf/dlambda2: Matern-3/2 d2(lambda^2) = 2; Matern-5/2 d2 kappa = 2/3, d2(lambda^4) = 12 lambda^2."""
+    name = _name(kernel)
+    lam = rate(name, rho)
+    if name == "OU":
+        return np.array([[0.0]])
+    if name == "matern32":
+        return np.array([[0.0, 0.0], [0.0, 2.0]])
+    return np.array([[0.0, 0.0, -2.0 / 3.0], [0.0, 2.0 / 3.0, 0.0], [-2.0 / 3.0, 0.0, 12.0 * lam * lam]])
+
+
+def transition_d2rho(kernel, d, rho, _chain=True):
+    """d2A(d)/drho2 = (lambda / rho)^2 d2A/dlambda2 + (2 lambda / rho^2) dA/dlambda  (_chain=False, tests only: the second term dropped)."""
+    lam = rate(kernel, rho)
+    out = (lam / rho) ** 2 * transition_d2lambda(kernel, d, rho)
+    if _chain:      # transition_drho = (-lambda / rho) dA/dlambda
+        out = out - (2.0 / rho) * transition_drho(kernel, d, rho)
+    return out
+
+
+def stationary_d2rho(kernel, rho, _chain=True):
+    """d2Pinf/drho2, by the same chain rule."""
+    lam = rate(kernel, rho)
+    out = (lam / rho) ** 2 * stationary_d2lambda(kernel, rho)
+    if _chain:
+        out = out - (2.0 / rho) * stationary_drho(kernel, rho)
+    return out
+
+
+def _hess_pass(name, train, alpha, rho, p, n, vb, a, b, slip=None):
+    """d2 loglik / d theta_a d theta_b (a, b in 0..L: alpha_1..alpha_L, rho) by the second-order tangent recursion over the training
+    observations in merge_order()'s order.  slip: loglik_hess_hyper()'s."""
+    L = len(alpha)
+    ev = sorted(train, key=lambda e: (e[0], e[1], e[2]))
+    ra, rb = a == L, b == L
+    chain = slip != "chain_rho"
+    zero = np.zeros((p, p))
+    Pinf = stationary(name, rho)
+    Qa = stationary_drho(name, rho) if ra else zero
+    Qb = stationary_drho(name, rho) if rb else zero
+    Qab = stationary_d2rho(name, rho, chain) if (ra and rb and slip != "no_d2pinf") else zero
+    P = _prior(name, rho, p, n, vb)
+    Pa, Pb, Pab = np.zeros((n, n)), np.zeros((n, n)), np.zeros((n, n))
+    Pa[:p, :p], Pb[:p, :p], Pab[:p, :p] = Qa, Qb, Qab
+    m, ma, mb, mab = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
+    hll, sprev = 0.0, None
+    for (s, band, _, r, s2) in ev:
+        d = 0.0 if sprev is None else s - sprev
+        sprev = s
+        A = transition(name, d, rho)
+        Aa = transition_drho(name, d, rho) if ra else zero
+        Ab = transition_drho(name, d, rho) if rb else zero
+        Aab = transition_d2rho(name, d, rho, chain) if (ra and rb and slip != "no_d2a") else zero
+        X = slice(0, p)
+        D, Da, Db, Dab = P[X, X] - Pinf, Pa[X, X] - Qa, Pb[X, X] - Qb, Pab[X, X] - Qab
+        cross = zero if slip == "no_cross" else Aa @ D @ Ab.T + Ab @ D @ Aa.T
+        mab[X] = Aab @ m[X] + Aa @ mb[X] + Ab @ ma[X] + A @ mab[X]
+        Pab[X, X] = (Aab @ D @ A.T + A @ D @ Aab.T + cross + Aa @ Db @ A.T + A @ Db @ Aa.T + Ab @ Da @ A.T + A @ Da @ Ab.T
+                     + A @ Dab @ A.T + Qab)
+        Pab[X, p:] = Aab @ P[X, p:] + Aa @ Pb[X, p:] + Ab @ Pa[X, p:] + A @ Pab[X, p:]
+        Pab[p:, X] = Pab[X, p:].T
+        ma[X], mb[X] = Aa @ m[X] + A @ ma[X], Ab @ m[X] + A @ mb[X]
+        Pa[X, X] = Aa @ D @ A.T + A @ Da @ A.T + A @ D @ Aa.T + Qa
+        Pb[X, X] = Ab @ D @ A.T + A @ Db @ A.T + A @ D @ Ab.T + Qb
+        Pa[X, p:], Pb[X, p:] = Aa @ P[X, p:] + A @ Pa[X, p:], Ab @ P[X, p:] + A @ Pb[X, p:]
+        Pa[p:, X], Pb[p:, X] = Pa[X, p:].T, Pb[X, p:].T
+        m[X] = A @ m[X]
+        P[X, X] = A @ D @ A.T + Pinf
+        P[X, p:] = A @ P[X, p:]
+        P[p:, X] = P[X, p:].T
+
+        h, ha, hb = np.zeros(n), np.zeros(n), np.zeros(n)
+        h[0] = alpha[band]
+        if n > p:
+            h[p + band] = 1.0
+        ha[0], hb[0] = float(band == a), float(band == b)
+        Ph = P @ h
+        Pha, Phb = Pa @ h + P @ ha, Pb @ h + P @ hb
+        Phab = Pab @ h + Pa @ hb + Pb @ ha
+        S = h @ Ph + s2
+        if not (S > 0.0 and math.isfinite(S)):
+            return math.nan
+        Sa, Sb = ha @ Ph + h @ Pha, hb @ Ph + h @ Phb
+        Sab = h @ Phab
+        eps = r - h @ m
+        ea, eb = -(ha @ m) - h @ ma, -(hb @ m) - h @ mb
+        eab = -(h @ mab)
+        if slip != "no_hahb":
+            Sab += ha @ Phb + hb @ Pha
+            eab -= ha @ mb + hb @ ma
+        inv = 1.0 / S
+        g = eps * inv
+        ga, gb = (ea - g * Sa) * inv, (eb - g * Sb) * inv
+        gab = (eab - ga * Sb - gb * Sa - g * Sab) * inv
+        hll -= 0.5 * (Sab * inv - Sa * Sb * inv * inv + 2.0 * ea * eb * inv + 2.0 * g * eab - 2.0 * g * inv * (ea * Sb + eb * Sa)
+                      - g * g * Sab + 2.0 * g * g * Sa * Sb * inv)
+        k = Ph * inv
+        ka, kb = Pha * inv - k * (inv * Sa), Phb * inv - k * (inv * Sb)
+        kab = Phab * inv - Pha * (inv * inv * Sb) - Phb * (inv * inv * Sa) - k * (inv * Sab) + k * (2.0 * inv * inv * Sa * Sb)
+        mab = mab + Phab * g + Pha * gb + Phb * ga + Ph * gab
+        ma, mb = ma + Pha * g + Ph * ga, mb + Phb * g + Ph * gb
+        m = m + Ph * g
+        Pab = Pab - np.outer(kab, Ph) - np.outer(ka, Phb) - np.outer(kb, Pha) - np.outer(k, Phab)
+        Pa = Pa - np.outer(ka, Ph) - np.outer(k, Pha)
+        Pb = Pb - np.outer(kb, Ph) - np.outer(k, Phb)
+        P = P - np.outer(k, Ph)
+        P, Pa, Pb, Pab = (0.5 * (Z + Z.T) for Z in (P, Pa, Pb, Pab))
+    return hll
+
+
+def loglik_hess_hyper(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True, _slip=None):
+    """(loglik, grad[2L+1], hess[L+1, L+1], info) of one (tau, alpha, rho): loglik()'s value and info, loglik_grad()'s full row and the
+    Hessian over [alpha_1..alpha_L, rho] by the filter's second-order forward sensitivities, each pair computed once and mirrored:
+    Objective.loglik_hess_hyper_markov_batch's row.  grad and hess are NaN where info != 0.
+    _slip (tests only) injects one mistake: "no_d2a" (A_rhorho left out), "no_d2pinf" (Pinf_rhorho left out of the prior and the step),
+    "no_cross" (the A_a D A_b' cross terms of the step left out), "no_hahb" (the h_a, h_b terms of S_ab and eps_ab left out), "chain_rho"
+    (the (2 lambda / rho^2) d/dlambda term of the rho rho chain rule dropped)."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b,
+                                                                       codes_first=True)
+    ll, grad, info = loglik_grad(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b)
+    hess = np.full((L + 1, L + 1), math.nan)
+    if info:
+        return ll, grad, hess, info
+    for a in range(L + 1):
+        for b in range(a, L + 1):
+            hess[a, b] = hess[b, a] = _hess_pass(name, train, alpha, rho, p, n, vb, a, b, slip=_slip)
+    return ll, grad, hess, 0
+
+
+def loglik_hess_hyper_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True):
+    """loglik_hess_hyper over M rows -> (loglik[M], grad[M, 2L+1], hess[M, L+1, L+1], info[M]): Objective.loglik_hess_hyper_markov_batch's
+    shape."""
+    L = len(tarray)
+    delays = np.asarray(delays, np.float64).reshape(-1, L)
+    alpha = np.asarray(alpha, np.float64).reshape(-1, L)
+    rho = np.asarray(rho, np.float64).reshape(-1)
+    out = [loglik_hess_hyper(kernel, tarray, yarray, stdarray, delays[i], alpha[i], rho[i], marginalise_b) for i in range(len(rho))]
+    return (np.array([o[0] for o in out]), np.array([o[1] for o in out]).reshape(-1, 2 * L + 1),
+            np.array([o[2] for o in out]).reshape(-1, L + 1, L + 1), np.array([o[3] for o in out], dtype=np.int32))
+
+
 JITTER = 1e-8   # added to every predictive variance and to sigma*^2 of a held-out point (gpcc_predict_batch's constant)
 
 
@@ -537,6 +714,16 @@ class MarkovObjective:
         return loglik_batch(self.kernel, *self.data, delays, alpha, rho, self.marginalise_b)
 
     loglik_batch = loglik_markov_batch
+
+    def loglik_hess_hyper_markov_batch(self, delays, alpha, rho):
+        """Objective.loglik_hess_hyper_markov_batch's result: (loglik[M], grad[M, 2L+1], hess[M, L+1, L+1], info[M])."""
+        return loglik_hess_hyper_batch(self.kernel, *self.data, delays, alpha, rho, self.marginalise_b)
+
+    def loglik_hess_hyper_batch(self, delays, alpha, rho):
+        """The same under the dense entry's name and shape (no Fisher information in linear time: None), so that
+        laplace.laplace_evidence runs over this objective."""
+        ll, grad, hess, info = self.loglik_hess_hyper_markov_batch(delays, alpha, rho)
+        return ll, grad, hess, None, info
 
     def _rows(self, delays, alpha, rho):
         delays = np.asarray(delays, np.float64).reshape(-1, self.L)

@@ -215,7 +215,8 @@ int gpcc_loglik_batch(gpcc_handle_t handle, int M, const double *delays, const d
  * this entry never allocates it.  Option "fit_markov" (default 0): 1 makes every optimiser round of gpcc_grid_loglik one call of this
  * entry instead of a gpcc_loglik_batch (GPCC_ERR_UNSUPPORTED where this entry is); read-only "markov_count": evaluations so far.
  * Predictions, held-out scores and the offsets' posterior in linear time: the three entries below; the gradient in linear time:
- * gpcc_loglik_grad_markov_batch after them; the Hessian stays dense.
+ * gpcc_loglik_grad_markov_batch after them; the (alpha, rho) block of the Hessian is gpcc_loglik_hess_hyper_markov_batch, the full
+ * Hessian (the rows of tau) and the Fisher information stay dense.
  * Blocking. */
 int gpcc_loglik_markov_batch(gpcc_handle_t handle, int M, const double *delays, const double *alpha, const double *rho,
                              double *loglik, int *info);
@@ -321,6 +322,25 @@ int gpcc_loglik_hess_batch(gpcc_handle_t h, int M, const double *delays, const d
  * same rules: fp64 only (an fp32 handle on its fp64 twin), a multi-device handle on device_ids[0].  Blocking. */
 int gpcc_loglik_hess_hyper_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                  double *loglik, double *grad, double *hess, double *fisher, int *info);
+
+/* The same block in LINEAR TIME for the Markov kernels (OU, Matern-3/2, Matern-5/2), exactly: the Kalman filter of
+ * gpcc_loglik_markov_batch carrying its second-order forward sensitivities.  loglik[M], info[M] and grad (M rows of
+ * P = 2L+1) come from gpcc_loglik_grad_markov_batch's launches inside the same call and are bitwise that entry's; hess (may be NULL:
+ * then the call is that entry): M row-major (L+1) x (L+1) blocks over [alpha_1..alpha_L, rho], every pair computed once and written to
+ * both halves (bitwise symmetric), NaN where info != 0.  One lane per (row, pair), no atomics: a row's bits depend on the row alone (any
+ * M, any row order).  Refusals, argument checks and info codes are gpcc_loglik_markov_batch's (rbf, and marginalise_b with L > 4:
+ * GPCC_ERR_UNSUPPORTED before any device work).  An instantiation <states of the process, offset states> that the compiler cannot keep
+ * out of scratch memory does not ship and is refused the same way, the message naming gpcc_loglik_hess_hyper_batch: at present <3, 4>
+ * alone, Matern-5/2 with marginalise_b and L = 4 (it takes all 512 registers of a lane and 28 bytes more); everything else that
+ * gpcc_loglik_markov_batch takes ships (DESIGN.md 4.18 has the table).
+ * NOT offered in linear time: the Fisher information (its expectation needs another recursion) and the rows of tau -- the full
+ * Hessian -- (OU's second-order tie convention is not a mean of two filter orders); both stay with the dense entries above.
+ * Memory: gpcc_loglik_grad_markov_batch's, plus 8 M bytes per pair ((L+1)(L+2)/2 of them) and 8 M (L+1)^2 bytes; none of the N^2
+ * workspace.  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Blocking.
+ * Option "laplace_markov" (default 0; refused where "fit_markov" is): gpcc_laplace_evidence's Newton rounds call this entry instead of
+ * gpcc_loglik_hess_hyper_batch. */
+int gpcc_loglik_hess_hyper_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                        double *loglik, double *grad, double *hess, int *info);
 
 /* Same with DEVICE pointers, enqueued behind `stream` (a hipStream_t, NULL = default stream) and
  * joined back into it: asynchronous, outputs valid once `stream` has drained. */

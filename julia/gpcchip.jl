@@ -193,6 +193,26 @@ function loglik_hess_hyper_batch(h::Handle, delays::Matrix{Float64}, alpha::Matr
     return ll, grad, hess, fisher, info
 end
 
+"the [α_1..α_L, ρ] block of the Hessian in LINEAR time (gpcc_loglik_hess_hyper_markov_batch: the Kalman filter's second-order forward
+sensitivities, one lane per (row, pair of parameters), DESIGN 4.18; OU, matern32, matern52): (ll[M], grad (2L+1)×M, hess
+(L+1)×(L+1)×M, info[M]).  ll, grad and info are bitwise loglik_grad_markov's; hess is bitwise symmetric, NaN where info != 0.  No Fisher
+information and no rows of τ in linear time (loglik_hess_hyper_batch / loglik_hess_batch have them).  Errors for rbf, for marginalise_b
+with more than 4 bands, and for matern52 with marginalise_b and 4 bands (that instantiation needs scratch memory and does not ship).
+The option "laplace_markov" (ccall((:gpcc_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Clong), h.ptr, "laplace_markov", 1)) makes
+laplace_evidence's Newton rounds call this entry."
+function loglik_hess_hyper_markov(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
+    M, P, n = length(rho), 2h.L + 1, h.L + 1
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    grad = Matrix{Float64}(undef, P, M)
+    hess = Array{Float64}(undef, n, n, M)                                 # symmetric: row- or column-major alike
+    rc = ccall((:gpcc_loglik_hess_hyper_markov_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, ll, grad, hess, info)
+    rc == 0 || error("gpcc_loglik_hess_hyper_markov_batch: " * lasterror(h.ptr))
+    return ll, grad, hess, info
+end
+
 "Laplace-marginalised evidence over α and ρ per delay (columns of delays, L×G), from (alpha0 L×G, rho0[G]), usually the fit's
 output.  Prior log-uniform in α and in ρ on [rhomin, rhomax]: log_evidence is log Z(τ) up to ONE additive constant shared by all
 delays -- use it only through getprobabilities (or differences).  -> (ll[G], alpha L×G, rho[G], log_evidence[G], cov (L+1)×(L+1)×G
