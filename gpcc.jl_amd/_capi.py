@@ -80,6 +80,9 @@ SIGNATURES = {
                                                            c_double_p, c_double_p, c_int_p]),
     "gpcc_sample_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p,
                                          c_double_p, ctypes.c_int, ctypes.c_ulonglong, c_double_p, c_int_p, c_double_p, c_double_p, c_int_p]),
+    "gpcc_sample_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_double_p,
+                                                c_double_p, c_double_p, ctypes.c_int, ctypes.c_ulonglong, c_double_p, c_int_p, c_double_p,
+                                                c_int_p]),
     "gpcc_posterior_offsets": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, ctypes.c_double, c_double_p,
                                               c_double_p, c_int_p]),
     "gpcc_mvnormal_logpdf": (ctypes.c_int, [ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p,

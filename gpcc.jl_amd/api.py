@@ -717,6 +717,45 @@ class Objective:
         out = (draws, rows, ll, info)
         return out + (zeta,) if return_noise else out
 
+    def sample_markov_batch(self, delays, alpha, rho, ttest, S, seed, weights=None, sigmatest=None):
+        """sample_batch in linear time (gpcc_sample_markov_batch: Matheron's rule over the Kalman filter, O(N + T) per draw; OU, matern32
+        and matern52 only) -> (draws, draw_row, loglik[M], info[M]) in sample_batch's layouts and modes.  The draws have sample_batch's
+        distribution N(mu_pred, Sigma_pred + JITTER I + diag(sigmatest^2)) exactly but are other draws (another linear map of other
+        normals: 4 (N + T + 1) per draw, so there is no return_noise); draw_row is sample_batch's for the same seed and weights.  loglik
+        and info of a drawn row are bitwise predict_markov_batch's; a failed row's draws are NaN (no test block to repair, hence no
+        fallback); rows without a draw: loglik NaN, info GPCC_SAMPLE_NOT_DRAWN = -14.  seed: Philox4x64-10 key (gpcc_amd.rng.point_normals
+        and gpcc_amd.markov.sample mirror it).  rbf, or marginalise_b with more than 4 bands: GpccError (unsupported)."""
+        if len(ttest) != self.L:
+            raise AssertionError("length(ttest) == L")
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        Nt, tt = _flatten(ttest)
+        T = int(Nt.sum())
+        S = int(S)
+        st = None
+        if sigmatest is not None:
+            if len(sigmatest) != self.L:
+                raise AssertionError("length(sigmatest) == L")
+            Ns, st = _flatten(sigmatest)
+            if not np.array_equal(Nt, Ns):
+                raise ValueError("band lengths differ between ttest and sigmatest")
+        w = None
+        if weights is not None:
+            w = _d(np.asarray(weights, dtype=np.float64).ravel())
+            if w.shape != (M,):
+                raise ValueError("weights must have M = %d entries" % M)
+        D = S if w is not None else M * S
+        draws = np.empty((max(D, 0), T), dtype=np.float64)
+        rows = np.empty(max(D, 0), dtype=np.int32)
+        ll = np.empty(M, dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        try:
+            self._chk(_capi.load().gpcc_sample_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _ip(Nt), _dp(tt),
+                                                            _dp(st) if st is not None else None, _dp(w) if w is not None else None, S,
+                                                            int(seed) & 0xFFFFFFFFFFFFFFFF, _dp(draws), _ip(rows), _dp(ll), _ip(info)))
+        except GpccError as e:
+            _raise_reference_error(e)
+        return draws, rows, ll, info
+
     def posterior_offsets(self, delays, alpha, rho):
         """(mu_postb, Sigma_postb) of marginaliseb.jl:248-252 (the reference wraps them in MvNormal)."""
         delays, alpha = _d(delays), _d(alpha)

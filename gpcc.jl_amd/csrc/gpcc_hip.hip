@@ -9,6 +9,7 @@
 #include "gpcc_sample.hip.h"
 #include "gpcc_markov.hip.h"
 #include "gpcc_markov_pred.hip.h"
+#include "gpcc_markov_sample.hip.h"
 #include "gpcc_markov_grad.hip.h"
 #include "gpcc_markov_hess.hip.h"
 #include "gpcc_chain_args.h"
@@ -248,6 +249,14 @@ struct gpcc_handle_s {
     int mkh_configured = 0;
     int laplace_markov = 0;              // option "laplace_markov": gpcc_laplace_evidence's rounds are gpcc_loglik_hess_hyper_markov_batch calls
     int markov_chunk_rows = 0;           // option "markov_chunk_rows": rows per chunk of gpcc_predict_markov_batch (0: by the scratch budget)
+    // linear-time draws (gpcc_sample_markov_batch): grown on demand -- the combine's weights of a chunk of rows (mksw_cap doubles), the
+    // scratch of a chunk of draws, r~ [N][lanes] and the accumulator [T][lanes] (mksrt_cap, mksacc_cap doubles), the points' indices,
+    // the lanes' lists and the rows' words (mksi_cap ints); the draws themselves share d_sdraw with gpcc_sample_batch
+    double *d_mksw = nullptr, *d_mksrt = nullptr, *d_mksacc = nullptr;
+    int *d_mksi = nullptr;
+    long mksw_cap = 0, mksrt_cap = 0, mksacc_cap = 0, mksi_cap = 0;
+    int mks_configured = 0;
+    int markov_sample_chunk_draws = 0;   // option "markov_sample_chunk_draws": draws per chunk of gpcc_sample_markov_batch (0: by the scratch budget)
     double *d_sep = nullptr, *d_seps = nullptr;     // separable factors of the points, the distance scale (GpccCtx::sep, ::seps)
     int *d_sepflag = nullptr;                       // per-tile-row flags (GpccCtx::sepflag)
     int fp32_refine = 1;                            // option "fp32_refine": 0 = no refinement of the quadratic forms
@@ -550,6 +559,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_mk);
     hipFree(h->d_mkt); hipFree(h->d_mktap); hipFree(h->d_mkmu); hipFree(h->d_mkvar); hipFree(h->d_mkmix); hipFree(h->d_mkw);
     hipFree(h->d_mkaux); hipFree(h->d_mkti); hipFree(h->d_mkauxi);
+    hipFree(h->d_mksw); hipFree(h->d_mksrt); hipFree(h->d_mksacc); hipFree(h->d_mksi);
     hipFree(h->d_mkgs); hipFree(h->d_mkgr);
     hipFree(h->d_mkhs); hipFree(h->d_mkhb);
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
@@ -661,6 +671,9 @@ extern "C" int gpcc_set_option(gpcc_handle_t h, const char *key, long v)
     } else if (!strcmp(key, "markov_chunk_rows")) {
         if (v < 0) return fail(h, GPCC_ERR_ARGUMENT, "markov_chunk_rows must be >= 0");
         h->markov_chunk_rows = (int)v;
+    } else if (!strcmp(key, "markov_sample_chunk_draws")) {
+        if (v < 0) return fail(h, GPCC_ERR_ARGUMENT, "markov_sample_chunk_draws must be >= 0");
+        h->markov_sample_chunk_draws = (int)v;
     } else if (!strcmp(key, "fit_device_unpack")) {
         h->fit_device_unpack = v != 0;
     } else if (!strcmp(key, "fit_threads")) {
@@ -745,6 +758,8 @@ extern "C" long gpcc_get_option(gpcc_handle_t h, const char *key)
     if (!strcmp(key, "markov_count")) return h->markov_count;
     if (!strcmp(key, "markov_chunk_rows")) return h->markov_chunk_rows;
     if (!strcmp(key, "markov_tap_bytes")) return 8 * h->mktap_cap;
+    if (!strcmp(key, "markov_sample_chunk_draws")) return h->markov_sample_chunk_draws;
+    if (!strcmp(key, "markov_sample_bytes")) return 8 * (h->mksw_cap + h->mksrt_cap + h->mksacc_cap) + 4 * h->mksi_cap;
     if (!strcmp(key, "fit_threads")) return h->fit_threads;
     if (!strcmp(key, "small_n_max")) return GPCC_SMALLW_MAXN;
     if (!strcmp(key, "small_wide_max")) return h->small_wide_max;
@@ -2947,6 +2962,191 @@ extern "C" int gpcc_sample_batch(gpcc_handle_t h, int M, const double *delays, c
     HIPCHK(h, hipMemcpyAsync(cinfo.data(), h->d_oinfo, sizeof(int) * Mc, hipMemcpyDeviceToHost, ms));
     HIPCHK(h, hipMemcpyAsync(draws, h->d_sdraw, sizeof(double) * D * T, hipMemcpyDeviceToHost, ms));
     if (zeta) HIPCHK(h, hipMemcpyAsync(zeta, h->d_szeta, sizeof(double) * D * T, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipStreamSynchronize(ms));
+    for (int k = 0; k < Mc; ++k) {
+        loglik[rows[k]] = cll[k];
+        info[rows[k]] = cinfo[k];
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Joint posterior draws in linear time (gpcc_sample_markov_batch; kernels: gpcc_markov_sample.hip.h): Matheron's rule
+// over the filter of 4.15 / 4.16.  The host picks the rows of mixture draws and compacts the drawn rows exactly as gpcc_sample_batch
+// does; every chunk of drawn rows then runs gpcc_markov_taps unchanged (its loglik and info are gpcc_predict_markov_batch's bits), the
+// combine that also leaves the weights, and, per chunk of draws, one lane per (row, draw) and the finish.  Nothing of the N^2 workspace.
+// ------------------------------------------------------------------------------------------
+extern "C" int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                        const int *Ntest, const double *ttest, const double *sigmatest, const double *weights, int S,
+                                        unsigned long long seed, double *draws, int *draw_row, double *loglik, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (S < 1) return fail(h, GPCC_ERR_ARGUMENT, "S=%d < 1", S);
+    if (!delays || !alpha || !rho || !Ntest || !ttest || !draws || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    if (weights && !draw_row) return fail(h, GPCC_ERR_ARGUMENT, "weights given: draw_row is required");
+    int rc = markov_refusals(h, "gpcc_sample_markov_batch", "gpcc_sample_batch");
+    if (rc) return rc;
+    if (route_fp64(h, "linear-time draws", rc, [&](gpcc_handle_t o) {
+            return gpcc_sample_markov_batch(o, M, delays, alpha, rho, Ntest, ttest, sigmatest, weights, S, seed, draws, draw_row, loglik,
+                                            info);
+        }))
+        return rc;
+    long T = 0;
+    rc = count_test_points(h, Ntest, T);
+    if (rc) return rc;
+    const long D = weights ? (long)S : (long)M * S;   // output rows
+    if (D > 0x7fffffffL) return fail(h, GPCC_ERR_ARGUMENT, "M S = %ld draws: at most 2^31 - 1 per call", D);
+    std::vector<double> cw;   // the cumulative weights c_m
+    rc = mixture_weights(h, M, weights, true, cw);
+    if (rc || M == 0) return rc;
+    // gpcc_sample_batch's choice of rows: the row of every draw, the drawn rows (compact, in row order), each one's ascending draws
+    std::vector<int> ndraw(M, 0);
+    if (weights) {
+        for (long s = 0; s < D; ++s) {
+            const int m = gpccrng::pick_row(seed, (uint64_t)s, cw.data(), weights, M);
+            draw_row[s] = m;
+            ++ndraw[m];
+        }
+    } else {
+        for (int m = 0; m < M; ++m) ndraw[m] = S;
+        if (draw_row)
+            for (long o = 0; o < D; ++o) draw_row[o] = (int)(o / S);
+    }
+    std::vector<int> rows, cidx(M, -1);
+    for (int m = 0; m < M; ++m) {
+        if (ndraw[m] > 0) { cidx[m] = (int)rows.size(); rows.push_back(m); }
+        else { loglik[m] = __builtin_nan(""); info[m] = GPCC_SAMPLE_NOT_DRAWN; }
+    }
+    const int Mc = (int)rows.size();
+    const long N = h->N, L = h->L;
+    std::vector<int> doff(Mc + 1, 0);
+    for (int k = 0; k < Mc; ++k) doff[k + 1] = doff[k] + ndraw[rows[k]];
+    // the lanes, sorted by row: ints[0 .. N) the training points' indices (filled below), then per lane its compact row, its draw index s
+    // and its row of `draws`, then per compact row the row word of its counters
+    std::vector<int> ints((size_t)N + 3 * D + Mc);
+    int *lrow = ints.data() + N, *ls = lrow + D, *lout = ls + D, *word = lout + D;
+    if (weights) {
+        std::vector<int> fill(doff.begin(), doff.end() - 1);
+        for (long s = 0; s < D; ++s) {
+            const int k = cidx[draw_row[s]], o = fill[k]++;
+            lrow[o] = k; ls[o] = (int)s; lout[o] = (int)s;
+        }
+    } else {
+        for (long o = 0; o < D; ++o) { lrow[o] = (int)(o / S); ls[o] = (int)(o % S); lout[o] = (int)o; }
+    }
+    for (int k = 0; k < Mc; ++k) word[k] = rows[k];
+    std::vector<double> cpar((size_t)Mc * (2 * L + 1));
+    for (int k = 0; k < Mc; ++k) {
+        const int m = rows[k];
+        for (long l = 0; l < L; ++l) {
+            cpar[(size_t)k * L + l] = delays[(size_t)m * L + l];
+            cpar[(size_t)Mc * L + (size_t)k * L + l] = alpha[(size_t)m * L + l];
+        }
+        cpar[(size_t)2 * Mc * L + k] = rho[m];
+    }
+    GPCC_ON_DEVICE(h, h->device);
+    const MarkovDims d = markov_dims(h);
+    const long ns = d.p + d.noff, nrec = ns + ns * (ns + 1) / 2;
+    // rows per chunk: gpcc_predict_markov_batch's rule; draws per chunk: what the scratch budget holds in whole waves, at least one
+    long chunk = GPCC_MKP_TAP_BYTES / (2 * T * nrec * 8);
+    if (chunk >= 64) chunk -= chunk % 64;
+    if (h->markov_chunk_rows > 0) chunk = h->markov_chunk_rows;
+    if (chunk < 1) chunk = 1;
+    if (chunk > Mc) chunk = Mc;
+    long dchunk = GPCC_MKS_SCRATCH_BYTES / (8 * (N + T));
+    dchunk -= dchunk % 64;
+    if (dchunk < 64) dchunk = 64;
+    if (h->markov_sample_chunk_draws > 0) dchunk = h->markov_sample_chunk_draws;
+    if (dchunk > D) dchunk = D;
+    const long lstride = (dchunk + 255) / 256 * 256;   // every lane of the widest launch owns a column of the scratch
+    std::vector<int> order, band;
+    int toff[GPCC_MARKOV_MAXL + 1];
+    markov_sort_tests(h, Ntest, ttest, T, order, band, toff);
+    std::vector<double> tt(2 * T);   // the sorted times, then sqrt(JITTER + sigma*^2)
+    std::vector<int> ti(2 * T);
+    for (long j = 0; j < T; ++j) {
+        const double sg = sigmatest ? sigmatest[order[j]] : 0.0;
+        tt[j] = ttest[order[j]];
+        tt[T + j] = sqrt(GPCC_MKP_JITTER + sg * sg);
+        ti[j] = band[j];
+        ti[T + j] = order[j];
+    }
+    double *dd, *da, *dr;
+    rc = markov_begin(h, Mc, cpar.data(), cpar.data() + (size_t)Mc * L, cpar.data() + (size_t)2 * Mc * L, dd, da, dr, [&] {
+        int g = grow_buf(h, &h->d_mkt, &h->mkt_cap, 2 * T);
+        if (!g) g = grow_buf(h, &h->d_mkti, &h->mkti_cap, 2 * T);
+        if (!g) g = grow_buf(h, &h->d_mktap, &h->mktap_cap, 2 * T * nrec * chunk);
+        if (!g) g = grow_buf(h, &h->d_mkmu, &h->mkmu_cap, chunk * T);
+        if (!g) g = grow_buf(h, &h->d_mkvar, &h->mkvar_cap, chunk * T);
+        if (!g) g = grow_buf(h, &h->d_mksw, &h->mksw_cap, 2 * T * ns * chunk);
+        if (!g) g = grow_buf(h, &h->d_mksrt, &h->mksrt_cap, N * lstride);
+        if (!g) g = grow_buf(h, &h->d_mksacc, &h->mksacc_cap, T * lstride);
+        if (!g) g = grow_buf(h, &h->d_mksi, &h->mksi_cap, (long)ints.size());
+        if (!g) g = grow_buf(h, &h->d_sdraw, &h->sdraw_cap, D * T);
+        return g;
+    });
+    if (rc) return rc;
+    for (long i = 0; i < N; ++i) ints[i] = h->mk_perm[i];
+    hipStream_t ms = h->main_stream;
+    HIPCHK(h, hipMemcpyAsync(h->d_mkt, tt.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_mkti, ti.data(), sizeof(int) * 2 * T, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_mksi, ints.data(), sizeof(int) * ints.size(), hipMemcpyHostToDevice, ms));
+    if (!h->mks_configured) {
+        HIPCHK(h, gpcc_mks_configure());
+        h->mks_configured = 1;
+    }
+    GpccMarkovPredArgs a;
+    rc = markov_pred_common(h, Mc, dd, da, dr, toff, T, a);
+    if (rc) return rc;
+    a.tap = h->d_mktap;
+    GpccMarkovCombineWArgs cwa;
+    GpccMarkovCombineArgs &c = cwa.c;
+    cwa.w = h->d_mksw;
+    c.tap = h->d_mktap; c.alpha = da; c.rho = dr; c.tband = h->d_mkti; c.tperm = h->d_mkti + T; c.mu = h->d_mkmu; c.var = h->d_mkvar;
+    c.L = h->L; c.T = (int)T;
+    for (int l = 0; l < GPCC_MARKOV_MAXL; ++l) c.mean_b[l] = l < h->L ? h->mean_b[l] : 0.0;
+    for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) c.sigma_b[l] = a.sigma_b[l];
+    GpccMarkovDrawArgs g;
+    g.pts = h->d_mk; g.perm = h->d_mksi; g.tpts = h->d_mkt; g.tperm = h->d_mkti + T;
+    g.delays = dd; g.alpha = da; g.rho = dr; g.w = h->d_mksw;
+    g.lane_row = h->d_mksi + N; g.lane_s = g.lane_row + D; g.row_word = g.lane_row + 3 * D;
+    g.rt = h->d_mksrt; g.acc = h->d_mksacc;
+    g.seed = seed; g.mixture = weights ? 1 : 0;
+    g.L = h->L; g.N = (int)N; g.T = (int)T; g.stage = 0; g.lstride = (int)lstride;
+    for (int l = 0; l <= GPCC_MARKOV_MAXL; ++l) { g.off[l] = a.off[l]; g.toff[l] = a.toff[l]; }
+    for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) g.sigma_b[l] = a.sigma_b[l];
+    GpccMarkovDrawFinishArgs f;
+    f.mu = h->d_mkmu; f.acc = h->d_mksacc; f.lane_row = g.lane_row; f.lane_out = g.lane_row + 2 * D; f.draws = h->d_sdraw;
+    f.T = (int)T; f.lstride = (int)lstride;
+    for (long row0 = 0; row0 < Mc; row0 += chunk) {
+        const int nrows = (int)(Mc - row0 < chunk ? Mc - row0 : chunk);
+        a.row0 = c.row0 = g.row0 = f.row0 = (int)row0;
+        a.rows = c.rows = nrows;
+        a.mstride = c.mstride = g.mstride = (int)chunk;
+        rc = markov_pred_launch(h, GPCC_MKP_TAP, a, 2);
+        if (rc) return rc;
+        hipError_t e = gpcc_mks_launch_combine(d.p, d.noff, cwa, ms);
+        if (e == hipSuccess) e = gpcc_mkp_launch_rowinfo(h->d_mkmu, h->d_mkvar, h->d_oinfo, h->N, (int)T, (int)row0, nrows, ms);
+        if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "linear-time draws, combine: %s", hipGetErrorString(e));
+        for (long lane0 = doff[row0]; lane0 < doff[row0 + nrows]; lane0 += dchunk) {
+            const long left = doff[row0 + nrows] - lane0;
+            g.lane0 = f.lane0 = (int)lane0;
+            g.lanes = f.lanes = (int)(left < dchunk ? left : dchunk);
+            size_t lds;
+            const int threads = markov_launch_shape(h, ((long)g.lanes + 63) / 64,
+                                                    [&](int thr, bool st) { return gpcc_mks_lds_bytes(g.N, g.T, g.L, thr, st); }, g.stage, lds);
+            if (lds > GPCC_MARKOV_LDS_MAX) return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_markov_draw: %zu bytes of LDS", lds);
+            e = gpcc_mks_launch_draw(d.p, d.noff, g, (g.lanes + threads - 1) / threads, threads, lds, ms);
+            if (e == hipSuccess) e = gpcc_mks_launch_finish(f, ms);
+            if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "linear-time draws: %s", hipGetErrorString(e));
+        }
+    }
+    std::vector<double> cll(Mc);
+    std::vector<int> cinfo(Mc);
+    HIPCHK(h, hipMemcpyAsync(cll.data(), h->d_out, sizeof(double) * Mc, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipMemcpyAsync(cinfo.data(), h->d_oinfo, sizeof(int) * Mc, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipMemcpyAsync(draws, h->d_sdraw, sizeof(double) * D * T, hipMemcpyDeviceToHost, ms));
     HIPCHK(h, hipStreamSynchronize(ms));
     for (int k = 0; k < Mc; ++k) {
         loglik[rows[k]] = cll[k];

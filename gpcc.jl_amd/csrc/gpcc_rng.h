@@ -7,6 +7,7 @@
 //              z = sqrt(-2 log u1) (cos, sin)(2 pi u2), u1 = ((x0 >> 11) + 1) 2^-53 in (0, 1], u2 = (x1 >> 11) 2^-53 in [0, 1)
 //   row choice draw s of the mixture: u = (x0 >> 11) 2^-53 of counter (s, 0, 2^64 - 1, 1); the first m with u c_{M-1} < c_m and
 //              w_m > 0, c_m = sum_{k <= m} w_k summed in row order
+//   points     the linear-time draws: block e of draw s of row m from counter (e, s, m, 2), normal4_stream
 // gpcc_amd/rng.py is the numpy mirror (tests/test_sample_cpu.py checks this header against it, and it against numpy's Philox).
 #pragma once
 #include <cmath>
@@ -58,6 +59,23 @@ GPCC_RNG_HD inline void normal4(uint64_t seed, uint64_t blk, uint64_t s, uint64_
 #pragma clang fp contract(off)
     const double TWO_PI = 6.283185307179586476925286766559;
     const u64x4 x = philox4x64(blk, s, m, 0, seed, 0);
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const double u1 = uniform53_open0(x.v[2 * p]), u2 = uniform53(x.v[2 * p + 1]);
+        const double r = sqrt(-2.0 * log(u1)), th = TWO_PI * u2;
+        z[2 * p] = r * cos(th);
+        z[2 * p + 1] = r * sin(th);
+    }
+}
+
+// the same four normals from counter (blk, s, m, stream): stream 0 is normal4's, 1 the row picks', 2 the point blocks of the linear-time
+// draws (gpcc_sample_markov_batch, DESIGN.md 4.19: blk indexes a point -- training points in gpcc_create's order, then the test points
+// in the caller's order, then one block for the offsets)
+GPCC_RNG_HD inline void normal4_stream(uint64_t seed, uint64_t blk, uint64_t s, uint64_t m, uint64_t stream, double z[4])
+{
+#pragma clang fp contract(off)
+    const double TWO_PI = 6.283185307179586476925286766559;
+    const u64x4 x = philox4x64(blk, s, m, stream, seed, 0);
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         const double u1 = uniform53_open0(x.v[2 * p]), u2 = uniform53(x.v[2 * p + 1]);

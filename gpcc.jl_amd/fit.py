@@ -275,6 +275,11 @@ def _sample_bands(L, ttest):
     return [np.asarray(ttest, dtype=np.float64).ravel()] * L
 
 
+def _check_sample_solver(solver):
+    if solver not in (None, "dense", "markov"):
+        raise ValueError("sample: solver must be None, 'dense' or 'markov', got %r" % (solver,))
+
+
 def _split_bands(draws, bands):
     off = np.concatenate([[0], np.cumsum([len(b) for b in bands])]).astype(int)
     return [draws[:, off[l]:off[l + 1]] for l in range(len(bands))]
@@ -289,7 +294,7 @@ class Predictor:
     solver "dense" (default): every form factorises the N x N matrix.  solver "markov" (OU, matern32, matern52): the per-band form and
     the three-argument form run in linear time (Objective.predict_markov_batch / heldout_loglik_markov_batch, one row; a test point
     whose combine or predictive variance fails raises PosDefException, there being no test block for nearestposdef to repair); the
-    JOINT form (Sigma_pred is T x T) and sample() stay dense."""
+    JOINT form (Sigma_pred is T x T) stays dense, and so does sample() unless it is called with solver="markov"."""
 
     def __init__(self, objective, delays, alpha, rho, solver="dense"):
         if solver not in ("dense", "markov"):
@@ -334,12 +339,22 @@ class Predictor:
         return ([mu[l * n:(l + 1) * n] for l in range(L)],
                 [np.sqrt(np.maximum(d[l * n:(l + 1) * n], 1e-6)) for l in range(L)])      # :301-303
 
-    def sample(self, ttest, S, seed, sigmatest=None):
+    def sample(self, ttest, S, seed, sigmatest=None, solver=None):
         """S joint draws of the light curves at ttest (Predictor's forms: a list of L arrays or one array for every band) -> per-band
         arrays (S, Ntest_l): mu_pred + chol(Sigma_pred + diag(sigmatest^2)) zeta, the latent curve without sigmatest (Sigma_pred holds
-        JITTER), a replicated observation with it (Objective.sample_batch, one row)."""
+        JITTER), a replicated observation with it (Objective.sample_batch, one row).  solver None (default) or "dense": those dense
+        draws, whatever the predictor's own solver.  solver "markov" (OU, matern32, matern52): draws of the same distribution in linear
+        time (Objective.sample_markov_batch; other normals, so other draws); a failed filter or combine raises
+        PosDefException."""
+        _check_sample_solver(solver)
         bands = _sample_bands(self.obj.L, ttest)
         st = None if sigmatest is None else _sample_bands(self.obj.L, sigmatest)
+        if solver == "markov":
+            draws, _, _, info = self.obj.sample_markov_batch(self.delays[None, :], self.alpha[None, :], [self.rho], bands, S, seed,
+                                                             sigmatest=st)
+            if info[0] > 0:
+                raise PosDefException(int(info[0]))
+            return _split_bands(draws, bands)
         draws, _, _, info = self.obj.sample_batch(self.delays[None, :], self.alpha[None, :], [self.rho], bands, S, seed, sigmatest=st)
         if 0 < info[0] <= self.obj.N:
             raise PosDefException(int(info[0]))
@@ -359,7 +374,7 @@ class DelayAveragedPredictor:
     held-out density is well defined too: loglik(ttest, ytest, sigmatest) = log sum_g p_g N(ytest; mu_g, Sigma_g)
     (Objective.heldout_loglik_batch).
     solver "markov" (OU, matern32, matern52): __call__ and loglik run in linear time (Objective.predict_markov_batch /
-    heldout_loglik_markov_batch); sample() stays dense."""
+    heldout_loglik_markov_batch); sample() stays dense unless it is called with solver="markov"."""
 
     def __init__(self, objective, delays, alpha, rho, weights, solver="dense"):
         if solver not in ("dense", "markov"):
@@ -395,12 +410,19 @@ class DelayAveragedPredictor:
             return self.obj.heldout_loglik_markov_batch(self.delays, self.alpha, self.rho, ttest, ytest, sigmatest, weights=self.weights)[3]
         return self.obj.heldout_loglik_batch(self.delays, self.alpha, self.rho, ttest, ytest, sigmatest, weights=self.weights)[3]
 
-    def sample(self, ttest, S, seed, sigmatest=None):
+    def sample(self, ttest, S, seed, sigmatest=None, solver=None):
         """S joint draws of the delay-averaged light curves -> (per-band arrays (S, Ntest_l), row[S]): draw s comes from the row
         row[s], picked with probability weights[row] / sum(weights), so (self.delays[row[s]], draws[.][s]) are joint (tau, f*)
-        samples.  ttest and sigmatest take Predictor's forms; without sigmatest the latent curves, with it replicated observations."""
+        samples.  ttest and sigmatest take Predictor's forms; without sigmatest the latent curves, with it replicated observations.
+        solver None (default) or "dense": Objective.sample_batch whatever the predictor's own solver; "markov": the same mixture drawn in
+        linear time (Objective.sample_markov_batch; the same rows for the same seed and weights, other normals)."""
+        _check_sample_solver(solver)
         bands = _sample_bands(self.obj.L, ttest)
         st = None if sigmatest is None else _sample_bands(self.obj.L, sigmatest)
+        if solver == "markov":
+            draws, rows, _, _ = self.obj.sample_markov_batch(self.delays, self.alpha, self.rho, bands, S, seed, weights=self.weights,
+                                                             sigmatest=st)
+            return _split_bands(draws, bands), rows
         draws, rows, _, _ = self.obj.sample_batch(self.delays, self.alpha, self.rho, bands, S, seed, weights=self.weights, sigmatest=st)
         return _split_bands(draws, bands), rows
 

@@ -586,32 +586,30 @@ def _spd_inverse(A):
     return Li.T @ Li
 
 
-def predict(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, marginalise_b=True, _slip=None):
-    """(mu[T], var[T], loglik, info) of one (tau, alpha, rho) at the test times ttest (a list of L arrays, any order; T = their total,
-    flattened in band order): predictTest's per-band mean and variance (JITTER included) by two filters and a combine, and the training
-    log-likelihood.  info: loglik()'s codes for the training filter (mu and var NaN then), else N + j for the first test point j
-    (1-based, flattened order) whose combine meets a pivot that is not positive and finite (mu and var NaN), else 0.
-    _slip (tests only): "no_flip" (D left out on the backward side), "tie_both" (a training point that ties with a test point used on
-    both sides), "no_prior" (-P0^-1 dropped), "no_jitter"."""
-    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b)
+def _test_list(L, ttest, delays):
+    """The test points for _pass [(s*, band, index in the caller's flattened order, 0, 0)] and their bands."""
     tests, band_of = [], []
     for l in range(L):
         for v in np.asarray(ttest[l], np.float64).reshape(-1):
             tests.append((v - delays[l], l, len(tests), 0.0, 0.0))
             band_of.append(l)
+    return tests, band_of
+
+
+def _smooth(name, train, tests, band_of, alpha, rho, p, n, vb, slip=None):
+    """Two filters over `train` and the combine at the test points -> (h'm_s[T], h'P_s h[T], loglik, info): predict()'s mean without the
+    band mean and variance without JITTER.  Linear in the residuals of `train`; its covariances do not depend on them."""
     T, N = len(tests), len(train)
     nan = np.full(T, math.nan)
-    if code:
-        return nan, nan.copy(), math.nan, code
     ll, info, _, _, fw, _ = _pass(name, train, tests, alpha, rho, p, n, vb)
     if info:
         return nan, nan.copy(), math.nan, info
-    _, _, _, _, bw, _ = _pass(name, train, tests, alpha, rho, p, n, vb, reverse=True, ties_first=(_slip == "tie_both"))
+    _, _, _, _, bw, _ = _pass(name, train, tests, alpha, rho, p, n, vb, reverse=True, ties_first=(slip == "tie_both"))
     P0 = _prior(name, rho, p, n, vb)
     sc = 1.0 / np.sqrt(np.diag(P0))
     I0 = np.linalg.inv(sc[:, None] * P0 * sc[None, :])
     D = np.ones(n)
-    if p >= 2 and _slip != "no_flip":
+    if p >= 2 and slip != "no_flip":
         D[1] = -1.0
     mu, var = np.empty(T), np.empty(T)
     for j in range(T):
@@ -622,7 +620,7 @@ def predict(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, margina
         Ib = _spd_inverse(sc[:, None] * Pb * sc[None, :])
         Ps = None
         if If is not None and Ib is not None:
-            Ps = _spd_inverse(If + Ib - (0.0 if _slip == "no_prior" else I0))
+            Ps = _spd_inverse(If + Ib - (0.0 if slip == "no_prior" else I0))
         if Ps is None:
             return nan, nan.copy(), ll, N + j + 1
         ms = Ps @ (If @ (sc * mf) + Ib @ (sc * mb))
@@ -631,9 +629,27 @@ def predict(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, margina
         if n > p:
             h[p + band_of[j]] = 1.0
         h = h / sc
-        mu[j] = h @ ms + means[band_of[j]]
-        var[j] = h @ Ps @ h + (0.0 if _slip == "no_jitter" else JITTER)
+        mu[j] = h @ ms
+        var[j] = h @ Ps @ h
     return mu, var, ll, 0
+
+
+def predict(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, marginalise_b=True, _slip=None):
+    """(mu[T], var[T], loglik, info) of one (tau, alpha, rho) at the test times ttest (a list of L arrays, any order; T = their total,
+    flattened in band order): predictTest's per-band mean and variance (JITTER included) by two filters and a combine, and the training
+    log-likelihood.  info: loglik()'s codes for the training filter (mu and var NaN then), else N + j for the first test point j
+    (1-based, flattened order) whose combine meets a pivot that is not positive and finite (mu and var NaN), else 0.
+    _slip (tests only): "no_flip" (D left out on the backward side), "tie_both" (a training point that ties with a test point used on
+    both sides), "no_prior" (-P0^-1 dropped), "no_jitter"."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b)
+    tests, band_of = _test_list(L, ttest, delays)
+    if code:
+        nan = np.full(len(tests), math.nan)
+        return nan, nan.copy(), math.nan, code
+    mu, var, ll, info = _smooth(name, train, tests, band_of, alpha, rho, p, n, vb, _slip)
+    if info:
+        return mu, var, ll, info
+    return mu + means[band_of], var + (0.0 if _slip == "no_jitter" else JITTER), ll, 0
 
 
 def heldout(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, ytest, sigmatest, marginalise_b=True, _slip=None):
@@ -670,6 +686,198 @@ def posterior_offsets(kernel, tarray, yarray, stdarray, delays, alpha, rho):
     if info:
         return np.full(L, math.nan), np.full((L, L), math.nan), math.nan, info
     return m[p:] + means, P[p:, p:].copy(), ll, 0
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Joint posterior draws in linear time (csrc/gpcc_markov_sample.hip.h), the same algorithm in numpy: Matheron's rule.
+#
+#   prior     the training and test points merged in ascending shifted time (training first on ties); the state x~ is simulated along
+#             them: x~ = C(inf) xi at the first point, then x~ <- A(d) x~ + C xi, C C' = Q(d) = Pinf - A Pinf A' (_sim_factor: the
+#             triangular factor of Q scaled by diag(Pinf)^-1/2 and evaluated without cancellation, process_noise_scaled; d = 0
+#             gives Q = 0 and tied points share one state); offsets b~_l = sqrt(Sigma_b_l) xi.  Synthetic residual r~_i = alpha x~_1(s_i) + b~ + sigma_i xi,
+#             prior value g~_j = alpha x~_1(s*_j) + b~
+#   correct   c = _smooth() of r~ in place of r (no band mean): linear in r~
+#   draw      f*_j = mu_j + g~_j - c_j + sqrt(JITTER + sigma*_j^2) xi  ~  N(mu_pred, Sigma_pred + JITTER I + diag sigma*^2)
+#   normals   one block of four per POINT (rng.point_normals: training point e in gpcc_create's order, then test point j in the
+#             caller's order, then the offsets): the first p drive the state into that point, the fourth is its noise
+# ----------------------------------------------------------------------------------------------------------------------------------
+SIM_SERIES_MAX = 1.0      # csrc/gpcc_markov_sample.hip.h: GPCC_MKS_SERIES_MAX, the largest x = lambda d that takes the series
+SIM_SERIES_TERMS = 26     # ... GPCC_MKS_SERIES_TERMS: the tail after 26 terms at y = 2 is below 1e-20 of the sum
+
+
+def _lower_gammas(K, y):
+    """gamma(k + 1, y) = int_0^y v^k e^-v dv for k = 0 .. K without cancellation: the top one by the all-positive series
+    y^(K+1) e^-y sum_m y^m / ((K + 1) ... (K + 1 + m)), the others by gamma(k, y) = (gamma(k + 1, y) + y^k e^-y) / k, a sum of positives."""
+    e = math.exp(-y)
+    term = 1.0 / (K + 1)
+    acc = term
+    for m in range(1, SIM_SERIES_TERMS):
+        term = term * y / (K + 1 + m)
+        acc += term
+    g = [0.0] * (K + 1)
+    g[K] = y ** (K + 1) * e * acc
+    for k in range(K, 0, -1):
+        g[k - 1] = (g[k] + y ** k * e) / k
+    return g
+
+
+def process_noise_scaled(kernel, d, rho):
+    """Q(d) = Pinf - A(d) Pinf A(d)' in the units of diag(Pinf)^1/2.  Formed that way it is a cancellation from a unit diagonal: at a
+    small lag x = lambda d its diagonal is ~x^5, x^3, x (Matern-5/2) and drowns in the rounding of A.  For x <= SIM_SERIES_MAX it is
+    evaluated as what it is, Q = q int_0^d a(s) a(s)' ds with a(s) the last column of A(s) (the white noise enters the highest
+    derivative; q = 2 lambda, 4 lambda^3, 16 lambda^5 / 3): scaled and with u = lambda s,
+        OU           1 - e^-2x
+        Matern-3/2   4 int b b' e^-2u du,        b = (u, 1 - u)
+        Matern-5/2   16/3 int b b' e^-2u du,     b = (u^2 / 2, sqrt3 u (1 - u / 2), 1 - 2u + u^2 / 2)
+    over 0 .. x, every integral int u^k e^-2u du = gamma(k + 1, 2x) / 2^(k+1) from _lower_gammas: each entry to a few eps of
+    sqrt(Q_ii Q_jj).  Beyond, where Q is of the order of Pinf, by the difference."""
+    name = _name(kernel)
+    lam = rate(name, rho)
+    x = lam * d
+    if not x <= SIM_SERIES_MAX:
+        Pinf = stationary(name, rho)
+        A = transition(name, d, rho)
+        sc = 1.0 / np.sqrt(np.diag(Pinf))
+        Q = Pinf - A @ Pinf @ A.T
+        return sc[:, None] * (0.5 * (Q + Q.T)) * sc[None, :]
+    if name == "OU":
+        return np.array([[-math.expm1(-2.0 * x)]])
+    if name == "matern32":
+        j = [g / 2.0 ** (k + 1) for k, g in enumerate(_lower_gammas(2, 2.0 * x))]
+        q01 = 4.0 * (j[1] - j[2])
+        return np.array([[4.0 * j[2], q01], [q01, 4.0 * (j[0] - 2.0 * j[1] + j[2])]])
+    j = [g / 2.0 ** (k + 1) for k, g in enumerate(_lower_gammas(4, 2.0 * x))]
+    c, s3 = 16.0 / 3.0, math.sqrt(3.0)
+    q01 = c * (0.5 * s3) * (j[3] - 0.5 * j[4])
+    q02 = c * (0.5 * j[2] - j[3] + 0.25 * j[4])
+    q12 = c * s3 * (j[1] - 2.5 * j[2] + 1.5 * j[3] - 0.25 * j[4])
+    return np.array([[c * 0.25 * j[4], q01, q02], [q01, c * 3.0 * (j[2] - j[3] + 0.25 * j[4]), q12],
+                     [q02, q12, c * (j[0] - 4.0 * j[1] + 5.0 * j[2] - 2.0 * j[3] + 0.25 * j[4])]])
+
+
+def _sim_factor(kernel, d, rho, _by_difference=False):
+    """C with C C' = Q(d) (d None: Pinf, the stationary draw): the triangular factor of process_noise_scaled(), eliminated from the last
+    component (the largest pivot) to the first, so C is upper triangular; a pivot that is not > 0 gives a zero column.  d = 0 gives
+    C = 0: tied points share one state.  _by_difference (tests only): Q by the difference at every lag."""
+    name = _name(kernel)
+    Pinf = stationary(name, rho)
+    p = len(Pinf)
+    sc = 1.0 / np.sqrt(np.diag(Pinf))
+    if d is None:
+        Q = sc[:, None] * Pinf * sc[None, :]
+    elif _by_difference:
+        A = transition(name, d, rho)
+        Q = Pinf - A @ Pinf @ A.T
+        Q = sc[:, None] * (0.5 * (Q + Q.T)) * sc[None, :]
+    else:
+        Q = process_noise_scaled(name, d, rho)
+    G = np.zeros((p, p))
+    for j in range(p - 1, -1, -1):
+        dj = Q[j, j] - sum(G[j, k] * G[j, k] for k in range(j + 1, p))
+        if not (dj > 0.0 and math.isfinite(dj)):
+            continue
+        G[j, j] = math.sqrt(dj)
+        for i in range(j):
+            G[i, j] = (Q[i, j] - sum(G[i, k] * G[j, k] for k in range(j + 1, p))) / G[j, j]
+    return G / sc[:, None]
+
+
+def _draw_setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest, marginalise_b):
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b)
+    tests, band_of = _test_list(L, ttest, delays)
+    # sorted position i of band l -> the point's index in gpcc_create's flattened order
+    orig, off = {}, 0
+    for l in range(L):
+        perm = np.argsort(np.asarray(tarray[l], np.float64), kind="stable")
+        for i, q in enumerate(perm):
+            orig[(l, i)] = off + int(q)
+        off += len(perm)
+    if sigmatest is None:
+        st = np.zeros(len(tests))
+    else:
+        st = np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in sigmatest]) if len(tests) else np.zeros(0)
+    return name, L, delays, alpha, rho, code, vb, means, p, n, train, tests, band_of, orig, st
+
+
+def _prior_draw(name, alpha, rho, vb, p, n, train, tests, orig, st, xi, slip=None):
+    """One prior draw from the normals xi (N + T + 1, 4) -> (r~ per entry of `train`, g~[T], noise[T])."""
+    N, T = len(train), len(tests)
+    ev = [(s, 0, b, i, True) for (s, b, i, _, _) in train] + [(s, 1, b, i, False) for (s, b, i, _, _) in tests]
+    ev.sort(key=lambda e: e[:4])
+    bt = np.zeros(len(alpha))
+    if n > p and slip != "no_offset_draw":
+        bt = np.sqrt(vb) * xi[N + T, :len(alpha)]
+    s2 = {(b, i): v for (_, b, i, _, v) in train}
+    rt, gt, noise = {}, np.empty(T), np.empty(T)
+    x, sprev = None, None
+    for pos, (s, _, b, i, is_train) in enumerate(ev):
+        e = pos if slip == "merged_index" else (orig[(b, i)] if is_train else N + i)
+        z = xi[e]
+        if x is None:
+            x = _sim_factor(name, None, rho) @ z[:p]
+        else:
+            x = transition(name, s - sprev, rho) @ x + _sim_factor(name, s - sprev, rho, slip == "q_by_difference") @ z[:p]
+        sprev = s
+        f = alpha[b] * x[0] + bt[b]
+        if is_train:
+            rt[(b, i)] = f + (0.0 if slip == "no_obs_noise" else math.sqrt(s2[(b, i)]) * z[3])
+        else:
+            gt[i] = f
+            noise[i] = math.sqrt(JITTER + st[i] * st[i]) * z[3]
+    return rt, gt, noise
+
+
+def _normals_of(N, T, seed, s, m, normals):
+    if normals is not None:
+        xi = np.asarray(normals, np.float64)
+        if xi.shape != (N + T + 1, 4):
+            raise ValueError("normals must have shape (N + T + 1, 4) = (%d, 4)" % (N + T + 1))
+        return xi
+    from . import rng
+    return rng.point_normals(seed, N + T + 1, [s], [m])[0]
+
+
+def prior_draw(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest=None, marginalise_b=True, seed=0, s=0, m=0,
+               normals=None, _slip=None):
+    """Step 1 of a linear-time draw -> (r~[N] in gpcc_create's flattened order, g~[T], noise[T] in the caller's flattened order): a draw
+    of the prior at the training and test points, the synthetic residuals with their observation noise, and the JITTER / sigma* noise of
+    the test points.  The normals are draw s of row m of `seed` (rng.point_normals; m = rng.MIXROW for a mixture draw) or `normals`,
+    an array (N + T + 1, 4).  _slip (tests only): "no_obs_noise", "no_offset_draw", "merged_index", "q_by_difference" (_sim_factor's)."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train, tests, band_of, orig, st = _draw_setup(
+        kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest, marginalise_b)
+    if code:
+        raise ValueError("prior_draw: alpha and rho must be positive")
+    xi = _normals_of(len(train), len(tests), seed, s, m, normals)
+    rt, gt, noise = _prior_draw(name, alpha, rho, vb, p, n, train, tests, orig, st, xi, _slip)
+    out = np.empty(len(train))
+    for key, v in rt.items():
+        out[orig[key]] = v
+    return out, gt, noise
+
+
+def sample(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest=None, marginalise_b=True, seed=0, s=0, m=0,
+           normals=None, _slip=None):
+    """(draw[T], loglik, info) of one (tau, alpha, rho): one joint posterior draw at the test times, distributed as
+    N(mu_pred, Sigma_pred + JITTER I + diag sigmatest^2) -- gpcc_sample_batch's distribution -- by Matheron's rule: predict()'s mean
+    plus a prior draw minus the smoother of the prior draw's synthetic data, plus the test noise.  loglik and info are predict()'s; a
+    failed row's draw is NaN.  Normals as prior_draw.  _slip (tests only): predict()'s "no_flip", "tie_both", "no_prior" (in both the
+    mean and the correction), prior_draw's, and "plus" (the correction added)."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train, tests, band_of, orig, st = _draw_setup(
+        kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest, marginalise_b)
+    T = len(tests)
+    if code:
+        return np.full(T, math.nan), math.nan, code
+    pslip = _slip if _slip in ("no_flip", "tie_both", "no_prior") else None
+    mu, _, ll, info = _smooth(name, train, tests, band_of, alpha, rho, p, n, vb, pslip)
+    if info:
+        return np.full(T, math.nan), ll, info
+    xi = _normals_of(len(train), T, seed, s, m, normals)
+    rt, gt, noise = _prior_draw(name, alpha, rho, vb, p, n, train, tests, orig, st, xi, _slip)
+    synth = [(sv, b, i, rt[(b, i)], v) for (sv, b, i, _, v) in train]
+    c, _, _, cinfo = _smooth(name, synth, tests, band_of, alpha, rho, p, n, vb, pslip)
+    if cinfo:
+        return np.full(T, math.nan), ll, cinfo
+    return mu + means[band_of] + gt + (c if _slip == "plus" else -c) + noise, ll, 0
 
 
 def mix_moments(mu, var, weights):
@@ -756,6 +964,30 @@ class MarkovObjective:
         out = [posterior_offsets(self.kernel, *self.data, delays[i], alpha[i], rho[i]) for i in range(len(rho))]
         return (np.array([o[0] for o in out]), np.array([o[1] for o in out]), np.array([o[2] for o in out]),
                 np.array([o[3] for o in out], dtype=np.int32))
+
+    def sample_markov_batch(self, delays, alpha, rho, ttest, S, seed, weights=None, sigmatest=None):
+        """Objective.sample_markov_batch's result: (draws, draw_row, loglik[M], info[M])."""
+        from . import rng
+        delays, alpha, rho = self._rows(delays, alpha, rho)
+        M, S = len(rho), int(S)
+        if S < 1:
+            raise ValueError("S=%d < 1" % S)
+        T = sum(len(np.reshape(a, -1)) for a in ttest)
+        if weights is not None:
+            w = np.asarray(weights, np.float64).ravel()
+            if w.shape != (M,) or not np.all(np.isfinite(w)) or np.any(w < 0) or not np.sum(w) > 0:
+                raise ValueError("weights must be M finite non-negative values with a positive sum")
+            draw_row = rng.pick_rows(seed, S, w)
+            which = [(int(draw_row[s]), s, rng.MIXROW) for s in range(S)]
+        else:
+            draw_row = np.repeat(np.arange(M, dtype=np.int32), S)
+            which = [(m, s, m) for m in range(M) for s in range(S)]
+        draws = np.full((len(which), T), math.nan)
+        ll, info = np.full(M, math.nan), np.full(M, -14, dtype=np.int32)          # GPCC_SAMPLE_NOT_DRAWN
+        for o, (row, s, word) in enumerate(which):
+            draws[o], ll[row], info[row] = sample(self.kernel, *self.data, delays[row], alpha[row], rho[row], ttest, sigmatest,
+                                                  self.marginalise_b, seed=seed, s=s, m=word)
+        return draws, draw_row, ll, info
 
     def close(self):
         pass

@@ -48,16 +48,18 @@ def uniform53_open0(x):
     return ((np.asarray(x, dtype=np.uint64) >> np.uint64(11)) + np.uint64(1)).astype(np.float64) * 2.0 ** -53
 
 
-def normals(seed, T, draws, rows):
-    """The standard normals of draws (s, m) -> array (len(draws), T): element j of draw s of row m from counter (j // 4, s, m, 0)
-    (m = MIXROW for a mixture draw).  draws and rows are equal-length sequences (rows may be one scalar)."""
+STREAM_NORMALS, STREAM_PICK, STREAM_POINTS = 0, 1, 2     # word 3 of the counter: the dense normals, the row picks, the point blocks
+
+
+def _blocks(seed, nb, draws, rows, stream):
+    """The Box-Muller normals of the blocks 0 .. nb-1 of draws (s, m) in one stream -> array (len(draws), nb, 4)."""
     s = np.asarray(draws, dtype=np.uint64).ravel()
     m = np.broadcast_to(np.asarray(rows, dtype=np.uint64), s.shape)
-    nb = (int(T) + 3) // 4
     ctr = np.zeros((len(s), nb, 4), dtype=np.uint64)
     ctr[:, :, 0] = np.arange(nb, dtype=np.uint64)[None, :]
     ctr[:, :, 1] = s[:, None]
     ctr[:, :, 2] = m[:, None]
+    ctr[:, :, 3] = stream
     x = philox4x64(ctr, np.array([seed, 0], dtype=np.uint64))
     z = np.empty((len(s), nb, 4))
     for p in range(2):
@@ -65,7 +67,22 @@ def normals(seed, T, draws, rows):
         r, th = np.sqrt(-2.0 * np.log(u1)), (2.0 * np.pi) * u2
         z[..., 2 * p] = r * np.cos(th)
         z[..., 2 * p + 1] = r * np.sin(th)
-    return z.reshape(len(s), 4 * nb)[:, :int(T)]
+    return z
+
+
+def normals(seed, T, draws, rows):
+    """The standard normals of draws (s, m) -> array (len(draws), T): element j of draw s of row m from counter (j // 4, s, m, 0)
+    (m = MIXROW for a mixture draw).  draws and rows are equal-length sequences (rows may be one scalar)."""
+    nb = (int(T) + 3) // 4
+    z = _blocks(seed, nb, draws, rows, STREAM_NORMALS)
+    return z.reshape(len(z), 4 * nb)[:, :int(T)]
+
+
+def point_normals(seed, points, draws, rows):
+    """The normals of the linear-time draws (gpcc_sample_markov_batch) -> array (len(draws), points, 4): block e of
+    draw s of row m from counter (e, s, m, 2) -- the header's normal4_stream(.., 2).  e indexes a point (training points in
+    gpcc_create's order, then the test points in the caller's order, then one block for the offsets), never a merged position."""
+    return _blocks(seed, int(points), draws, rows, STREAM_POINTS)
 
 
 def pick_uniforms(seed, S):

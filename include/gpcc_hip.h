@@ -151,6 +151,8 @@ int gpcc_multi_stats(gpcc_handle_t handle, double *compute_ms, double *gather_ms
  *                                     same likelihood evaluated in linear time, so the fit's trajectory agrees to rounding, not bitwise)
  *   markov_chunk_rows        0        gpcc_predict_markov_batch: rows per chunk of its tap scratch; 0 = what fits 128 MiB (results do not
  *                                     depend on it)
+ *   markov_sample_chunk_draws 0       gpcc_sample_markov_batch: draws per chunk of its scratch; 0 = what fits 128 MiB in whole waves
+ *                                     (results do not depend on it)
  *   fp32_refine              1        fp32 handles: fp64 refinement of the quadratic forms
  *   fp32_guard               1        fp32 handles: evaluations whose pivot ratios exceed the limits are repeated in fp64
  *   fp32_assemble            1        fp32 handles: tiles inside one band pair are evaluated in fp32
@@ -442,6 +444,36 @@ int gpcc_sample_batch(gpcc_handle_t h, int M, const double *delays, const double
                       const double *ttest, const double *sigmatest, const double *weights, int S, unsigned long long seed,
                       double *draws, int *draw_row, double *zeta, double *loglik, int *info);
 
+/* gpcc_sample_batch's draws in LINEAR time for the Markov kernels (OU, Matern-3/2, Matern-5/2): the same arguments, modes and layouts
+ * (no zeta: a draw takes 4 (N + T + 1) normals), the same distribution N(mu_pred, Sigma_pred + JITTER I + diag(sigmatest^2)) exactly,
+ * other draws -- another linear map of other normals.  By Matheron's rule (kernels: csrc/gpcc_markov_sample.hip.h)
+ *   f*_j = mu_j + g~_j - c_j + sqrt(JITTER + sigmatest_j^2) xi,
+ * mu the mean of gpcc_predict_markov_batch, (r~, g~) a draw of the prior at the training and test points -- the state-space model of
+ * gpcc_loglik_markov_batch simulated along the points merged by shifted time (x~ <- A(d) x~ + C xi with C C' = Pinf - A Pinf A', C the
+ * triangular factor of that matrix scaled by diag(Pinf)^-1/2, eliminated from the last component; for lambda d <= 1 the matrix is
+ * evaluated without cancellation, by incomplete-gamma series; tied points share one state), r~ with the observation noise, the offsets drawn from their prior when they are marginalised -- and c the smoother of gpcc_predict_markov_batch applied to r~ in place of Y - bbar.
+ * O(N + T) work per draw; no T x T factor and nothing of the N^2 workspace.
+ * Random numbers (csrc/gpcc_rng.h): Philox4x64-10, key (seed, 0), counter (e, s, m, 2) -- word 3 = 2 keeps the stream apart from
+ * gpcc_sample_batch's normals (0) and the row picks (1) -- for draw s of row m (m = 2^64 - 1 in mixture mode).  e names a POINT, not
+ * its place in the merge: e < N is training point e in gpcc_create's flattened order, N <= e < N + T test point e - N in the caller's
+ * order, e = N + T the offsets.  Of the block's four Box-Muller normals the first p (the state dimension, 1 / 2 / 3) drive the
+ * simulated state into that point and the fourth is its observation (training) or JITTER / sigmatest (test) noise; the block N + T
+ * holds the L <= 4 offsets.  The mixture's rows are gpcc_sample_batch's: draw_row is identical for the same seed and weights.
+ * Rows without a draw get loglik NaN and info GPCC_SAMPLE_NOT_DRAWN.  loglik and info of a drawn row are bitwise
+ * gpcc_predict_markov_batch's for the same row and test set; a failed row's draws are NaN and change nothing else; the call returns 0.
+ * Refusals (rbf; marginalise_b with L > 4) and the fp64 / multi-device rules are gpcc_predict_markov_batch's.  A draw's bits depend on
+ * the seed, the row's parameters, s and m alone: not on M, S (the first S' draws of a call with S > S' are those of a call with S'),
+ * the chunking, the row order in mixture mode, fp32 vs fp64 handles.
+ * Memory, grown on demand (a handle that never calls this allocates none of it): gpcc_predict_markov_batch's buffers for a chunk of
+ * rows (its rule, option "markov_chunk_rows") with 16 T n more bytes per row for the combine's weights (n = p + offset states); the
+ * scratch of a chunk of draws, 8 (N + T) bytes per draw in flight, as many draws as fit 128 MiB in whole waves of 64 (at least one
+ * wave; option "markov_sample_chunk_draws" > 0 sets the number), rounded up to 256; 8 D T bytes for the draws (D = M S, or S; shared
+ * with gpcc_sample_batch); 4 (N + 3 D + M) bytes of lists.  Option "markov_sample_bytes" (read only) reports the weights, the scratch
+ * and the lists.  Blocking. */
+int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const int *Ntest,
+                             const double *ttest, const double *sigmatest, const double *weights, int S, unsigned long long seed,
+                             double *draws, int *draw_row, double *loglik, int *info);
+
 /* Posterior of the offsets b (src/gpccfixdelay_marginaliseb.jl:248-252): mu_postb[L], Sigma_postb[L x L]
  * (column-major, symmetrised).  The N x N solves (Sobs + K) \ [Q Y] run on the device as an augmented
  * factorisation; only the final L x L inverse is host arithmetic. */
@@ -500,7 +532,7 @@ enum {
     GPCC_LAPLACE_NOT_MAXIMUM = -11,     /* -Hessian not positive definite at the last point */
     GPCC_LAPLACE_ON_BOUND = -12,        /* the mode lies on the box (gpcc_laplace_evidence: rho = rhomin or rhomax) */
     GPCC_LAPLACE_BAD_START = -13,       /* gpcc_newton_batch: the start was rejected (non-finite value) */
-    GPCC_SAMPLE_NOT_DRAWN = -14         /* gpcc_sample_batch: the row received no draw of the mixture and was not factorised */
+    GPCC_SAMPLE_NOT_DRAWN = -14         /* gpcc_sample_batch, gpcc_sample_markov_batch: the row received no draw of the mixture and was not factorised */
 };
 
 /* The Newton polish of gpcc_laplace_evidence on its own (host only): P independent maximisations of l(u), u in R^n, in lock-step.

@@ -303,6 +303,30 @@ function sample_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}
     return draws, rows, ll, info, (return_noise ? ζ : nothing)
 end
 
+"sample_batch in LINEAR time for OU, matern32 and matern52 (gpcc_sample_markov_batch: Matheron's rule over the Kalman filter, O(N + T) per
+draw, no T×T factor): the same distribution N(μpred, Σpred + JITTER I + diag(σtest²)), other draws -> (draws (T × D), draw_row[D], ll[M],
+info[M]) in sample_batch's layouts and modes.  draw_row is sample_batch's for the same seed and weights; ll and info of a drawn column
+are predict_markov_batch's (draws NaN where info != 0); columns without a draw: ll NaN, info -14."
+function sample_markov_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64}, ttest, S::Integer,
+                             seed::Integer; weights = nothing, σtest = nothing)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M) && length(ttest) == h.L
+    Nt = Cint[length(a) for a in ttest]
+    tt = Float64.(reduce(vcat, ttest))
+    T = length(tt)
+    st = σtest === nothing ? C_NULL : Float64.(reduce(vcat, σtest))
+    D = weights === nothing ? M * S : S
+    draws, rows = Matrix{Float64}(undef, T, D), Vector{Cint}(undef, D)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    w = weights === nothing ? C_NULL : Float64.(weights)
+    rc = ccall((:gpcc_sample_markov_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+                Culonglong, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, Nt, tt, st, w, S, UInt64(seed), draws, rows, ll, info)
+    rc == 0 || error("gpcc_sample_markov_batch: " * lasterror(h.ptr))
+    return draws, rows, ll, info
+end
+
 "Drop-in body of objective(α, ρ) (gpccfixdelay_marginaliseb.jl:133-141): throws what the Julia code throws."
 function objective(h::Handle, τ, α, ρ)
     ll, info = loglik_batch(h, reshape(Float64.(τ), :, 1), reshape(Float64.(α), :, 1), [Float64(ρ)])
