@@ -6,9 +6,12 @@ _markov_cases.lightcurves (N = 110; every time and delay a multiple of 2^-10, so
 "ties", "before" and "plain").  Test times per band: (a) beyond the data on both sides, (b) exactly on training points of the same band
 and, in shifted time, of another band, (c) one time repeated, (d) handed over unsorted, (e) every other case one band has none.
 
-References and bars are the dense entries' own, measured on the reference side and never from the code under test:
-_predict_witness.predict_row and bar (max(1e-10, 64 eps cond_1(K)) x scale) for mu and var, _heldout_witness.heldout_row and bar for
-the held-out value, the reference's formulas (marginaliseb.jl:248-250) with rtol 1e-7 / atol 1e-12 for postb."""
+References here are the fp64 dense witnesses, _predict_witness.predict_row for mu and var, _heldout_witness.heldout_row for the held-out
+value, the reference's formulas (marginaliseb.jl:248-250) for postb, under the conditioning-scaled bars that the dense parity tests have
+always used: max(1e-10, 64 eps cond_1(K)) x scale, and rtol 1e-7 / atol 1e-12 for postb.  Those bars are loose -- with b marginalised
+the variance bar is above the 1e-8 jitter itself -- and measure no error of anything; the same cases are held against an
+extended-precision reference under a bar measured on the reference side in tests/_predict_highprec.py
+(tests/test_predict_highprec_cpu.py, tests/test_gpu_predict_highprec.py)."""
 import itertools
 
 import numpy as np
