@@ -136,12 +136,14 @@ def predict_from(m, dtype=LD, nb=NB):
     return mu, var, np.sum(np.abs(kB * w[:, None]), axis=0) + np.abs(mean[m.bs]), cdiag + v2
 
 
-def heldout_from(m, ytest, sigmatest, dtype=LD, nb=NB, direct=False):
-    """(l, terms of l) of a Model and a test set, the algebra in `dtype`.  direct: S and the mean as the module's docstring (and the
-    witness) writes them.  Otherwise, with marginalised b, the same two by conditioning on b first (the docstring's "offsets apart")."""
-    r, mean, Sigb = (a.astype(dtype) for a in (m.r, m.mean, m.Sigb))
-    yt, st = _flat(ytest).astype(dtype), _flat(sigmatest).astype(dtype)
-    T, L = len(yt), len(mean)
+def posterior_from(m, sigmatest, dtype=LD, nb=NB, direct=False):
+    """(centred mean[T], S[T, T]) of a Model's test points under test noise sigmatest (flattened, in `dtype`): S = cB + diag(sigma*^2 +
+    JITTER) - V'V symmetrised, the mean without the band means.  direct: both as the module's docstring (and the witness) writes them.
+    Otherwise, with marginalised b, the same two by conditioning on b first (the docstring's "offsets apart").  heldout_from's first
+    half, and what the joint draws factor (_sample_highprec.py)."""
+    r, Sigb = m.r.astype(dtype), m.Sigb.astype(dtype)
+    st = sigmatest
+    T, L = len(st), len(Sigb)
     if direct or not np.any(m.Sigb):
         K, kB, S = m.K.astype(dtype), m.kB.astype(dtype), m.cB.astype(dtype)
         _, X = _factor(K, nb)
@@ -162,7 +164,15 @@ def heldout_from(m, ytest, sigmatest, dtype=LD, nb=NB, direct=False):
         S = S - V.T @ V + W.T @ W
         mu = V.T @ z + W.T @ (XA @ (XQ.T @ z))
     S[np.diag_indices(T)] += st * st + dtype(JITTER)
-    S = (S + S.T) / 2
+    return mu, (S + S.T) / 2
+
+
+def heldout_from(m, ytest, sigmatest, dtype=LD, nb=NB, direct=False):
+    """(l, terms of l) of a Model and a test set, the algebra in `dtype`; direct: posterior_from's."""
+    mean = m.mean.astype(dtype)
+    yt, st = _flat(ytest).astype(dtype), _flat(sigmatest).astype(dtype)
+    T = len(yt)
+    mu, S = posterior_from(m, st, dtype, nb, direct)
     Cs, Xs = _factor(S, nb)
     z = Xs @ (yt - (mu + mean[m.bs]))
     quad, logs, const = (z @ z) / 2, np.log(np.diagonal(Cs)), T * np.log(2 * dtype(PI)) / 2
