@@ -5,7 +5,8 @@ numpy.longdouble (x87 80-bit on x86: eps ~1.1e-19), on the CPU.  It is the refer
 
 The model is _grad_witness.py's: K = alpha_b alpha_b' k(s; rho) + diag(sigma^2), plus 100 var_b (sample variance, n - 1) on
 same-band pairs when b is marginalised, s_ij = (t_i - tau_{b_i}) - (t_j - tau_{b_j}), r = y - mean_b.  The factorisation is a
-blocked Cholesky (numpy.linalg does not take longdouble, matmul does), then X = C^-1, z = X r, w = X' z, K^-1 = X' X,
+blocked Cholesky (numpy.linalg does not take longdouble, matmul does), then z = C^-1 r by blocked forward substitution (all the
+value needs: evaluate(value_only=True), the reference of tests/_loglik_highprec.py), X = C^-1, w = X' z, K^-1 = X' X,
 G = w w' - K^-1, and every derivative is the trace formula  d loglik / d theta = 1/2 sum_ij G_ij dK_ij / d theta.
 
 The kernels' derivatives, with r = |s|:
@@ -81,11 +82,12 @@ def _tri_inv(C):
     return X
 
 
-def cholesky_inverse(K, nb=NB):
-    """Blocked (right-looking by block column, blocks of nb) Cholesky K = C C' and X = C^-1 -> (C, X, info); info as LAPACK potrf."""
+def cholesky_blocked(K, nb=NB):
+    """Blocked (right-looking by block column, blocks of nb) Cholesky K = C C' -> (C, [C_kk^-1 per diagonal block], info); info as
+    LAPACK potrf."""
     N = K.shape[0]
     C = np.zeros_like(K)
-    X = np.zeros_like(K)
+    Xd = []
     for k in range(0, N, nb):
         e = min(k + nb, N)
         A = K[k:e, k:e] - C[k:e, :k] @ C[k:e, :k].T
@@ -94,9 +96,30 @@ def cholesky_inverse(K, nb=NB):
             return None, None, info
         C[k:e, k:e] = Ckk
         Xkk = _tri_inv(Ckk)
-        X[k:e, k:e] = Xkk
+        Xd.append(Xkk)
         if e < N:
             C[e:, k:e] = (K[e:, k:e] - C[e:, :k] @ C[k:e, :k].T) @ Xkk.T
+    return C, Xd, 0
+
+
+def forward_solve(C, Xd, r, nb=NB):
+    """z = C^-1 r by blocked forward substitution with the inverted diagonal blocks of cholesky_blocked."""
+    z = np.zeros_like(r)
+    for b, k in enumerate(range(0, C.shape[0], nb)):
+        e = min(k + nb, C.shape[0])
+        z[k:e] = Xd[b] @ (r[k:e] - C[k:e, :k] @ z[:k])
+    return z
+
+
+def cholesky_inverse(K, nb=NB):
+    """cholesky_blocked and X = C^-1 -> (C, X, info)."""
+    N = K.shape[0]
+    C, Xd, info = cholesky_blocked(K, nb)
+    if info:
+        return None, None, info
+    X = np.zeros_like(K)
+    for b, k in enumerate(range(0, N, nb)):
+        X[k:min(k + nb, N), k:min(k + nb, N)] = Xd[b]
     for k in range(nb, N, nb):            # block row k of X: X_k,<k = -X_kk C_k,<k X_<k,<k (X_<k,<k lower triangular)
         e = min(k + nb, N)
         T = np.empty((e - k, k), dtype=K.dtype)
@@ -131,9 +154,10 @@ class Reference:
     parts: dict = field(default_factory=dict, repr=False)
 
 
-def evaluate(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True, keep=False):
+def evaluate(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True, keep=False, value_only=False):
     """The log-likelihood, its gradient, the terms' scale and cond_1(K) in extended precision.  keep=True keeps the matrices
-    that tile_gradient needs."""
+    that tile_gradient needs.  value_only=True: the factor, z = C^-1 r by forward substitution and the log-determinant only -- the
+    same loglik bit for bit, no gradient, and cond_1 of the fp64 rounding of K from LAPACK (it only scales a bar)."""
     L = len(tarray)
     band = np.concatenate([np.full(len(t), l) for l, t in enumerate(tarray)])
     t = np.concatenate([np.asarray(a, np.float64) for a in tarray]).astype(LD)
@@ -156,12 +180,21 @@ def evaluate(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b
                         for a, m in zip(yarray, mean)], dtype=LD)
         K = K + 100 * var[band][:, None] * same
     ref = Reference(N=N, L=L)
+    r = y - mean[band]
+    if value_only:
+        C, Xd, info = cholesky_blocked(K)
+        if info:
+            ref.info = info
+            return ref
+        z = forward_solve(C, Xd, r)
+        ref.loglik = float(-(z @ z) / 2 - np.sum(np.log(np.diagonal(C))) - N * np.log(2 * np.pi * LD(1)) / 2)
+        ref.cond = float(np.linalg.cond(K.astype(np.float64), 1))
+        return ref
     C, X, info = cholesky_inverse(K)
     if info:
         ref.info = info
         return ref
-    r = y - mean[band]
-    z = X @ r
+    z = forward_solve(C, [X[k:k + NB, k:k + NB] for k in range(0, N, NB)], r)   # (the value-only route's z, bit for bit)
     w = X.T @ z
     Kinv = inverse_from_factor(X)
     ref.loglik = float(-(z @ z) / 2 - np.sum(np.log(np.diagonal(C))) - N * np.log(2 * np.pi * LD(1)) / 2)

@@ -37,16 +37,20 @@ class Cases:
     def __init__(self, group):
         self.group, self.jobs, self.rows = group, [], []
 
-    def add(self, name, data, mb, delays, alpha, rho, ll, grad, label):
+    def add(self, name, data, mb, delays, alpha, rho, ll, grad, label, vl=None):
+        """vl: loglik_batch's value of the same row, where the case has it."""
         self.jobs.append((name, *data, delays, alpha, rho, mb))
-        self.rows.append((float(ll), np.array(grad), len(alpha), label))
+        self.rows.append((float(ll), np.array(grad), len(alpha), label, None if vl is None else float(vl)))
 
     def check(self, pool):
         worst, where = 0.0, None
-        for ref, (ll, g, L, label) in zip(pool.map(H.evaluate_job, self.jobs), self.rows):
+        for ref, (ll, g, L, label, vl) in zip(pool.map(H.evaluate_job, self.jobs), self.rows):
             assert ref.info == 0, (label, ref.info)
-            # the value: the same conditioning-scaled bar, relative to max(1, |loglik|)
-            assert abs(ll - ref.loglik) <= max(1e-11, 64 * H.EPS64 * ref.cond) * max(1.0, abs(ref.loglik)), (label, ll, ref.loglik)
+            # the value: the same conditioning-scaled bar, relative to max(1, |loglik|) -- the gradient call's and loglik_batch's
+            value_bar = max(1e-11, 64 * H.EPS64 * ref.cond) * max(1.0, abs(ref.loglik))
+            assert abs(ll - ref.loglik) <= value_bar, (label, ll, ref.loglik)
+            if vl is not None:
+                assert abs(vl - ref.loglik) <= value_bar, (label, vl, ref.loglik)
             r = H.ratio(g, ref)
             assert r <= 1.0, (label, r, g, ref.grad, ref.cond)
             if L > 1:   # a common shift of all delays leaves the likelihood unchanged
@@ -61,13 +65,14 @@ class Cases:
 
 def _run(obj, delays, alpha, rho):
     """The gradient call, and loglik_batch on the same rows: the same info, NaN rows where it is not 0.  (The values of the two
-    paths differ by up to ~eps64 cond(K) relative: each is compared with the reference in Cases.check.)"""
+    paths differ by up to ~eps64 cond(K) relative: each is compared with the reference in Cases.check.)
+    -> (ll, grad, info, vl)."""
     ll, grad, info = obj.loglik_grad_batch(delays, alpha, rho)
     vl, vinfo = obj.loglik_batch(delays, alpha, rho)
     assert np.array_equal(info, vinfo), (info, vinfo)
     ok = info == 0
     assert np.isnan(grad[~ok]).all() and np.isnan(ll[~ok]).all() and np.isnan(vl[~ok]).all()
-    return ll, grad, info
+    return ll, grad, info, vl
 
 
 def _no_one_point_band_with_b(data, name):
@@ -89,11 +94,11 @@ def test_tile_geometry(pool):
                     _no_one_point_band_with_b(data, name)
                     continue
                 with gpcc_amd.Objective(*data, KERNELS[name], marginalise_b=mb, slots_per_stream=8) as obj:
-                    ll, grad, info = _run(obj, delays, alpha, rho)
+                    ll, grad, info, vl = _run(obj, delays, alpha, rho)
                 assert (info == 0).all(), (N, name, mb, info)
                 rows = range(3) if N < 600 else [ki % 3]   # (the reference's time)
                 for i in rows:
-                    cases.add(name, data, mb, delays[i], alpha[i], rho[i], ll[i], grad[i], (N, name, mb, i))
+                    cases.add(name, data, mb, delays[i], alpha[i], rho[i], ll[i], grad[i], (N, name, mb, i), vl=vl[i])
     cases.check(pool)
 
 
@@ -107,10 +112,10 @@ def test_many_bands(pool):
         for name in KERNELS:
             for mb in modes:
                 with gpcc_amd.Objective(*data, KERNELS[name], marginalise_b=mb, slots_per_stream=8) as obj:
-                    ll, grad, info = _run(obj, delays, alpha, rho)
+                    ll, grad, info, vl = _run(obj, delays, alpha, rho)
                 assert (info == 0).all() and grad.shape == (3, 17)
                 for i in range(3):
-                    cases.add(name, data, mb, delays[i], alpha[i], rho[i], ll[i], grad[i], (sum(Nl), Nl[0], name, mb, i))
+                    cases.add(name, data, mb, delays[i], alpha[i], rho[i], ll[i], grad[i], (sum(Nl), Nl[0], name, mb, i), vl=vl[i])
         if Nl[0] == 1:
             _no_one_point_band_with_b(data, "OU")
     # N = 1030 on one row
@@ -118,9 +123,9 @@ def test_many_bands(pool):
     data = W.ragged_data(Nl, seed=5)
     delays, alpha, rho = W.random_params(8, 1, seed=6)
     with gpcc_amd.Objective(*data, gpcc_amd.matern52, marginalise_b=False, slots_per_stream=8) as obj:
-        ll, grad, info = _run(obj, delays, alpha, rho)
+        ll, grad, info, vl = _run(obj, delays, alpha, rho)
     assert info[0] == 0
-    cases.add("matern52", data, False, delays[0], alpha[0], rho[0], ll[0], grad[0], (1030, "matern52"))
+    cases.add("matern52", data, False, delays[0], alpha[0], rho[0], ll[0], grad[0], (1030, "matern52"), vl=vl[0])
     cases.check(pool)
 
 
@@ -158,10 +163,10 @@ def test_degenerate_geometry(pool):
                     _no_one_point_band_with_b(data, name)
                     continue
                 with gpcc_amd.Objective(*data, KERNELS[name], marginalise_b=mb, slots_per_stream=8) as obj:
-                    ll, grad, info = _run(obj, delays, alpha, rho)
+                    ll, grad, info, vl = _run(obj, delays, alpha, rho)
                 assert (info == 0).all(), (label, name, mb, info)
                 for i in range(M):
-                    cases.add(name, data, mb, delays[i], alpha[i], rho[i], ll[i], grad[i], (label, name, mb, i))
+                    cases.add(name, data, mb, delays[i], alpha[i], rho[i], ll[i], grad[i], (label, name, mb, i), vl=vl[i])
     cases.check(pool)
 
 
@@ -181,13 +186,13 @@ def test_hyperparameter_envelope(pool):
             for name in KERNELS:
                 for mb in (True, False):
                     with gpcc_amd.Objective(*data, KERNELS[name], marginalise_b=mb, slots_per_stream=8) as obj:
-                        ll, grad, info = _run(obj, delays, alpha, rho)
+                        ll, grad, info, vl = _run(obj, delays, alpha, rho)
                     for i in range(len(combos)):
                         if info[i] != 0:
                             failed += 1
                             continue
                         cases.add(name, data, mb, delays[i], alpha[i], rho[i], ll[i], grad[i],
-                                  (sum(Nl), sig, name, mb) + combos[i])
+                                  (sum(Nl), sig, name, mb) + combos[i], vl=vl[i])
     print("hyper-parameter envelope: %d rows failed on the device (NaN, loglik_batch's info)" % failed)
     cases.check(pool)
 
@@ -222,7 +227,7 @@ def test_failure_in_a_chosen_tile(pool):
     rho = np.full(M, 3.0)
     cases = Cases("failure in a chosen tile")
     with gpcc_amd.Objective(*data, gpcc_amd.OU, marginalise_b=False, slots_per_stream=8) as obj:
-        ll, grad, info = _run(obj, delays, alpha, rho)
+        ll, grad, info, vl = _run(obj, delays, alpha, rho)
         print("failure rows: info %s (expected %s)" % (info, want))
         assert list(info) == want
         bad = np.array(want) > 0
@@ -230,7 +235,7 @@ def test_failure_in_a_chosen_tile(pool):
         for i in np.flatnonzero(~bad):
             l1, g1, i1 = obj.loglik_grad_batch(delays[i:i + 1], alpha[i:i + 1], rho[i:i + 1])
             assert i1[0] == 0 and l1[0] == ll[i] and np.array_equal(g1[0], grad[i]), i
-            cases.add("OU", data, False, delays[i], alpha[i], rho[i], ll[i], grad[i], ("valid row", i))
+            cases.add("OU", data, False, delays[i], alpha[i], rho[i], ll[i], grad[i], ("valid row", i), vl=vl[i])
     cases.check(pool)
 
 
