@@ -71,6 +71,10 @@ SIGNATURES = {
                                           c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
     "gpcc_heldout_loglik_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_double_p,
                                                  c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "gpcc_loo_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                      c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "gpcc_loo_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                             c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
     "gpcc_predict_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_double_p,
                                                  c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
     "gpcc_heldout_loglik_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p,

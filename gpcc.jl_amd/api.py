@@ -9,6 +9,7 @@ Names and argument meaning follow /root/reference/src:
                                                           (marginalise_b=False: src/gpccfixdelay.jl:131-139)
 Every numeric result comes from libgpcc_hip.so (HIP kernels); nothing here computes on the CPU.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -135,6 +136,9 @@ def mvnormal_logpdf(mu, Sigma, x, device=0):
     return ll.value
 
 
+LooResult = collections.namedtuple("LooResult", "mu var lp loo loglik info mix_lp mix_loo")
+
+
 def logsumexp_rows(values, p):
     """log sum_m p_m exp(values_m) as gpcc_heldout_mix forms it: one running, max-shifted log-sum-exp over the rows in row order, rows
     with p_m = 0 skipped; NaN if a row with p_m > 0 is NaN; one row of weight 1 gives its own value bitwise."""
@@ -177,6 +181,7 @@ class Objective:
         Ns, s = _flatten(stdarray)
         assert np.array_equal(Nl, Ny) and np.array_equal(Nl, Ns), "band lengths differ between t, y, sigma"
         self.L, self.Nl, self.N = L, Nl.copy(), int(Nl.sum())
+        self.yflat = y.copy()     # the fluxes in the order they were handed over (the leave-one-out residuals are taken against them)
         self.marginalise_b = bool(marginalise_b)
         self.device = int(device)
         lib = _capi.load()
@@ -398,6 +403,50 @@ class Objective:
         self._chk(_capi.load().gpcc_loglik_grad_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _dp(grad),
                                                       _ip(info)))
         return ll, grad, info
+
+    def _loo(self, entry, delays, alpha, rho, weights, outputs):
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        N = self.N
+        names = ("mu", "var", "lp", "loo", "mix_lp", "mix_loo", "loglik", "info")
+        want = set(names if outputs is None else outputs)
+        if not want <= set(names):
+            raise ValueError("unknown outputs %r (of %r)" % (sorted(want - set(names)), names))
+        w = None
+        if weights is not None:
+            w = _d(np.asarray(weights, dtype=np.float64).ravel())
+            if w.shape != (M,):
+                raise ValueError("weights must have M = %d entries" % M)
+        elif outputs is None:
+            want -= {"mix_lp", "mix_loo"}
+        shapes = {"mu": (M, N), "var": (M, N), "lp": (M, N), "loo": (M,), "mix_lp": (N,), "mix_loo": (1,), "loglik": (M,)}
+        buf = {k: np.empty(shapes[k], dtype=np.float64) for k in shapes if k in want}
+        info = np.zeros(M, dtype=np.int32) if "info" in want else None
+        ptr = {k: (_dp(buf[k]) if k in buf else None) for k in shapes}
+        try:
+            self._chk(entry(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(w) if w is not None else None, ptr["mu"], ptr["var"],
+                            ptr["lp"], ptr["loo"], ptr["mix_lp"], ptr["mix_loo"], ptr["loglik"], _ip(info) if info is not None else None))
+        except GpccError as e:
+            _raise_reference_error(e)
+        return LooResult(buf.get("mu"), buf.get("var"), buf.get("lp"), buf.get("loo"), buf.get("loglik"), info, buf.get("mix_lp"),
+                         float(buf["mix_loo"][0]) if "mix_loo" in buf else None)
+
+    def loo_batch(self, delays, alpha, rho, weights=None, outputs=None):
+        """Exact leave-one-out predictive scores at M rows (tau, alpha, rho) (gpcc_loo_batch) -> LooResult(mu[M, N], var[M, N],
+        lp[M, N], loo[M], loglik[M], info[M], mix_lp[N], mix_loo).  Point i, in the order the light curves were handed over (band 1,
+        then band 2, ...), has the mean mu, variance var and log-density lp of y_i given every other observation, under exactly the
+        model of objective(alpha, rho) (no JITTER); loo = sum_i lp.  loglik and info are bitwise loglik_grad_batch's, except
+        info = N + i for the first point whose variance is not positive and finite; failed rows are NaN.  With weights (M entries,
+        p = weights / sum(weights), zero-weight rows skipped): mix_lp_i = -log sum_m p_m exp(-lp_mi), the exact LOO log-density of the
+        delay mixture with alpha and rho fixed per delay, and mix_loo = sum_i mix_lp_i; None without weights.  outputs: the names to
+        compute (default: all); the others come back as None and are never copied."""
+        return self._loo(_capi.load().gpcc_loo_batch, delays, alpha, rho, weights, outputs)
+
+    def loo_markov_batch(self, delays, alpha, rho, weights=None, outputs=None):
+        """loo_batch in linear time (gpcc_loo_markov_batch: two Kalman filters tapped at every training point before its update, and
+        the two-filter combine at the point; OU, matern32 and matern52 only) -> the same LooResult.  loglik and info are bitwise
+        loglik_markov_batch's, except info = N + i for the first point (the caller's order) whose variance is not positive and finite.
+        rbf, or marginalise_b with more than 4 bands: GpccError (unsupported)."""
+        return self._loo(_capi.load().gpcc_loo_markov_batch, delays, alpha, rho, weights, outputs)
 
     def loglik_grad_markov_batch(self, delays, alpha, rho):
         """loglik_grad_batch in linear time (gpcc_loglik_grad_markov_batch: the Kalman filter's forward sensitivities, one lane per

@@ -6,9 +6,11 @@
 #include "gpcc_hess.hip.h"
 #include "gpcc_pred.hip.h"
 #include "gpcc_heldout.hip.h"
+#include "gpcc_loo.hip.h"
 #include "gpcc_sample.hip.h"
 #include "gpcc_markov.hip.h"
 #include "gpcc_markov_pred.hip.h"
+#include "gpcc_markov_loo.hip.h"
 #include "gpcc_markov_sample.hip.h"
 #include "gpcc_markov_grad.hip.h"
 #include "gpcc_markov_hess.hip.h"
@@ -200,6 +202,17 @@ struct gpcc_handle_s {
     // column of the triangular inverse (nt tiles), w = K^-1 r (Np) and the per-tile partials (nt(nt+1)/2 x 3 L^2)
     double *d_glinv = nullptr, *d_gscr = nullptr, *d_gw = nullptr, *d_gpart3 = nullptr, *d_ggrad = nullptr;
     long grad_slots = 0, ggrad_cap = 0;
+    // leave-one-out scores (gpcc_loo_batch): the gradient's buffers above, plus diag(K^-1) per workspace slot (Np), the rows' mu, var and
+    // lp (M x N each, those asked for), their sums (M), the mixture state (4 N + 1) and the weights (M); allocated on first use
+    double *d_lood = nullptr, *d_loomu = nullptr, *d_loovar = nullptr, *d_loolp = nullptr, *d_loosum = nullptr, *d_loomix = nullptr,
+           *d_loow = nullptr;
+    long lood_cap = 0, loomu_cap = 0, loovar_cap = 0, loolp_cap = 0, loosum_cap = 0, loomix_cap = 0, loow_cap = 0;
+    hipEvent_t ev_lmix = nullptr;   // orders the mixture steps of consecutive groups by row
+    // ... in linear time (gpcc_loo_markov_batch): the same row buffers for one chunk of rows, the tap scratch d_mktap, and the sorted
+    // points' bands and positions in the caller's order (2 N ints)
+    int *d_mkli = nullptr;
+    long mkli_cap = 0;
+    int mkl_configured = 0;
     // Hessian (gpcc_loglik_hess_batch): allocated on its first call, for hess_slots <= workspace slots (hess_bytes_per_slot each: the
     // dense K^-1, M_theta = K^-1 D_theta for every parameter, u, z and the partials) and the outputs of the batch (hess and fisher blocks)
     double *d_hc = nullptr, *d_hm = nullptr, *d_hu = nullptr, *d_hz = nullptr, *d_htab = nullptr, *d_htr = nullptr, *d_hout = nullptr;
@@ -567,6 +580,9 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_smean); hipFree(h->d_sdraw); hipFree(h->d_szeta); hipFree(h->d_slist); hipFree(h->d_soff);
     if (h->ev_pmix) hipEventDestroy(h->ev_pmix);
     if (h->ev_hmix) hipEventDestroy(h->ev_hmix);
+    hipFree(h->d_lood); hipFree(h->d_loomu); hipFree(h->d_loovar); hipFree(h->d_loolp); hipFree(h->d_loosum); hipFree(h->d_loomix);
+    hipFree(h->d_loow); hipFree(h->d_mkli);
+    if (h->ev_lmix) hipEventDestroy(h->ev_lmix);
     hipFree(h->d_ocond); hipFree(h->d_fb_idx); hipFree(h->d_fb_par); hipFree(h->d_fb_out); hipFree(h->d_fb_info);
     if (h->fb) gpcc_destroy(h->fb);
     if (h->main_stream) hipStreamDestroy(h->main_stream);
@@ -1936,6 +1952,98 @@ extern "C" int gpcc_loglik_grad_batch(gpcc_handle_t h, int M, const double *dela
 }
 
 // ------------------------------------------------------------------------------------------
+// Exact leave-one-out predictive scores (gpcc_loo_batch; kernels: gpcc_loo.hip.h).  A group runs the gradient's part 1
+// unchanged (its loglik and info are gpcc_loglik_grad_batch's bits), then diag(K^-1) from one read of X = L^-1 and the finish; with
+// weights, the per-point mixture step in row order, carried from group to group.  No gpcc_grad_tiles launch.
+// ------------------------------------------------------------------------------------------
+// the argument rules gpcc_loo_batch and gpcc_loo_markov_batch share
+static int loo_check_args(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const double *weights,
+                          const double *mix_lp, const double *mix_loo)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (!delays || !alpha || !rho) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    if (!weights && (mix_lp || mix_loo)) return fail(h, GPCC_ERR_ARGUMENT, "mix_lp and mix_loo need weights");
+    return 0;
+}
+
+// the buffers of the rows' results that both entries share: those of mu, var, lp that are asked for (lp also for the mixture)
+static int ensure_loo_rows(gpcc_handle_t h, int M, bool mu, bool var, bool lp, bool mix)
+{
+    const long MN = (long)M * h->N;
+    int rc = grow_buf(h, &h->d_loosum, &h->loosum_cap, (long)M);
+    if (!rc && mu) rc = grow_buf(h, &h->d_loomu, &h->loomu_cap, MN);
+    if (!rc && var) rc = grow_buf(h, &h->d_loovar, &h->loovar_cap, MN);
+    if (!rc && lp) rc = grow_buf(h, &h->d_loolp, &h->loolp_cap, MN);
+    if (!rc && mix) rc = grow_buf(h, &h->d_loomix, &h->loomix_cap, 4L * h->N + 1);
+    if (!rc && mix) rc = grow_buf(h, &h->d_loow, &h->loow_cap, (long)M);
+    if (!rc && mix && !h->ev_lmix) HIPCHK(h, hipEventCreateWithFlags(&h->ev_lmix, hipEventDisableTiming));
+    return rc;
+}
+
+extern "C" int gpcc_loo_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                              const double *weights, double *mu_out, double *var_out, double *lp_out, double *loo, double *mix_lp,
+                              double *mix_loo, double *loglik, int *info)
+{
+    int rc = loo_check_args(h, M, delays, alpha, rho, weights, mix_lp, mix_loo);
+    if (rc) return rc;
+    if (route_fp64(h, "leave-one-out scores", rc, [&](gpcc_handle_t o) {
+            return gpcc_loo_batch(o, M, delays, alpha, rho, weights, mu_out, var_out, lp_out, loo, mix_lp, mix_loo, loglik, info);
+        }))
+        return rc;
+    std::vector<double> p;   // the normalised weights p_m = w_m / sum w
+    rc = mixture_weights(h, M, weights, false, p);
+    if (rc || M == 0) return rc;
+    GPCC_ON_DEVICE(h, h->device);
+    const bool mix = mix_lp || mix_loo;
+    const long N = h->N;
+    double *dd, *da, *dr;
+    rc = ensure_workspace(h);
+    if (!rc) rc = ensure_grad(h);
+    if (!rc) rc = grow_buf(h, &h->d_lood, &h->lood_cap, (long)h->Np * h->grad_slots);
+    if (!rc) rc = ensure_staging(h, M);
+    if (!rc) rc = ensure_loo_rows(h, M, mu_out != nullptr, var_out != nullptr, lp_out || mix, mix);
+    if (!rc) rc = stage_params(h, M, delays, alpha, rho, dd, da, dr);
+    if (rc) return rc;
+    hipStream_t ms = h->main_stream;
+    if (mix) HIPCHK(h, hipMemcpyAsync(h->d_loow, p.data(), sizeof(double) * M, hipMemcpyHostToDevice, ms));
+    GpccCtx c = make_ctx(h);
+    c.linv = h->d_glinv;
+    c.linv_keep = 1;
+    GpccLooBuf lb;
+    lb.mu = mu_out ? h->d_loomu : nullptr; lb.var = var_out ? h->d_loovar : nullptr; lb.lp = (lp_out || mix) ? h->d_loolp : nullptr;
+    lb.loo = h->d_loosum; lb.mix = h->d_loomix;
+    const int pblocks = (int)((N + GPCC_LOO_THREADS - 1) / GPCC_LOO_THREADS);
+    rc = run_groups(h, M, (long)h->ws_streams * h->ws_slots, dd, da, dr, [&](const GpccGroup &g, hipStream_t st, int gi, int ngroups) {
+        enqueue_grad_inverse(h, c, g, st);
+        gpcc_loo_diag<<<g.cnt * c.nt * GpccP64::NCH, GPCC_LOO_THREADS, 0, st>>>(c, g, h->d_lood);
+        gpcc_loo_finish<<<g.cnt, GPCC_LOO_THREADS, 0, st>>>(c, g, h->d_lood, h->d_gw, lb);
+        const int r = launch_status(h, "kernel launch failed");
+        if (r || !mix) return r;
+        hipError_t e = hipSuccess;   // after the previous group's mixture step, whichever stream ran it
+        if (gi > 0) e = hipStreamWaitEvent(st, h->ev_lmix, 0);
+        if (e == hipSuccess) {
+            gpcc_loo_mix<<<pblocks, GPCC_LOO_THREADS, 0, st>>>(lb.lp, 0, h->d_loow, g.first, g.cnt, (int)N, lb.mix, gi == 0 ? 1 : 0);
+            if (gi == ngroups - 1) gpcc_loo_mix_sum<<<1, GPCC_LOO_THREADS, 0, st>>>((int)N, lb.mix);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(h->ev_lmix, st);
+        return e == hipSuccess ? 0 : fail(h, GPCC_ERR_HIP, "leave-one-out mixture: %s", hipGetErrorString(e));
+    });
+    if (rc) return rc;
+    if (loglik) HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
+    if (info) HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
+    if (mu_out) HIPCHK(h, hipMemcpyAsync(mu_out, h->d_loomu, sizeof(double) * M * N, hipMemcpyDeviceToHost, ms));
+    if (var_out) HIPCHK(h, hipMemcpyAsync(var_out, h->d_loovar, sizeof(double) * M * N, hipMemcpyDeviceToHost, ms));
+    if (lp_out) HIPCHK(h, hipMemcpyAsync(lp_out, h->d_loolp, sizeof(double) * M * N, hipMemcpyDeviceToHost, ms));
+    if (loo) HIPCHK(h, hipMemcpyAsync(loo, h->d_loosum, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
+    if (mix_lp) HIPCHK(h, hipMemcpyAsync(mix_lp, h->d_loomix + 3 * N, sizeof(double) * N, hipMemcpyDeviceToHost, ms));
+    if (mix_loo) HIPCHK(h, hipMemcpyAsync(mix_loo, h->d_loomix + 4 * N, sizeof(double), hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipStreamSynchronize(ms));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // The exact linear-time log-likelihood of the Markov kernels (gpcc_loglik_markov_batch; kernel: gpcc_markov.hip.h): a
 // Kalman filter over the observations merged by shifted time, one lane per evaluation, one launch per call.  It needs the light
 // curves with every band sorted by time (built here on the first call) and the staging buffers, nothing of the N^2 workspace.
@@ -2222,6 +2330,98 @@ extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *d
         HIPCHK(h, hipMemcpyAsync(mix_var, h->d_mkmix + 5 * T, sizeof(double) * T, hipMemcpyDeviceToHost, ms));
     }
     return markov_finish(h, M, loglik, info);
+}
+
+// Exact leave-one-out scores in linear time (gpcc_loo_markov_batch; kernels: gpcc_markov_loo.hip.h): per chunk of rows
+// the two filters with a tap at every training point, the combine at the points, the per-row finish and, with weights, the mixture
+// step of gpcc_loo_batch in row order.  The chunk is the rows whose taps fit GPCC_MKP_TAP_BYTES (option "markov_chunk_rows" sets it).
+extern "C" int gpcc_loo_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                     const double *weights, double *mu_out, double *var_out, double *lp_out, double *loo, double *mix_lp,
+                                     double *mix_loo, double *loglik, int *info)
+{
+    int rc = loo_check_args(h, M, delays, alpha, rho, weights, mix_lp, mix_loo);
+    if (!rc) rc = markov_refusals(h, "gpcc_loo_markov_batch", "gpcc_loo_batch");
+    if (rc) return rc;
+    if (route_fp64(h, "linear-time leave-one-out scores", rc, [&](gpcc_handle_t o) {
+            return gpcc_loo_markov_batch(o, M, delays, alpha, rho, weights, mu_out, var_out, lp_out, loo, mix_lp, mix_loo, loglik, info);
+        }))
+        return rc;
+    const MarkovDims d = markov_dims(h);
+    if (!gpcc_mkl_available(d.p, d.noff))
+        return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loo_markov_batch: the filter <%d, %d> is not built (it would spill); use gpcc_loo_batch",
+                    d.p, d.noff);
+    std::vector<double> p;   // the normalised weights p_m = w_m / sum w
+    rc = mixture_weights(h, M, weights, false, p);
+    if (rc || M == 0) return rc;
+    GPCC_ON_DEVICE(h, h->device);
+    const bool mix = mix_lp || mix_loo;
+    const long N = h->N, ns = d.p + d.noff, nrec = ns + ns * (ns + 1) / 2;
+    // rows per chunk: what the scratch budget holds (whole waves when it holds one), or the option
+    long chunk = GPCC_MKP_TAP_BYTES / (2 * N * nrec * 8);
+    if (chunk >= 64) chunk -= chunk % 64;
+    if (h->markov_chunk_rows > 0) chunk = h->markov_chunk_rows;
+    if (chunk < 1) chunk = 1;
+    if (chunk > M) chunk = M;
+    double *dd, *da, *dr;
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
+        int g = grow_buf(h, &h->d_mkli, &h->mkli_cap, 2 * N);
+        if (!g) g = grow_buf(h, &h->d_mktap, &h->mktap_cap, 2 * N * nrec * chunk);
+        if (!g) g = ensure_loo_rows(h, (int)chunk, true, true, true, mix);
+        if (!g) g = grow_buf(h, &h->d_loosum, &h->loosum_cap, (long)M);
+        if (!g && mix) g = grow_buf(h, &h->d_loow, &h->loow_cap, (long)M);
+        return g;
+    });
+    if (rc) return rc;
+    if (!h->mkl_configured) {
+        HIPCHK(h, gpcc_mkl_configure());
+        h->mkl_configured = 1;
+    }
+    hipStream_t ms = h->main_stream;
+    std::vector<int> pi(2 * N);   // per sorted point: its band, its position in the caller's order
+    for (long i = 0; i < N; ++i) { pi[i] = h->band_host[h->mk_perm[i]]; pi[N + i] = h->mk_perm[i]; }
+    HIPCHK(h, hipMemcpyAsync(h->d_mkli, pi.data(), sizeof(int) * 2 * N, hipMemcpyHostToDevice, ms));
+    if (mix) HIPCHK(h, hipMemcpyAsync(h->d_loow, p.data(), sizeof(double) * M, hipMemcpyHostToDevice, ms));
+    GpccMarkovLooArgs a;
+    markov_fill_args(h, M, dd, da, dr, a);
+    a.tap = h->d_mktap;
+    GpccMarkovLooCombineArgs c;
+    c.tap = h->d_mktap; c.alpha = da; c.rho = dr; c.pts = h->d_mk; c.pband = h->d_mkli; c.pperm = h->d_mkli + N;
+    c.mu = h->d_loomu; c.var = h->d_loovar; c.lp = h->d_loolp;
+    c.L = h->L; c.N = (int)N;
+    for (int l = 0; l < GPCC_MARKOV_MAXL; ++l) c.mean_b[l] = l < h->L ? h->mean_b[l] : 0.0;
+    for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) c.sigma_b[l] = a.sigma_b[l];
+    const int pblocks = (int)((N + GPCC_LOO_THREADS - 1) / GPCC_LOO_THREADS);
+    for (long row0 = 0; row0 < M; row0 += chunk) {
+        const int rows = (int)(M - row0 < chunk ? M - row0 : chunk);
+        a.row0 = c.row0 = (int)row0;
+        a.rows = c.rows = rows;
+        a.mstride = c.mstride = (int)chunk;
+        size_t lds;
+        const int threads = markov_launch_shape(h, (((long)rows + 63) / 64) * 2,
+                                                [&](int thr, bool st) { return gpcc_mkl_lds_bytes(a.N, a.L, thr, st); }, a.stage, lds);
+        if (lds > GPCC_MARKOV_LDS_MAX) return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_markov_loo_taps: %zu bytes of LDS", lds);
+        hipError_t e = gpcc_mkl_launch_taps(d.p, d.noff, a, (rows + threads - 1) / threads, threads, lds, ms);
+        if (e == hipSuccess) e = gpcc_mkl_launch_combine(d.p, d.noff, c, ms);
+        if (e == hipSuccess) e = gpcc_mkl_launch_rows(h->d_loomu, h->d_loovar, h->d_loolp, h->d_loosum, h->d_oinfo, (int)N, (int)row0, rows, ms);
+        if (e == hipSuccess && mix) {
+            gpcc_loo_mix<<<pblocks, GPCC_LOO_THREADS, 0, ms>>>(h->d_loolp, row0, h->d_loow, (int)row0, rows, (int)N, h->d_loomix,
+                                                              row0 == 0 ? 1 : 0);
+            if (row0 + rows == M) gpcc_loo_mix_sum<<<1, GPCC_LOO_THREADS, 0, ms>>>((int)N, h->d_loomix);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "linear-time leave-one-out scores: %s", hipGetErrorString(e));
+        if (mu_out) HIPCHK(h, hipMemcpyAsync(mu_out + row0 * N, h->d_loomu, sizeof(double) * rows * N, hipMemcpyDeviceToHost, ms));
+        if (var_out) HIPCHK(h, hipMemcpyAsync(var_out + row0 * N, h->d_loovar, sizeof(double) * rows * N, hipMemcpyDeviceToHost, ms));
+        if (lp_out) HIPCHK(h, hipMemcpyAsync(lp_out + row0 * N, h->d_loolp, sizeof(double) * rows * N, hipMemcpyDeviceToHost, ms));
+    }
+    if (loo) HIPCHK(h, hipMemcpyAsync(loo, h->d_loosum, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
+    if (mix_lp) HIPCHK(h, hipMemcpyAsync(mix_lp, h->d_loomix + 3 * N, sizeof(double) * N, hipMemcpyDeviceToHost, ms));
+    if (mix_loo) HIPCHK(h, hipMemcpyAsync(mix_loo, h->d_loomix + 4 * N, sizeof(double), hipMemcpyDeviceToHost, ms));
+    if (loglik) HIPCHK(h, hipMemcpyAsync(loglik, h->d_out, sizeof(double) * M, hipMemcpyDeviceToHost, ms));
+    if (info) HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipStreamSynchronize(ms));
+    h->markov_count += M;
+    return 0;
 }
 
 extern "C" int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,

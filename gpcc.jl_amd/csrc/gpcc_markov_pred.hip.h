@@ -256,6 +256,7 @@ __device__ __forceinline__ bool gpcc_mkp_spd_inverse(const double (&A)[NS][NS], 
 }
 
 // one lane per (row of the chunk, sorted test point): grid (ceil(rows / 64), T), 64 threads
+// (gpcc_markov_loo_combine of gpcc_markov_loo.hip.h carries a copy of this arithmetic: a fix here belongs there too)
 template <int P, int NOFF>
 __global__ void __launch_bounds__(64) gpcc_markov_combine(const GpccMarkovCombineArgs a)
 {

@@ -13,6 +13,8 @@ every delay of a grid sees the SAME random draws because each gpcc call seeds it
 /root/reference: `makepositive` is taken to be softplus and `transformbetween(x, a, b)` to be
 a + (b - a) * logistic(x), the package's documented purpose; `safewrapper` is taken to turn exceptions
 (PosDefException) into +Inf of the negative objective."""
+import collections
+
 import numpy as np
 
 from . import laplace
@@ -285,6 +287,18 @@ def _split_bands(draws, bands):
     return [draws[:, off[l]:off[l + 1]] for l in range(len(bands))]
 
 
+class LooScores(collections.namedtuple("LooScores", "mu sigma lp z total")):
+    """Leave-one-out predictive scores of the training points, in the order the light curves were handed over: mean mu, standard
+    deviation sigma and log-density lp of y_i given every other observation, the standardised residual z = (y - mu) / sigma (a large
+    |z| flags a bad epoch or an underestimated error bar) and total = sum(lp), the score that compares kernels or delays."""
+
+
+def _loo_entry(obj, solver):
+    if solver not in ("dense", "markov"):
+        raise ValueError("solver must be 'dense' or 'markov', got %r" % (solver,))
+    return obj.loo_markov_batch if solver == "markov" else obj.loo_batch
+
+
 class Predictor:
     """The `predictTest` closure returned by gpcc() (marginaliseb.jl:259-343), three call forms:
       pred(ttest)                       ttest = list of L arrays  -> (mu_pred, Sigma_pred), joint    (:259-289)
@@ -338,6 +352,16 @@ class Predictor:
         d = np.diag(Sig)
         return ([mu[l * n:(l + 1) * n] for l in range(L)],
                 [np.sqrt(np.maximum(d[l * n:(l + 1) * n], 1e-6)) for l in range(L)])      # :301-303
+
+    def loo(self, solver=None):
+        """Exact leave-one-out scores of the training points under this fit -> LooScores (Objective.loo_batch, one row; no refit and
+        no JITTER: p(y_i | y_-i) of the model the likelihood uses).  solver None: the predictor's own; "dense" or "markov" (OU,
+        matern32, matern52: linear time).  A failed row raises PosDefException."""
+        res = _loo_entry(self.obj, solver or self.solver)(self.delays[None, :], self.alpha[None, :], [self.rho])
+        if res.info[0] > 0:
+            raise PosDefException(int(res.info[0]))
+        sigma = np.sqrt(res.var[0])
+        return LooScores(res.mu[0], sigma, res.lp[0], (self.obj.yflat - res.mu[0]) / sigma, float(res.loo[0]))
 
     def sample(self, ttest, S, seed, sigmatest=None, solver=None):
         """S joint draws of the light curves at ttest (Predictor's forms: a list of L arrays or one array for every band) -> per-band
@@ -409,6 +433,22 @@ class DelayAveragedPredictor:
         if self.solver == "markov":
             return self.obj.heldout_loglik_markov_batch(self.delays, self.alpha, self.rho, ttest, ytest, sigmatest, weights=self.weights)[3]
         return self.obj.heldout_loglik_batch(self.delays, self.alpha, self.rho, ttest, ytest, sigmatest, weights=self.weights)[3]
+
+    def loo(self, solver=None):
+        """Exact leave-one-out scores of the delay mixture, alpha and rho fixed per delay -> LooScores.  lp_i = -log sum_g p_g
+        exp(-lp_gi) (the weighted harmonic mean of the rows' densities: Objective.loo_batch's mix_lp) and total = sum(lp).  Given
+        y_-i the mixture's weights are q_gi proportional to p_g exp(-lp_gi); mu and sigma are the mean and the standard deviation of
+        that mixture of the rows' Gaussians, z = (y - mu) / sigma.  Rows of weight 0 are left out; a failed row with weight makes
+        everything NaN.  solver as Predictor.loo."""
+        res = _loo_entry(self.obj, solver or self.solver)(self.delays, self.alpha, self.rho, weights=self.weights)
+        keep = self.weights > 0
+        p = self.weights[keep] / self.weights[keep].sum()
+        x = np.log(p)[:, None] - res.lp[keep]
+        q = np.exp(x - x.max(axis=0))
+        q = q / q.sum(axis=0)
+        mu = np.sum(q * res.mu[keep], axis=0)
+        sigma = np.sqrt(np.sum(q * (res.var[keep] + (res.mu[keep] - mu) ** 2), axis=0))
+        return LooScores(mu, sigma, res.mix_lp, (self.obj.yflat - mu) / sigma, float(res.mix_loo))
 
     def sample(self, ttest, S, seed, sigmatest=None, solver=None):
         """S joint draws of the delay-averaged light curves -> (per-band arrays (S, Ntest_l), row[S]): draw s comes from the row

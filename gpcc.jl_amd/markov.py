@@ -880,6 +880,149 @@ def sample(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmates
     return mu + means[band_of] + gt + (c if _slip == "plus" else -c) + noise, ll, 0
 
 
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Exact leave-one-out predictive scores in linear time (csrc/gpcc_markov_loo.hip.h), the same algorithm in numpy.
+#
+#   taps      the forward filter walks the training points in merge_order()'s order (shifted time, then band, then position); at point i
+#             the state propagated to s_i BEFORE the update with point i is kept.  The backward filter walks exactly the reverse order
+#             (lags |d|) and keeps the same: every other point, tied with i or not, is then on exactly one side of i.
+#   combine   predict()'s: P_s = (P_f^-1 + P_b^-1 - P0^-1)^-1, m_s = P_s (P_f^-1 m_f + P_b^-1 m_b), scaled by diag(P0)^-1/2, the
+#             backward state mapped by D; with h of the point's band
+#                 mu_i = h'm_s + mean(y_band),  var_i = h'P_s h + sigma_i^2,  lp_i = -(log 2 pi + log var_i + (y_i - mu_i)^2 / var_i) / 2
+#             (no JITTER: p(y_i | y_-i) of the model the likelihood uses), reported in the caller's order.
+#   mixture   with alpha and rho fixed per delay the exact LOO density of the delay mixture is the weighted HARMONIC mean of the rows'
+#             densities: mix_lp_i = -log sum_m p_m exp(-lp_mi) (loo_mix).
+# ----------------------------------------------------------------------------------------------------------------------------------
+def _loo_taps(name, ev, alpha, rho, p, n, vb, reverse, after_update=False):
+    """One filter over the events `ev` [(s, band, position, r, sigma^2)] in the order given (reverse: descending s, lags |d|) ->
+    (loglik, info, {(band, position): (m, P) at the point before its update (after_update: after it)})."""
+    Pinf = stationary(name, rho)
+    P = _prior(name, rho, p, n, vb)
+    m = np.zeros(n)
+    ll, info, sprev, taps = 0.0, 0, None, {}
+    for step, (s, b, i, r, s2) in enumerate(ev):
+        d = 0.0 if sprev is None else (sprev - s if reverse else s - sprev)
+        sprev = s
+        m, P = _propagate(name, m, P, Pinf, d, rho, p)
+        if not after_update:
+            taps[(b, i)] = (m.copy(), P.copy())
+        h = np.zeros(n)
+        h[0] = alpha[b]
+        if n > p:
+            h[p + b] = 1.0
+        Ph = P @ h
+        S = h @ Ph + s2
+        if not (S > 0.0 and math.isfinite(S)):
+            return math.nan, step + 1, taps
+        eps = r - h @ m
+        ll -= 0.5 * (LOG2PI + math.log(S) + eps * eps / S)
+        m = m + Ph * (eps / S)
+        P = P - np.outer(Ph, Ph) / S
+        P = 0.5 * (P + P.T)
+        if after_update:
+            taps[(b, i)] = (m.copy(), P.copy())
+    return ll, info, taps
+
+
+LOO_SLIPS = ("with_self", "tie_both", "no_sigma", "jitter", "sorted_order", "arith_mix")
+
+
+def loo(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True, _slip=None):
+    """(mu[N], var[N], lp[N], loo, loglik, info) of one (tau, alpha, rho): mean, variance and log-density of y_i given every other
+    observation and their sum, Objective.loo_markov_batch's row, in the caller's order (band 1 as given, then band 2, ...).  info:
+    loglik()'s codes for the filter, else N + i for the first point i (1-based, the caller's order) whose combine meets a pivot, or
+    whose variance is, not positive and finite (mu, var, lp and loo NaN then, loglik valid), else 0.
+    _slip (tests only) injects one mistake: "with_self" (the forward state AFTER the update with point i: the point is not left out),
+    "tie_both" (the backward walk keeps the forward order among points that tie in shifted time, so a tied point is counted on both
+    sides or on neither), "no_sigma" (the variance of the noiseless curve, without sigma_i^2), "jitter" (predictTest's 1e-8 added),
+    "sorted_order" (outputs left in the order of the bands sorted by time); "arith_mix" acts in loo_mix()."""
+    if _slip is not None and _slip not in LOO_SLIPS:
+        raise ValueError("unknown slip %r" % (_slip,))
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b)
+    N = len(train)
+    nan = np.full(N, math.nan)
+    if code:
+        return nan, nan.copy(), nan.copy(), math.nan, math.nan, code
+    fwd = sorted(train, key=lambda e: e[:3])
+    ll, info, fw = _loo_taps(name, fwd, alpha, rho, p, n, vb, False, after_update=(_slip == "with_self"))
+    if info:
+        return nan, nan.copy(), nan.copy(), math.nan, math.nan, info
+    bwd = sorted(train, key=lambda e: (-e[0], e[1], e[2])) if _slip == "tie_both" else fwd[::-1]
+    _, _, bw = _loo_taps(name, bwd, alpha, rho, p, n, vb, True)
+    P0 = _prior(name, rho, p, n, vb)
+    sc = 1.0 / np.sqrt(np.diag(P0))
+    I0 = np.linalg.inv(sc[:, None] * P0 * sc[None, :])
+    D = np.ones(n)
+    if p >= 2:
+        D[1] = -1.0
+    # the caller's position of sorted point (band, position)
+    off = np.concatenate([[0], np.cumsum([len(t) for t in tarray])])
+    perms = [np.argsort(np.asarray(t, np.float64), kind="stable") for t in tarray]
+    mu, var, lp = nan.copy(), nan.copy(), nan.copy()
+    bad = N
+    for (s, b, i, r, s2) in train:
+        o = int(off[b] + (i if _slip == "sorted_order" else perms[b][i]))
+        Ps = None
+        if (b, i) in bw:
+            mf, Pf = fw[(b, i)]
+            mb, Pb = bw[(b, i)]
+            mb, Pb = D * mb, D[:, None] * Pb * D[None, :]
+            If = _spd_inverse(sc[:, None] * Pf * sc[None, :])
+            Ib = _spd_inverse(sc[:, None] * Pb * sc[None, :])
+            if If is not None and Ib is not None:
+                Ps = _spd_inverse(If + Ib - I0)
+        v = math.nan
+        if Ps is not None:
+            ms = Ps @ (If @ (sc * mf) + Ib @ (sc * mb))
+            h = np.zeros(n)
+            h[0] = alpha[b]
+            if n > p:
+                h[p + b] = 1.0
+            h = h / sc
+            mean = h @ ms
+            v = h @ Ps @ h + (0.0 if _slip == "no_sigma" else s2) + (JITTER if _slip == "jitter" else 0.0)
+        if not (v > 0.0 and math.isfinite(v) and mean == mean):
+            bad = min(bad, o)
+            continue
+        e = r - mean
+        mu[o], var[o], lp[o] = mean + means[b], v, -0.5 * (LOG2PI + math.log(v) + e * e / v)
+    if bad < N:
+        return nan, nan.copy(), nan.copy(), math.nan, ll, N + bad + 1
+    return mu, var, lp, float(np.sum(lp)), ll, 0
+
+
+def loo_mix(lp, weights, _slip=None):
+    """(mix_lp[N], mix_loo) of the rows' lp[M, N]: mix_lp_i = -log sum_m p_m exp(-lp_mi), p = w / sum w, the device's running
+    max-shifted log-sum-exp per point in row order (zero-weight rows skipped; a failed row with weight makes it NaN; one row of weight 1
+    returns its own bits), and mix_loo = sum_i mix_lp_i.  _slip "arith_mix": the arithmetic mean log sum_m p_m exp(lp_mi) instead."""
+    lp = np.asarray(lp, np.float64)
+    w = np.asarray(weights, np.float64)
+    p = w / np.sum(w)
+    sg = 1.0 if _slip == "arith_mix" else -1.0
+    out = np.empty(lp.shape[1])
+    for i in range(lp.shape[1]):
+        mx, s, nan = -math.inf, 0.0, False
+        for m_ in range(len(p)):
+            if p[m_] == 0.0:
+                continue
+            x = sg * lp[m_, i]
+            if x != x:
+                nan = True
+                continue
+            lx = math.log(p[m_]) + x
+            if lx == -math.inf:
+                continue
+            if s == 0.0:
+                mx, s = lx, 1.0
+            elif lx <= mx:
+                s += math.exp(lx - mx)
+            else:
+                s = s * math.exp(mx - lx) + 1.0
+                mx = lx
+        out[i] = math.nan if nan else (sg * -math.inf if s == 0.0 else sg * (mx + math.log(s)))
+    return out, float(np.sum(out))
+
+
 def mix_moments(mu, var, weights):
     """The device's mixture over rows (gpcc_predict_batch's semantics): p = w / sum w, a running weighted mean and sum of squared
     deviations in row order; zero-weight rows skipped."""
@@ -917,6 +1060,7 @@ class MarkovObjective:
     def __init__(self, tarray, yarray, stdarray, kernel, marginalise_b=True):
         self.data = (tarray, yarray, stdarray)
         self.kernel, self.marginalise_b, self.L = _name(kernel), bool(marginalise_b), len(tarray)
+        self.yflat = np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in yarray])
 
     def loglik_markov_batch(self, delays, alpha, rho):
         return loglik_batch(self.kernel, *self.data, delays, alpha, rho, self.marginalise_b)
@@ -955,6 +1099,17 @@ class MarkovObjective:
         held = np.array([o[0] for o in out])
         mix = mix_logsumexp(held, weights) if weights is not None else None
         return held, np.array([o[1] for o in out]), np.array([o[2] for o in out], dtype=np.int32), mix
+
+    def loo_markov_batch(self, delays, alpha, rho, weights=None, outputs=None):
+        """Objective.loo_markov_batch's result: LooResult(mu[M, N], var[M, N], lp[M, N], loo[M], loglik[M], info[M], mix_lp, mix_loo)
+        (outputs is accepted and ignored: everything is computed)."""
+        from .api import LooResult
+        delays, alpha, rho = self._rows(delays, alpha, rho)
+        out = [loo(self.kernel, *self.data, delays[i], alpha[i], rho[i], self.marginalise_b) for i in range(len(rho))]
+        lp = np.array([o[2] for o in out])
+        mix = loo_mix(lp, weights) if weights is not None else (None, None)
+        return LooResult(np.array([o[0] for o in out]), np.array([o[1] for o in out]), lp, np.array([o[3] for o in out]),
+                         np.array([o[4] for o in out]), np.array([o[5] for o in out], dtype=np.int32), mix[0], mix[1])
 
     def posterior_offsets_markov_batch(self, delays, alpha, rho):
         """Objective.posterior_offsets_markov_batch's result: (mu_b[M, L], Sigma_b[M, L, L], loglik[M], info[M])."""

@@ -418,6 +418,50 @@ int gpcc_heldout_loglik_batch(gpcc_handle_t h, int M, const double *delays, cons
                               const double *ttest, const double *ytest, const double *sigmatest, const double *weights,
                               double *heldout, double *mix_heldout, double *loglik, int *info);
 
+/* Exact leave-one-out (LOO) predictive scores at M rows (tau, alpha, rho) -- gpcc_predict_batch's row layout.  K, bbar and Y are
+ * exactly objective(alpha, rho)'s (B included when b is marginalised); no JITTER is added: this is p(y_i | y_-i) of the model the
+ * likelihood uses.  With G = K^-1 and w = G (Y - bbar), for every training point i, numbered in the CALLER'S order (band 1 as handed
+ * to gpcc_create, then band 2, ...):
+ *   var_i = 1 / G_ii,  mu_i = y_i - w_i / G_ii,  lp_i = -(log 2 pi + log var_i + (y_i - mu_i)^2 / var_i) / 2,  loo = sum_i lp_i.
+ * mu_out, var_out and lp_out are M x N, row-major; loo is M; mix_lp is N; mix_loo is 1.  Every output may be NULL (loglik and info
+ * too).  loglik[m] and info[m] are bitwise gpcc_loglik_grad_batch's (the same factorisation path), and
+ *   info 0: success;  1 .. N (or < 0): the training matrix failed, as gpcc_loglik_batch reports it -- the row's outputs NaN;
+ *   N + i (1 <= i <= N): point i is the first whose LOO variance is not positive and finite -- the row's mu, var, lp and loo NaN,
+ *   loglik[m] valid.  A failed row changes no other row.
+ * Mixture (weights != NULL, M entries): p_m = w_m / sum w.  With alpha and rho fixed per delay, the exact LOO density of the mixture
+ * is the weighted HARMONIC mean of the rows' densities (p(y_i | y_-i) = p(y) / p(y_-i)):
+ *   mix_lp_i = -log sum_m p_m exp(-lp_mi),  mix_loo = sum_i mix_lp_i,
+ * one running max-shifted log-sum-exp per point over the rows in row order (one row of weight 1 returns its own bits); rows with
+ * p_m = 0 are skipped, failed or not; a failed row with p_m > 0 makes mix_lp and mix_loo NaN (the call still returns 0).  A negative
+ * or non-finite weight, or sum w = 0, returns GPCC_ERR_ARGUMENT before any device work, as does mix_lp or mix_loo without weights.
+ * Path: the gradient's factorisation, X = L^-1 and w (gpcc_loglik_grad_batch without its tile products), then G_ii = sum_k X_ki^2 from
+ * one read of the N^2 / 2 doubles of X (kernels: csrc/gpcc_loo.hip.h).  Always fp64 (an fp32 handle on its fp64 twin);
+ * a multi-device handle computes on device_ids[0].  No atomics: bitwise repeatable, and a row's bits do not depend on M, the group,
+ * the stream / slot options or the row order.  Memory: the gradient's buffers, 8 Np bytes per workspace slot, 8 M N bytes for each of
+ * mu, var, lp that is asked for (lp also for the mixture), 8 M bytes, and with a mixture 32 N + 8 M bytes.  Blocking. */
+int gpcc_loo_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const double *weights,
+                   double *mu_out, double *var_out, double *lp_out, double *loo, double *mix_lp, double *mix_loo, double *loglik,
+                   int *info);
+
+/* gpcc_loo_batch in LINEAR time for the Markov kernels (OU, Matern-3/2, Matern-5/2), exact: the same arguments, outputs, NULL rules,
+ * weight checks and mixture.  The posterior of the process at training point i given every other observation is the two-filter combine
+ * of gpcc_predict_markov_batch taken at the point itself -- the forward filter's state propagated to s_i = t_i - tau_band before its
+ * update with point i, and the backward filter's likewise, the backward walk being the exact reverse of the forward merged order (ties
+ * included), so that every other point is on exactly one side of i -- and with h of the point's band
+ *   mu_i = h'm_s + mean(y_band),  var_i = h'P_s h + sigma_i^2.
+ * Outputs are in the caller's order.  loglik[m] and info[m] (-1, -2, 1 .. N) are bitwise gpcc_loglik_markov_batch's; info[m] = N + i:
+ * point i (1-based, the caller's order) is the first whose combine met a pivot, or whose variance is, not positive and finite -- the
+ * row's mu, var, lp and loo NaN, loglik[m] valid.  Refusals: gpcc_loglik_markov_batch's (GPCC_ERR_UNSUPPORTED: rbf; marginalise_b with
+ * L > 4).  Kernels: csrc/gpcc_markov_loo.hip.h (one lane per (row, direction), then one lane per (row, point)), DESIGN.md 4.20.  A row's
+ * bits do not depend on M, the chunking, the row order or the launch shape.  Always fp64 (an fp32 handle on its fp64 twin); a
+ * multi-device handle computes on device_ids[0].  Memory, grown on demand: gpcc_loglik_markov_batch's, 8 N bytes of point indices, the
+ * tap scratch 16 N (n + n (n + 1) / 2) bytes per row of a chunk (n = p + L offsets <= 7; shared with gpcc_predict_markov_batch), the
+ * chunk being the rows that fit 128 MiB (whole waves of 64 when it holds one; at least one row; option "markov_chunk_rows" > 0 sets
+ * it), 24 N bytes per row of the chunk, 8 M bytes, and with a mixture 32 N + 8 M bytes; none of the N^2 workspace.  Blocking. */
+int gpcc_loo_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const double *weights,
+                          double *mu_out, double *var_out, double *lp_out, double *loo, double *mix_lp, double *mix_loo, double *loglik,
+                          int *info);
+
 /* Joint posterior draws of the light curves at M rows (tau, alpha, rho) -- gpcc_predict_batch's row layout -- on one test set shared by
  * every row (Ntest[l] points per band, flattened in band order in ttest; 1 <= T = sum Ntest <= 32768; Ntest[l] = 0 allowed).  One draw
  * of row m is f* = mu_pred + chol(Sigma_pred + JITTER I + diag(sigmatest^2)) zeta, zeta ~ N(0, I_T), with gpcc_predict's mu_pred and

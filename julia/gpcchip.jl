@@ -118,6 +118,37 @@ function heldout_loglik_markov_batch(h::Handle, delays::Matrix{Float64}, alpha::
     return held, ll, info, (weights === nothing ? nothing : mix[1])
 end
 
+"Exact leave-one-out predictive scores at M rows (gpcc_loo_batch; linear = true: gpcc_loo_markov_batch, OU / matern32 / matern52 in
+linear time): for every training point i, in the order the light curves were handed over, the mean, variance and log-density of y_i
+given every other observation, under the model of objective(alpha, rho) (no JITTER) -> (mu N×M, var N×M, lp N×M, loo[M], ll[M], info[M],
+mix) with mix = nothing, or with weights (mix_lp[N], mix_loo): mix_lp_i = -log sum_m p_m exp(-lp_mi), the exact LOO log-density of the
+delay mixture.  info = N + i: point i is the first whose variance is not positive and finite (the column is NaN)."
+function loo_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64};
+                   weights::Union{Nothing,Vector{Float64}} = nothing, linear::Bool = false)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    N = Int(ccall((:gpcc_get_option, LIB), Clong, (Ptr{Cvoid}, Cstring), h.ptr, "N"))
+    mu, var, lp = Matrix{Float64}(undef, N, M), Matrix{Float64}(undef, N, M), Matrix{Float64}(undef, N, M)
+    loo, ll, info = Vector{Float64}(undef, M), Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    mlp, mloo = Vector{Float64}(undef, N), Vector{Float64}(undef, 1)
+    wp = weights === nothing ? C_NULL : pointer(weights)
+    GC.@preserve weights begin
+        rc = linear ?
+            ccall((:gpcc_loo_markov_batch, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                   Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+                  h.ptr, M, delays, alpha, rho, wp, mu, var, lp, loo, weights === nothing ? C_NULL : pointer(mlp),
+                  weights === nothing ? C_NULL : pointer(mloo), ll, info) :
+            ccall((:gpcc_loo_batch, LIB), Cint,
+                  (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                   Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+                  h.ptr, M, delays, alpha, rho, wp, mu, var, lp, loo, weights === nothing ? C_NULL : pointer(mlp),
+                  weights === nothing ? C_NULL : pointer(mloo), ll, info)
+    end
+    rc == 0 || error("gpcc_loo_batch: " * lasterror(h.ptr))
+    return mu, var, lp, loo, ll, info, (weights === nothing ? nothing : (mlp, mloo[1]))
+end
+
 "posterior_offsets at M rows in LINEAR time (gpcc_posterior_offsets_markov_batch: the offset block of the filter's final state):
 (mu_postb L×M, Sigma_postb L×L×M, ll[M], info[M]); columns with info != 0 are NaN.  Needs marginalise_b."
 function posterior_offsets_markov_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
