@@ -14,6 +14,7 @@
 #include "gpcc_markov_sample.hip.h"
 #include "gpcc_markov_grad.hip.h"
 #include "gpcc_markov_hess.hip.h"
+#include "gpcc_markov_hess_tau.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -260,6 +261,11 @@ struct gpcc_handle_s {
     double *d_mkhs = nullptr, *d_mkhb = nullptr;
     long mkhs_cap = 0, mkhb_cap = 0;
     int mkh_configured = 0;
+    // linear-time rows of tau of the Hessian (gpcc_loglik_hess_markov_batch): the per-pair results [tau pair slots][M] and the blocks
+    // [M][(2L + 1)^2]
+    double *d_mkts = nullptr, *d_mktb = nullptr;
+    long mkts_cap = 0, mktb_cap = 0;
+    int mkt_configured = 0;
     int laplace_markov = 0;              // option "laplace_markov": gpcc_laplace_evidence's rounds are gpcc_loglik_hess_hyper_markov_batch calls
     int markov_chunk_rows = 0;           // option "markov_chunk_rows": rows per chunk of gpcc_predict_markov_batch (0: by the scratch budget)
     // linear-time draws (gpcc_sample_markov_batch): grown on demand -- the combine's weights of a chunk of rows (mksw_cap doubles), the
@@ -575,6 +581,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_mksw); hipFree(h->d_mksrt); hipFree(h->d_mksacc); hipFree(h->d_mksi);
     hipFree(h->d_mkgs); hipFree(h->d_mkgr);
     hipFree(h->d_mkhs); hipFree(h->d_mkhb);
+    hipFree(h->d_mkts); hipFree(h->d_mktb);
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
     hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
     hipFree(h->d_smean); hipFree(h->d_sdraw); hipFree(h->d_szeta); hipFree(h->d_slist); hipFree(h->d_soff);
@@ -2595,6 +2602,38 @@ extern "C" int gpcc_loglik_grad_markov_batch(gpcc_handle_t h, int M, const doubl
 // and gradient come from the gradient entry's launches inside the same call (bitwise gpcc_loglik_grad_markov_batch's by construction);
 // it needs what that entry needs plus the pair slots and the blocks, nothing of the N^2 workspace.
 // ------------------------------------------------------------------------------------------
+// the block's buffers for M rows on top of the gradient's, and its launches over the M staged rows: the gradient's, then (with_hess)
+// gpcc_markov_hess and its finish kernel, the blocks left in d_mkhb.  gpcc_loglik_hess_markov_batch shares both
+static int markov_hess_hyper_grow(gpcc_handle_t h, int M, bool with_hess)
+{
+    const int n = h->L + 1;
+    int g = markov_grad_grow(h, M);
+    if (!g && with_hess) g = grow_buf(h, &h->d_mkhs, &h->mkhs_cap, (long)gpcc_markov_hess_slots(h->L) * M);
+    return (g || !with_hess) ? g : grow_buf(h, &h->d_mkhb, &h->mkhb_cap, (long)n * n * M);
+}
+
+static int markov_hess_hyper_enqueue(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, double *grad, bool with_hess)
+{
+    const MarkovDims d = markov_dims(h);
+    const int slots = gpcc_markov_hess_slots(h->L);
+    const int rc = markov_grad_enqueue(h, M, dd, da, dr, grad);
+    if (rc || !with_hess) return rc;
+    if (!h->mkh_configured) {
+        HIPCHK(h, gpcc_markov_hess_configure());
+        h->mkh_configured = 1;
+    }
+    GpccMarkovHessArgs a;
+    markov_fill_args(h, M, dd, da, dr, a);
+    a.slot = h->d_mkhs; a.hess = h->d_mkhb;
+    size_t lds;
+    const int threads = markov_launch_shape(h, (((long)M + 63) / 64) * slots,
+                                            [&](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }, a.stage, lds);
+    const hipError_t e = gpcc_markov_hess_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), slots, threads, lds,
+                                                 h->main_stream);
+    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_hess: %s", hipGetErrorString(e));
+    return 0;
+}
+
 extern "C" int gpcc_loglik_hess_hyper_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                                    double *loglik, double *grad, double *hess, int *info)
 {
@@ -2614,32 +2653,66 @@ extern "C" int gpcc_loglik_hess_hyper_markov_batch(gpcc_handle_t h, int M, const
                    [&](gpcc_handle_t o) { return gpcc_loglik_hess_hyper_markov_batch(o, M, delays, alpha, rho, loglik, grad, hess, info); }))
         return rc;
     GPCC_ON_DEVICE(h, h->device);
+    double *dd, *da, *dr;
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] { return markov_hess_hyper_grow(h, M, hess != nullptr); });
+    if (rc) return rc;
+    rc = markov_hess_hyper_enqueue(h, M, dd, da, dr, grad, hess != nullptr);
+    if (rc) return rc;
+    if (hess) HIPCHK(h, hipMemcpyAsync(hess, h->d_mkhb, sizeof(double) * (h->L + 1) * (h->L + 1) * M, hipMemcpyDeviceToHost, h->main_stream));
+    return markov_finish(h, M, loglik, info);
+}
+
+// ------------------------------------------------------------------------------------------
+// The linear-time full Hessian of the Markov kernels (gpcc_loglik_hess_markov_batch; kernel: gpcc_markov_hess_tau.hip.h, DESIGN.md
+// 4.21): the rows of tau by the same second-order forward sensitivities, one lane per (row, pair slot with a tau).  Value, info,
+// gradient and the leading (alpha, rho) block come from gpcc_loglik_hess_hyper_markov_batch's launches inside the same call (bitwise
+// that entry's by construction); it needs what that entry needs plus the new slots and the full blocks, nothing of the N^2 workspace.
+// ------------------------------------------------------------------------------------------
+extern "C" int gpcc_loglik_hess_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                             double *loglik, double *grad, double *hess, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (M == 0) return 0;
+    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    int rc = markov_refusals(h, "gpcc_loglik_hess_markov_batch", "gpcc_loglik_hess_batch");
+    if (rc) return rc;
+    {
+        const MarkovDims d = markov_dims(primary(h));
+        if (!gpcc_markov_hess_tau_shipped(d.p, d.noff))
+            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_hess_markov_batch: the instantiation <%d, %d> (states of the process, "
+                        "offset states) needs scratch memory and does not ship; use gpcc_loglik_hess_batch", d.p, d.noff);
+    }
+    if (route_fp64(h, "linear-time Hessian", rc,
+                   [&](gpcc_handle_t o) { return gpcc_loglik_hess_markov_batch(o, M, delays, alpha, rho, loglik, grad, hess, info); }))
+        return rc;
+    GPCC_ON_DEVICE(h, h->device);
     const MarkovDims d = markov_dims(h);
-    const int n = h->L + 1, slots = gpcc_markov_hess_slots(h->L);
+    const int W = 2 * h->L + 1, slots = gpcc_markov_hess_tau_slots(h->L);
     double *dd, *da, *dr;
     rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
-        int g = markov_grad_grow(h, M);
-        if (!g && hess) g = grow_buf(h, &h->d_mkhs, &h->mkhs_cap, (long)slots * M);
-        return (g || !hess) ? g : grow_buf(h, &h->d_mkhb, &h->mkhb_cap, (long)n * n * M);
+        int g = markov_hess_hyper_grow(h, M, hess != nullptr);
+        if (!g && hess) g = grow_buf(h, &h->d_mkts, &h->mkts_cap, (long)slots * M);
+        return (g || !hess) ? g : grow_buf(h, &h->d_mktb, &h->mktb_cap, (long)W * W * M);
     });
     if (rc) return rc;
-    rc = markov_grad_enqueue(h, M, dd, da, dr, grad);
+    rc = markov_hess_hyper_enqueue(h, M, dd, da, dr, grad, hess != nullptr);
     if (rc) return rc;
     if (hess) {
-        if (!h->mkh_configured) {
-            HIPCHK(h, gpcc_markov_hess_configure());
-            h->mkh_configured = 1;
+        if (!h->mkt_configured) {
+            HIPCHK(h, gpcc_markov_hess_tau_configure());
+            h->mkt_configured = 1;
         }
-        GpccMarkovHessArgs a;
+        GpccMarkovHessTauArgs a;
         markov_fill_args(h, M, dd, da, dr, a);
-        a.slot = h->d_mkhs; a.hess = h->d_mkhb;
+        a.slot = h->d_mkts; a.hyper = h->d_mkhb; a.hess = h->d_mktb;
         size_t lds;
         const int threads = markov_launch_shape(h, (((long)M + 63) / 64) * slots,
                                                 [&](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }, a.stage, lds);
-        const hipError_t e = gpcc_markov_hess_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), slots, threads, lds,
-                                                     h->main_stream);
-        if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_hess: %s", hipGetErrorString(e));
-        HIPCHK(h, hipMemcpyAsync(hess, h->d_mkhb, sizeof(double) * n * n * M, hipMemcpyDeviceToHost, h->main_stream));
+        const hipError_t e = gpcc_markov_hess_tau_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), slots, threads, lds,
+                                                         h->main_stream);
+        if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_hess_tau: %s", hipGetErrorString(e));
+        HIPCHK(h, hipMemcpyAsync(hess, h->d_mktb, sizeof(double) * W * W * M, hipMemcpyDeviceToHost, h->main_stream));
     }
     return markov_finish(h, M, loglik, info);
 }

@@ -19,8 +19,8 @@
 //            ll_ab -= (S_ab / S - S_a S_b / S^2 + 2 eps_a eps_b / S + 2 g eps_ab - 2 g (eps_a S_b + eps_b S_a) / S - g^2 S_ab
 //                      + 2 g^2 S_a S_b / S) / 2,  then the second tangents of mu += Ph g and C -= k Ph', k = Ph / S
 //
-// NOT HERE.  The Fisher information (its expectation needs another recursion) and the rows of tau (OU's second-order tie convention
-// is not a mean of two filter orders) stay with gpcc_loglik_hess_batch / gpcc_loglik_hess_hyper_batch.
+// NOT HERE.  The Fisher information (its expectation needs another recursion) stays with gpcc_loglik_hess_batch /
+// gpcc_loglik_hess_hyper_batch.  The rows of tau are gpcc_markov_hess_tau.hip.h's (gpcc_loglik_hess_markov_batch), built from these pieces.
 //
 // gpcc_markov_hess<P, NOFF>: ONE LANE PER (ROW, PAIR SLOT), a <= b, the slot being blockIdx.y: (L + 1)(L + 2) / 2 slots in the order
 // (0,0), (0,1), .., (0,L), (1,1), ..  A workgroup is uniform in its pair, and the walk is a template on the kind of pair: an

@@ -112,6 +112,36 @@ def laplace_covariance(H, free, L=None):
     return cov, True
 
 
+def delay_covariance(objective, delays, alpha, rho, free=None, solver="dense"):
+    """The Laplace covariance of the delays (and hyper-parameters) at one point (delays[L], alpha[L], rho): one Hessian call over
+    [alpha_1..alpha_L, rho, tau_1..tau_L] -- objective.loglik_hess_batch (solver "dense") or objective.loglik_hess_markov_batch (solver
+    "markov": linear time, OU / matern32 / matern52; Objective's or markov.MarkovObjective's) -- then
+    laplace_covariance over `free` -> (cov, ok).  free defaults to every alpha, rho and tau_2..tau_L (the first delay fixed: a common
+    shift of all delays leaves the likelihood unchanged).  ok is False and cov all NaN when the point cannot be evaluated (info != 0),
+    when a needed entry of the Hessian is NaN (solver "markov" with OU at a delay that makes two bands' shifted times collide: use
+    "dense" there) or when -H_ff is not positive definite.  ValueError for another solver, or for a `free` that holds every delay."""
+    if solver not in ("dense", "markov"):
+        raise ValueError("solver must be 'dense' or 'markov', got %r" % (solver,))
+    delays = np.asarray(delays, dtype=np.float64).reshape(1, -1)
+    L = delays.shape[1]
+    alpha = np.asarray(alpha, dtype=np.float64).reshape(1, L)
+    rho = np.asarray(rho, dtype=np.float64).reshape(1)
+    if free is None:
+        free = list(range(L + 1)) + list(range(L + 2, 2 * L + 1))
+    free = np.asarray(free)
+    idx = np.flatnonzero(free) if free.dtype == bool else free.astype(int).ravel()
+    if set(range(L + 1, 2 * L + 1)) <= set(idx.tolist()):
+        raise ValueError("free holds every delay: a common shift of all delays leaves the likelihood unchanged, fix at least one")
+    if solver == "markov":
+        _, _, hess, info = objective.loglik_hess_markov_batch(delays, alpha, rho)
+    else:
+        _, _, hess, _, info = objective.loglik_hess_batch(delays, alpha, rho)
+    H = np.asarray(hess, dtype=np.float64)[0]
+    if info[0] != 0 or not np.all(np.isfinite(H[np.ix_(idx, idx)])):
+        return np.full((len(idx), len(idx)), np.nan), False
+    return laplace_covariance(H, idx, L)
+
+
 def nearestposdef(A, minimumeigenvalue=1e-6):
     """MiscUtil.nearestposdef(A; minimumeigenvalue) as used at marginaliseb.jl:331 -- MiscUtil's source is not
     available (unregistered dependency), so this is the assumed definition: symmetrise, eigendecompose, lift every

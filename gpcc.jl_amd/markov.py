@@ -304,8 +304,19 @@ def loglik_grad_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marg
 #                      + 2 g^2 S_a S_b / S) / 2,
 #             then the second tangents of m += Ph g and P -= k Ph', k = Ph / S
 #
-# The Fisher information is not offered in linear time (its expectation needs another recursion), nor the rows of tau (OU's
-# second-order tie convention is not a mean of two filter orders): both stay with the dense Hessian.
+# The rows of tau (loglik_hess; csrc/gpcc_markov_hess_tau.hip.h) are the same recursion with other tangents of the
+# transition.  With c_l = d lag / d tau_l = -[band = l] + [bprev = l] (0 at the first point; _grad_pass's dd) and F = companion():
+#
+#   A_tau_l = c_l F A,   A_rho,tau_l = c_l (F_rho A + F A_rho),   A_tau_l,tau_m = c_l c_m F F A,   A_alpha,. = 0,
+#
+# and every tangent of Pinf, of the prior and of h by a tau is zero.  The Matern kernels are twice differentiable at zero lag, so the
+# fixed-order second tangent is the derivative, ties or not.  OU is not: on a row where two points of different bands have exactly
+# equal shifted times (a step with d == 0 and band != bprev) no second derivative by tau exists, the dense Hessian's convention there
+# (k_ss = 1 / rho^2, k_rs = 0) is bilinear in the one-sided dK's, so no filter order returns it, and every entry with a tau index is
+# NaN (info stays 0; value, gradient and the (alpha, rho) block are untouched): use the dense Hessian for OU on a grid of delays that
+# collides with the cadence.
+#
+# The Fisher information is not offered in linear time (its expectation needs another recursion): it stays with the dense Hessian.
 # ----------------------------------------------------------------------------------------------------------------------------------
 def transition_d2lambda(kernel, d, rho):
     """d2A(d)/dlambda2, in closed form per kernel."""
@@ -352,33 +363,61 @@ def stationary_d2rho(kernel, rho, _chain=True):
     return out
 
 
+def companion_drho(kernel, rho):
+    """dF/drho, with dlambda/drho = -lambda / rho."""
+    name = _name(kernel)
+    lam = rate(name, rho)
+    dl = -lam / rho
+    if name == "OU":
+        return np.array([[-dl]])
+    if name == "matern32":
+        return np.array([[0.0, 0.0], [-2.0 * lam * dl, -2.0 * dl]])
+    return np.array([[0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [-3.0 * lam * lam * dl, -6.0 * lam * dl, -3.0 * dl]])
+
+
 def _hess_pass(name, train, alpha, rho, p, n, vb, a, b, slip=None):
-    """d2 loglik / d theta_a d theta_b (a, b in 0..L: alpha_1..alpha_L, rho) by the second-order tangent recursion over the training
-    observations in merge_order()'s order.  slip: loglik_hess_hyper()'s."""
+    """d2 loglik / d theta_a d theta_b (a <= b in 0..2L: alpha_1..alpha_L, rho, tau_1..tau_L) by the second-order tangent recursion
+    over the training observations in merge_order()'s order.  A pair with a tau on an OU row with a cross-band tie in shifted time has
+    no second derivative: NaN.  slip: loglik_hess_hyper()'s and loglik_hess()'s."""
     L = len(alpha)
     ev = sorted(train, key=lambda e: (e[0], e[1], e[2]))
     ra, rb = a == L, b == L
+    ta, tb = a - L - 1, b - L - 1           # the band of a tau (negative: not a tau)
     chain = slip != "chain_rho"
     zero = np.zeros((p, p))
     Pinf = stationary(name, rho)
     Qa = stationary_drho(name, rho) if ra else zero
     Qb = stationary_drho(name, rho) if rb else zero
     Qab = stationary_d2rho(name, rho, chain) if (ra and rb and slip != "no_d2pinf") else zero
+    F = companion(name, rho)
+    Fr = zero if slip == "no_dF" else companion_drho(name, rho)
     P = _prior(name, rho, p, n, vb)
     Pa, Pb, Pab = np.zeros((n, n)), np.zeros((n, n)), np.zeros((n, n))
     Pa[:p, :p], Pb[:p, :p], Pab[:p, :p] = Qa, Qb, Qab
     m, ma, mb, mab = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
-    hll, sprev = 0.0, None
+    hll, sprev, bprev = 0.0, None, -1
     for (s, band, _, r, s2) in ev:
         d = 0.0 if sprev is None else s - sprev
-        sprev = s
+        if tb >= 0 and name == "OU" and sprev is not None and d == 0.0 and band != bprev:
+            return math.nan
+        # c_l = d lag / d tau_l: -[band = l] + [bprev = l], 0 at the first point
+        ca = 0.0 if (ta < 0 or sprev is None) else -float(band == ta) + (0.0 if slip == "tau_one_lag" else float(bprev == ta))
+        cb = 0.0 if (tb < 0 or sprev is None) else -float(band == tb) + (0.0 if slip == "tau_one_lag" else float(bprev == tb))
+        sprev, bprev = s, band
         A = transition(name, d, rho)
-        Aa = transition_drho(name, d, rho) if ra else zero
-        Ab = transition_drho(name, d, rho) if rb else zero
-        Aab = transition_d2rho(name, d, rho, chain) if (ra and rb and slip != "no_d2a") else zero
+        Aa = transition_drho(name, d, rho) if ra else (ca * (F @ A) if ca != 0.0 else zero)
+        Ab = transition_drho(name, d, rho) if rb else (cb * (F @ A) if cb != 0.0 else zero)
+        if ra and rb:
+            Aab = transition_d2rho(name, d, rho, chain) if slip != "no_d2a" else zero
+        elif ra and cb != 0.0:
+            Aab = cb * (Fr @ A + F @ Aa)
+        elif ca != 0.0 and cb != 0.0 and slip != "no_d2tau":
+            Aab = (ca * cb) * (F @ (F @ A))
+        else:
+            Aab = zero
         X = slice(0, p)
         D, Da, Db, Dab = P[X, X] - Pinf, Pa[X, X] - Qa, Pb[X, X] - Qb, Pab[X, X] - Qab
-        cross = zero if slip == "no_cross" else Aa @ D @ Ab.T + Ab @ D @ Aa.T
+        cross = zero if (slip == "no_cross" or (slip == "no_cross_tau" and tb >= 0)) else Aa @ D @ Ab.T + Ab @ D @ Aa.T
         mab[X] = Aab @ m[X] + Aa @ mb[X] + Ab @ ma[X] + A @ mab[X]
         Pab[X, X] = (Aab @ D @ A.T + A @ D @ Aab.T + cross + Aa @ Db @ A.T + A @ Db @ Aa.T + Ab @ Da @ A.T + A @ Da @ Ab.T
                      + A @ Dab @ A.T + Qab)
@@ -462,6 +501,41 @@ def loglik_hess_hyper_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho
     out = [loglik_hess_hyper(kernel, tarray, yarray, stdarray, delays[i], alpha[i], rho[i], marginalise_b) for i in range(len(rho))]
     return (np.array([o[0] for o in out]), np.array([o[1] for o in out]).reshape(-1, 2 * L + 1),
             np.array([o[2] for o in out]).reshape(-1, L + 1, L + 1), np.array([o[3] for o in out], dtype=np.int32))
+
+
+def loglik_hess(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True, _slip=None):
+    """(loglik, grad[2L+1], hess[2L+1, 2L+1], info) of one (tau, alpha, rho): loglik_hess_hyper()'s value, gradient, info and leading
+    (L+1) x (L+1) block, and the rows of tau by the same recursion, over [alpha_1..alpha_L, rho, tau_1..tau_L]:
+    Objective.loglik_hess_markov_batch's row.  Each pair is computed once and mirrored.  grad and hess are NaN where info != 0.  On an
+    OU row with a cross-band tie in shifted time every entry with a tau index is NaN and info stays 0 (no second derivative exists
+    there: use the dense Hessian); with one band the tau entries are exact zeros.
+    _slip (tests only) injects one mistake: "no_d2tau" (A_tautau left out), "no_dF" (the F_rho A term of A_rho,tau left out),
+    "no_cross_tau" (the A_a D A_b' cross terms of the step left out when b is a tau), "tau_one_lag" (only the lag before a point of band
+    l is differentiated, not the one after)."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b,
+                                                                       codes_first=True)
+    W = 2 * L + 1
+    ll, grad, hyper, info = loglik_hess_hyper(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b)
+    hess = np.full((W, W), math.nan)
+    if info:
+        return ll, grad, hess, info
+    hess[:L + 1, :L + 1] = hyper
+    for a in range(W):
+        for b in range(max(a, L + 1), W):
+            hess[a, b] = hess[b, a] = _hess_pass(name, train, alpha, rho, p, n, vb, a, b, slip=_slip)
+    return ll, grad, hess, 0
+
+
+def loglik_hess_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True):
+    """loglik_hess over M rows -> (loglik[M], grad[M, 2L+1], hess[M, 2L+1, 2L+1], info[M]): Objective.loglik_hess_markov_batch's shape."""
+    L = len(tarray)
+    W = 2 * L + 1
+    delays = np.asarray(delays, np.float64).reshape(-1, L)
+    alpha = np.asarray(alpha, np.float64).reshape(-1, L)
+    rho = np.asarray(rho, np.float64).reshape(-1)
+    out = [loglik_hess(kernel, tarray, yarray, stdarray, delays[i], alpha[i], rho[i], marginalise_b) for i in range(len(rho))]
+    return (np.array([o[0] for o in out]), np.array([o[1] for o in out]).reshape(-1, W),
+            np.array([o[2] for o in out]).reshape(-1, W, W), np.array([o[3] for o in out], dtype=np.int32))
 
 
 JITTER = 1e-8   # added to every predictive variance and to sigma*^2 of a held-out point (gpcc_predict_batch's constant)
@@ -1076,6 +1150,10 @@ class MarkovObjective:
         laplace.laplace_evidence runs over this objective."""
         ll, grad, hess, info = self.loglik_hess_hyper_markov_batch(delays, alpha, rho)
         return ll, grad, hess, None, info
+
+    def loglik_hess_markov_batch(self, delays, alpha, rho):
+        """Objective.loglik_hess_markov_batch's result: (loglik[M], grad[M, 2L+1], hess[M, 2L+1, 2L+1], info[M])."""
+        return loglik_hess_batch(self.kernel, *self.data, delays, alpha, rho, self.marginalise_b)
 
     def _rows(self, delays, alpha, rho):
         delays = np.asarray(delays, np.float64).reshape(-1, self.L)

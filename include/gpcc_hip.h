@@ -218,7 +218,7 @@ int gpcc_loglik_batch(gpcc_handle_t handle, int M, const double *delays, const d
  * entry instead of a gpcc_loglik_batch (GPCC_ERR_UNSUPPORTED where this entry is); read-only "markov_count": evaluations so far.
  * Predictions, held-out scores and the offsets' posterior in linear time: the three entries below; the gradient in linear time:
  * gpcc_loglik_grad_markov_batch after them; the (alpha, rho) block of the Hessian is gpcc_loglik_hess_hyper_markov_batch, the full
- * Hessian (the rows of tau) and the Fisher information stay dense.
+ * Hessian (the rows of tau) gpcc_loglik_hess_markov_batch; the Fisher information stays dense.
  * Blocking. */
 int gpcc_loglik_markov_batch(gpcc_handle_t handle, int M, const double *delays, const double *alpha, const double *rho,
                              double *loglik, int *info);
@@ -335,14 +335,39 @@ int gpcc_loglik_hess_hyper_batch(gpcc_handle_t h, int M, const double *delays, c
  * out of scratch memory does not ship and is refused the same way, the message naming gpcc_loglik_hess_hyper_batch: at present <3, 4>
  * alone, Matern-5/2 with marginalise_b and L = 4 (it takes all 512 registers of a lane and 28 bytes more); everything else that
  * gpcc_loglik_markov_batch takes ships (DESIGN.md 4.18 has the table).
- * NOT offered in linear time: the Fisher information (its expectation needs another recursion) and the rows of tau -- the full
- * Hessian -- (OU's second-order tie convention is not a mean of two filter orders); both stay with the dense entries above.
+ * NOT offered in linear time: the Fisher information (its expectation needs another recursion), which stays with the dense entries
+ * above.  The rows of tau -- the full Hessian -- are gpcc_loglik_hess_markov_batch below.
  * Memory: gpcc_loglik_grad_markov_batch's, plus 8 M bytes per pair ((L+1)(L+2)/2 of them) and 8 M (L+1)^2 bytes; none of the N^2
  * workspace.  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Blocking.
  * Option "laplace_markov" (default 0; refused where "fit_markov" is): gpcc_laplace_evidence's Newton rounds call this entry instead of
  * gpcc_loglik_hess_hyper_batch. */
 int gpcc_loglik_hess_hyper_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                         double *loglik, double *grad, double *hess, int *info);
+
+/* The FULL Hessian in LINEAR TIME for the Markov kernels, over theta = [alpha_1..alpha_L, rho, tau_1..tau_L], P = 2L+1
+ * (gpcc_loglik_hess_batch's order): the same second-order forward sensitivities with the tangents of the transition by the lags
+ * (kernel: csrc/gpcc_markov_hess_tau.hip.h).  loglik[M], info[M] and grad are bitwise gpcc_loglik_grad_markov_batch's
+ * and the leading (L+1) x (L+1) block of every hess block is bitwise gpcc_loglik_hess_hyper_markov_batch's: both come from that
+ * entry's launches inside the same call.  hess (may be NULL: then the call is gpcc_loglik_grad_markov_batch): M row-major P x P
+ * blocks, every pair computed once and written to both halves (bitwise symmetric), NaN where info != 0.  There is no Fisher argument:
+ * the Fisher information still needs a recursion of its own.
+ *   TIES.  Matern-3/2 and Matern-5/2 are twice differentiable at zero lag: the rows of tau are exact whether or not two bands' shifted
+ *   times coincide.  OU is not.  On a row in which two points of DIFFERENT bands have exactly equal shifted times (a delay equal to a
+ *   difference of two observation times) no second derivative by tau exists, and gpcc_loglik_hess_batch's convention there
+ *   (k_ss = 1/rho^2, k_rs = 0) is bilinear in the one-sided derivatives of K, so no order of the filter returns it: for such a row
+ *   EVERY ENTRY WITH A tau INDEX IS NaN, info[m] stays 0, and loglik, grad and the leading (alpha, rho) block are untouched.  Use
+ *   gpcc_loglik_hess_batch for OU on a grid of delays that collides with the cadence.  OU rows without such a tie are exact.  With
+ *   L = 1 the tau entries are exact zeros.
+ * Refusals, argument checks, info codes and memory rules are gpcc_loglik_markov_batch's (rbf, and marginalise_b with L > 4:
+ * GPCC_ERR_UNSUPPORTED before any device work; -1 / -2 rows never touch the others).  An instantiation that needs scratch memory does
+ * not ship and is refused the same way, the message naming gpcc_loglik_hess_batch (DESIGN.md 4.21 has the table; <3, 4>, Matern-5/2
+ * with marginalise_b and L = 4, is refused as it is by gpcc_loglik_hess_hyper_markov_batch).
+ * Path: one lane per (row, pair slot) with a tau in the pair -- L^2 (alpha, tau), L (rho, tau), L (tau_l, tau_l) and L (L - 1) / 2
+ * (tau_l, tau_m) slots -- in one launch, then a kernel that writes the blocks.  No atomics: a row's bits depend on the row alone.
+ * Memory: gpcc_loglik_hess_hyper_markov_batch's, plus 8 M bytes per new slot and 8 M P^2 bytes, grown on demand; none of the N^2
+ * workspace.  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Blocking. */
+int gpcc_loglik_hess_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                  double *loglik, double *grad, double *hess, int *info);
 
 /* Same with DEVICE pointers, enqueued behind `stream` (a hipStream_t, NULL = default stream) and
  * joined back into it: asynchronous, outputs valid once `stream` has drained. */
