@@ -1,7 +1,11 @@
 // gpcc_markov.hip.h -- the exact linear-time log-likelihood of the Markov kernels (OU, Matern-3/2, Matern-5/2) for gfx950:
 // gpcc_loglik_markov_batch of include/gpcc_hip.h; gpcc.jl_amd/markov.py is the same algorithm in numpy.  This file owns
-// the Kalman filter itself (gpcc_mk_init, gpcc_mk_transition, gpcc_mk_propagate, gpcc_mk_update): gpcc_markov_eval below and
-// gpcc_markov_taps of gpcc_markov_pred.hip.h are two walks over the data around the one step.
+// the Kalman filter itself (gpcc_mk_init, gpcc_mk_transition, gpcc_mk_propagate, gpcc_mk_update) and the forward walk over the data
+// around it (GpccMkLane, gpcc_mk_open, gpcc_mk_next).  Seven kernels walk the data around the one step.  Four go forward once and share
+// this file's cursor: gpcc_markov_eval below, gpcc_markov_grad, gpcc_markov_hess and gpcc_markov_hess_tau (their own headers).  Three
+// go forward and backward and share the cursor of gpcc_markov_pred.hip.h (GpccMkpLane, gpcc_mkp_next): gpcc_markov_taps there,
+// gpcc_markov_draw (gpcc_markov_sample.hip.h) and gpcc_markov_loo_taps (gpcc_markov_loo.hip.h).  The merged order -- the lowest band
+// first on ties, and each exception to it -- is written in those two places only.
 //
 // f with one of these kernels is a stationary Gauss-Markov process of state dimension P = 1, 2, 3 (f, f', f''), so with all
 // observations merged in the order of their shifted times s = t - tau_band, K = alpha alpha' k(s - s') + Sobs (+ B) is the covariance
@@ -49,7 +53,7 @@ static inline size_t gpcc_markov_lds_bytes(int N, int L, int threads, bool stage
 // element (i, j) of a symmetric matrix kept in its upper triangle (constant indices after unrolling)
 #define GPCC_MK_SYM(Q, i, j) ((i) <= (j) ? Q[i][j] : Q[j][i])
 
-// ---- the filter, shared by gpcc_markov_eval and gpcc_markov_taps (gpcc_markov_pred.hip.h).  Everything is __forceinline__ and takes its
+// ---- the filter, shared by every kernel of the linear-time path.  Everything is __forceinline__ and takes its
 // arrays by reference, so that after unrolling they stay in registers; the compiler's FMA contraction of these statements, in this
 // order, decides the bits of every entry point ----
 
@@ -215,61 +219,111 @@ __device__ __forceinline__ bool gpcc_mk_update(int b, double al, double r, doubl
     return ok;
 }
 
+// ---- the forward walk, shared by gpcc_markov_eval below, gpcc_markov_grad, gpcc_markov_hess and gpcc_markov_hess_tau: what a lane
+// keeps outside its registers, the kernel's prologue (gpcc_mk_open) and the choice of the next observation (gpcc_mk_next).  ARGS:
+// any argument struct with GpccMarkovArgs' fields ----
+
+struct GpccMkLane {
+    const double *pts;                     // t[N] | r[N] | sigma^2[N]: the staged copy in LDS, or global memory
+    double *shead, *stau, *salpha;         // LDS, [band][thread]: the shifted time of each band's next point, tau, alpha
+    int *scur;                             // LDS, [band][thread]: the index of each band's next point
+    int nthr, tid;
+    long row;                              // blockIdx.x * nthr + tid
+    bool valid;                            // row < M; a lane beyond M walks row M - 1 and stores nothing
+    double rho;
+    int info;                              // gpcc_mk_load_row's
+};
+
+// the observation taken: its band, residual, variance, the band's alpha and the lag from the one before (0 at the first)
+struct GpccMkPoint {
+    int b;
+    double r, s2, al, d;
+};
+
+// the prologue: carves the workgroup's dynamic LDS (gpcc_markov_lds_bytes), stages pts, loads the lane's row, sets the cursors
+template <class ARGS>
+__device__ __forceinline__ GpccMkLane gpcc_mk_open(const ARGS &a, double *lds)
+{
+    GpccMkLane ln;
+    const int tid = ln.tid = threadIdx.x, nthr = ln.nthr = blockDim.x, L = a.L, N = a.N;
+    ln.shead = lds + (a.stage ? 3L * N : 0);
+    ln.stau = ln.shead + L * nthr;
+    ln.salpha = ln.stau + L * nthr;
+    ln.scur = (int *)(ln.salpha + L * nthr);
+    if (a.stage)
+        for (int i = tid; i < 3 * N; i += nthr) lds[i] = a.pts[i];
+    ln.pts = a.stage ? (const double *)lds : a.pts;
+    ln.row = (long)blockIdx.x * nthr + tid;
+    ln.valid = ln.row < a.M;
+    const long m_ = ln.valid ? ln.row : a.M - 1;
+    ln.rho = a.rho[m_];
+    ln.info = gpcc_mk_load_row(a, m_, ln.rho, ln.stau, ln.salpha, nthr, tid);
+    __syncthreads();
+    for (int l = 0; l < L; ++l) {
+        ln.scur[l * nthr + tid] = a.off[l];
+        ln.shead[l * nthr + tid] = ln.pts[a.off[l]] - ln.stau[l * nthr + tid];
+    }
+    return ln;
+}
+
+// step j: the L-way merge takes the band whose head has the smallest shifted time, the lowest band on ties, moves its cursor on,
+// refills its head and forms the lag from sprev (the shifted time of step j - 1: the caller's, updated here).  RANKED, a compile-time
+// rule (as a run-time one it costs gpcc_markov_eval registers): a band's rank among ties is its index, except band rb's, which is rr
+// (the gradient's first / last pair, gpcc_markov_grad.hip.h)
+template <bool RANKED, class ARGS>
+__device__ __forceinline__ GpccMkPoint gpcc_mk_next(const ARGS &a, const GpccMkLane &ln, int j, double &sprev, int rb, int rr)
+{
+    const int N = a.N, nthr = ln.nthr, tid = ln.tid;
+    int b = -1, rk = 0;
+    double s = 0.0;
+    for (int l = 0; l < a.L; ++l) {
+        const double sl = ln.shead[l * nthr + tid];
+        const bool live = ln.scur[l * nthr + tid] < a.off[l + 1];
+        const int rl = (RANKED && l == rb) ? rr : l;
+        const bool take = live && (b < 0 || sl < s || (RANKED && sl == s && rl < rk));
+        b = take ? l : b;
+        s = take ? sl : s;
+        rk = take ? rl : rk;
+    }
+    const int i = ln.scur[b * nthr + tid];
+    const GpccMkPoint p = {b, ln.pts[N + i], ln.pts[2 * N + i], ln.salpha[b * nthr + tid], (j == 0) ? 0.0 : s - sprev};
+    ln.scur[b * nthr + tid] = i + 1;
+    if (i + 1 < a.off[b + 1]) ln.shead[b * nthr + tid] = ln.pts[i + 1] - ln.stau[b * nthr + tid];
+    sprev = s;
+    return p;
+}
+
+// the unranked rule has no rank pair to take; the ranked one cannot be called without
+template <bool RANKED, class ARGS>
+__device__ __forceinline__ GpccMkPoint gpcc_mk_next(const ARGS &a, const GpccMkLane &ln, int j, double &sprev)
+{
+    static_assert(!RANKED, "gpcc_mk_next<true> needs the band rb and its rank rr");
+    return gpcc_mk_next<false>(a, ln, j, sprev, -1, 0);
+}
+
 template <int P, int NOFF>
 __global__ void __launch_bounds__(256) gpcc_markov_eval(const GpccMarkovArgs a)
 {
     constexpr int NS = P + NOFF;
     extern __shared__ __attribute__((aligned(16))) double gpcc_mk_lds[];
-    const int tid = threadIdx.x, nthr = blockDim.x, L = a.L, N = a.N;
-    double *shead = gpcc_mk_lds + (a.stage ? 3L * N : 0);
-    double *stau = shead + L * nthr, *salpha = stau + L * nthr;
-    int *scur = (int *)(salpha + L * nthr);
-    if (a.stage)
-        for (int i = tid; i < 3 * N; i += nthr) gpcc_mk_lds[i] = a.pts[i];
-    const double *pts = a.stage ? (const double *)gpcc_mk_lds : a.pts;
-
-    const long row = (long)blockIdx.x * nthr + tid;
-    const bool valid = row < a.M;
-    const long m_ = valid ? row : a.M - 1;
-    const double rho = a.rho[m_];
-    int info = gpcc_mk_load_row(a, m_, rho, stau, salpha, nthr, tid);
-    __syncthreads();
-    for (int l = 0; l < L; ++l) {
-        scur[l * nthr + tid] = a.off[l];
-        shead[l * nthr + tid] = pts[a.off[l]] - stau[l * nthr + tid];
-    }
+    const GpccMkLane ln = gpcc_mk_open(a, gpcc_mk_lds);
 
     double lam, lam2, Q[P][P], mu[NS], C[NS][NS];
-    gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
+    gpcc_mk_init<P, NOFF>(ln.rho, a.sigma_b, lam, lam2, Q, mu, C);
 
     double ll = 0.0, sprev = 0.0;
-    for (int j = 0; j < N; ++j) {
-        // merge: the band whose head has the smallest shifted time, the lowest band on ties
-        int b = -1;
-        double s = 0.0;
-        for (int l = 0; l < L; ++l) {
-            const double sl = shead[l * nthr + tid];
-            const bool live = scur[l * nthr + tid] < a.off[l + 1];
-            const bool take = live && (b < 0 || sl < s);
-            b = take ? l : b;
-            s = take ? sl : s;
-        }
-        const int i = scur[b * nthr + tid];
-        const double r = pts[N + i], s2 = pts[2 * N + i], al = salpha[b * nthr + tid];
-        scur[b * nthr + tid] = i + 1;
-        if (i + 1 < a.off[b + 1]) shead[b * nthr + tid] = pts[i + 1] - stau[b * nthr + tid];
-        const double d = (j == 0) ? 0.0 : s - sprev;
-        sprev = s;
-
+    int info = ln.info;
+    for (int j = 0; j < a.N; ++j) {
+        const GpccMkPoint p = gpcc_mk_next<false>(a, ln, j, sprev);
         double A[P][P];
-        gpcc_mk_transition<P>(lam, lam2, d, A);
+        gpcc_mk_transition<P>(lam, lam2, p.d, A);
         gpcc_mk_propagate<P, NOFF>(A, Q, mu, C);
-        const bool ok = gpcc_mk_update<P, NOFF>(b, al, r, s2, mu, C, ll);
+        const bool ok = gpcc_mk_update<P, NOFF>(p.b, p.al, p.r, p.s2, mu, C, ll);
         info = (info == 0 && !ok) ? j + 1 : info;   // first predictive variance that is not positive and finite
     }
-    if (valid) {
-        a.out_loglik[row] = info ? __builtin_nan("") : ll;
-        a.out_info[row] = info;
+    if (ln.valid) {
+        a.out_loglik[ln.row] = info ? __builtin_nan("") : ll;
+        a.out_info[ln.row] = info;
     }
 }
 

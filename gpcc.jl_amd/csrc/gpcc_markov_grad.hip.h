@@ -24,10 +24,11 @@
 // gpcc_markov_grad<P, NOFF>: ONE LANE PER (ROW, PARAMETER SLOT), the slot being blockIdx.y, so a workgroup is uniform in what it
 // differentiates: L alpha slots, one rho slot, L tau slots (OU: 2L).  The body is specialised by the kind of slot: an alpha lane
 // carries no dA, a tau lane forms dA only on the steps next to a point of its band, the rho lane on every step.  State and tangent
-// state are register-resident (2 (n + n (n + 1) / 2) <= 70 doubles at n = 7); cursors, heads, tau and alpha in LDS, [band][thread],
-// and the light curves staged in LDS when they fit, exactly as in gpcc_markov_eval (gpcc_markov_lds_bytes is the accounting of both).
-// The primal recursion is the one filter step of gpcc_markov.hip.h, called once.  Per-slot results go to slot[slot][row], so a wave's
-// stores coalesce.  Lanes beyond M compute row M - 1 again and store nothing.  No atomics, no communication between lanes.
+// state are register-resident (2 (n + n (n + 1) / 2) <= 70 doubles at n = 7).  The lane and its merge are gpcc_markov.hip.h's
+// (gpcc_mk_open, gpcc_mk_next with the ranked tie rule; LDS as gpcc_markov_lds_bytes counts it); the walk keeps the band of the point
+// before (bprev) for the lags' tangents.  The primal recursion is the one filter step of gpcc_markov.hip.h, called once.  Per-slot
+// results go to slot[slot][row], so a wave's stores coalesce.  Lanes beyond M compute row M - 1 again and store nothing.  No atomics,
+// no communication between lanes.
 #pragma once
 #include "gpcc_markov.hip.h"
 
@@ -259,13 +260,12 @@ __device__ __forceinline__ void gpcc_mkg_update(int b, double al, bool dh, doubl
 }
 
 // one lane's walk: KIND of slot, tb: the band of an alpha or tau slot, rb / rr: the band whose rank among ties is rr instead of its
-// index (rb = -1: none)
+// index (rb = -1: none), handed to gpcc_mk_next<true>
 template <int P, int NOFF, int KIND>
-__device__ __forceinline__ double gpcc_mkg_walk(const GpccMarkovGradArgs &a, const double *pts, double *shead, const double *stau,
-                                                const double *salpha, int *scur, double rho, int tb, int rb, int rr, int nthr, int tid)
+__device__ __forceinline__ double gpcc_mkg_walk(const GpccMarkovGradArgs &a, const GpccMkLane &ln, int tb, int rb, int rr)
 {
     constexpr int NS = P + NOFF;
-    const int L = a.L, N = a.N;
+    const double rho = ln.rho;
     double lam, lam2, Q[P][P], mu[NS], C[NS][NS];
     gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
     // the tangents: zero, except the rho lane's prior state (dPinf)
@@ -281,25 +281,10 @@ __device__ __forceinline__ double gpcc_mkg_walk(const GpccMarkovGradArgs &a, con
 
     double ll = 0.0, dll = 0.0, sprev = 0.0;
     int bprev = -1;
-    for (int j = 0; j < N; ++j) {
-        // merge: the band whose head has the smallest shifted time; on ties the lowest rank (a band's rank is its index, except rb's)
-        int b = -1, rk = 0;
-        double s = 0.0;
-        for (int l = 0; l < L; ++l) {
-            const double sl = shead[l * nthr + tid];
-            const bool live = scur[l * nthr + tid] < a.off[l + 1];
-            const int rl = (l == rb) ? rr : l;
-            const bool take = live && (b < 0 || sl < s || (sl == s && rl < rk));
-            b = take ? l : b;
-            s = take ? sl : s;
-            rk = take ? rl : rk;
-        }
-        const int i = scur[b * nthr + tid];
-        const double r = pts[N + i], s2 = pts[2 * N + i], al = salpha[b * nthr + tid];
-        scur[b * nthr + tid] = i + 1;
-        if (i + 1 < a.off[b + 1]) shead[b * nthr + tid] = pts[i + 1] - stau[b * nthr + tid];
-        const double d = (j == 0) ? 0.0 : s - sprev;
-        sprev = s;
+    for (int j = 0; j < a.N; ++j) {
+        const GpccMkPoint p = gpcc_mk_next<true>(a, ln, j, sprev, rb, rr);
+        const int b = p.b;
+        const double d = p.d;
 
         double A[P][P], Ad[P][P];
         gpcc_mk_transition<P>(lam, lam2, d, A);
@@ -320,8 +305,8 @@ __device__ __forceinline__ double gpcc_mkg_walk(const GpccMarkovGradArgs &a, con
         bprev = b;
         gpcc_mkg_propagate<P, NOFF, KIND>(A, Ad, ad, Q, Qd, mu, C, dmu, dC);
         gpcc_mk_propagate<P, NOFF>(A, Q, mu, C);
-        gpcc_mkg_update<P, NOFF, KIND>(b, al, KIND == GPCC_MKG_ALPHA && b == tb, r, s2, mu, C, dmu, dC, dll);
-        gpcc_mk_update<P, NOFF>(b, al, r, s2, mu, C, ll);
+        gpcc_mkg_update<P, NOFF, KIND>(b, p.al, KIND == GPCC_MKG_ALPHA && b == tb, p.r, p.s2, mu, C, dmu, dC, dll);
+        gpcc_mk_update<P, NOFF>(b, p.al, p.r, p.s2, mu, C, ll);
     }
     return dll;
 }
@@ -330,38 +315,21 @@ template <int P, int NOFF>
 __global__ void __launch_bounds__(256) gpcc_markov_grad(const GpccMarkovGradArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double gpcc_mkg_lds[];
-    const int tid = threadIdx.x, nthr = blockDim.x, L = a.L, N = a.N;
-    double *shead = gpcc_mkg_lds + (a.stage ? 3L * N : 0);
-    double *stau = shead + L * nthr, *salpha = stau + L * nthr;
-    int *scur = (int *)(salpha + L * nthr);
-    if (a.stage)
-        for (int i = tid; i < 3 * N; i += nthr) gpcc_mkg_lds[i] = a.pts[i];
-    const double *pts = a.stage ? (const double *)gpcc_mkg_lds : a.pts;
-
-    const long row = (long)blockIdx.x * nthr + tid;
-    const bool valid = row < a.M;
-    const long m_ = valid ? row : a.M - 1;
-    const double rho = a.rho[m_];
-    gpcc_mk_load_row(a, m_, rho, stau, salpha, nthr, tid);
-    __syncthreads();
-    for (int l = 0; l < L; ++l) {
-        scur[l * nthr + tid] = a.off[l];
-        shead[l * nthr + tid] = pts[a.off[l]] - stau[l * nthr + tid];
-    }
+    const GpccMkLane ln = gpcc_mk_open(a, gpcc_mkg_lds);
+    const int L = a.L;
 
     // what this workgroup differentiates (uniform)
     const int slot = blockIdx.y;
     double dll;
     if (slot < L) {
-        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_ALPHA>(a, pts, shead, stau, salpha, scur, rho, slot, -1, 0, nthr, tid);
+        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_ALPHA>(a, ln, slot, -1, 0);
     } else if (slot == L) {
-        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_RHO>(a, pts, shead, stau, salpha, scur, rho, -1, -1, 0, nthr, tid);
+        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_RHO>(a, ln, -1, -1, 0);
     } else {
         const int q = slot - L - 1, tb = a.twice ? q >> 1 : q;
-        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_TAU>(a, pts, shead, stau, salpha, scur, rho, tb, a.twice ? tb : -1, (q & 1) ? L : -1, nthr,
-                                                   tid);
+        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_TAU>(a, ln, tb, a.twice ? tb : -1, (q & 1) ? L : -1);
     }
-    if (valid) a.slot[(long)slot * a.M + row] = dll;
+    if (ln.valid) a.slot[(long)slot * a.M + ln.row] = dll;
 }
 
 // ---- launches (gpcc_markov_grad_inst.hip: an object of its own) ----

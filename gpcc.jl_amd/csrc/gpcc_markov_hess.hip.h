@@ -23,14 +23,14 @@
 // gpcc_loglik_hess_hyper_batch.  The rows of tau are gpcc_markov_hess_tau.hip.h's (gpcc_loglik_hess_markov_batch), built from these pieces.
 //
 // gpcc_markov_hess<P, NOFF>: ONE LANE PER (ROW, PAIR SLOT), a <= b, the slot being blockIdx.y: (L + 1)(L + 2) / 2 slots in the order
-// (0,0), (0,1), .., (0,L), (1,1), ..  A workgroup is uniform in its pair, and the walk is a template on the kind of pair: an
-// alpha alpha lane forms no tangent of A, an alpha rho lane A_rho, the rho rho lane A_rho and A_rhorho; a diagonal pair carries three
-// sets, the others four.  State and tangents are register-resident (4 (n + n (n + 1) / 2) = 140 doubles at n = 7, in the unified
-// 512-register file at one wave per SIMD); cursors, heads, tau and alpha in LDS, [band][thread], the light curves staged in LDS when
-// they fit, exactly as in gpcc_markov_eval (gpcc_markov_lds_bytes).  The primal recursion is the one filter step of gpcc_markov.hip.h.
-// Per-slot results go to slot[slot][row]; gpcc_markov_hess_finish writes every pair to both halves of the row's (L+1) x (L+1) block
-// (bitwise symmetric), NaN where info != 0.  Lanes beyond M compute row M - 1 again and store nothing.  No atomics: a row's bits depend
-// on the row alone.
+// (0,0), (0,1), .., (0,L), (1,1), ..  A workgroup is uniform in its pair, and the walk is a template on the kind of pair: an alpha
+// alpha lane forms no tangent of A, an alpha rho lane A_rho, the rho rho lane A_rho and A_rhorho; a diagonal pair carries three sets,
+// the others four.  State and tangents are register-resident (4 (n + n (n + 1) / 2) = 140 doubles at n = 7, in the unified
+// 512-register file at one wave per SIMD).  The lane and its merge are gpcc_markov.hip.h's (gpcc_mk_open, gpcc_mk_next<false>:
+// gpcc_markov_eval's order; LDS as gpcc_markov_lds_bytes counts it), as the primal recursion is its one filter step.  Per-slot
+// results go to slot[slot][row]; gpcc_markov_hess_finish writes every pair to both halves of the row's (L+1) x (L+1) block (bitwise
+// symmetric), NaN where info != 0.  Lanes beyond M compute row M - 1 again and store nothing.  No atomics: a row's bits depend on the
+// row alone.
 #pragma once
 #include "gpcc_markov_grad.hip.h"
 
@@ -215,14 +215,13 @@ __device__ __forceinline__ void gpcc_mkh_update(int b, double al, bool ha, bool 
 
 // one lane's walk over the merged observations for the pair (pa, pb) of kind PAIR (pa, pb: the bands of its alphas)
 template <int P, int NOFF, int PAIR>
-__device__ __forceinline__ double gpcc_mkh_walk(const GpccMarkovHessArgs &a, const double *pts, double *shead, const double *stau,
-                                                const double *salpha, int *scur, double rho, int pa, int pb, int nthr, int tid)
+__device__ __forceinline__ double gpcc_mkh_walk(const GpccMarkovHessArgs &a, const GpccMkLane &ln, int pa, int pb)
 {
     constexpr int NS = P + NOFF;
     constexpr bool DIAG = PAIR == GPCC_MKH_AA_DIAG || PAIR == GPCC_MKH_RR;
     constexpr bool RHO = PAIR == GPCC_MKH_AR || PAIR == GPCC_MKH_RR;      // some tangent of A is formed
     constexpr int KA = PAIR == GPCC_MKH_RR ? GPCC_MKG_RHO : GPCC_MKG_ALPHA, KB = RHO ? GPCC_MKG_RHO : GPCC_MKG_ALPHA;
-    const int L = a.L, N = a.N;
+    const double rho = ln.rho;
     double lam, lam2, Q[P][P], mu[NS], C[NS][NS];
     gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
     // Pinf_rho, Pinf_rhorho = (lambda / rho)^2 d2Pinf/dlambda2 - (2 / rho) Pinf_rho, and a zero block
@@ -256,23 +255,10 @@ __device__ __forceinline__ double gpcc_mkh_walk(const GpccMarkovHessArgs &a, con
     }
 
     double ll = 0.0, dll = 0.0, hll = 0.0, sprev = 0.0;
-    for (int j = 0; j < N; ++j) {
-        // merge: the band whose head has the smallest shifted time, the lowest band on ties (gpcc_markov_eval's order)
-        int b = -1;
-        double s = 0.0;
-        for (int l = 0; l < L; ++l) {
-            const double sl = shead[l * nthr + tid];
-            const bool live = scur[l * nthr + tid] < a.off[l + 1];
-            const bool take = live && (b < 0 || sl < s);
-            b = take ? l : b;
-            s = take ? sl : s;
-        }
-        const int i = scur[b * nthr + tid];
-        const double r = pts[N + i], s2 = pts[2 * N + i], al = salpha[b * nthr + tid];
-        scur[b * nthr + tid] = i + 1;
-        if (i + 1 < a.off[b + 1]) shead[b * nthr + tid] = pts[i + 1] - stau[b * nthr + tid];
-        const double d = (j == 0) ? 0.0 : s - sprev;
-        sprev = s;
+    for (int j = 0; j < a.N; ++j) {
+        const GpccMkPoint p = gpcc_mk_next<false>(a, ln, j, sprev);
+        const int b = p.b;
+        const double d = p.d, al = p.al, r = p.r, s2 = p.s2;
 
         double A[P][P], Ar[P][P], Arr[P][P];
         gpcc_mk_transition<P>(lam, lam2, d, A);
@@ -310,24 +296,8 @@ template <int P, int NOFF>
 __global__ void __launch_bounds__(256) gpcc_markov_hess(const GpccMarkovHessArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double gpcc_mkh_lds[];
-    const int tid = threadIdx.x, nthr = blockDim.x, L = a.L, N = a.N;
-    double *shead = gpcc_mkh_lds + (a.stage ? 3L * N : 0);
-    double *stau = shead + L * nthr, *salpha = stau + L * nthr;
-    int *scur = (int *)(salpha + L * nthr);
-    if (a.stage)
-        for (int i = tid; i < 3 * N; i += nthr) gpcc_mkh_lds[i] = a.pts[i];
-    const double *pts = a.stage ? (const double *)gpcc_mkh_lds : a.pts;
-
-    const long row = (long)blockIdx.x * nthr + tid;
-    const bool valid = row < a.M;
-    const long m_ = valid ? row : a.M - 1;
-    const double rho = a.rho[m_];
-    gpcc_mk_load_row(a, m_, rho, stau, salpha, nthr, tid);
-    __syncthreads();
-    for (int l = 0; l < L; ++l) {
-        scur[l * nthr + tid] = a.off[l];
-        shead[l * nthr + tid] = pts[a.off[l]] - stau[l * nthr + tid];
-    }
+    const GpccMkLane ln = gpcc_mk_open(a, gpcc_mkh_lds);
+    const int L = a.L;
 
     // the pair of this workgroup (uniform): slot -> (pa, pb), pa <= pb, rows of the upper triangle one after the other
     const int slot = blockIdx.y;
@@ -339,14 +309,14 @@ __global__ void __launch_bounds__(256) gpcc_markov_hess(const GpccMarkovHessArgs
     const int pb = pa + rest;
     double hll;
     if (pa == L)
-        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_RR>(a, pts, shead, stau, salpha, scur, rho, -1, -1, nthr, tid);
+        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_RR>(a, ln, -1, -1);
     else if (pb == L)
-        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AR>(a, pts, shead, stau, salpha, scur, rho, pa, -1, nthr, tid);
+        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AR>(a, ln, pa, -1);
     else if (pa == pb)
-        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AA_DIAG>(a, pts, shead, stau, salpha, scur, rho, pa, pa, nthr, tid);
+        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AA_DIAG>(a, ln, pa, pa);
     else
-        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AA_OFF>(a, pts, shead, stau, salpha, scur, rho, pa, pb, nthr, tid);
-    if (valid) a.slot[(long)slot * a.M + row] = hll;
+        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AA_OFF>(a, ln, pa, pb);
+    if (ln.valid) a.slot[(long)slot * a.M + ln.row] = hll;
 }
 
 // ---- the instantiations that ship, per P (gpcc_markov_hess_inst.hip: one object per P).  One that the compiler cannot keep out of

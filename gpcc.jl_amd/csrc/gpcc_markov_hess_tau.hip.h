@@ -24,13 +24,14 @@
 // NaN in its slot: on such a row every entry with a tau index is NaN, info stays 0, and value, gradient and the (alpha, rho) block are
 // untouched.  With L = 1 every c is 0 and the entries are exact zeros.
 //
-// gpcc_markov_hess_tau<P, NOFF>: ONE LANE PER (ROW, PAIR SLOT), the slot being blockIdx.y, so a workgroup is uniform in its pair:
-// L^2 + L + L (L + 1) / 2 slots in the order (alpha_a, tau_l) [a L + l], (rho, tau_l), (tau_l, tau_l), (tau_l, tau_m) l < m row by row.
+// gpcc_markov_hess_tau<P, NOFF>: ONE LANE PER (ROW, PAIR SLOT), the slot being blockIdx.y, so a workgroup is uniform in its pair: L^2
+// + L + L (L + 1) / 2 slots in the order (alpha_a, tau_l) [a L + l], (rho, tau_l), (tau_l, tau_l), (tau_l, tau_m) l < m row by row.
 // The walk is a template on the kind of pair; a diagonal pair carries three sets, the others four.  State and tangents are
-// register-resident, cursors, heads, tau and alpha in LDS [band][thread], the light curves staged in LDS when they fit
-// (gpcc_markov_lds_bytes), exactly as in gpcc_markov_hess.  gpcc_markov_hess_tau_finish writes the (2L+1) x (2L+1) block: the leading
-// (L+1) x (L+1) block copied from gpcc_markov_hess_finish's of the same call, every tau pair to both halves (bitwise symmetric), NaN
-// where info != 0.  Lanes beyond M compute row M - 1 again and store nothing.  No atomics: a row's bits depend on the row alone.
+// register-resident.  The lane and its merge are gpcc_markov.hip.h's (gpcc_mk_open, gpcc_mk_next<false>: gpcc_markov_eval's order;
+// LDS as gpcc_markov_lds_bytes counts it); the walk keeps bprev, the lags' tangents ca / cb and OU's tie flag.
+// gpcc_markov_hess_tau_finish writes the (2L+1) x (2L+1) block: the leading (L+1) x (L+1) block copied from gpcc_markov_hess_finish's
+// of the same call, every tau pair to both halves (bitwise symmetric), NaN where info != 0.  Lanes beyond M compute row M - 1 again
+// and store nothing.  No atomics: a row's bits depend on the row alone.
 #pragma once
 #include "gpcc_markov_hess.hip.h"
 
@@ -135,13 +136,12 @@ __device__ __forceinline__ void gpcc_mkt_cross(const double (&A)[P][P], const do
 // one lane's walk over the merged observations for a pair of kind PAIR.  pa: the band of the pair's alpha (GPCC_MKT_AT), ta: of its
 // first tau (GPCC_MKT_TT_OFF), tb: of its (second) tau.  NaN on an OU row with a cross-band tie
 template <int P, int NOFF, int PAIR>
-__device__ __forceinline__ double gpcc_mkt_walk(const GpccMarkovHessTauArgs &a, const double *pts, double *shead, const double *stau,
-                                                const double *salpha, int *scur, double rho, int pa, int ta, int tb, int nthr, int tid)
+__device__ __forceinline__ double gpcc_mkt_walk(const GpccMarkovHessTauArgs &a, const GpccMkLane &ln, int pa, int ta, int tb)
 {
     constexpr int NS = P + NOFF;
     constexpr bool DIAG = PAIR == GPCC_MKT_TT_DIAG;
     constexpr int KA = PAIR == GPCC_MKT_AT ? GPCC_MKG_ALPHA : (PAIR == GPCC_MKT_RT ? GPCC_MKG_RHO : GPCC_MKG_TAU);
-    const int L = a.L, N = a.N;
+    const double rho = ln.rho;
     double lam, lam2, Q[P][P], mu[NS], C[NS][NS];
     gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
     // Pinf_rho (zero unless the pair has rho) and a zero block
@@ -173,23 +173,10 @@ __device__ __forceinline__ double gpcc_mkt_walk(const GpccMarkovHessTauArgs &a, 
     double ll = 0.0, dll = 0.0, hll = 0.0, sprev = 0.0;
     int bprev = -1;
     bool tie = false;
-    for (int j = 0; j < N; ++j) {
-        // merge: the band whose head has the smallest shifted time, the lowest band on ties (gpcc_markov_eval's order)
-        int b = -1;
-        double s = 0.0;
-        for (int l = 0; l < L; ++l) {
-            const double sl = shead[l * nthr + tid];
-            const bool live = scur[l * nthr + tid] < a.off[l + 1];
-            const bool take = live && (b < 0 || sl < s);
-            b = take ? l : b;
-            s = take ? sl : s;
-        }
-        const int i = scur[b * nthr + tid];
-        const double r = pts[N + i], s2 = pts[2 * N + i], al = salpha[b * nthr + tid];
-        scur[b * nthr + tid] = i + 1;
-        if (i + 1 < a.off[b + 1]) shead[b * nthr + tid] = pts[i + 1] - stau[b * nthr + tid];
-        const double d = (j == 0) ? 0.0 : s - sprev;
-        sprev = s;
+    for (int j = 0; j < a.N; ++j) {
+        const GpccMkPoint p = gpcc_mk_next<false>(a, ln, j, sprev);
+        const int b = p.b;
+        const double d = p.d, al = p.al, r = p.r, s2 = p.s2;
         if constexpr (P == 1) tie = tie || (j > 0 && d == 0.0 && b != bprev);
         // the lags' tangents by the pair's taus
         const int cb = (j == 0) ? 0 : (int)(bprev == tb) - (int)(b == tb);
@@ -258,35 +245,19 @@ template <int P, int NOFF>
 __global__ void __launch_bounds__(256) gpcc_markov_hess_tau(const GpccMarkovHessTauArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) double gpcc_mkt_lds[];
-    const int tid = threadIdx.x, nthr = blockDim.x, L = a.L, N = a.N;
-    double *shead = gpcc_mkt_lds + (a.stage ? 3L * N : 0);
-    double *stau = shead + L * nthr, *salpha = stau + L * nthr;
-    int *scur = (int *)(salpha + L * nthr);
-    if (a.stage)
-        for (int i = tid; i < 3 * N; i += nthr) gpcc_mkt_lds[i] = a.pts[i];
-    const double *pts = a.stage ? (const double *)gpcc_mkt_lds : a.pts;
-
-    const long row = (long)blockIdx.x * nthr + tid;
-    const bool valid = row < a.M;
-    const long m_ = valid ? row : a.M - 1;
-    const double rho = a.rho[m_];
-    gpcc_mk_load_row(a, m_, rho, stau, salpha, nthr, tid);
-    __syncthreads();
-    for (int l = 0; l < L; ++l) {
-        scur[l * nthr + tid] = a.off[l];
-        shead[l * nthr + tid] = pts[a.off[l]] - stau[l * nthr + tid];
-    }
+    const GpccMkLane ln = gpcc_mk_open(a, gpcc_mkt_lds);
+    const int L = a.L;
 
     // the pair of this workgroup (uniform)
     const int slot = blockIdx.y;
     double hll;
     if (slot < L * L) {
-        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_AT>(a, pts, shead, stau, salpha, scur, rho, slot / L, -1, slot % L, nthr, tid);
+        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_AT>(a, ln, slot / L, -1, slot % L);
     } else if (slot < L * L + L) {
-        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_RT>(a, pts, shead, stau, salpha, scur, rho, -1, -1, slot - L * L, nthr, tid);
+        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_RT>(a, ln, -1, -1, slot - L * L);
     } else if (slot < L * L + 2 * L) {
         const int l = slot - L * L - L;
-        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_TT_DIAG>(a, pts, shead, stau, salpha, scur, rho, -1, l, l, nthr, tid);
+        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_TT_DIAG>(a, ln, -1, l, l);
     } else {
         // (tau_l, tau_m), l < m, rows of the strict upper triangle one after the other
         int ta = 0, rest = slot - L * L - 2 * L;
@@ -294,9 +265,9 @@ __global__ void __launch_bounds__(256) gpcc_markov_hess_tau(const GpccMarkovHess
             rest -= L - 1 - ta;
             ++ta;
         }
-        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_TT_OFF>(a, pts, shead, stau, salpha, scur, rho, -1, ta, ta + 1 + rest, nthr, tid);
+        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_TT_OFF>(a, ln, -1, ta, ta + 1 + rest);
     }
-    if (valid) a.slot[(long)slot * a.M + row] = hll;
+    if (ln.valid) a.slot[(long)slot * a.M + ln.row] = hll;
 }
 
 // ---- the instantiations that ship, per P (gpcc_markov_hess_tau_inst.hip: one object per P).  One that the compiler cannot keep out

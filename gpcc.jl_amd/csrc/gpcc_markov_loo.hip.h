@@ -6,13 +6,14 @@
 // The posterior of the process at training point i given every OTHER observation is the two-filter combine of DESIGN.md 4.16 taken at
 // the point itself: the forward filter's state propagated to s_i BEFORE the update with point i, and the backward filter's likewise.
 //
-// gpcc_markov_loo_taps<P, NOFF>: ONE LANE PER (ROW, blockIdx.y).  blockIdx.y = 0: the filter of gpcc_markov_eval over the L-way merge of
-//   the bands in ascending shifted time (the lowest band first on ties); 1: the same points in exactly the reverse order (descending
-//   shifted time, the highest band first on ties, each band from its last point), lags |d| -- so every other point, tied or not, is on
-//   exactly one side of i.  At each point the state after gpcc_mk_propagate and before gpcc_mk_update is stored to the scratch
-//   [direction][point][component][row] (a wave's stores coalesce); the filter's chain is gpcc_markov_eval's, one call site of each
-//   step function, so lane 0's log-likelihood and info are its bits.  The direction is uniform per workgroup.  Lanes beyond the chunk's
-//   rows compute its last row again and store nothing.
+// gpcc_markov_loo_taps<P, NOFF>: ONE LANE PER (ROW, blockIdx.y).  blockIdx.y = 0: the filter of gpcc_markov_eval over the L-way merge
+//   of the bands in ascending shifted time (the lowest band first on ties); 1: the same points in exactly the reverse order
+//   (descending shifted time, the highest band first on ties, each band from its last point), lags |d| -- so every other point, tied
+//   or not, is on exactly one side of i.  The cursor is gpcc_markov_pred.hip.h's one-stream gpcc_mkp_next<true>: NOT
+//   gpcc_markov_taps' rule, which takes the lowest band in both directions.  At each point the state after gpcc_mk_propagate and
+//   before gpcc_mk_update is stored to the scratch [direction][point][component][row] (a wave's stores coalesce); the filter's chain
+//   is gpcc_markov_eval's, one call site of each step function, so lane 0's log-likelihood and info are its bits.  The direction is
+//   uniform per workgroup.  Lanes beyond the chunk's rows compute its last row again and store nothing.
 // gpcc_markov_loo_combine<P, NOFF>: one lane per (row, point): P_s = (P_f^-1 + P_b^-1 - P0^-1)^-1, m_s = P_s (P_f^-1 m_f + P_b^-1 m_b),
 //   scaled by diag(P0)^-1/2, the backward state mapped by D = diag(1, -1, 1); with h of the point's band
 //       mu_i = h'm_s + mean(y_band),  var_i = h'P_s h + sigma_i^2,  lp_i = -(log 2 pi + log var_i + (y_i - mu_i)^2 / var_i) / 2,
@@ -65,37 +66,18 @@ __global__ void __launch_bounds__(256) gpcc_markov_loo_taps(const GpccMarkovLooA
     const double rho = a.rho[m_];
     int info = gpcc_mk_load_row(a, m_, rho, stau, salpha, nthr, tid);
     __syncthreads();
-    const int step = rev ? -1 : 1;
-    for (int l = 0; l < L; ++l) {
-        const int i0 = rev ? a.off[l + 1] - 1 : a.off[l];
-        scur[l * nthr + tid] = i0;
-        const double base = pts[i0] - stau[l * nthr + tid];
-        shead[l * nthr + tid] = rev ? -base : base;
-    }
+    const GpccMkpLane cur = {pts, nullptr, shead, stau, scur, nthr, tid};
+    gpcc_mkp_rewind<false>(a, cur, rev);
 
     double lam, lam2, Q[P][P], mu[NS], C[NS][NS];
     gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
 
     double ll = 0.0, sprev = 0.0;
     for (int j = 0; j < N; ++j) {
-        // merge: the band whose head has the smallest key; on ties the lowest band forward, the highest backward
-        int b = -1;
-        double s = 0.0;
-        for (int l = 0; l < L; ++l) {
-            const double sl = shead[l * nthr + tid];
-            const int i = scur[l * nthr + tid];
-            const bool live = rev ? i >= a.off[l] : i < a.off[l + 1];
-            const bool take = live && (b < 0 || sl < s || (rev && sl == s));
-            b = take ? l : b;
-            s = take ? sl : s;
-        }
-        const int i = scur[b * nthr + tid];
-        const double r = pts[N + i], s2 = pts[2 * N + i], al = salpha[b * nthr + tid];
-        scur[b * nthr + tid] = i + step;
-        if (rev ? i - 1 >= a.off[b] : i + 1 < a.off[b + 1]) {
-            const double base = pts[i + step] - stau[b * nthr + tid];
-            shead[b * nthr + tid] = rev ? -base : base;
-        }
+        // the next point: on ties the lowest band forward, the highest backward
+        const GpccMkpPoint p = gpcc_mkp_next<true>(a, cur, rev);
+        const int b = p.band, i = p.i;
+        const double s = p.key, r = pts[N + i], s2 = pts[2 * N + i], al = salpha[b * nthr + tid];
         const double d = (j == 0) ? 0.0 : s - sprev;
         sprev = s;
 

@@ -2,7 +2,8 @@
 // Matern-3/2, Matern-5/2) for gfx950: gpcc_predict_markov_batch, gpcc_heldout_loglik_markov_batch and
 // gpcc_posterior_offsets_markov_batch of include/gpcc_hip.h; gpcc.jl_amd/markov.py (predict, heldout,
 // posterior_offsets) is the same algorithm in numpy.  The state-space model and the filter's step (gpcc_mk_*) are gpcc_markov.hip.h's;
-// nothing is approximated.
+// nothing is approximated.  This file owns the walk in either direction over training and test bands (GpccMkpLane, gpcc_mkp_rewind,
+// gpcc_mkp_next), which gpcc_markov_draw and gpcc_markov_loo_taps share.
 //
 // gpcc_markov_taps<P, NOFF, MODE>: ONE LANE PER (ROW, blockIdx.y).  The filter of gpcc_markov_eval with the same register-resident
 // state and the same functions, walking a 2L-way merge: L training streams that update the state and L test streams.
@@ -10,8 +11,9 @@
 //                           time, lags |d|; the process reversed in time is the same process with f' negated, which the combine
 //                           applies).  A test point is tapped: a COPY of the state is propagated to it and stored to the scratch
 //                           [direction][test point][component][row], so that a wave's stores coalesce; the filter's own chain is not
-//                           split, so lane 0's log-likelihood is bitwise gpcc_markov_eval's.  Ties in shifted time: a training point
-//                           that ties with a test point is on the forward side only (forward: training first; backward: test first).
+//                           split, so lane 0's log-likelihood is bitwise gpcc_markov_eval's.  Ties in shifted time (gpcc_mkp_next): a
+//                           training point that ties with a test point is on the forward side only (forward: training first;
+//                           backward: test first).
 //   MODE = GPCC_MKP_UPDATE  blockIdx.y = 0: the training filter alone; 1: the filter over training U test, the test points being
 //                           observations (residual and variance from tpts).  Their difference is the held-out log-likelihood.
 //                           Lane 0 can store the offset block of its final state (the offsets' posterior).
@@ -61,6 +63,124 @@ static inline size_t gpcc_mkp_lds_bytes(int N, int T, int tw, int L, int threads
     return (stage ? (size_t)24 * N + (size_t)8 * tw * T : 0) + (size_t)GPCC_MKP_LANE_BYTES * L * threads;
 }
 
+// ---- the walk in either direction, shared by gpcc_markov_taps below, gpcc_markov_draw (gpcc_markov_sample.hip.h) and
+// gpcc_markov_loo_taps (gpcc_markov_loo.hip.h).  A stream is L bands of sorted points (band l: off[l] .. off[l + 1] - 1) with its
+// cursors and heads in L slots of the lane's arrays: the training stream in slots 0 .. L - 1, the test stream in L .. 2L - 1.  A head
+// is the KEY of the band's next point: its shifted time walking forward, minus that walking backward (rev), so the smallest key is
+// next and a lag is a difference of keys.  Each kernel stages its points in its own layout and names the two time arrays ----
+
+struct GpccMkpLane {
+    const double *t, *tt;                  // the times of the training and of the test points (LDS when staged)
+    double *shead, *stau;                  // LDS: heads [slot][thread], tau [band][thread]
+    int *scur;                             // LDS: cursors [slot][thread]
+    int nthr, tid;
+};
+
+// the point taken: of the test stream or not, its band, its index and its key
+struct GpccMkpPoint {
+    bool is_test;
+    int band, i;
+    double key;
+};
+
+// every band's cursor to its first point of the direction (rev: its last), and its head; TESTS: both streams, else the training one
+template <bool TESTS, class ARGS>
+__device__ __forceinline__ void gpcc_mkp_rewind(const ARGS &a, const GpccMkpLane &c, bool rev)
+{
+    const int L = a.L, nthr = c.nthr, tid = c.tid;
+    for (int l = 0; l < L; ++l) {
+        const int i0 = rev ? a.off[l + 1] - 1 : a.off[l];
+        c.scur[l * nthr + tid] = i0;
+        const double base = c.t[i0] - c.stau[l * nthr + tid];
+        c.shead[l * nthr + tid] = rev ? -base : base;
+        if constexpr (TESTS) {
+            const int q0 = rev ? a.toff[l + 1] - 1 : a.toff[l];
+            c.scur[(L + l) * nthr + tid] = q0;
+            if (a.toff[l + 1] > a.toff[l]) {
+                const double tb = c.tt[q0] - c.stau[l * nthr + tid];
+                c.shead[(L + l) * nthr + tid] = rev ? -tb : tb;
+            }
+        }
+    }
+}
+
+// one stream's merge (slots slot0 .. slot0 + L - 1): b, the band with points left whose head has the smallest key (-1: none left),
+// and the key s.  Ties: the lowest band in both directions; REVERSE_TIES: the highest band when rev
+template <bool REVERSE_TIES>
+__device__ __forceinline__ void gpcc_mkp_pick(const GpccMkpLane &c, const int (&off)[GPCC_MARKOV_MAXL + 1], int L, int slot0, bool rev, int &b,
+                                              double &s)
+{
+    b = -1;
+    s = 0.0;
+    for (int l = 0; l < L; ++l) {
+        const double sl = c.shead[(slot0 + l) * c.nthr + c.tid];
+        const int i = c.scur[(slot0 + l) * c.nthr + c.tid];
+        const bool live = rev ? i >= off[l] : i < off[l + 1];
+        const bool take = live && (b < 0 || sl < s || (REVERSE_TIES && rev && sl == s));
+        b = take ? l : b;
+        s = take ? sl : s;
+    }
+}
+
+// takes the point at the head of the slot at k (= slot * nthr + tid): its index; the cursor moves on
+__device__ __forceinline__ int gpcc_mkp_advance(const GpccMkpLane &c, int k, bool rev)
+{
+    const int i = c.scur[k];
+    c.scur[k] = i + (rev ? -1 : 1);
+    return i;
+}
+
+// the head at k once point i of band b of the training (TEST: the test) stream is taken: the key of the band's next point, if any
+template <bool TEST, class ARGS>
+__device__ __forceinline__ void gpcc_mkp_refill(const ARGS &a, const GpccMkpLane &c, int k, int b, int i, bool rev)
+{
+    const double *t = c.t;
+    const int *off = a.off;
+    if constexpr (TEST) {
+        t = c.tt;
+        off = a.toff;
+    }
+    if (rev ? i - 1 >= off[b] : i + 1 < off[b + 1]) {
+        const double base = t[i + (rev ? -1 : 1)] - c.stau[b * c.nthr + c.tid];
+        c.shead[k] = rev ? -base : base;
+    }
+}
+
+// one step over both streams (use_tests false: the training stream alone).  A training point goes first on ties, except walking
+// backward, where the tying training point belongs to the forward side
+template <class ARGS>
+__device__ __forceinline__ GpccMkpPoint gpcc_mkp_next(const ARGS &a, const GpccMkpLane &c, bool rev, bool use_tests)
+{
+    int b, q = -1;
+    double s, sq = 0.0;
+    gpcc_mkp_pick<false>(c, a.off, a.L, 0, rev, b, s);
+    if (use_tests) gpcc_mkp_pick<false>(c, a.toff, a.L, a.L, rev, q, sq);
+    GpccMkpPoint p;
+    p.is_test = q >= 0 && (b < 0 || sq < s || (rev && sq == s));
+    p.band = p.is_test ? q : b;
+    p.key = p.is_test ? sq : s;
+    const int k = (p.is_test ? a.L + q : b) * c.nthr + c.tid;
+    p.i = gpcc_mkp_advance(c, k, rev);
+    if (p.is_test)
+        gpcc_mkp_refill<true>(a, c, k, q, p.i, rev);
+    else
+        gpcc_mkp_refill<false>(a, c, k, b, p.i, rev);
+    return p;
+}
+
+// one step over the training stream alone, with the tie rule as a parameter: REVERSE_TIES makes the backward walk the exact reverse
+// of the forward one, which gpcc_markov_loo_taps needs and the two-stream walks do not have (markov.py mirrors both rules)
+template <bool REVERSE_TIES, class ARGS>
+__device__ __forceinline__ GpccMkpPoint gpcc_mkp_next(const ARGS &a, const GpccMkpLane &c, bool rev)
+{
+    GpccMkpPoint p;
+    p.is_test = false;
+    gpcc_mkp_pick<REVERSE_TIES>(c, a.off, a.L, 0, rev, p.band, p.key);
+    p.i = gpcc_mkp_advance(c, p.band * c.nthr + c.tid, rev);
+    gpcc_mkp_refill<false>(a, c, p.band * c.nthr + c.tid, p.band, p.i, rev);
+    return p;
+}
+
 template <int P, int NOFF, int MODE>
 __global__ void __launch_bounds__(256) gpcc_markov_taps(const GpccMarkovPredArgs a)
 {
@@ -87,19 +207,8 @@ __global__ void __launch_bounds__(256) gpcc_markov_taps(const GpccMarkovPredArgs
     const double rho = a.rho[m_];
     int info = gpcc_mk_load_row(a, m_, rho, stau, salpha, nthr, tid);
     __syncthreads();
-    const int step = rev ? -1 : 1;
-    for (int l = 0; l < L; ++l) {
-        const int i0 = rev ? a.off[l + 1] - 1 : a.off[l];
-        scur[l * nthr + tid] = i0;
-        const double base = pts[i0] - stau[l * nthr + tid];
-        shead[l * nthr + tid] = rev ? -base : base;
-        const int q0 = rev ? a.toff[l + 1] - 1 : a.toff[l];
-        scur[(L + l) * nthr + tid] = q0;
-        if (a.toff[l + 1] > a.toff[l]) {
-            const double tb = tpts[q0] - stau[l * nthr + tid];
-            shead[(L + l) * nthr + tid] = rev ? -tb : tb;
-        }
-    }
+    const GpccMkpLane cur = {pts, tpts, shead, stau, scur, nthr, tid};
+    gpcc_mkp_rewind<true>(a, cur, rev);
 
     double lam, lam2, Q[P][P], mu[NS], C[NS][NS];
     gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
@@ -108,41 +217,14 @@ __global__ void __launch_bounds__(256) gpcc_markov_taps(const GpccMarkovPredArgs
     int jt = 0, at = 0;         // jt: updates so far
     const int total = N + (use_tests ? T : 0);
     for (int j = 0; j < total; ++j) {
-        // merge: the training band whose head has the smallest key, the lowest band on ties; the same among the test bands
-        int b = -1, q = -1;
-        double s = 0.0, sq = 0.0;
-        for (int l = 0; l < L; ++l) {
-            const double sl = shead[l * nthr + tid];
-            const int i = scur[l * nthr + tid];
-            const bool live = rev ? i >= a.off[l] : i < a.off[l + 1];
-            const bool take = live && (b < 0 || sl < s);
-            b = take ? l : b;
-            s = take ? sl : s;
-        }
-        if (use_tests)
-            for (int l = 0; l < L; ++l) {
-                const double sl = shead[(L + l) * nthr + tid];
-                const int i = scur[(L + l) * nthr + tid];
-                const bool live = rev ? i >= a.toff[l] : i < a.toff[l + 1];
-                const bool take = live && (q < 0 || sl < sq);
-                q = take ? l : q;
-                sq = take ? sl : sq;
-            }
-        // a training point goes first on ties, except in the backward filter, where the tying point belongs to the forward side
-        const bool is_test = q >= 0 && (b < 0 || sq < s || (rev && sq == s));
         // the point taken: its band, key, residual and variance (a tapped test point has none and ends the step)
-        int band;
-        double key, r, s2;
-        if (is_test) {
-            const int i = scur[(L + q) * nthr + tid];
-            scur[(L + q) * nthr + tid] = i + step;
-            if (rev ? i - 1 >= a.toff[q] : i + 1 < a.toff[q + 1]) {
-                const double tb = tpts[i + step] - stau[q * nthr + tid];
-                shead[(L + q) * nthr + tid] = rev ? -tb : tb;
-            }
+        const GpccMkpPoint p = gpcc_mkp_next(a, cur, rev, use_tests);
+        const int i = p.i;
+        double r, s2;
+        if (p.is_test) {
             if constexpr (MODE == GPCC_MKP_TAP) {
                 // the state after the training points before this test point, propagated to it: on a copy
-                const double d = (jt == 0) ? 0.0 : sq - sprev;
+                const double d = (jt == 0) ? 0.0 : p.key - sprev;
                 double A[P][P], mu2[NS], C2[NS][NS];
                 gpcc_mk_transition<P>(lam, lam2, d, A);
 #pragma unroll
@@ -164,29 +246,21 @@ __global__ void __launch_bounds__(256) gpcc_markov_taps(const GpccMarkovPredArgs
                 }
                 continue;
             }
-            band = q; key = sq;
             r = MODE == GPCC_MKP_TAP ? 0.0 : tpts[T + i];
             s2 = MODE == GPCC_MKP_TAP ? 0.0 : tpts[2 * T + i];
             at = (info == 0) ? i : at;
         } else {
-            const int i = scur[b * nthr + tid];
-            scur[b * nthr + tid] = i + step;
-            if (rev ? i - 1 >= a.off[b] : i + 1 < a.off[b + 1]) {
-                const double base = pts[i + step] - stau[b * nthr + tid];
-                shead[b * nthr + tid] = rev ? -base : base;
-            }
-            band = b; key = s;
             r = pts[N + i];
             s2 = pts[2 * N + i];
         }
         // one filter step, as in gpcc_markov_eval
-        const double al = salpha[band * nthr + tid];
-        const double d = (jt == 0) ? 0.0 : key - sprev;
-        sprev = key;
+        const double al = salpha[p.band * nthr + tid];
+        const double d = (jt == 0) ? 0.0 : p.key - sprev;
+        sprev = p.key;
         double A[P][P];
         gpcc_mk_transition<P>(lam, lam2, d, A);
         gpcc_mk_propagate<P, NOFF>(A, Q, mu, C);
-        const bool ok = gpcc_mk_update<P, NOFF>(band, al, r, s2, mu, C, ll);
+        const bool ok = gpcc_mk_update<P, NOFF>(p.band, al, r, s2, mu, C, ll);
         info = (info == 0 && !ok) ? jt + 1 : info;   // first predictive variance that is not positive and finite
         ++jt;
     }

@@ -10,7 +10,8 @@
 // in the taps' layout [direction][test point][component][row].  (A kernel of its own: gpcc_markov_combine keeps its code object.)
 //
 // gpcc_markov_draw<P, NOFF>: ONE LANE PER (ROW, DRAW), gpcc_markov_taps' lane -- state in registers, cursors / heads / tau / alpha in
-// LDS [band][thread], the points staged in LDS when they fit -- walking the merged training and test points twice.
+// LDS [band][thread], the points staged in LDS when they fit (in this kernel's own layout) -- walking the merged training and test
+// points twice, each time with the shared cursor of gpcc_markov_pred.hip.h (gpcc_mkp_rewind, gpcc_mkp_next).
 //   forward   the point's Philox block (counter (e, s, m, 2): e the POINT, not the merged position) gives four normals; the simulated
 //             state x~ <- A(d) x~ + C xi[0 .. P) with C C' = Pinf - A Pinf A' (gpcc_mks_advance; A = 0 at the first point; d = 0 gives
 //             C = 0: tied points share one state).  Training point: r~ = alpha x~_1 + b~ + sigma xi[3] goes to the scratch [point][lane] and
@@ -247,23 +248,12 @@ __global__ void __launch_bounds__(256) gpcc_markov_draw(const GpccMarkovDrawArgs
     }
     double *rt = a.rt + slot, *acc = a.acc + slot;
     const long ls = a.lstride, ms = a.mstride;
+    const GpccMkpLane cur = {pt, tt, shead, stau, scur, nthr, tid};
 
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
         const bool rev = pass == 1;
-        const int step = rev ? -1 : 1;
-        for (int l = 0; l < L; ++l) {
-            const int i0 = rev ? a.off[l + 1] - 1 : a.off[l];
-            scur[l * nthr + tid] = i0;
-            const double base = pt[i0] - stau[l * nthr + tid];
-            shead[l * nthr + tid] = rev ? -base : base;
-            const int q0 = rev ? a.toff[l + 1] - 1 : a.toff[l];
-            scur[(L + l) * nthr + tid] = q0;
-            if (a.toff[l + 1] > a.toff[l]) {
-                const double tb = tt[q0] - stau[l * nthr + tid];
-                shead[(L + l) * nthr + tid] = rev ? -tb : tb;
-            }
-        }
+        gpcc_mkp_rewind<true>(a, cur, rev);
         double lam, lam2, Q[P][P], mu[NS], C[NS][NS], x[P];
         gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
 #pragma unroll
@@ -271,42 +261,10 @@ __global__ void __launch_bounds__(256) gpcc_markov_draw(const GpccMarkovDrawArgs
         double ll = 0.0, sprev = 0.0, xprev = 0.0;
         int jt = 0;          // updates so far
         for (int j = 0; j < N + T; ++j) {
-            // the merge of gpcc_markov_taps
-            int b = -1, q = -1;
-            double s = 0.0, sq = 0.0;
-            for (int l = 0; l < L; ++l) {
-                const double sl = shead[l * nthr + tid];
-                const int i = scur[l * nthr + tid];
-                const bool live = rev ? i >= a.off[l] : i < a.off[l + 1];
-                const bool take = live && (b < 0 || sl < s);
-                b = take ? l : b;
-                s = take ? sl : s;
-            }
-            for (int l = 0; l < L; ++l) {
-                const double sl = shead[(L + l) * nthr + tid];
-                const int i = scur[(L + l) * nthr + tid];
-                const bool live = rev ? i >= a.toff[l] : i < a.toff[l + 1];
-                const bool take = live && (q < 0 || sl < sq);
-                q = take ? l : q;
-                sq = take ? sl : sq;
-            }
-            const bool is_test = q >= 0 && (b < 0 || sq < s || (rev && sq == s));
-            const int band = is_test ? q : b;
-            const double key = is_test ? sq : s;
-            const int cb = (is_test ? L + q : b) * nthr + tid;
-            const int i = scur[cb];
-            scur[cb] = i + step;
-            if (is_test) {
-                if (rev ? i - 1 >= a.toff[q] : i + 1 < a.toff[q + 1]) {
-                    const double tb = tt[i + step] - stau[q * nthr + tid];
-                    shead[cb] = rev ? -tb : tb;
-                }
-            } else {
-                if (rev ? i - 1 >= a.off[b] : i + 1 < a.off[b + 1]) {
-                    const double base = pt[i + step] - stau[b * nthr + tid];
-                    shead[cb] = rev ? -base : base;
-                }
-            }
+            const GpccMkpPoint p = gpcc_mkp_next(a, cur, rev, true);
+            const bool is_test = p.is_test;
+            const int band = p.band, i = p.i;
+            const double key = p.key;
             const double al = salpha[band * nthr + tid];
             double boff = 0.0;
 #pragma unroll
