@@ -213,7 +213,6 @@ struct gpcc_handle_s {
     // points' bands and positions in the caller's order (2 N ints)
     int *d_mkli = nullptr;
     long mkli_cap = 0;
-    int mkl_configured = 0;
     // Hessian (gpcc_loglik_hess_batch): allocated on its first call, for hess_slots <= workspace slots (hess_bytes_per_slot each: the
     // dense K^-1, M_theta = K^-1 D_theta for every parameter, u, z and the partials) and the outputs of the batch (hess and fisher blocks)
     double *d_hc = nullptr, *d_hm = nullptr, *d_hu = nullptr, *d_hz = nullptr, *d_htab = nullptr, *d_htr = nullptr, *d_hout = nullptr;
@@ -242,6 +241,7 @@ struct gpcc_handle_s {
     double *d_mk = nullptr;
     std::vector<int> mk_perm;
     int mk_cus = 0;
+    unsigned mk_lds_raised = 0;          // one bit per MarkovKernel: this handle has raised the kernel's limit of dynamic LDS on its device
     std::atomic<long> markov_count{0};   // evaluations that took it so far ("markov_count")
     int fit_markov = 0;                  // option "fit_markov": gpcc_grid_loglik's optimiser rounds are gpcc_loglik_markov_batch calls
     // linear-time predictions, held-out log-likelihoods and offsets' posterior (gpcc_predict_markov_batch and its siblings): allocated
@@ -252,20 +252,16 @@ struct gpcc_handle_s {
     double *d_mkt = nullptr, *d_mktap = nullptr, *d_mkmu = nullptr, *d_mkvar = nullptr, *d_mkmix = nullptr, *d_mkw = nullptr, *d_mkaux = nullptr;
     int *d_mkti = nullptr, *d_mkauxi = nullptr;
     long mkt_cap = 0, mkti_cap = 0, mktap_cap = 0, mkmu_cap = 0, mkvar_cap = 0, mkmix_cap = 0, mkw_cap = 0, mkaux_cap = 0, mkauxi_cap = 0;
-    int mkp_configured = 0;
     // linear-time gradient (gpcc_loglik_grad_markov_batch): the per-slot results [slots][M] and the rows [M][2L + 1], grown on demand
     double *d_mkgs = nullptr, *d_mkgr = nullptr;
     long mkgs_cap = 0, mkgr_cap = 0;
-    int mkg_configured = 0;
     // linear-time Hessian block (gpcc_loglik_hess_hyper_markov_batch): the per-pair results [pair slots][M] and the blocks [M][(L + 1)^2]
     double *d_mkhs = nullptr, *d_mkhb = nullptr;
     long mkhs_cap = 0, mkhb_cap = 0;
-    int mkh_configured = 0;
     // linear-time rows of tau of the Hessian (gpcc_loglik_hess_markov_batch): the per-pair results [tau pair slots][M] and the blocks
     // [M][(2L + 1)^2]
     double *d_mkts = nullptr, *d_mktb = nullptr;
     long mkts_cap = 0, mktb_cap = 0;
-    int mkt_configured = 0;
     int laplace_markov = 0;              // option "laplace_markov": gpcc_laplace_evidence's rounds are gpcc_loglik_hess_hyper_markov_batch calls
     int markov_chunk_rows = 0;           // option "markov_chunk_rows": rows per chunk of gpcc_predict_markov_batch (0: by the scratch budget)
     // linear-time draws (gpcc_sample_markov_batch): grown on demand -- the combine's weights of a chunk of rows (mksw_cap doubles), the
@@ -274,7 +270,6 @@ struct gpcc_handle_s {
     double *d_mksw = nullptr, *d_mksrt = nullptr, *d_mksacc = nullptr;
     int *d_mksi = nullptr;
     long mksw_cap = 0, mksrt_cap = 0, mksacc_cap = 0, mksi_cap = 0;
-    int mks_configured = 0;
     int markov_sample_chunk_draws = 0;   // option "markov_sample_chunk_draws": draws per chunk of gpcc_sample_markov_batch (0: by the scratch budget)
     double *d_sep = nullptr, *d_seps = nullptr;     // separable factors of the points, the distance scale (GpccCtx::sep, ::seps)
     int *d_sepflag = nullptr;                       // per-tile-row flags (GpccCtx::sepflag)
@@ -687,7 +682,7 @@ extern "C" int gpcc_set_option(gpcc_handle_t h, const char *key, long v)
         if (v != 0 && h->mb && h->L > GPCC_MARKOV_MAX_OFFSETS)
             return fail(h, GPCC_ERR_UNSUPPORTED, "%s: marginalise_b with L=%d bands (the filter keeps at most %d offset states)", key, h->L,
                         GPCC_MARKOV_MAX_OFFSETS);
-        if (v != 0 && !fit && !gpcc_markov_hess_shipped(h->kernel_id == GPCC_KERNEL_OU ? 1 : (h->kernel_id == GPCC_KERNEL_MATERN32 ? 2 : 3), h->mb ? h->L : 0))
+        if (v != 0 && !fit && !gpcc_mk_ships<GpccMkShipsHess>(h->kernel_id == GPCC_KERNEL_OU ? 1 : (h->kernel_id == GPCC_KERNEL_MATERN32 ? 2 : 3), h->mb ? h->L : 0))
             return fail(h, GPCC_ERR_UNSUPPORTED, "laplace_markov: the linear-time Hessian block of this kernel with %d offset states does not ship; "
                         "its evidence stays dense", h->L);
         (fit ? h->fit_markov : h->laplace_markov) = v != 0;
@@ -2077,7 +2072,6 @@ static int ensure_markov(gpcc_handle_t h)
     int cus = 0;
     HIPCHK(h, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
     h->mk_cus = cus > 0 ? cus : 1;
-    HIPCHK(h, gpcc_markov_configure());
     double *d = nullptr;
     HIPCHK(h, hipMalloc(&d, sizeof(double) * 3 * N));
     const hipError_t e = hipMemcpy(d, pts.data(), sizeof(double) * 3 * N, hipMemcpyHostToDevice);
@@ -2143,16 +2137,38 @@ static void markov_fill_args(gpcc_handle_t h, int M, const double *dd, const dou
     for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) a.sigma_b[l] = l < noff ? h->sigma_b[l] : 0.0;
 }
 
-// the launch shape of `waves` waves of lanes: one wave per workgroup while the chip has a CU for every wave, two or four waves sharing
-// one staged copy beyond; the light curves (and test points) go to LDS when they fit beside the lanes' cursors.  lds_bytes(threads,
-// stage): the kernel's dynamic LDS.  -> threads per workgroup
-template <typename LdsBytes>
-static int markov_launch_shape(gpcc_handle_t h, long waves, LdsBytes &&lds_bytes, int &stage, size_t &lds)
+// the kernels with dynamic LDS, for gpcc_handle::mk_lds_raised
+enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU };
+
+// The launch of every kernel of the filter, `name` in messages: one lane per row, `rows` rows along x and ny lanes per row along y.
+// The shape: one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy beyond; the light
+// curves (and test points) go to LDS when they fit beside the lanes' cursors -- stage, an argument of the kernel, says so.
+// lds_bytes(threads, stage): the kernel's dynamic LDS.  The refusal guards every family alike; for gpcc_markov_eval, _grad, _hess and
+// _hess_tau, whose launches went without it, it cannot fire: unstaged they take 28 bytes x 8 bands x 256 lanes = 56 KiB at most (nor
+// can it at present for the taps and the draws: 40 bytes per lane and band, 80 KiB).  launch(g): the family's launch function on g;
+// the first launch of a kernel by this handle raises the kernel's LDS limit on the handle's device (g.raise_lds)
+template <typename LdsBytes, typename Launch>
+static int markov_launch(gpcc_handle_t h, const char *name, MarkovKernel kernel, long rows, int ny, int &stage, LdsBytes &&lds_bytes,
+                         Launch &&launch)
 {
+    const long waves = ((rows + 63) / 64) * ny;
     const int wpb = waves <= h->mk_cus ? 1 : (waves <= 2L * h->mk_cus ? 2 : 4), threads = 64 * wpb;
     stage = lds_bytes(threads, true) <= GPCC_MARKOV_LDS_MAX ? 1 : 0;
-    lds = lds_bytes(threads, stage != 0);
-    return threads;
+    const size_t lds = lds_bytes(threads, stage != 0);
+    if (lds > GPCC_MARKOV_LDS_MAX) return fail(h, GPCC_ERR_UNSUPPORTED, "%s: %zu bytes of LDS", name, lds);
+    const MarkovDims d = markov_dims(h);
+    const unsigned bit = 1u << kernel;
+    const GpccMkLaunch g = {d.p, d.noff, (int)((rows + threads - 1) / threads), threads, lds, h->main_stream, !(h->mk_lds_raised & bit)};
+    const hipError_t e = launch(g);
+    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "%s: %s", name, hipGetErrorString(e));
+    h->mk_lds_raised |= bit;
+    return 0;
+}
+
+// the dynamic LDS of the kernels that stage the light curves alone
+static auto markov_filter_lds(gpcc_handle_t h)
+{
+    return [h](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); };
 }
 
 // gpcc_markov_eval over the M staged rows: loglik and info left in d_out / d_oinfo
@@ -2160,13 +2176,19 @@ static int markov_eval_launch(gpcc_handle_t h, int M, const double *dd, const do
 {
     GpccMarkovArgs a;
     markov_fill_args(h, M, dd, da, dr, a);
-    size_t lds;
-    const int threads = markov_launch_shape(h, ((long)M + 63) / 64,
-                                            [&](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }, a.stage, lds);
-    const MarkovDims d = markov_dims(h);
-    const hipError_t e = gpcc_markov_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), threads, lds, h->main_stream);
-    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_eval: %s", hipGetErrorString(e));
-    return 0;
+    return markov_launch(h, "gpcc_markov_eval", MK_EVAL, M, 1, a.stage, markov_filter_lds(h),
+                         [&](const GpccMkLaunch &g) { return gpcc_markov_launch(g, a); });
+}
+
+// a derivative kernel (gradient, Hessian block, Hessian's rows of tau) and its finish kernel over the M staged rows, one lane per
+// (row, slot); a holds the kernel's own fields, the filter's are filled here
+template <typename ARGS, typename Launch>
+static int markov_slots_launch(gpcc_handle_t h, const char *name, MarkovKernel kernel, int M, const double *dd, const double *da,
+                               const double *dr, int slots, ARGS &a, Launch &&launch)
+{
+    markov_fill_args(h, M, dd, da, dr, a);
+    return markov_launch(h, name, kernel, M, slots, a.stage, markov_filter_lds(h),
+                         [&](const GpccMkLaunch &g) { return launch(g, slots, a); });
 }
 
 extern "C" int gpcc_loglik_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
@@ -2221,33 +2243,43 @@ static void markov_sort_tests(gpcc_handle_t h, const int *Ntest, const double *t
 
 // the arguments every launch of gpcc_markov_taps shares: the filter's, the test points (toff: their bands' offsets, or NULL for none)
 // and one chunk of all M rows
-static int markov_pred_common(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, const int *toff, long T,
-                              GpccMarkovPredArgs &a)
+static void markov_pred_common(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, const int *toff, long T,
+                               GpccMarkovPredArgs &a)
 {
-    if (!h->mkp_configured) {
-        HIPCHK(h, gpcc_mkp_configure());
-        h->mkp_configured = 1;
-    }
     markov_fill_args(h, M, dd, da, dr, a);
     a.tpts = h->d_mkt; a.T = (int)T;
     a.tap = nullptr; a.ll2 = nullptr; a.info2 = nullptr; a.at2 = nullptr; a.fin = nullptr;
     a.row0 = 0; a.rows = M; a.mstride = M;
     for (int l = 0; l <= GPCC_MARKOV_MAXL; ++l) a.toff[l] = toff ? toff[l] : 0;
-    return 0;
 }
 
 // `rows` rows x ny lanes of gpcc_markov_taps
 static int markov_pred_launch(gpcc_handle_t h, int mode, GpccMarkovPredArgs &a, int ny)
 {
     const int tw = mode == GPCC_MKP_TAP ? 1 : 3;
-    size_t lds;
-    const int threads = markov_launch_shape(h, (((long)a.rows + 63) / 64) * ny,
-                                            [&](int thr, bool st) { return gpcc_mkp_lds_bytes(a.N, a.T, tw, a.L, thr, st); }, a.stage, lds);
-    if (lds > GPCC_MARKOV_LDS_MAX) return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_markov_taps: %zu bytes of LDS", lds);
-    const MarkovDims d = markov_dims(h);
-    const hipError_t e = gpcc_mkp_launch_taps(mode, d.p, d.noff, a, (a.rows + threads - 1) / threads, ny, threads, lds, h->main_stream);
-    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_taps: %s", hipGetErrorString(e));
-    return 0;
+    return markov_launch(h, "gpcc_markov_taps", mode == GPCC_MKP_TAP ? MK_TAPS_TAP : MK_TAPS_UPDATE, a.rows, ny, a.stage,
+                         [&](int thr, bool st) { return gpcc_mkp_lds_bytes(a.N, a.T, tw, a.L, thr, st); },
+                         [&](const GpccMkLaunch &g) { return gpcc_mkp_launch_taps(g, mode, ny, a); });
+}
+
+// rows per chunk of an entry that keeps the two filters' taps (nrec doubles each) at `points` points of every row: what the scratch
+// budget holds (whole waves when it holds one), or the option; 1 .. M
+static long markov_tap_chunk(gpcc_handle_t h, long points, long nrec, long M)
+{
+    long chunk = GPCC_MKP_TAP_BYTES / (2 * points * nrec * 8);
+    if (chunk >= 64) chunk -= chunk % 64;
+    if (h->markov_chunk_rows > 0) chunk = h->markov_chunk_rows;
+    if (chunk < 1) chunk = 1;
+    return chunk > M ? M : chunk;
+}
+
+// the arguments of gpcc_markov_combine (and gpcc_markov_combine_w) beside a's taps; the chunk's rows are set per launch
+static void markov_combine_args(gpcc_handle_t h, const GpccMarkovPredArgs &a, GpccMarkovCombineArgs &c)
+{
+    c.tap = a.tap; c.alpha = a.alpha; c.rho = a.rho; c.tband = h->d_mkti; c.tperm = h->d_mkti + a.T; c.mu = h->d_mkmu; c.var = h->d_mkvar;
+    c.L = h->L; c.T = a.T;
+    for (int l = 0; l < GPCC_MARKOV_MAXL; ++l) c.mean_b[l] = l < h->L ? h->mean_b[l] : 0.0;
+    for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) c.sigma_b[l] = a.sigma_b[l];
 }
 
 extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
@@ -2275,12 +2307,7 @@ extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *d
     GPCC_ON_DEVICE(h, h->device);
     const MarkovDims d = markov_dims(h);
     const long ns = d.p + d.noff, nrec = ns + ns * (ns + 1) / 2;
-    // rows per chunk: what the scratch budget holds (whole waves when it holds one), or the option
-    long chunk = GPCC_MKP_TAP_BYTES / (2 * T * nrec * 8);
-    if (chunk >= 64) chunk -= chunk % 64;
-    if (h->markov_chunk_rows > 0) chunk = h->markov_chunk_rows;
-    if (chunk < 1) chunk = 1;
-    if (chunk > M) chunk = M;
+    const long chunk = markov_tap_chunk(h, T, nrec, M);
     std::vector<int> order, band;
     int toff[GPCC_MARKOV_MAXL + 1];
     markov_sort_tests(h, Ntest, ttest, T, order, band, toff);
@@ -2307,14 +2334,10 @@ extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *d
         HIPCHK(h, hipMemsetAsync(h->d_mkmix, 0, sizeof(double) * 4 * T, ms));
     }
     GpccMarkovPredArgs a;
-    rc = markov_pred_common(h, M, dd, da, dr, toff, T, a);
-    if (rc) return rc;
+    markov_pred_common(h, M, dd, da, dr, toff, T, a);
     a.tap = h->d_mktap;
     GpccMarkovCombineArgs c;
-    c.tap = h->d_mktap; c.alpha = da; c.rho = dr; c.tband = h->d_mkti; c.tperm = h->d_mkti + T; c.mu = h->d_mkmu; c.var = h->d_mkvar;
-    c.L = h->L; c.T = (int)T;
-    for (int l = 0; l < GPCC_MARKOV_MAXL; ++l) c.mean_b[l] = l < h->L ? h->mean_b[l] : 0.0;
-    for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) c.sigma_b[l] = a.sigma_b[l];
+    markov_combine_args(h, a, c);
     for (long row0 = 0; row0 < M; row0 += chunk) {
         const int rows = (int)(M - row0 < chunk ? M - row0 : chunk);
         a.row0 = c.row0 = (int)row0;
@@ -2354,7 +2377,7 @@ extern "C" int gpcc_loo_markov_batch(gpcc_handle_t h, int M, const double *delay
         }))
         return rc;
     const MarkovDims d = markov_dims(h);
-    if (!gpcc_mkl_available(d.p, d.noff))
+    if (!gpcc_mk_ships<GpccMkShipsAll>(d.p, d.noff))
         return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loo_markov_batch: the filter <%d, %d> is not built (it would spill); use gpcc_loo_batch",
                     d.p, d.noff);
     std::vector<double> p;   // the normalised weights p_m = w_m / sum w
@@ -2363,12 +2386,7 @@ extern "C" int gpcc_loo_markov_batch(gpcc_handle_t h, int M, const double *delay
     GPCC_ON_DEVICE(h, h->device);
     const bool mix = mix_lp || mix_loo;
     const long N = h->N, ns = d.p + d.noff, nrec = ns + ns * (ns + 1) / 2;
-    // rows per chunk: what the scratch budget holds (whole waves when it holds one), or the option
-    long chunk = GPCC_MKP_TAP_BYTES / (2 * N * nrec * 8);
-    if (chunk >= 64) chunk -= chunk % 64;
-    if (h->markov_chunk_rows > 0) chunk = h->markov_chunk_rows;
-    if (chunk < 1) chunk = 1;
-    if (chunk > M) chunk = M;
+    const long chunk = markov_tap_chunk(h, N, nrec, M);
     double *dd, *da, *dr;
     rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
         int g = grow_buf(h, &h->d_mkli, &h->mkli_cap, 2 * N);
@@ -2379,10 +2397,6 @@ extern "C" int gpcc_loo_markov_batch(gpcc_handle_t h, int M, const double *delay
         return g;
     });
     if (rc) return rc;
-    if (!h->mkl_configured) {
-        HIPCHK(h, gpcc_mkl_configure());
-        h->mkl_configured = 1;
-    }
     hipStream_t ms = h->main_stream;
     std::vector<int> pi(2 * N);   // per sorted point: its band, its position in the caller's order
     for (long i = 0; i < N; ++i) { pi[i] = h->band_host[h->mk_perm[i]]; pi[N + i] = h->mk_perm[i]; }
@@ -2403,12 +2417,11 @@ extern "C" int gpcc_loo_markov_batch(gpcc_handle_t h, int M, const double *delay
         a.row0 = c.row0 = (int)row0;
         a.rows = c.rows = rows;
         a.mstride = c.mstride = (int)chunk;
-        size_t lds;
-        const int threads = markov_launch_shape(h, (((long)rows + 63) / 64) * 2,
-                                                [&](int thr, bool st) { return gpcc_mkl_lds_bytes(a.N, a.L, thr, st); }, a.stage, lds);
-        if (lds > GPCC_MARKOV_LDS_MAX) return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_markov_loo_taps: %zu bytes of LDS", lds);
-        hipError_t e = gpcc_mkl_launch_taps(d.p, d.noff, a, (rows + threads - 1) / threads, threads, lds, ms);
-        if (e == hipSuccess) e = gpcc_mkl_launch_combine(d.p, d.noff, c, ms);
+        rc = markov_launch(h, "gpcc_markov_loo_taps", MK_LOO_TAPS, rows, 2, a.stage,
+                           [&](int thr, bool st) { return gpcc_mkl_lds_bytes(a.N, a.L, thr, st); },
+                           [&](const GpccMkLaunch &g) { return gpcc_mkl_launch_taps(g, a); });
+        if (rc) return rc;
+        hipError_t e = gpcc_mkl_launch_combine(d.p, d.noff, c, ms);
         if (e == hipSuccess) e = gpcc_mkl_launch_rows(h->d_loomu, h->d_loovar, h->d_loolp, h->d_loosum, h->d_oinfo, (int)N, (int)row0, rows, ms);
         if (e == hipSuccess && mix) {
             gpcc_loo_mix<<<pblocks, GPCC_LOO_THREADS, 0, ms>>>(h->d_loolp, row0, h->d_loow, (int)row0, rows, (int)N, h->d_loomix,
@@ -2480,8 +2493,7 @@ extern "C" int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const do
     HIPCHK(h, hipMemcpyAsync(h->d_mkti, order.data(), sizeof(int) * T, hipMemcpyHostToDevice, ms));
     if (weights) HIPCHK(h, hipMemcpyAsync(h->d_mkw, p.data(), sizeof(double) * M, hipMemcpyHostToDevice, ms));
     GpccMarkovPredArgs a;
-    rc = markov_pred_common(h, M, dd, da, dr, toff, T, a);
-    if (rc) return rc;
+    markov_pred_common(h, M, dd, da, dr, toff, T, a);
     double *d_held = h->d_mkaux + M, *d_mix = h->d_mkaux + 2L * M;
     a.ll2 = h->d_mkaux; a.info2 = h->d_mkauxi; a.at2 = h->d_mkauxi + M;
     rc = markov_pred_launch(h, GPCC_MKP_UPDATE, a, 2);
@@ -2517,8 +2529,7 @@ extern "C" int gpcc_posterior_offsets_markov_batch(gpcc_handle_t h, int M, const
     });
     if (rc) return rc;
     GpccMarkovPredArgs a;
-    rc = markov_pred_common(h, M, dd, da, dr, nullptr, 0, a);
-    if (rc) return rc;
+    markov_pred_common(h, M, dd, da, dr, nullptr, 0, a);
     a.fin = h->d_mkaux;
     rc = markov_pred_launch(h, GPCC_MKP_UPDATE, a, 1);
     if (rc) return rc;
@@ -2554,23 +2565,13 @@ static int markov_grad_grow(gpcc_handle_t h, int M)
 
 static int markov_grad_enqueue(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, double *grad)
 {
-    const MarkovDims d = markov_dims(h);
-    const int W = 2 * h->L + 1, twice = d.p == 1, slots = gpcc_markov_grad_slots(h->L, twice != 0);
-    if (!h->mkg_configured) {
-        HIPCHK(h, gpcc_markov_grad_configure());
-        h->mkg_configured = 1;
-    }
+    const int W = 2 * h->L + 1, twice = markov_dims(h).p == 1, slots = gpcc_markov_grad_slots(h->L, twice != 0);
     int rc = markov_eval_launch(h, M, dd, da, dr);
     if (rc) return rc;
     GpccMarkovGradArgs a;
-    markov_fill_args(h, M, dd, da, dr, a);
     a.slot = h->d_mkgs; a.grad = h->d_mkgr; a.twice = twice;
-    size_t lds;
-    const int threads = markov_launch_shape(h, (((long)M + 63) / 64) * slots,
-                                            [&](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }, a.stage, lds);
-    const hipError_t e = gpcc_markov_grad_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), slots, threads, lds,
-                                                 h->main_stream);
-    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_grad: %s", hipGetErrorString(e));
+    rc = markov_slots_launch(h, "gpcc_markov_grad", MK_GRAD, M, dd, da, dr, slots, a, gpcc_markov_grad_launch);
+    if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(grad, h->d_mkgr, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
     return 0;
 }
@@ -2614,24 +2615,11 @@ static int markov_hess_hyper_grow(gpcc_handle_t h, int M, bool with_hess)
 
 static int markov_hess_hyper_enqueue(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, double *grad, bool with_hess)
 {
-    const MarkovDims d = markov_dims(h);
-    const int slots = gpcc_markov_hess_slots(h->L);
     const int rc = markov_grad_enqueue(h, M, dd, da, dr, grad);
     if (rc || !with_hess) return rc;
-    if (!h->mkh_configured) {
-        HIPCHK(h, gpcc_markov_hess_configure());
-        h->mkh_configured = 1;
-    }
     GpccMarkovHessArgs a;
-    markov_fill_args(h, M, dd, da, dr, a);
     a.slot = h->d_mkhs; a.hess = h->d_mkhb;
-    size_t lds;
-    const int threads = markov_launch_shape(h, (((long)M + 63) / 64) * slots,
-                                            [&](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }, a.stage, lds);
-    const hipError_t e = gpcc_markov_hess_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), slots, threads, lds,
-                                                 h->main_stream);
-    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_hess: %s", hipGetErrorString(e));
-    return 0;
+    return markov_slots_launch(h, "gpcc_markov_hess", MK_HESS, M, dd, da, dr, gpcc_markov_hess_slots(h->L), a, gpcc_markov_hess_launch);
 }
 
 extern "C" int gpcc_loglik_hess_hyper_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
@@ -2645,7 +2633,7 @@ extern "C" int gpcc_loglik_hess_hyper_markov_batch(gpcc_handle_t h, int M, const
     if (rc) return rc;
     {
         const MarkovDims d = markov_dims(primary(h));
-        if (!gpcc_markov_hess_shipped(d.p, d.noff))
+        if (!gpcc_mk_ships<GpccMkShipsHess>(d.p, d.noff))
             return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_hess_hyper_markov_batch: the instantiation <%d, %d> (states of the process, "
                         "offset states) needs scratch memory and does not ship; use gpcc_loglik_hess_hyper_batch", d.p, d.noff);
     }
@@ -2679,7 +2667,7 @@ extern "C" int gpcc_loglik_hess_markov_batch(gpcc_handle_t h, int M, const doubl
     if (rc) return rc;
     {
         const MarkovDims d = markov_dims(primary(h));
-        if (!gpcc_markov_hess_tau_shipped(d.p, d.noff))
+        if (!gpcc_mk_ships<GpccMkShipsHess>(d.p, d.noff))
             return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_hess_markov_batch: the instantiation <%d, %d> (states of the process, "
                         "offset states) needs scratch memory and does not ship; use gpcc_loglik_hess_batch", d.p, d.noff);
     }
@@ -2687,7 +2675,6 @@ extern "C" int gpcc_loglik_hess_markov_batch(gpcc_handle_t h, int M, const doubl
                    [&](gpcc_handle_t o) { return gpcc_loglik_hess_markov_batch(o, M, delays, alpha, rho, loglik, grad, hess, info); }))
         return rc;
     GPCC_ON_DEVICE(h, h->device);
-    const MarkovDims d = markov_dims(h);
     const int W = 2 * h->L + 1, slots = gpcc_markov_hess_tau_slots(h->L);
     double *dd, *da, *dr;
     rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
@@ -2699,19 +2686,10 @@ extern "C" int gpcc_loglik_hess_markov_batch(gpcc_handle_t h, int M, const doubl
     rc = markov_hess_hyper_enqueue(h, M, dd, da, dr, grad, hess != nullptr);
     if (rc) return rc;
     if (hess) {
-        if (!h->mkt_configured) {
-            HIPCHK(h, gpcc_markov_hess_tau_configure());
-            h->mkt_configured = 1;
-        }
         GpccMarkovHessTauArgs a;
-        markov_fill_args(h, M, dd, da, dr, a);
         a.slot = h->d_mkts; a.hyper = h->d_mkhb; a.hess = h->d_mktb;
-        size_t lds;
-        const int threads = markov_launch_shape(h, (((long)M + 63) / 64) * slots,
-                                                [&](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }, a.stage, lds);
-        const hipError_t e = gpcc_markov_hess_tau_launch(d.p, d.noff, a, (int)(((long)M + threads - 1) / threads), slots, threads, lds,
-                                                         h->main_stream);
-        if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_hess_tau: %s", hipGetErrorString(e));
+        rc = markov_slots_launch(h, "gpcc_markov_hess_tau", MK_HESS_TAU, M, dd, da, dr, slots, a, gpcc_markov_hess_tau_launch);
+        if (rc) return rc;
         HIPCHK(h, hipMemcpyAsync(hess, h->d_mktb, sizeof(double) * W * W * M, hipMemcpyDeviceToHost, h->main_stream));
     }
     return markov_finish(h, M, loglik, info);
@@ -3322,11 +3300,7 @@ extern "C" int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *de
     const MarkovDims d = markov_dims(h);
     const long ns = d.p + d.noff, nrec = ns + ns * (ns + 1) / 2;
     // rows per chunk: gpcc_predict_markov_batch's rule; draws per chunk: what the scratch budget holds in whole waves, at least one
-    long chunk = GPCC_MKP_TAP_BYTES / (2 * T * nrec * 8);
-    if (chunk >= 64) chunk -= chunk % 64;
-    if (h->markov_chunk_rows > 0) chunk = h->markov_chunk_rows;
-    if (chunk < 1) chunk = 1;
-    if (chunk > Mc) chunk = Mc;
+    const long chunk = markov_tap_chunk(h, T, nrec, Mc);
     long dchunk = GPCC_MKS_SCRATCH_BYTES / (8 * (N + T));
     dchunk -= dchunk % 64;
     if (dchunk < 64) dchunk = 64;
@@ -3365,21 +3339,13 @@ extern "C" int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *de
     HIPCHK(h, hipMemcpyAsync(h->d_mkt, tt.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, ms));
     HIPCHK(h, hipMemcpyAsync(h->d_mkti, ti.data(), sizeof(int) * 2 * T, hipMemcpyHostToDevice, ms));
     HIPCHK(h, hipMemcpyAsync(h->d_mksi, ints.data(), sizeof(int) * ints.size(), hipMemcpyHostToDevice, ms));
-    if (!h->mks_configured) {
-        HIPCHK(h, gpcc_mks_configure());
-        h->mks_configured = 1;
-    }
     GpccMarkovPredArgs a;
-    rc = markov_pred_common(h, Mc, dd, da, dr, toff, T, a);
-    if (rc) return rc;
+    markov_pred_common(h, Mc, dd, da, dr, toff, T, a);
     a.tap = h->d_mktap;
     GpccMarkovCombineWArgs cwa;
     GpccMarkovCombineArgs &c = cwa.c;
     cwa.w = h->d_mksw;
-    c.tap = h->d_mktap; c.alpha = da; c.rho = dr; c.tband = h->d_mkti; c.tperm = h->d_mkti + T; c.mu = h->d_mkmu; c.var = h->d_mkvar;
-    c.L = h->L; c.T = (int)T;
-    for (int l = 0; l < GPCC_MARKOV_MAXL; ++l) c.mean_b[l] = l < h->L ? h->mean_b[l] : 0.0;
-    for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) c.sigma_b[l] = a.sigma_b[l];
+    markov_combine_args(h, a, c);
     GpccMarkovDrawArgs g;
     g.pts = h->d_mk; g.perm = h->d_mksi; g.tpts = h->d_mkt; g.tperm = h->d_mkti + T;
     g.delays = dd; g.alpha = da; g.rho = dr; g.w = h->d_mksw;
@@ -3406,12 +3372,11 @@ extern "C" int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *de
             const long left = doff[row0 + nrows] - lane0;
             g.lane0 = f.lane0 = (int)lane0;
             g.lanes = f.lanes = (int)(left < dchunk ? left : dchunk);
-            size_t lds;
-            const int threads = markov_launch_shape(h, ((long)g.lanes + 63) / 64,
-                                                    [&](int thr, bool st) { return gpcc_mks_lds_bytes(g.N, g.T, g.L, thr, st); }, g.stage, lds);
-            if (lds > GPCC_MARKOV_LDS_MAX) return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_markov_draw: %zu bytes of LDS", lds);
-            e = gpcc_mks_launch_draw(d.p, d.noff, g, (g.lanes + threads - 1) / threads, threads, lds, ms);
-            if (e == hipSuccess) e = gpcc_mks_launch_finish(f, ms);
+            rc = markov_launch(h, "gpcc_markov_draw", MK_DRAW, g.lanes, 1, g.stage,
+                               [&](int thr, bool st) { return gpcc_mks_lds_bytes(g.N, g.T, g.L, thr, st); },
+                               [&](const GpccMkLaunch &sh) { return gpcc_mks_launch_draw(sh, g); });
+            if (rc) return rc;
+            e = gpcc_mks_launch_finish(f, ms);
             if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "linear-time draws: %s", hipGetErrorString(e));
         }
     }

@@ -28,6 +28,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <type_traits>
 
 #define GPCC_MARKOV_MAX_OFFSETS 4
 #define GPCC_MARKOV_MAXL 8
@@ -327,10 +328,64 @@ __global__ void __launch_bounds__(256) gpcc_markov_eval(const GpccMarkovArgs a)
     }
 }
 
-// the instantiations (P, NOFF) of every kernel of the filter, here and in gpcc_markov_pred.hip.h
-#define GPCC_MK_EACH(F) \
-    F(1, 0) F(1, 1) F(1, 2) F(1, 3) F(1, 4) F(2, 0) F(2, 1) F(2, 2) F(2, 3) F(2, 4) F(3, 0) F(3, 1) F(3, 2) F(3, 3) F(3, 4)
+// ---- which <P, NOFF> ship, and their launch: once, for the seven families of the linear-time path ----
 
-// the launch of instantiation (p, noff) (gpcc_markov_inst.hip: its own object) and the LDS limit of all of them on the current device
-hipError_t gpcc_markov_launch(int p, int noff, const GpccMarkovArgs &a, int blocks, int threads, size_t lds, hipStream_t s);
-hipError_t gpcc_markov_configure();
+// What a family ships is a statement next to its kernel: a struct whose max_noff[P - 1] is the largest NOFF built for P states of the
+// process (every NOFF below it is built too).  The dispatch below instantiates exactly these, so the objects hold exactly these, and
+// the host refuses what gpcc_mk_ships() denies.  One that the compiler cannot keep out of scratch memory does not ship
+// (tools/kernel_resources.py).  GpccMkShipsAll: every family but the two of the Hessian (gpcc_markov_hess.hip.h)
+struct GpccMkShipsAll { static constexpr int max_noff[3] = {GPCC_MARKOV_MAX_OFFSETS, GPCC_MARKOV_MAX_OFFSETS, GPCC_MARKOV_MAX_OFFSETS}; };
+
+template <class SHIPS>
+static inline bool gpcc_mk_ships(int p, int noff)
+{
+    return p >= 1 && p <= 3 && noff >= 0 && noff <= SHIPS::max_noff[p - 1];
+}
+
+// one launch: the instantiation, the workgroups along x (the family's launch function knows y), the workgroup and its dynamic LDS.
+// raise_lds: the handle launches this kernel for the first time, so the launch first lifts the kernel's limit of dynamic LDS above
+// the default 64 KiB for the staged light curves -- on the one instantiation the handle uses, on the handle's (the current) device
+struct GpccMkLaunch {
+    int p, noff, blocks, threads;
+    size_t lds;
+    hipStream_t s;
+    bool raise_lds;
+};
+
+// f(std::integral_constant<int, P>, std::integral_constant<int, NOFF>) for the runtime (p, noff), over what SHIPS ships with
+// PLO <= P <= PHI (an object split by P, -DGPCC_INST_P, dispatches over its own P only); hipErrorInvalidValue for anything else
+template <class SHIPS, int PLO = 1, int PHI = 3, int P = PLO, int NOFF = 0, class F>
+static inline hipError_t gpcc_mk_dispatch(int p, int noff, F &&f)
+{
+    if constexpr (P > PHI) {
+        return hipErrorInvalidValue;
+    } else if constexpr (NOFF > SHIPS::max_noff[P - 1]) {
+        return gpcc_mk_dispatch<SHIPS, PLO, PHI, P + 1, 0>(p, noff, f);
+    } else {
+        if (p == P && noff == NOFF) return f(std::integral_constant<int, P>{}, std::integral_constant<int, NOFF>{});
+        return gpcc_mk_dispatch<SHIPS, PLO, PHI, P, NOFF + 1>(p, noff, f);
+    }
+}
+
+// one kernel on its grid (the combine kernels: no dynamic LDS, nothing to raise)
+template <class ARGS>
+static inline hipError_t gpcc_mk_launch_kernel(void (*kernel)(ARGS), dim3 grid, int threads, size_t lds, hipStream_t s, bool raise_lds,
+                                               const ARGS &a)
+{
+    if (raise_lds) {
+        const hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GPCC_MARKOV_LDS_MAX);
+        if (e != hipSuccess) return e;
+    }
+    kernel<<<grid, dim3(threads), lds, s>>>(a);
+    return hipGetLastError();
+}
+
+// ... and a filter kernel on g's shape, ny workgroups along y
+template <class ARGS>
+static inline hipError_t gpcc_mk_launch_kernel(void (*kernel)(ARGS), const GpccMkLaunch &g, int ny, const ARGS &a)
+{
+    return gpcc_mk_launch_kernel(kernel, dim3(g.blocks, ny), g.threads, g.lds, g.s, g.raise_lds, a);
+}
+
+// gpcc_markov_eval<g.p, g.noff> on the grid (g.blocks) (gpcc_markov_inst.hip: its own object)
+hipError_t gpcc_markov_launch(const GpccMkLaunch &g, const GpccMarkovArgs &a);

@@ -333,7 +333,5 @@ __global__ void __launch_bounds__(256) gpcc_markov_grad(const GpccMarkovGradArgs
 }
 
 // ---- launches (gpcc_markov_grad_inst.hip: an object of its own) ----
-hipError_t gpcc_markov_grad_configure();
-// grid (blocks, slots) of gpcc_markov_grad<p, noff>, then the finish kernel over the M rows
-hipError_t gpcc_markov_grad_launch(int p, int noff, const GpccMarkovGradArgs &a, int blocks, int slots, int threads, size_t lds,
-                                   hipStream_t s);
+// grid (g.blocks, slots) of gpcc_markov_grad<g.p, g.noff>, then the finish kernel over the M rows
+hipError_t gpcc_markov_grad_launch(const GpccMkLaunch &g, int slots, const GpccMarkovGradArgs &a);

@@ -1,6 +1,6 @@
-// gpcc_markov_grad_inst.hip -- the instantiations of gpcc_markov_grad<P, NOFF> (P = 1, 2, 3 states of the process, NOFF = 0 .. 4
-// offset states; each holds the alpha, rho and tau bodies), the finish kernel and their launch, as an object of their own
-// (gpcc.jl_amd/build.py compiles the objects side by side).
+// gpcc_markov_grad_inst.hip -- the instantiations of gpcc_markov_grad<P, NOFF> that ship (GpccMkShipsAll of gpcc_markov.hip.h; each
+// holds the alpha, rho and tau bodies), the finish kernel and their launch, as an object of their own (gpcc.jl_amd/build.py compiles
+// the objects side by side).
 #include "gpcc_markov_grad.hip.h"
 
 // the M x (2L + 1) rows from the slots: the tau pairs of OU averaged (first + last, in this order), NaN rows where info != 0
@@ -22,32 +22,12 @@ static __global__ void __launch_bounds__(64) gpcc_markov_grad_finish(const GpccM
     }
 }
 
-hipError_t gpcc_markov_grad_launch(int p, int noff, const GpccMarkovGradArgs &a, int blocks, int slots, int threads, size_t lds,
-                                   hipStream_t s)
+hipError_t gpcc_markov_grad_launch(const GpccMkLaunch &g, int slots, const GpccMarkovGradArgs &a)
 {
-#define GPCC_MKG_CASE(PP, NN)                                                                  \
-    if (p == PP && noff == NN) {                                                               \
-        gpcc_markov_grad<PP, NN><<<dim3(blocks, slots), dim3(threads), lds, s>>>(a);           \
-        const hipError_t e = hipGetLastError();                                                \
-        if (e != hipSuccess) return e;                                                         \
-        gpcc_markov_grad_finish<<<dim3((a.M + 63) / 64), dim3(64), 0, s>>>(a);                 \
-        return hipGetLastError();                                                              \
-    }
-    GPCC_MK_EACH(GPCC_MKG_CASE)
-#undef GPCC_MKG_CASE
-    return hipErrorInvalidValue;
-}
-
-// more than the default 64 KiB of dynamic LDS for the staged light curves (per device, idempotent)
-hipError_t gpcc_markov_grad_configure()
-{
-#define GPCC_MKG_ATTR(PP, NN)                                                                                                        \
-    {                                                                                                                                \
-        const hipError_t e = hipFuncSetAttribute((const void *)gpcc_markov_grad<PP, NN>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                 GPCC_MARKOV_LDS_MAX);                                                               \
-        if (e != hipSuccess) return e;                                                                                               \
-    }
-    GPCC_MK_EACH(GPCC_MKG_ATTR)
-#undef GPCC_MKG_ATTR
-    return hipSuccess;
+    const hipError_t e = gpcc_mk_dispatch<GpccMkShipsAll>(g.p, g.noff, [&](auto P, auto NOFF) {
+        return gpcc_mk_launch_kernel(gpcc_markov_grad<P(), NOFF()>, g, slots, a);
+    });
+    if (e != hipSuccess) return e;
+    gpcc_markov_grad_finish<<<dim3((a.M + 63) / 64), dim3(64), 0, g.s>>>(a);
+    return hipGetLastError();
 }

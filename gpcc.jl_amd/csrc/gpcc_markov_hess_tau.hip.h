@@ -270,53 +270,9 @@ __global__ void __launch_bounds__(256) gpcc_markov_hess_tau(const GpccMarkovHess
     if (ln.valid) a.slot[(long)slot * a.M + ln.row] = hll;
 }
 
-// ---- the instantiations that ship, per P (gpcc_markov_hess_tau_inst.hip: one object per P).  One that the compiler cannot keep out
-// of scratch memory does not ship (tools/kernel_resources.py; the table is in DESIGN.md 4.21 and
-// profiles/markov/kernel_resources_hess_tau.log): gpcc_loglik_hess_markov_batch returns GPCC_ERR_UNSUPPORTED for it and names the dense
-// entry.  <3, 4> cannot ship: the leading block is refused there already ----
-#define GPCC_MKT_EACH_P1(F) F(1, 0) F(1, 1) F(1, 2) F(1, 3) F(1, 4)
-#define GPCC_MKT_EACH_P2(F) F(2, 0) F(2, 1) F(2, 2) F(2, 3) F(2, 4)
-#define GPCC_MKT_EACH_P3(F) F(3, 0) F(3, 1) F(3, 2) F(3, 3)
+// ---- the instantiations that ship (gpcc_markov_hess_tau_inst.hip: one object per P) are GpccMkShipsHess, those of the leading block:
+// <3, 4> is refused there already (the table of this family is in DESIGN.md 4.21 and profiles/markov/kernel_resources_hess_tau.log);
+// gpcc_loglik_hess_markov_batch returns GPCC_ERR_UNSUPPORTED for it and names the dense entry ----
 
-static inline bool gpcc_markov_hess_tau_shipped(int p, int noff)
-{
-#define GPCC_MKT_IS(PP, NN) \
-    if (p == PP && noff == NN) return gpcc_markov_hess_shipped(p, noff);
-    GPCC_MKT_EACH_P1(GPCC_MKT_IS) GPCC_MKT_EACH_P2(GPCC_MKT_IS) GPCC_MKT_EACH_P3(GPCC_MKT_IS)
-#undef GPCC_MKT_IS
-    return false;
-}
-
-// per P: the launch of gpcc_markov_hess_tau<P, noff> on the grid (blocks, slots), and the LDS limit of its instantiations on the current
-// device
-template <int P>
-hipError_t gpcc_markov_hess_tau_launch_p(int noff, const GpccMarkovHessTauArgs &a, int blocks, int slots, int threads, size_t lds,
-                                         hipStream_t s);
-template <int P>
-hipError_t gpcc_markov_hess_tau_configure_p();
-template <> hipError_t gpcc_markov_hess_tau_launch_p<1>(int, const GpccMarkovHessTauArgs &, int, int, int, size_t, hipStream_t);
-template <> hipError_t gpcc_markov_hess_tau_launch_p<2>(int, const GpccMarkovHessTauArgs &, int, int, int, size_t, hipStream_t);
-template <> hipError_t gpcc_markov_hess_tau_launch_p<3>(int, const GpccMarkovHessTauArgs &, int, int, int, size_t, hipStream_t);
-template <> hipError_t gpcc_markov_hess_tau_configure_p<1>();
-template <> hipError_t gpcc_markov_hess_tau_configure_p<2>();
-template <> hipError_t gpcc_markov_hess_tau_configure_p<3>();
-// the finish kernel over the M rows
-hipError_t gpcc_markov_hess_tau_finish_launch(const GpccMarkovHessTauArgs &a, hipStream_t s);
-
-static inline hipError_t gpcc_markov_hess_tau_configure()
-{
-    hipError_t e = gpcc_markov_hess_tau_configure_p<1>();
-    if (e == hipSuccess) e = gpcc_markov_hess_tau_configure_p<2>();
-    if (e == hipSuccess) e = gpcc_markov_hess_tau_configure_p<3>();
-    return e;
-}
-
-// gpcc_markov_hess_tau<p, noff> on the grid (blocks, slots), then the finish kernel
-static inline hipError_t gpcc_markov_hess_tau_launch(int p, int noff, const GpccMarkovHessTauArgs &a, int blocks, int slots, int threads,
-                                                     size_t lds, hipStream_t s)
-{
-    const hipError_t e = p == 1   ? gpcc_markov_hess_tau_launch_p<1>(noff, a, blocks, slots, threads, lds, s)
-                         : p == 2 ? gpcc_markov_hess_tau_launch_p<2>(noff, a, blocks, slots, threads, lds, s)
-                                  : gpcc_markov_hess_tau_launch_p<3>(noff, a, blocks, slots, threads, lds, s);
-    return e != hipSuccess ? e : gpcc_markov_hess_tau_finish_launch(a, s);
-}
+// gpcc_markov_hess_tau<g.p, g.noff> on the grid (g.blocks, slots), then the finish kernel over the M rows (gpcc_markov_hess_tau_inst.hip)
+hipError_t gpcc_markov_hess_tau_launch(const GpccMkLaunch &g, int slots, const GpccMarkovHessTauArgs &a);

@@ -1,47 +1,22 @@
-// gpcc_markov_hess_tau_inst.hip -- the instantiations of gpcc_markov_hess_tau<P, NOFF> for one P = GPCC_INST_P (1, 2, 3 states of the
-// process; NOFF = 0 .. 4 offset states, each holding the four bodies of the kinds of pair), their launch, and with P = 1 the finish
-// kernel: three objects (gpcc.jl_amd/build.py compiles the objects side by side).
+// gpcc_markov_hess_tau_inst.hip -- the instantiations of gpcc_markov_hess_tau<P, NOFF> that ship (GpccMkShipsHess of gpcc_markov_hess.hip.h; each
+// holds the four bodies of the kinds of pair) for one P = GPCC_INST_P, and their launch; with P = 1 also the finish kernel and the
+// launch of the family, which picks the object: three objects (gpcc.jl_amd/build.py compiles the objects side by side).
 #include "gpcc_markov_hess_tau.hip.h"
 
 #ifndef GPCC_INST_P
 #error "GPCC_INST_P (1, 2 or 3) selects the instantiations of this object"
 #endif
 
-#if GPCC_INST_P == 1
-#define GPCC_MKT_EACH(F) GPCC_MKT_EACH_P1(F)
-#elif GPCC_INST_P == 2
-#define GPCC_MKT_EACH(F) GPCC_MKT_EACH_P2(F)
-#else
-#define GPCC_MKT_EACH(F) GPCC_MKT_EACH_P3(F)
-#endif
+// gpcc_markov_hess_tau<P, g.noff> on the grid (g.blocks, slots): each object defines its own P's
+template <int P>
+hipError_t gpcc_markov_hess_tau_launch_p(const GpccMkLaunch &g, int slots, const GpccMarkovHessTauArgs &a);
 
 template <>
-hipError_t gpcc_markov_hess_tau_launch_p<GPCC_INST_P>(int noff, const GpccMarkovHessTauArgs &a, int blocks, int slots, int threads,
-                                                      size_t lds, hipStream_t s)
+hipError_t gpcc_markov_hess_tau_launch_p<GPCC_INST_P>(const GpccMkLaunch &g, int slots, const GpccMarkovHessTauArgs &a)
 {
-#define GPCC_MKT_CASE(PP, NN)                                                                      \
-    if (noff == NN) {                                                                              \
-        gpcc_markov_hess_tau<PP, NN><<<dim3(blocks, slots), dim3(threads), lds, s>>>(a);           \
-        return hipGetLastError();                                                                  \
-    }
-    GPCC_MKT_EACH(GPCC_MKT_CASE)
-#undef GPCC_MKT_CASE
-    return hipErrorInvalidValue;
-}
-
-// more than the default 64 KiB of dynamic LDS for the staged light curves (per device, idempotent)
-template <>
-hipError_t gpcc_markov_hess_tau_configure_p<GPCC_INST_P>()
-{
-#define GPCC_MKT_ATTR(PP, NN)                                                                                                            \
-    {                                                                                                                                    \
-        const hipError_t e = hipFuncSetAttribute((const void *)gpcc_markov_hess_tau<PP, NN>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                 GPCC_MARKOV_LDS_MAX);                                                                   \
-        if (e != hipSuccess) return e;                                                                                                   \
-    }
-    GPCC_MKT_EACH(GPCC_MKT_ATTR)
-#undef GPCC_MKT_ATTR
-    return hipSuccess;
+    return gpcc_mk_dispatch<GpccMkShipsHess, GPCC_INST_P, GPCC_INST_P>(g.p, g.noff, [&](auto P, auto NOFF) {
+        return gpcc_mk_launch_kernel(gpcc_markov_hess_tau<P(), NOFF()>, g, slots, a);
+    });
 }
 
 #if GPCC_INST_P == 1
@@ -66,9 +41,14 @@ static __global__ void __launch_bounds__(64) gpcc_markov_hess_tau_finish(const G
         for (int k = l + 1; k < L; ++k, ++slot) H[(n + l) * W + n + k] = H[(n + k) * W + n + l] = bad ? nan : a.slot[(long)slot * a.M + m];
 }
 
-hipError_t gpcc_markov_hess_tau_finish_launch(const GpccMarkovHessTauArgs &a, hipStream_t s)
+template <> hipError_t gpcc_markov_hess_tau_launch_p<2>(const GpccMkLaunch &, int, const GpccMarkovHessTauArgs &);   // (the other two objects')
+template <> hipError_t gpcc_markov_hess_tau_launch_p<3>(const GpccMkLaunch &, int, const GpccMarkovHessTauArgs &);
+
+hipError_t gpcc_markov_hess_tau_launch(const GpccMkLaunch &g, int slots, const GpccMarkovHessTauArgs &a)
 {
-    gpcc_markov_hess_tau_finish<<<dim3((a.M + 63) / 64), dim3(64), 0, s>>>(a);
+    const hipError_t e = gpcc_mk_dispatch<GpccMkShipsHess>(g.p, g.noff, [&](auto P, auto) { return gpcc_markov_hess_tau_launch_p<P()>(g, slots, a); });
+    if (e != hipSuccess) return e;
+    gpcc_markov_hess_tau_finish<<<dim3((a.M + 63) / 64), dim3(64), 0, g.s>>>(a);
     return hipGetLastError();
 }
 #endif

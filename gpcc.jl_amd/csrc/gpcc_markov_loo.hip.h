@@ -201,10 +201,9 @@ __global__ void __launch_bounds__(64) gpcc_markov_loo_combine(const GpccMarkovLo
 static inline size_t gpcc_mkl_lds_bytes(int N, int L, int threads, bool stage) { return gpcc_markov_lds_bytes(N, L, threads, stage); }
 
 // ---- launches (gpcc_markov_loo_inst.hip: an object of its own) ----
-hipError_t gpcc_mkl_configure();
-// false: the instantiation <p, noff> is not shipped (it would spill to scratch memory)
-bool gpcc_mkl_available(int p, int noff);
-hipError_t gpcc_mkl_launch_taps(int p, int noff, const GpccMarkovLooArgs &a, int blocks, int threads, size_t lds, hipStream_t s);
+// grid (g.blocks, 2): the forward and the backward filter
+hipError_t gpcc_mkl_launch_taps(const GpccMkLaunch &g, const GpccMarkovLooArgs &a);
+// grid (N, ceil(rows / 64)), 64 threads
 hipError_t gpcc_mkl_launch_combine(int p, int noff, const GpccMarkovLooCombineArgs &a, hipStream_t s);
 // per row of the chunk (mu, var, lp: [rows][N]): a failed filter (info != 0) makes the row NaN; else the first NaN of var (caller's
 // order, i from 0) sets info = N + i + 1 and makes the row NaN; loo[row0 + row] = sum_i lp_i (NaN for a failed row)

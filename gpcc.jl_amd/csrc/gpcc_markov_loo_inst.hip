@@ -1,51 +1,20 @@
-// gpcc_markov_loo_inst.hip -- the instantiations of gpcc_markov_loo_taps<P, NOFF> and gpcc_markov_loo_combine<P, NOFF> (P = 1, 2, 3
-// states of the process, NOFF = 0 .. 4 offset states), the per-row kernel beside them and their launches, as an object of their own
-// (gpcc.jl_amd/build.py compiles the objects side by side).
+// gpcc_markov_loo_inst.hip -- the instantiations of gpcc_markov_loo_taps<P, NOFF> and gpcc_markov_loo_combine<P, NOFF> that ship
+// (GpccMkShipsAll of gpcc_markov.hip.h: none spills or uses scratch memory, profiles/markov/kernel_resources_loo.log), the per-row
+// kernel beside them and their launches, as an object of their own (gpcc.jl_amd/build.py compiles the objects side by side).
 #include "gpcc_markov_loo.hip.h"
 
-// Every instantiation is shipped: none spills or uses scratch memory (profiles/markov/kernel_resources_loo.log).  One that did would
-// be listed here and refused by gpcc_loo_markov_batch before any device work.
-bool gpcc_mkl_available(int p, int noff)
+hipError_t gpcc_mkl_launch_taps(const GpccMkLaunch &g, const GpccMarkovLooArgs &a)
 {
-    return p >= 1 && p <= 3 && noff >= 0 && noff <= GPCC_MARKOV_MAX_OFFSETS;
-}
-
-hipError_t gpcc_mkl_launch_taps(int p, int noff, const GpccMarkovLooArgs &a, int blocks, int threads, size_t lds, hipStream_t s)
-{
-#define GPCC_MKL_CASE(PP, NN)                                                                                        \
-    if (p == PP && noff == NN) {                                                                                     \
-        gpcc_markov_loo_taps<PP, NN><<<dim3(blocks, 2), dim3(threads), lds, s>>>(a);                                 \
-        return hipGetLastError();                                                                                    \
-    }
-    GPCC_MK_EACH(GPCC_MKL_CASE)
-#undef GPCC_MKL_CASE
-    return hipErrorInvalidValue;
+    return gpcc_mk_dispatch<GpccMkShipsAll>(g.p, g.noff, [&](auto P, auto NOFF) {
+        return gpcc_mk_launch_kernel(gpcc_markov_loo_taps<P(), NOFF()>, g, 2, a);
+    });
 }
 
 hipError_t gpcc_mkl_launch_combine(int p, int noff, const GpccMarkovLooCombineArgs &a, hipStream_t s)
 {
-#define GPCC_MKL_CASE(PP, NN)                                                                                        \
-    if (p == PP && noff == NN) {                                                                                     \
-        gpcc_markov_loo_combine<PP, NN><<<dim3(a.N, (a.rows + 63) / 64), dim3(64), 0, s>>>(a);                       \
-        return hipGetLastError();                                                                                    \
-    }
-    GPCC_MK_EACH(GPCC_MKL_CASE)
-#undef GPCC_MKL_CASE
-    return hipErrorInvalidValue;
-}
-
-// more than the default 64 KiB of dynamic LDS for the staged light curves (per device, idempotent)
-hipError_t gpcc_mkl_configure()
-{
-#define GPCC_MKL_ATTR(PP, NN)                                                                                                        \
-    {                                                                                                                                \
-        const hipError_t e = hipFuncSetAttribute((const void *)gpcc_markov_loo_taps<PP, NN>,                                         \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, GPCC_MARKOV_LDS_MAX);                   \
-        if (e != hipSuccess) return e;                                                                                               \
-    }
-    GPCC_MK_EACH(GPCC_MKL_ATTR)
-#undef GPCC_MKL_ATTR
-    return hipSuccess;
+    return gpcc_mk_dispatch<GpccMkShipsAll>(p, noff, [&](auto P, auto NOFF) {
+        return gpcc_mk_launch_kernel(gpcc_markov_loo_combine<P(), NOFF()>, dim3(a.N, (a.rows + 63) / 64), 64, 0, s, false, a);
+    });
 }
 
 // one workgroup per row of the chunk (256 threads)

@@ -420,10 +420,9 @@ __global__ void __launch_bounds__(64) gpcc_markov_combine(const GpccMarkovCombin
 }
 
 // ---- launches (gpcc_markov_pred_inst.hip: an object of its own) ----
-hipError_t gpcc_mkp_configure();
-// mode GPCC_MKP_TAP / GPCC_MKP_UPDATE; grid (blocks, ny)
-hipError_t gpcc_mkp_launch_taps(int mode, int p, int noff, const GpccMarkovPredArgs &a, int blocks, int ny, int threads, size_t lds,
-                                hipStream_t s);
+// mode GPCC_MKP_TAP / GPCC_MKP_UPDATE (two kernels); grid (g.blocks, ny)
+hipError_t gpcc_mkp_launch_taps(const GpccMkLaunch &g, int mode, int ny, const GpccMarkovPredArgs &a);
+// grid (ceil(rows / 64), T), 64 threads
 hipError_t gpcc_mkp_launch_combine(int p, int noff, const GpccMarkovCombineArgs &a, hipStream_t s);
 // per row of the chunk: a failed training filter (info != 0) makes the row NaN; else the first NaN of the row (caller's order, j from
 // 0) sets info = N + j + 1 and makes the row NaN

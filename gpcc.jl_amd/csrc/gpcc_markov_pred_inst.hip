@@ -1,51 +1,21 @@
-// gpcc_markov_pred_inst.hip -- the instantiations of gpcc_markov_taps<P, NOFF, MODE> and gpcc_markov_combine<P, NOFF> (P = 1, 2, 3
-// states of the process, NOFF = 0 .. 4 offset states), the small per-row kernels beside them and their launches, as an object of their
-// own (gpcc.jl_amd/build.py compiles the objects side by side).
+// gpcc_markov_pred_inst.hip -- the instantiations of gpcc_markov_taps<P, NOFF, MODE> and gpcc_markov_combine<P, NOFF> that ship
+// (GpccMkShipsAll of gpcc_markov.hip.h), the small per-row kernels beside them and their launches, as an object of their own
+// (gpcc.jl_amd/build.py compiles the objects side by side).
 #include "gpcc_markov_pred.hip.h"
 
-hipError_t gpcc_mkp_launch_taps(int mode, int p, int noff, const GpccMarkovPredArgs &a, int blocks, int ny, int threads, size_t lds,
-                                hipStream_t s)
+hipError_t gpcc_mkp_launch_taps(const GpccMkLaunch &g, int mode, int ny, const GpccMarkovPredArgs &a)
 {
-#define GPCC_MKP_CASE(PP, NN)                                                                                        \
-    if (p == PP && noff == NN) {                                                                                     \
-        if (mode == GPCC_MKP_TAP)                                                                                    \
-            gpcc_markov_taps<PP, NN, GPCC_MKP_TAP><<<dim3(blocks, ny), dim3(threads), lds, s>>>(a);                  \
-        else                                                                                                         \
-            gpcc_markov_taps<PP, NN, GPCC_MKP_UPDATE><<<dim3(blocks, ny), dim3(threads), lds, s>>>(a);               \
-        return hipGetLastError();                                                                                    \
-    }
-    GPCC_MK_EACH(GPCC_MKP_CASE)
-#undef GPCC_MKP_CASE
-    return hipErrorInvalidValue;
+    return gpcc_mk_dispatch<GpccMkShipsAll>(g.p, g.noff, [&](auto P, auto NOFF) {
+        return mode == GPCC_MKP_TAP ? gpcc_mk_launch_kernel(gpcc_markov_taps<P(), NOFF(), GPCC_MKP_TAP>, g, ny, a)
+                                    : gpcc_mk_launch_kernel(gpcc_markov_taps<P(), NOFF(), GPCC_MKP_UPDATE>, g, ny, a);
+    });
 }
 
 hipError_t gpcc_mkp_launch_combine(int p, int noff, const GpccMarkovCombineArgs &a, hipStream_t s)
 {
-#define GPCC_MKP_CASE(PP, NN)                                                                                        \
-    if (p == PP && noff == NN) {                                                                                     \
-        gpcc_markov_combine<PP, NN><<<dim3((a.rows + 63) / 64, a.T), dim3(64), 0, s>>>(a);                           \
-        return hipGetLastError();                                                                                    \
-    }
-    GPCC_MK_EACH(GPCC_MKP_CASE)
-#undef GPCC_MKP_CASE
-    return hipErrorInvalidValue;
-}
-
-// more than the default 64 KiB of dynamic LDS for the staged light curves and test points (per device, idempotent)
-hipError_t gpcc_mkp_configure()
-{
-#define GPCC_MKP_ATTR(PP, NN)                                                                                                        \
-    {                                                                                                                                \
-        hipError_t e = hipFuncSetAttribute((const void *)gpcc_markov_taps<PP, NN, GPCC_MKP_TAP>,                                     \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, GPCC_MARKOV_LDS_MAX);                         \
-        if (e == hipSuccess)                                                                                                         \
-            e = hipFuncSetAttribute((const void *)gpcc_markov_taps<PP, NN, GPCC_MKP_UPDATE>,                                         \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, GPCC_MARKOV_LDS_MAX);                                \
-        if (e != hipSuccess) return e;                                                                                               \
-    }
-    GPCC_MK_EACH(GPCC_MKP_ATTR)
-#undef GPCC_MKP_ATTR
-    return hipSuccess;
+    return gpcc_mk_dispatch<GpccMkShipsAll>(p, noff, [&](auto P, auto NOFF) {
+        return gpcc_mk_launch_kernel(gpcc_markov_combine<P(), NOFF()>, dim3((a.rows + 63) / 64, a.T), 64, 0, s, false, a);
+    });
 }
 
 static __global__ void __launch_bounds__(64) gpcc_markov_rowinfo(double *mu, double *var, int *info, int N, int T, int row0, int rows)

@@ -416,8 +416,9 @@ __global__ void __launch_bounds__(64) gpcc_markov_combine_w(const GpccMarkovComb
 }
 
 // ---- launches (gpcc_markov_sample_inst.hip: an object of its own) ----
-hipError_t gpcc_mks_configure();
+// grid (ceil(rows / 64), T), 64 threads
 hipError_t gpcc_mks_launch_combine(int p, int noff, const GpccMarkovCombineWArgs &a, hipStream_t s);
-hipError_t gpcc_mks_launch_draw(int p, int noff, const GpccMarkovDrawArgs &a, int blocks, int threads, size_t lds, hipStream_t s);
+// grid (g.blocks): one lane per draw
+hipError_t gpcc_mks_launch_draw(const GpccMkLaunch &g, const GpccMarkovDrawArgs &a);
 // draws[lane_out][j] = mu[row][j] + acc[j][lane]: 64 x 64 tiles of (lane, test point) transposed through LDS
 hipError_t gpcc_mks_launch_finish(const GpccMarkovDrawFinishArgs &a, hipStream_t s);

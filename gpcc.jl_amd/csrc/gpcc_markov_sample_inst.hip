@@ -1,45 +1,21 @@
-// gpcc_markov_sample_inst.hip -- the instantiations of gpcc_markov_draw<P, NOFF> and gpcc_markov_combine_w<P, NOFF> (P = 1, 2, 3 states of
-// the process, NOFF = 0 .. 4 offset states), the finish kernel and their launches, as an object of their own (gpcc.jl_amd/build.py
+// gpcc_markov_sample_inst.hip -- the instantiations of gpcc_markov_draw<P, NOFF> and gpcc_markov_combine_w<P, NOFF> that ship
+// (GpccMkShipsAll of gpcc_markov.hip.h), the finish kernel and their launches, as an object of their own (gpcc.jl_amd/build.py
 // compiles the objects side by side).
 #include "gpcc_markov_sample.hip.h"
 
 hipError_t gpcc_mks_launch_combine(int p, int noff, const GpccMarkovCombineWArgs &a, hipStream_t s)
 {
-#define GPCC_MKS_CASE(PP, NN)                                                                                        \
-    if (p == PP && noff == NN) {                                                                                     \
-        gpcc_markov_combine_w<PP, NN><<<dim3((a.c.rows + 63) / 64, a.c.T), dim3(64), 0, s>>>(a);                     \
-        return hipGetLastError();                                                                                    \
-    }
-    GPCC_MK_EACH(GPCC_MKS_CASE)
-#undef GPCC_MKS_CASE
-    return hipErrorInvalidValue;
+    return gpcc_mk_dispatch<GpccMkShipsAll>(p, noff, [&](auto P, auto NOFF) {
+        return gpcc_mk_launch_kernel(gpcc_markov_combine_w<P(), NOFF()>, dim3((a.c.rows + 63) / 64, a.c.T), 64, 0, s, false, a);
+    });
 }
 
-hipError_t gpcc_mks_launch_draw(int p, int noff, const GpccMarkovDrawArgs &a, int blocks, int threads, size_t lds, hipStream_t s)
+hipError_t gpcc_mks_launch_draw(const GpccMkLaunch &g, const GpccMarkovDrawArgs &a)
 {
-    if ((long)blocks * threads > a.lstride || a.lanes < 1 || a.lanes > a.lstride) return hipErrorInvalidValue;   // the scratch's columns
-#define GPCC_MKS_CASE(PP, NN)                                                                                        \
-    if (p == PP && noff == NN) {                                                                                     \
-        gpcc_markov_draw<PP, NN><<<dim3(blocks), dim3(threads), lds, s>>>(a);                                        \
-        return hipGetLastError();                                                                                    \
-    }
-    GPCC_MK_EACH(GPCC_MKS_CASE)
-#undef GPCC_MKS_CASE
-    return hipErrorInvalidValue;
-}
-
-// more than the default 64 KiB of dynamic LDS for the staged points (per device, idempotent)
-hipError_t gpcc_mks_configure()
-{
-#define GPCC_MKS_ATTR(PP, NN)                                                                                                        \
-    {                                                                                                                                \
-        const hipError_t e = hipFuncSetAttribute((const void *)gpcc_markov_draw<PP, NN>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                 GPCC_MARKOV_LDS_MAX);                                                               \
-        if (e != hipSuccess) return e;                                                                                               \
-    }
-    GPCC_MK_EACH(GPCC_MKS_ATTR)
-#undef GPCC_MKS_ATTR
-    return hipSuccess;
+    if ((long)g.blocks * g.threads > a.lstride || a.lanes < 1 || a.lanes > a.lstride) return hipErrorInvalidValue;   // the scratch's columns
+    return gpcc_mk_dispatch<GpccMkShipsAll>(g.p, g.noff, [&](auto P, auto NOFF) {
+        return gpcc_mk_launch_kernel(gpcc_markov_draw<P(), NOFF()>, g, 1, a);
+    });
 }
 
 // grid (ceil(lanes / 64), ceil(T / 64)), 256 threads: a tile of 64 lanes x 64 test points is read along the lanes (acc is

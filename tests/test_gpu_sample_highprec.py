@@ -212,7 +212,7 @@ def _unstaged_problem():
 def test_unstaged_draws_are_the_staged_ones(oracle):
     """L = 8 without offsets, N + T = 6496: the points fit LDS beside the cursors of one wave (20 (N + T) + 8 + 40 L 64 = 150 408 <=
     156 KiB) and not beside those of two (170 888).  64 draws are one wave per workgroup: staged.  64 CUs' worth of waves plus one --
-    one chunk by markov_sample_chunk_draws -- are two waves per workgroup (markov_launch_shape): unstaged, every lane reading global
+    one chunk by markov_sample_chunk_draws -- are two waves per workgroup (markov_launch): unstaged, every lane reading global
     memory.  A draw's bits depend on seed, row, s and m alone, so the first 64 draws of both calls are equal bitwise.
     Scratch: 8 (N + T) bytes per lane of the 256-rounded chunk, 0.81 GiB at 256 CUs."""
     import torch
