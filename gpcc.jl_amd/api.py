@@ -496,7 +496,7 @@ class Objective:
         """The hyper-parameter block of the Hessian in linear time (gpcc_loglik_hess_hyper_markov_batch: the Kalman filter's second-order
         forward sensitivities, one lane per (row, pair of parameters); OU, matern32 and matern52 only) -> (loglik[M], grad[M, 2L+1],
         hess[M, L+1, L+1], info[M]).  loglik, grad and info are bitwise loglik_grad_markov_batch's; hess is bitwise symmetric and NaN where
-        info != 0.  No Fisher information in linear time: loglik_hess_hyper_batch has it.  The rows of tau: loglik_hess_markov_batch.
+        info != 0.  The Fisher information in linear time: loglik_fisher_markov_batch.  The rows of tau: loglik_hess_markov_batch.
         rbf, or marginalise_b with more than 4 bands: GpccError (unsupported)."""
         M, delays, alpha, rho = self._params(delays, alpha, rho)
         P, n = 2 * self.L + 1, self.L + 1
@@ -515,8 +515,8 @@ class Objective:
         and info are bitwise loglik_grad_markov_batch's and hess[:, :L+1, :L+1] bitwise loglik_hess_hyper_markov_batch's; hess is bitwise
         symmetric and NaN where info != 0.  OU has no second derivative by tau on a row where two points of different bands have
         exactly equal shifted times: there every entry with a tau index is NaN while info stays 0 and everything else is untouched --
-        use loglik_hess_batch for OU on a grid of delays that collides with the cadence.  The Matern kernels are exact at ties.  No
-        Fisher information in linear time.  rbf, marginalise_b with more than 4 bands, or matern52 with marginalise_b and 4 bands:
+        use loglik_hess_batch for OU on a grid of delays that collides with the cadence.  The Matern kernels are exact at ties.  The
+        Fisher information in linear time: loglik_fisher_markov_batch.  rbf, marginalise_b with more than 4 bands, or matern52 with marginalise_b and 4 bands:
         GpccError (unsupported)."""
         M, delays, alpha, rho = self._params(delays, alpha, rho)
         P = 2 * self.L + 1
@@ -527,6 +527,25 @@ class Objective:
         self._chk(_capi.load().gpcc_loglik_hess_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _dp(grad),
                                                              _dp(hess), _ip(info)))
         return ll, grad, hess, info
+
+    def loglik_fisher_markov_batch(self, delays, alpha, rho):
+        """The expected (Fisher) information in linear time (gpcc_loglik_fisher_markov_batch: the Kalman filter carrying the second
+        moments of its means and of their tangents, one lane per (row, pair); OU, matern32 and matern52 only) -> (loglik[M], grad[M, P],
+        fisher[M, P, P], info[M]), P = 2L+1 in loglik_hess_batch's order [alpha_1..alpha_L, rho, tau_1..tau_L].  loglik, grad and info
+        are bitwise loglik_grad_markov_batch's; fisher is bitwise symmetric, NaN where info != 0, positive semi-definite at any point,
+        and depends on the fluxes through the offsets' prior variances only.  On an OU row where two points of different bands have
+        exactly equal shifted times every entry with a tau index is NaN while info stays 0 and the (alpha, rho) block is exact -- use
+        loglik_hess_batch's Fisher information there.  The Matern kernels are exact at ties.  rbf, marginalise_b with more than 4
+        bands, or matern52 with marginalise_b and 4 bands: GpccError (unsupported)."""
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        P = 2 * self.L + 1
+        ll = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, P), dtype=np.float64)
+        fisher = np.empty((M, P, P), dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        self._chk(_capi.load().gpcc_loglik_fisher_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _dp(grad),
+                                                               _dp(fisher), _ip(info)))
+        return ll, grad, fisher, info
 
     def laplace_evidence(self, delays, alpha0, rho0, rhomin=0.1, rhomax=20.0, max_rounds=50, g_tol=1e-6, solver="dense"):
         """The Laplace-marginalised evidence over alpha and rho per row of delays (G, L), from (alpha0[G, L], rho0[G]) (usually

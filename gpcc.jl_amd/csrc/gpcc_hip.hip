@@ -15,6 +15,7 @@
 #include "gpcc_markov_grad.hip.h"
 #include "gpcc_markov_hess.hip.h"
 #include "gpcc_markov_hess_tau.hip.h"
+#include "gpcc_markov_fisher.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -262,6 +263,9 @@ struct gpcc_handle_s {
     // [M][(2L + 1)^2]
     double *d_mkts = nullptr, *d_mktb = nullptr;
     long mkts_cap = 0, mktb_cap = 0;
+    // linear-time Fisher information (gpcc_loglik_fisher_markov_batch): the per-pair results [pair slots][M] and the blocks [M][(2L + 1)^2]
+    double *d_mkfs = nullptr, *d_mkfb = nullptr;
+    long mkfs_cap = 0, mkfb_cap = 0;
     int laplace_markov = 0;              // option "laplace_markov": gpcc_laplace_evidence's rounds are gpcc_loglik_hess_hyper_markov_batch calls
     int markov_chunk_rows = 0;           // option "markov_chunk_rows": rows per chunk of gpcc_predict_markov_batch (0: by the scratch budget)
     // linear-time draws (gpcc_sample_markov_batch): grown on demand -- the combine's weights of a chunk of rows (mksw_cap doubles), the
@@ -577,6 +581,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_mkgs); hipFree(h->d_mkgr);
     hipFree(h->d_mkhs); hipFree(h->d_mkhb);
     hipFree(h->d_mkts); hipFree(h->d_mktb);
+    hipFree(h->d_mkfs); hipFree(h->d_mkfb);
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
     hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
     hipFree(h->d_smean); hipFree(h->d_sdraw); hipFree(h->d_szeta); hipFree(h->d_slist); hipFree(h->d_soff);
@@ -2138,7 +2143,7 @@ static void markov_fill_args(gpcc_handle_t h, int M, const double *dd, const dou
 }
 
 // the kernels with dynamic LDS, for gpcc_handle::mk_lds_raised
-enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU };
+enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER };
 
 // The launch of every kernel of the filter, `name` in messages: one lane per row, `rows` rows along x and ny lanes per row along y.
 // The shape: one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy beyond; the light
@@ -2180,15 +2185,22 @@ static int markov_eval_launch(gpcc_handle_t h, int M, const double *dd, const do
                          [&](const GpccMkLaunch &g) { return gpcc_markov_launch(g, a); });
 }
 
-// a derivative kernel (gradient, Hessian block, Hessian's rows of tau) and its finish kernel over the M staged rows, one lane per
-// (row, slot); a holds the kernel's own fields, the filter's are filled here
+// a derivative kernel (gradient, Hessian block, Hessian's rows of tau, Fisher information) and its finish kernel over the M staged
+// rows, one lane per (row, slot); a holds the kernel's own fields, the filter's are filled here.  lds_bytes: markov_launch's
+template <typename ARGS, typename LdsBytes, typename Launch>
+static int markov_slots_launch(gpcc_handle_t h, const char *name, MarkovKernel kernel, int M, const double *dd, const double *da,
+                               const double *dr, int slots, ARGS &a, LdsBytes &&lds_bytes, Launch &&launch)
+{
+    markov_fill_args(h, M, dd, da, dr, a);
+    return markov_launch(h, name, kernel, M, slots, a.stage, lds_bytes, [&](const GpccMkLaunch &g) { return launch(g, slots, a); });
+}
+
+// ... for the kernels that stage the light curves alone
 template <typename ARGS, typename Launch>
 static int markov_slots_launch(gpcc_handle_t h, const char *name, MarkovKernel kernel, int M, const double *dd, const double *da,
                                const double *dr, int slots, ARGS &a, Launch &&launch)
 {
-    markov_fill_args(h, M, dd, da, dr, a);
-    return markov_launch(h, name, kernel, M, slots, a.stage, markov_filter_lds(h),
-                         [&](const GpccMkLaunch &g) { return launch(g, slots, a); });
+    return markov_slots_launch(h, name, kernel, M, dd, da, dr, slots, a, markov_filter_lds(h), launch);
 }
 
 extern "C" int gpcc_loglik_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
@@ -2691,6 +2703,56 @@ extern "C" int gpcc_loglik_hess_markov_batch(gpcc_handle_t h, int M, const doubl
         rc = markov_slots_launch(h, "gpcc_markov_hess_tau", MK_HESS_TAU, M, dd, da, dr, slots, a, gpcc_markov_hess_tau_launch);
         if (rc) return rc;
         HIPCHK(h, hipMemcpyAsync(hess, h->d_mktb, sizeof(double) * W * W * M, hipMemcpyDeviceToHost, h->main_stream));
+    }
+    return markov_finish(h, M, loglik, info);
+}
+
+// ------------------------------------------------------------------------------------------
+// The linear-time Fisher information of the Markov kernels (gpcc_loglik_fisher_markov_batch; kernel: gpcc_markov_fisher.hip.h, DESIGN.md
+// 4.22): the second moments of the filter's means and of their tangents, one lane per (row, pair slot).  Value, info and gradient come
+// from the gradient entry's launches inside the same call (bitwise gpcc_loglik_grad_markov_batch's by construction); it needs what that
+// entry needs plus the pair slots and the blocks, nothing of the N^2 workspace.
+// ------------------------------------------------------------------------------------------
+extern "C" int gpcc_loglik_fisher_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                               double *loglik, double *grad, double *fisher, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (M == 0) return 0;
+    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    int rc = markov_refusals(h, "gpcc_loglik_fisher_markov_batch", "gpcc_loglik_hess_batch");
+    if (rc) return rc;
+    if (fisher) {
+        const MarkovDims d = markov_dims(primary(h));
+        if (!gpcc_mk_ships<GpccMkShipsFisher>(d.p, d.noff))
+            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_fisher_markov_batch: the instantiation <%d, %d> (states of the process, "
+                        "offset states) needs scratch memory and does not ship; use gpcc_loglik_hess_batch", d.p, d.noff);
+    }
+    if (route_fp64(h, "linear-time Fisher information", rc,
+                   [&](gpcc_handle_t o) { return gpcc_loglik_fisher_markov_batch(o, M, delays, alpha, rho, loglik, grad, fisher, info); }))
+        return rc;
+    GPCC_ON_DEVICE(h, h->device);
+    const int W = 2 * h->L + 1, slots = gpcc_markov_fisher_slots(h->L);
+    double *dd, *da, *dr;
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
+        int g = markov_grad_grow(h, M);
+        if (!g && fisher) g = grow_buf(h, &h->d_mkfs, &h->mkfs_cap, (long)slots * M);
+        return (g || !fisher) ? g : grow_buf(h, &h->d_mkfb, &h->mkfb_cap, (long)W * W * M);
+    });
+    if (rc) return rc;
+    rc = markov_grad_enqueue(h, M, dd, da, dr, grad);
+    if (rc) return rc;
+    if (fisher) {
+        GpccMarkovFisherArgs a;
+        a.slot = h->d_mkfs; a.fisher = h->d_mkfb;
+        // (the instantiations that keep D in LDS take that much more per lane: fewer points are staged beside it)
+        const MarkovDims d = markov_dims(h);
+        const auto lds = [h, d](int thr, bool st) {
+            return gpcc_markov_lds_bytes(h->N, h->L, thr, st) + gpcc_markov_fisher_lds_extra(d.p, d.noff, thr);
+        };
+        rc = markov_slots_launch(h, "gpcc_markov_fisher", MK_FISHER, M, dd, da, dr, slots, a, lds, gpcc_markov_fisher_launch);
+        if (rc) return rc;
+        HIPCHK(h, hipMemcpyAsync(fisher, h->d_mkfb, sizeof(double) * W * W * M, hipMemcpyDeviceToHost, h->main_stream));
     }
     return markov_finish(h, M, loglik, info);
 }

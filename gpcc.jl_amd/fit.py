@@ -112,16 +112,21 @@ def laplace_covariance(H, free, L=None):
     return cov, True
 
 
-def delay_covariance(objective, delays, alpha, rho, free=None, solver="dense"):
+def delay_covariance(objective, delays, alpha, rho, free=None, solver="dense", curvature="hessian"):
     """The Laplace covariance of the delays (and hyper-parameters) at one point (delays[L], alpha[L], rho): one Hessian call over
     [alpha_1..alpha_L, rho, tau_1..tau_L] -- objective.loglik_hess_batch (solver "dense") or objective.loglik_hess_markov_batch (solver
     "markov": linear time, OU / matern32 / matern52; Objective's or markov.MarkovObjective's) -- then
     laplace_covariance over `free` -> (cov, ok).  free defaults to every alpha, rho and tau_2..tau_L (the first delay fixed: a common
     shift of all delays leaves the likelihood unchanged).  ok is False and cov all NaN when the point cannot be evaluated (info != 0),
     when a needed entry of the Hessian is NaN (solver "markov" with OU at a delay that makes two bands' shifted times collide: use
-    "dense" there) or when -H_ff is not positive definite.  ValueError for another solver, or for a `free` that holds every delay."""
+    "dense" there) or when -H_ff is not positive definite.  ValueError for another solver, or for a `free` that holds every delay.
+    curvature="fisher": the expected (Fisher) information I in place of -H, cov = (I_ff)^-1 -- positive semi-definite at any point, not
+    only at a maximum, and independent of the fluxes (a cadence's forecast) -- from objective.loglik_hess_batch's Fisher matrix (solver
+    "dense") or objective.loglik_fisher_markov_batch (solver "markov"); the same ok rules."""
     if solver not in ("dense", "markov"):
         raise ValueError("solver must be 'dense' or 'markov', got %r" % (solver,))
+    if curvature not in ("hessian", "fisher"):
+        raise ValueError("curvature must be 'hessian' or 'fisher', got %r" % (curvature,))
     delays = np.asarray(delays, dtype=np.float64).reshape(1, -1)
     L = delays.shape[1]
     alpha = np.asarray(alpha, dtype=np.float64).reshape(1, L)
@@ -132,7 +137,13 @@ def delay_covariance(objective, delays, alpha, rho, free=None, solver="dense"):
     idx = np.flatnonzero(free) if free.dtype == bool else free.astype(int).ravel()
     if set(range(L + 1, 2 * L + 1)) <= set(idx.tolist()):
         raise ValueError("free holds every delay: a common shift of all delays leaves the likelihood unchanged, fix at least one")
-    if solver == "markov":
+    if curvature == "fisher":
+        if solver == "markov":
+            _, _, fisher, info = objective.loglik_fisher_markov_batch(delays, alpha, rho)
+        else:
+            _, _, _, fisher, info = objective.loglik_hess_batch(delays, alpha, rho)
+        hess = -np.asarray(fisher, dtype=np.float64)
+    elif solver == "markov":
         _, _, hess, info = objective.loglik_hess_markov_batch(delays, alpha, rho)
     else:
         _, _, hess, _, info = objective.loglik_hess_batch(delays, alpha, rho)

@@ -316,7 +316,8 @@ def loglik_grad_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marg
 # NaN (info stays 0; value, gradient and the (alpha, rho) block are untouched): use the dense Hessian for OU on a grid of delays that
 # collides with the cadence.
 #
-# The Fisher information is not offered in linear time (its expectation needs another recursion): it stays with the dense Hessian.
+# The Fisher information has a recursion of its own (loglik_fisher below; csrc/gpcc_markov_fisher.hip.h): it carries
+# second moments of the filter's means in place of the means and the second tangents.
 # ----------------------------------------------------------------------------------------------------------------------------------
 def transition_d2lambda(kernel, d, rho):
     """d2A(d)/dlambda2, in closed form per kernel."""
@@ -534,6 +535,145 @@ def loglik_hess_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marg
     alpha = np.asarray(alpha, np.float64).reshape(-1, L)
     rho = np.asarray(rho, np.float64).reshape(-1)
     out = [loglik_hess(kernel, tarray, yarray, stdarray, delays[i], alpha[i], rho[i], marginalise_b) for i in range(len(rho))]
+    return (np.array([o[0] for o in out]), np.array([o[1] for o in out]).reshape(-1, W),
+            np.array([o[2] for o in out]).reshape(-1, W, W), np.array([o[3] for o in out], dtype=np.int32))
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# The Fisher information in linear time (csrc/gpcc_markov_fisher.hip.h), the same algorithm in numpy.  The expectation
+# of -l_ab over the data of the model at theta: the innovation eps_k is independent of the past with variance S_k, its tangent
+# eps_a = -h_a'm - h'm_a depends on the past only, so
+#
+#   I_ab = sum_k [ S_a S_b / (2 S^2) + E[eps_a eps_b] / S ].
+#
+# No data enters: beside P, P_a, P_b (the gradient's tangents, _grad_pass's) the second moments of the means are carried, all n x n
+# and zero at the start (the prior mean is 0): C_a = E[m_a m'], C_b = E[m_b m'], D = E[m_a m_b'].  Z = E[m m'] = Pi - P with Pi =
+# blockdiag(Pinf, Sigma_b) the prior covariance: the state is stationary.  With Abar = blockdiag(A, I), Abar_a = blockdiag(A_a, 0):
+#
+#   predict   (Z before the step)  D <- Abar_a Z Abar_b' + Abar_a C_b' Abar' + Abar C_a Abar_b' + Abar D Abar',
+#             C_a <- Abar_a Z Abar' + Abar C_a Abar',  then P_a, P_b, P as _grad_pass
+#   update    (Z after the predict)  g = Ph / S,  g_a = (Ph)_a / S - Ph S_a / S^2,
+#             u_a = E[eps_a m'] = -h_a'Z - h'C_a,  v_ab = E[eps_a m_b'] = -h_a'C_b' - h'D,  v_ba = -h_b'C_a' - h'D',
+#             w = E[eps_a eps_b] = h_a'Z h_b + h_a'C_b'h + h'C_a h_b + h'D h:
+#             I_ab += S_a S_b / (2 S^2) + w / S,
+#             D += g v_ab + v_ba'g' + w g g' + S g_a g_b',  C_a += g u_a + S g_a g',  then P_a, P_b, P as _grad_pass
+#
+# The merged order is merge_order()'s, fixed.  The Matern kernels are C^1 at zero lag: exact, ties or not.  OU has a kink, the dense
+# convention at an exact tie of two bands is the mean of the one-sided dK's and the Fisher information is bilinear in them, so on such
+# a row every entry with a tau index is NaN (info stays 0, the (alpha, rho) block is exact): loglik_hess's contract.
+# ----------------------------------------------------------------------------------------------------------------------------------
+FISHER_SLIPS = ("no_innov", "prior_moment", "no_gain_tangent", "no_dh_moment", "tau_one_lag")
+
+
+def _fisher_pass(name, train, alpha, rho, p, n, vb, a, b, slip=None):
+    """I_ab (a <= b in 0..2L: alpha_1..alpha_L, rho, tau_1..tau_L) by the moment recursion over the training observations in
+    merge_order()'s order; the residuals are not read.  A pair with a tau on an OU row with a cross-band tie: NaN.  slip: loglik_fisher()'s."""
+    L = len(alpha)
+    ev = sorted(train, key=lambda e: (e[0], e[1], e[2]))
+    ra, rb = a == L, b == L
+    ta, tb = a - L - 1, b - L - 1           # the band of a tau (negative: not a tau)
+    X = slice(0, p)
+    zero = np.zeros((p, p))
+    Pinf = stationary(name, rho)
+    Qa = stationary_drho(name, rho) if ra else zero
+    Qb = stationary_drho(name, rho) if rb else zero
+    F = companion(name, rho)
+    Pi = _prior(name, rho, p, n, vb)
+    P = Pi.copy()
+    Pa, Pb = np.zeros((n, n)), np.zeros((n, n))
+    Pa[X, X], Pb[X, X] = Qa, Qb
+    Ca, Cb, D = np.zeros((n, n)), np.zeros((n, n)), np.zeros((n, n))
+    Ab_, Aa_, Ab__ = np.eye(n), np.zeros((n, n)), np.zeros((n, n))      # Abar, Abar_a, Abar_b
+    fish, sprev, bprev = 0.0, None, -1
+    for (s, band, _, _, s2) in ev:
+        d = 0.0 if sprev is None else s - sprev
+        if tb >= 0 and name == "OU" and sprev is not None and d == 0.0 and band != bprev:
+            return math.nan
+        ca = 0.0 if (ta < 0 or sprev is None) else -float(band == ta) + (0.0 if slip == "tau_one_lag" else float(bprev == ta))
+        cb = 0.0 if (tb < 0 or sprev is None) else -float(band == tb) + (0.0 if slip == "tau_one_lag" else float(bprev == tb))
+        sprev, bprev = s, band
+        A = transition(name, d, rho)
+        Aa = transition_drho(name, d, rho) if ra else (ca * (F @ A) if ca != 0.0 else zero)
+        Ab = transition_drho(name, d, rho) if rb else (cb * (F @ A) if cb != 0.0 else zero)
+        Ab_[X, X], Aa_[X, X], Ab__[X, X] = A, Aa, Ab
+        Z = Pi if slip == "prior_moment" else Pi - P
+        D = Aa_ @ Z @ Ab__.T + Aa_ @ Cb.T @ Ab_.T + Ab_ @ Ca @ Ab__.T + Ab_ @ D @ Ab_.T
+        Ca = Aa_ @ Z @ Ab_.T + Ab_ @ Ca @ Ab_.T
+        Cb = Ab__ @ Z @ Ab_.T + Ab_ @ Cb @ Ab_.T
+        D0, Da, Db = P[X, X] - Pinf, Pa[X, X] - Qa, Pb[X, X] - Qb
+        Pa[X, X] = Aa @ D0 @ A.T + A @ Da @ A.T + A @ D0 @ Aa.T + Qa
+        Pb[X, X] = Ab @ D0 @ A.T + A @ Db @ A.T + A @ D0 @ Ab.T + Qb
+        Pa[X, p:], Pb[X, p:] = Aa @ P[X, p:] + A @ Pa[X, p:], Ab @ P[X, p:] + A @ Pb[X, p:]
+        Pa[p:, X], Pb[p:, X] = Pa[X, p:].T, Pb[X, p:].T
+        P[X, X] = A @ D0 @ A.T + Pinf
+        P[X, p:] = A @ P[X, p:]
+        P[p:, X] = P[X, p:].T
+
+        h, ha, hb = np.zeros(n), np.zeros(n), np.zeros(n)
+        h[0] = alpha[band]
+        if n > p:
+            h[p + band] = 1.0
+        ha[0], hb[0] = float(band == a), float(band == b)
+        Ph = P @ h
+        Pha, Phb = Pa @ h + P @ ha, Pb @ h + P @ hb
+        S = h @ Ph + s2
+        if not (S > 0.0 and math.isfinite(S)):
+            return math.nan
+        Sa, Sb = ha @ Ph + h @ Pha, hb @ Ph + h @ Phb
+        inv = 1.0 / S
+        g = Ph * inv
+        ga, gb = Pha * inv - g * (inv * Sa), Phb * inv - g * (inv * Sb)
+        Z = Pi if slip == "prior_moment" else Pi - P
+        ma, mb = (np.zeros(n), np.zeros(n)) if slip == "no_dh_moment" else (ha, hb)
+        ua, ub = -(ma @ Z) - h @ Ca, -(mb @ Z) - h @ Cb
+        vab, vba = -(ma @ Cb.T) - h @ D, -(mb @ Ca.T) - h @ D.T
+        w = ma @ Z @ mb + ma @ Cb.T @ h + h @ Ca @ mb + h @ D @ h
+        fish += 0.5 * Sa * Sb * inv * inv + (0.0 if slip == "no_innov" else w * inv)
+        D = D + np.outer(g, vab) + np.outer(vba, g) + w * np.outer(g, g)
+        Ca, Cb = Ca + np.outer(g, ua), Cb + np.outer(g, ub)
+        if slip != "no_gain_tangent":
+            D = D + S * np.outer(ga, gb)
+            Ca, Cb = Ca + S * np.outer(ga, g), Cb + S * np.outer(gb, g)
+        Pa = Pa - np.outer(ga, Ph) - np.outer(g, Pha)
+        Pb = Pb - np.outer(gb, Ph) - np.outer(g, Phb)
+        P = P - np.outer(g, Ph)
+        P, Pa, Pb = (0.5 * (M_ + M_.T) for M_ in (P, Pa, Pb))
+    return fish
+
+
+def loglik_fisher(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True, pairs=None, _slip=None):
+    """(loglik, grad[2L+1], fisher[2L+1, 2L+1], info) of one (tau, alpha, rho): loglik_grad()'s value, gradient and info, and the expected
+    (Fisher) information over [alpha_1..alpha_L, rho, tau_1..tau_L] by the moment recursion above: Objective.loglik_fisher_markov_batch's
+    row.  It depends on the fluxes through the offsets' prior variances only (not at all without marginalise_b), and is positive
+    semi-definite at any point.  Each pair is computed once and mirrored; pairs (a list of (a, b)) restricts the work to those entries
+    and leaves the others NaN.  grad and fisher are NaN where info != 0.  On an OU row with a cross-band tie in shifted time every entry
+    with a tau index is NaN and info stays 0; with one band the tau entries are exact zeros.
+    _slip (tests only) injects one mistake: "no_innov" (the E[eps_a eps_b] / S term left out), "prior_moment" (Z = Pi instead of Pi - P),
+    "no_gain_tangent" (the S g_a terms of the moments' update left out), "no_dh_moment" (h_a, h_b left out of u, v and w), "tau_one_lag"
+    (only the lag before a point of band l is differentiated, not the one after)."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b,
+                                                                       codes_first=True)
+    W = 2 * L + 1
+    ll, grad, info = loglik_grad(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b)
+    fisher = np.full((W, W), math.nan)
+    if info:
+        return ll, grad, fisher, info
+    todo = [(a, b) for a in range(W) for b in range(a, W)] if pairs is None else sorted({(min(a, b), max(a, b)) for a, b in pairs})
+    for a, b in todo:
+        if not (0 <= a and b < W):
+            raise ValueError("pair (%d, %d) outside 0..%d" % (a, b, W - 1))
+        fisher[a, b] = fisher[b, a] = _fisher_pass(name, train, alpha, rho, p, n, vb, a, b, slip=_slip)
+    return ll, grad, fisher, 0
+
+
+def loglik_fisher_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True, pairs=None):
+    """loglik_fisher over M rows -> (loglik[M], grad[M, 2L+1], fisher[M, 2L+1, 2L+1], info[M]): Objective.loglik_fisher_markov_batch's shape."""
+    L = len(tarray)
+    W = 2 * L + 1
+    delays = np.asarray(delays, np.float64).reshape(-1, L)
+    alpha = np.asarray(alpha, np.float64).reshape(-1, L)
+    rho = np.asarray(rho, np.float64).reshape(-1)
+    out = [loglik_fisher(kernel, tarray, yarray, stdarray, delays[i], alpha[i], rho[i], marginalise_b, pairs) for i in range(len(rho))]
     return (np.array([o[0] for o in out]), np.array([o[1] for o in out]).reshape(-1, W),
             np.array([o[2] for o in out]).reshape(-1, W, W), np.array([o[3] for o in out], dtype=np.int32))
 
@@ -1146,7 +1286,7 @@ class MarkovObjective:
         return loglik_hess_hyper_batch(self.kernel, *self.data, delays, alpha, rho, self.marginalise_b)
 
     def loglik_hess_hyper_batch(self, delays, alpha, rho):
-        """The same under the dense entry's name and shape (no Fisher information in linear time: None), so that
+        """The same under the dense entry's name and shape (the Fisher information is loglik_fisher_markov_batch's: None here), so that
         laplace.laplace_evidence runs over this objective."""
         ll, grad, hess, info = self.loglik_hess_hyper_markov_batch(delays, alpha, rho)
         return ll, grad, hess, None, info
@@ -1154,6 +1294,10 @@ class MarkovObjective:
     def loglik_hess_markov_batch(self, delays, alpha, rho):
         """Objective.loglik_hess_markov_batch's result: (loglik[M], grad[M, 2L+1], hess[M, 2L+1, 2L+1], info[M])."""
         return loglik_hess_batch(self.kernel, *self.data, delays, alpha, rho, self.marginalise_b)
+
+    def loglik_fisher_markov_batch(self, delays, alpha, rho):
+        """Objective.loglik_fisher_markov_batch's result: (loglik[M], grad[M, 2L+1], fisher[M, 2L+1, 2L+1], info[M])."""
+        return loglik_fisher_batch(self.kernel, *self.data, delays, alpha, rho, self.marginalise_b)
 
     def _rows(self, delays, alpha, rho):
         delays = np.asarray(delays, np.float64).reshape(-1, self.L)

@@ -218,7 +218,7 @@ int gpcc_loglik_batch(gpcc_handle_t handle, int M, const double *delays, const d
  * entry instead of a gpcc_loglik_batch (GPCC_ERR_UNSUPPORTED where this entry is); read-only "markov_count": evaluations so far.
  * Predictions, held-out scores and the offsets' posterior in linear time: the three entries below; the gradient in linear time:
  * gpcc_loglik_grad_markov_batch after them; the (alpha, rho) block of the Hessian is gpcc_loglik_hess_hyper_markov_batch, the full
- * Hessian (the rows of tau) gpcc_loglik_hess_markov_batch; the Fisher information stays dense.
+ * Hessian (the rows of tau) gpcc_loglik_hess_markov_batch; the Fisher information gpcc_loglik_fisher_markov_batch.
  * Blocking. */
 int gpcc_loglik_markov_batch(gpcc_handle_t handle, int M, const double *delays, const double *alpha, const double *rho,
                              double *loglik, int *info);
@@ -335,8 +335,8 @@ int gpcc_loglik_hess_hyper_batch(gpcc_handle_t h, int M, const double *delays, c
  * out of scratch memory does not ship and is refused the same way, the message naming gpcc_loglik_hess_hyper_batch: at present <3, 4>
  * alone, Matern-5/2 with marginalise_b and L = 4 (it takes all 512 registers of a lane and 28 bytes more); everything else that
  * gpcc_loglik_markov_batch takes ships (DESIGN.md 4.18 has the table).
- * NOT offered in linear time: the Fisher information (its expectation needs another recursion), which stays with the dense entries
- * above.  The rows of tau -- the full Hessian -- are gpcc_loglik_hess_markov_batch below.
+ * The Fisher information in linear time has a recursion and an entry of its own, gpcc_loglik_fisher_markov_batch below.  The rows of
+ * tau -- the full Hessian -- are gpcc_loglik_hess_markov_batch below.
  * Memory: gpcc_loglik_grad_markov_batch's, plus 8 M bytes per pair ((L+1)(L+2)/2 of them) and 8 M (L+1)^2 bytes; none of the N^2
  * workspace.  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Blocking.
  * Option "laplace_markov" (default 0; refused where "fit_markov" is): gpcc_laplace_evidence's Newton rounds call this entry instead of
@@ -350,7 +350,7 @@ int gpcc_loglik_hess_hyper_markov_batch(gpcc_handle_t h, int M, const double *de
  * and the leading (L+1) x (L+1) block of every hess block is bitwise gpcc_loglik_hess_hyper_markov_batch's: both come from that
  * entry's launches inside the same call.  hess (may be NULL: then the call is gpcc_loglik_grad_markov_batch): M row-major P x P
  * blocks, every pair computed once and written to both halves (bitwise symmetric), NaN where info != 0.  There is no Fisher argument:
- * the Fisher information still needs a recursion of its own.
+ * the Fisher information is gpcc_loglik_fisher_markov_batch's.
  *   TIES.  Matern-3/2 and Matern-5/2 are twice differentiable at zero lag: the rows of tau are exact whether or not two bands' shifted
  *   times coincide.  OU is not.  On a row in which two points of DIFFERENT bands have exactly equal shifted times (a delay equal to a
  *   difference of two observation times) no second derivative by tau exists, and gpcc_loglik_hess_batch's convention there
@@ -368,6 +368,31 @@ int gpcc_loglik_hess_hyper_markov_batch(gpcc_handle_t h, int M, const double *de
  * workspace.  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Blocking. */
 int gpcc_loglik_hess_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                   double *loglik, double *grad, double *hess, int *info);
+
+/* The expected (FISHER) INFORMATION in LINEAR TIME for the Markov kernels, over theta = [alpha_1..alpha_L, rho, tau_1..tau_L], P = 2L+1
+ * (gpcc_loglik_hess_batch's order and, up to rounding, its `fisher`): I_ab = sum_k [ S_a S_b / (2 S^2) + E[eps_a eps_b] / S ] over the
+ * filter's steps, the expectation taken by carrying the second moments of the filter's means and of their tangents beside the
+ * covariance and its tangents (kernel: csrc/gpcc_markov_fisher.hip.h).  It is positive semi-definite at any point and
+ * reads no flux (with marginalise_b the fluxes enter through the offsets' prior variances only): it answers how well a cadence
+ * constrains the delay before any data exist.  loglik[M], info[M] and grad come from gpcc_loglik_grad_markov_batch's launches inside
+ * the same call and are bitwise that entry's.  fisher (may be NULL: then the call is gpcc_loglik_grad_markov_batch): M row-major P x P
+ * blocks, every pair computed once and written to both halves (bitwise symmetric), NaN where info != 0.
+ *   TIES.  Matern-3/2 and Matern-5/2 are exact whether or not two bands' shifted times coincide.  OU has a kink at zero lag: on a row
+ *   in which two points of DIFFERENT bands have exactly equal shifted times gpcc_loglik_hess_batch's convention (k_s(0) = 0) is the
+ *   mean of the one-sided derivatives of K, the Fisher information is bilinear in them, and no order of the filter returns it: for such
+ *   a row EVERY ENTRY WITH A tau INDEX IS NaN, info[m] stays 0 and the (alpha, rho) block is exact (gpcc_loglik_hess_markov_batch's
+ *   contract).  With L = 1 the tau entries are exact zeros.
+ * Refusals, argument checks, info codes and memory rules are gpcc_loglik_markov_batch's (rbf, and marginalise_b with L > 4:
+ * GPCC_ERR_UNSUPPORTED before any device work; -1 / -2 rows never touch the others).  An instantiation <states of the process, offset
+ * states> that the compiler cannot keep out of scratch memory does not ship and is refused the same way when fisher is not NULL, the
+ * message naming gpcc_loglik_hess_batch: at present <3, 4> alone, Matern-5/2 with marginalise_b and L = 4; <3, 3> keeps one of its
+ * moment matrices in LDS (DESIGN.md 4.22 has the table and the layouts tried).
+ * Path: one lane per (row, pair slot), P (P + 1) / 2 slots, in one launch, then a kernel that writes the blocks.  No atomics: a row's
+ * bits depend on the row alone (any M, any row order).
+ * Memory: gpcc_loglik_grad_markov_batch's, plus 8 M bytes per slot and 8 M P^2 bytes, grown on demand; none of the N^2 workspace.
+ * Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Blocking. */
+int gpcc_loglik_fisher_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                    double *loglik, double *grad, double *fisher, int *info);
 
 /* Same with DEVICE pointers, enqueued behind `stream` (a hipStream_t, NULL = default stream) and
  * joined back into it: asynchronous, outputs valid once `stream` has drained. */

@@ -226,8 +226,8 @@ end
 
 "the [α_1..α_L, ρ] block of the Hessian in LINEAR time (gpcc_loglik_hess_hyper_markov_batch: the Kalman filter's second-order forward
 sensitivities, one lane per (row, pair of parameters), DESIGN 4.18; OU, matern32, matern52): (ll[M], grad (2L+1)×M, hess
-(L+1)×(L+1)×M, info[M]).  ll, grad and info are bitwise loglik_grad_markov's; hess is bitwise symmetric, NaN where info != 0.  No Fisher
-information in linear time (loglik_hess_hyper_batch has it); the rows of τ: loglik_hess_markov below.  Errors for rbf, for marginalise_b
+(L+1)×(L+1)×M, info[M]).  ll, grad and info are bitwise loglik_grad_markov's; hess is bitwise symmetric, NaN where info != 0.  The Fisher
+information in linear time: loglik_fisher_markov below; the rows of τ: loglik_hess_markov below.  Errors for rbf, for marginalise_b
 with more than 4 bands, and for matern52 with marginalise_b and 4 bands (that instantiation needs scratch memory and does not ship).
 The option "laplace_markov" (ccall((:gpcc_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Clong), h.ptr, "laplace_markov", 1)) makes
 laplace_evidence's Newton rounds call this entry."
@@ -250,7 +250,7 @@ sensitivities with the tangents of the transition by the lags, one lane per (row
 block bitwise loglik_hess_hyper_markov's; hess is bitwise symmetric, NaN where info != 0.  OU has no second derivative by τ on a row
 where two points of different bands have exactly equal shifted times: there every entry with a τ index is NaN, info stays 0 and the
 rest is untouched -- use loglik_hess_batch for OU on a grid of delays that collides with the cadence.  The Matérn kernels are exact
-at ties.  No Fisher information in linear time.  Errors as loglik_hess_hyper_markov."
+at ties.  The Fisher information in linear time: loglik_fisher_markov.  Errors as loglik_hess_hyper_markov."
 function loglik_hess_markov(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
     M, P = length(rho), 2h.L + 1
     @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
@@ -262,6 +262,26 @@ function loglik_hess_markov(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Fl
                h.ptr, M, delays, alpha, rho, ll, grad, hess, info)
     rc == 0 || error("gpcc_loglik_hess_markov_batch: " * lasterror(h.ptr))
     return ll, grad, hess, info
+end
+
+"the expected (FISHER) information over [α_1..α_L, ρ, τ_1..τ_L] in LINEAR time (gpcc_loglik_fisher_markov_batch: the Kalman filter
+carrying the second moments of its means and of their tangents, one lane per (row, pair), DESIGN 4.22; OU, matern32, matern52):
+(ll[M], grad (2L+1)×M, fisher (2L+1)×(2L+1)×M, info[M]).  ll, grad and info are bitwise loglik_grad_markov's; fisher is bitwise
+symmetric, NaN where info != 0, positive semi-definite at any point, and reads the fluxes through the offsets' prior variances only.
+On an OU row where two points of different bands have exactly equal shifted times every entry with a τ index is NaN, info stays 0 and
+the (α, ρ) block is exact -- use loglik_hess_batch's fisher there.  The Matérn kernels are exact at ties.  Errors for rbf, for
+marginalise_b with more than 4 bands, and for matern52 with marginalise_b and 4 bands (that instantiation does not ship)."
+function loglik_fisher_markov(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
+    M, P = length(rho), 2h.L + 1
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    grad = Matrix{Float64}(undef, P, M)
+    fisher = Array{Float64}(undef, P, P, M)                               # symmetric: row- or column-major alike
+    rc = ccall((:gpcc_loglik_fisher_markov_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, ll, grad, fisher, info)
+    rc == 0 || error("gpcc_loglik_fisher_markov_batch: " * lasterror(h.ptr))
+    return ll, grad, fisher, info
 end
 
 "Laplace-marginalised evidence over α and ρ per delay (columns of delays, L×G), from (alpha0 L×G, rho0[G]), usually the fit's
