@@ -306,6 +306,47 @@ class Objective:
         self._chk(_capi.load().gpcc_loglik_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _ip(info)))
         return ll, info
 
+    def realisations(self, Y):
+        """Y of loglik_markov_realisations as one (R, N) array: a list of L arrays (R, N_l) side by side, or the (R, N) array itself."""
+        if isinstance(Y, (list, tuple)):
+            if len(Y) != self.L:
+                raise ValueError("Y must hold L = %d arrays (R, N_l)" % self.L)
+            Y = np.concatenate([np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in Y], axis=1)
+        Y = _d(np.atleast_2d(Y))
+        if Y.shape[1] != self.N or Y.shape[0] < 1:
+            raise ValueError("Y must be (R, N) = (R >= 1, %d)" % self.N)
+        return Y
+
+    def loglik_markov_realisations(self, Y, delays, alpha, rho, center="own"):
+        """The linear-time objective of R flux realisations on this handle's cadence in one pass (gpcc_loglik_markov_multi_batch: per
+        parameter row the filter's covariance recursion runs once and drives R means; OU, matern32 and matern52 only) ->
+        (loglik[M, R], info[M]).  Y: a list of L arrays (R, N_l), or one (R, N) array, each row in the order the handle took y.
+        The model is the handle's: times, sigma, kernel, b-mode and, with marginalise_b, the offsets' prior variances of the y the
+        handle was created with.  center: "own" subtracts each realisation's own band means (without marginalise_b the value is then
+        that of a fresh Objective on (t, Y_r, sigma)), "handle" the handle's band means, an (R, L) array is subtracted as given.
+        info is loglik_markov_batch's and depends on the row only; a row with info != 0 is NaN throughout, a flux that is not finite
+        makes its own column NaN.  Cell (m, r) is bitwise the same for any M, R and order; it is not bitwise loglik_markov_batch's.
+        rbf, or marginalise_b with more than 4 bands: GpccError (unsupported)."""
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        Y = self.realisations(Y)
+        R = Y.shape[0]
+        if isinstance(center, str):
+            if center not in ("own", "handle"):
+                raise ValueError('center must be "own", "handle" or an (R, L) array')
+            mean = None
+            if center == "own":
+                edges = np.concatenate([[0], np.cumsum(self.Nl)])
+                mean = _d(np.stack([Y[:, edges[l]:edges[l + 1]].sum(axis=1) / self.Nl[l] for l in range(self.L)], axis=1))
+        else:
+            mean = _d(center)
+            if mean.shape != (R, self.L):
+                raise ValueError("center must be (R, L) = (%d, %d)" % (R, self.L))
+        ll = np.empty((M, R), dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        self._chk(_capi.load().gpcc_loglik_markov_multi_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), R, _dp(Y),
+                                                              _dp(mean) if mean is not None else None, _dp(ll), _ip(info)))
+        return ll, info
+
     def predict_markov_batch(self, delays, alpha, rho, ttest, weights=None):
         """predict_batch in linear time (gpcc_predict_markov_batch: two Kalman filters and a combine per row, O(N + T); OU, matern32 and
         matern52 only) -> (mu[M, T], var[M, T], loglik[M], info[M], mix_mu[T], mix_var[T]), what predict_batch returns.  ttest need not

@@ -16,6 +16,7 @@
 #include "gpcc_markov_hess.hip.h"
 #include "gpcc_markov_hess_tau.hip.h"
 #include "gpcc_markov_fisher.hip.h"
+#include "gpcc_markov_multi.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -266,6 +267,13 @@ struct gpcc_handle_s {
     // linear-time Fisher information (gpcc_loglik_fisher_markov_batch): the per-pair results [pair slots][M] and the blocks [M][(2L + 1)^2]
     double *d_mkfs = nullptr, *d_mkfb = nullptr;
     long mkfs_cap = 0, mkfb_cap = 0;
+    // linear-time log-likelihood of many realisations (gpcc_loglik_markov_multi_batch): grown on demand, for one chunk of realisations --
+    // the fluxes as the caller holds them (mkmy_cap doubles), their packed residuals (mkmr_cap), the means (mkmm_cap), the chunk's
+    // results [M][chunk] (mkmo_cap) and the sort permutation (N ints, uploaded once)
+    double *d_mkmy = nullptr, *d_mkmr = nullptr, *d_mkmm = nullptr, *d_mkmo = nullptr;
+    int *d_mkmp = nullptr;
+    long mkmy_cap = 0, mkmr_cap = 0, mkmm_cap = 0, mkmo_cap = 0, mkmp_cap = 0;
+    int markov_multi_chunk = 0;          // option "markov_multi_chunk": realisations per chunk of gpcc_loglik_markov_multi_batch (0: by the scratch budget)
     int laplace_markov = 0;              // option "laplace_markov": gpcc_laplace_evidence's rounds are gpcc_loglik_hess_hyper_markov_batch calls
     int markov_chunk_rows = 0;           // option "markov_chunk_rows": rows per chunk of gpcc_predict_markov_batch (0: by the scratch budget)
     // linear-time draws (gpcc_sample_markov_batch): grown on demand -- the combine's weights of a chunk of rows (mksw_cap doubles), the
@@ -582,6 +590,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_mkhs); hipFree(h->d_mkhb);
     hipFree(h->d_mkts); hipFree(h->d_mktb);
     hipFree(h->d_mkfs); hipFree(h->d_mkfb);
+    hipFree(h->d_mkmy); hipFree(h->d_mkmr); hipFree(h->d_mkmm); hipFree(h->d_mkmo); hipFree(h->d_mkmp);
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
     hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
     hipFree(h->d_smean); hipFree(h->d_sdraw); hipFree(h->d_szeta); hipFree(h->d_slist); hipFree(h->d_soff);
@@ -694,6 +703,9 @@ extern "C" int gpcc_set_option(gpcc_handle_t h, const char *key, long v)
     } else if (!strcmp(key, "markov_chunk_rows")) {
         if (v < 0) return fail(h, GPCC_ERR_ARGUMENT, "markov_chunk_rows must be >= 0");
         h->markov_chunk_rows = (int)v;
+    } else if (!strcmp(key, "markov_multi_chunk")) {
+        if (v < 0) return fail(h, GPCC_ERR_ARGUMENT, "markov_multi_chunk must be >= 0");
+        h->markov_multi_chunk = (int)v;
     } else if (!strcmp(key, "markov_sample_chunk_draws")) {
         if (v < 0) return fail(h, GPCC_ERR_ARGUMENT, "markov_sample_chunk_draws must be >= 0");
         h->markov_sample_chunk_draws = (int)v;
@@ -782,6 +794,13 @@ extern "C" long gpcc_get_option(gpcc_handle_t h, const char *key)
     if (!strcmp(key, "markov_chunk_rows")) return h->markov_chunk_rows;
     if (!strcmp(key, "markov_tap_bytes")) return 8 * h->mktap_cap;
     if (!strcmp(key, "markov_sample_chunk_draws")) return h->markov_sample_chunk_draws;
+    if (!strcmp(key, "markov_multi_chunk")) return h->markov_multi_chunk;
+    if (!strcmp(key, "markov_multi_bytes")) return 8 * (h->mkmy_cap + h->mkmr_cap + h->mkmm_cap + h->mkmo_cap) + 4 * h->mkmp_cap;
+    if (!strcmp(key, "markov_multi_block")) {
+        const gpcc_handle_t q = primary(h);
+        if (q->kernel_id == GPCC_KERNEL_RBF) return 0;   // realisations per lane of this handle's filter <P, NOFF>; 0: refused
+        return gpcc_markov_multi_rb(q->kernel_id == GPCC_KERNEL_OU ? 1 : (q->kernel_id == GPCC_KERNEL_MATERN32 ? 2 : 3), q->mb ? q->L : 0);
+    }
     if (!strcmp(key, "markov_sample_bytes")) return 8 * (h->mksw_cap + h->mksrt_cap + h->mksacc_cap) + 4 * h->mksi_cap;
     if (!strcmp(key, "fit_threads")) return h->fit_threads;
     if (!strcmp(key, "small_n_max")) return GPCC_SMALLW_MAXN;
@@ -2143,7 +2162,7 @@ static void markov_fill_args(gpcc_handle_t h, int M, const double *dd, const dou
 }
 
 // the kernels with dynamic LDS, for gpcc_handle::mk_lds_raised
-enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER };
+enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI };
 
 // The launch of every kernel of the filter, `name` in messages: one lane per row, `rows` rows along x and ny lanes per row along y.
 // The shape: one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy beyond; the light
@@ -2224,6 +2243,99 @@ extern "C" int gpcc_loglik_markov_batch(gpcc_handle_t h, int M, const double *de
     rc = markov_finish(h, M, loglik, info);
     if (rc) return rc;
     h->markov_count += M;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The linear-time log-likelihood of many flux realisations per row (gpcc_loglik_markov_multi_batch; kernel: gpcc_markov_multi.hip.h,
+// DESIGN.md 4.23): one lane per (row, block of RB realisations) carries the row's covariance recursion once and RB means through it.
+// It needs what gpcc_loglik_markov_batch needs plus the chunk's buffers below, nothing of the N^2 workspace.  The realisations go
+// through in chunks of whole blocks whose buffers (fluxes, packed residuals, results: 16 N + 8 M bytes a realisation) fit
+// GPCC_MKM_BYTES, at least one block, at most 65535 (the grid's y); option "markov_multi_chunk" sets the chunk.  A cell's value does
+// not depend on its block or chunk.
+// ------------------------------------------------------------------------------------------
+#define GPCC_MKM_BYTES ((long)128 << 20)
+
+extern "C" int gpcc_loglik_markov_multi_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                              int R, const double *Y, const double *mean, double *loglik, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (M == 0) return 0;
+    if (R < 1) return fail(h, GPCC_ERR_ARGUMENT, "R=%d < 1", R);
+    if (!Y) return fail(h, GPCC_ERR_ARGUMENT, "NULL Y");
+    if (!delays || !alpha || !rho || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    int rc = markov_refusals(h, "gpcc_loglik_markov_multi_batch", "gpcc_loglik_batch on one handle per realisation");
+    if (rc) return rc;
+    {
+        const MarkovDims d = markov_dims(primary(h));
+        if (!gpcc_markov_multi_rb(d.p, d.noff))
+            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_markov_multi_batch: the instantiation <%d, %d> (states of the process, "
+                                                 "offset states) does not ship; use gpcc_loglik_batch on one handle per realisation", d.p, d.noff);
+    }
+    if (route_fp64(h, "linear-time log-likelihood of many realisations", rc,
+                   [&](gpcc_handle_t o) { return gpcc_loglik_markov_multi_batch(o, M, delays, alpha, rho, R, Y, mean, loglik, info); }))
+        return rc;
+    GPCC_ON_DEVICE(h, h->device);
+    const long N = h->N;
+    const int L = h->L;
+    const MarkovDims d = markov_dims(h);
+    const int rb = gpcc_markov_multi_rb(d.p, d.noff);
+    long chunk = h->markov_multi_chunk > 0 ? h->markov_multi_chunk : GPCC_MKM_BYTES / (16 * N + 8 * (long)M);
+    chunk = std::min(std::max(chunk / rb, 1L), 65535L) * rb;                 // whole blocks
+    chunk = std::min(chunk, ((long)R + rb - 1) / rb * rb);
+    double *dd, *da, *dr;
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
+        int g = grow_buf(h, &h->d_mkmy, &h->mkmy_cap, chunk * N);
+        if (!g) g = grow_buf(h, &h->d_mkmr, &h->mkmr_cap, chunk * N);
+        if (!g) g = grow_buf(h, &h->d_mkmm, &h->mkmm_cap, chunk * L);
+        if (!g) g = grow_buf(h, &h->d_mkmo, &h->mkmo_cap, chunk * M);
+        if (!g && !h->mkmp_cap) {
+            g = grow_buf(h, &h->d_mkmp, &h->mkmp_cap, N);
+            if (!g) HIPCHK(h, hipMemcpy(h->d_mkmp, h->mk_perm.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+        }
+        return g;
+    });
+    if (rc) return rc;
+    const hipStream_t ms = h->main_stream;
+    GpccMarkovMultiArgs a;
+    markov_fill_args(h, M, dd, da, dr, a);
+    a.out_loglik = h->d_mkmo;
+    a.res = h->d_mkmr;
+    GpccMarkovMultiPackArgs pk;
+    pk.Y = h->d_mkmy; pk.mean = h->d_mkmm; pk.perm = h->d_mkmp; pk.res = h->d_mkmr;
+    pk.N = (int)N; pk.L = L; pk.rb = rb;
+    for (int l = 0; l <= GPCC_MARKOV_MAXL; ++l) pk.off[l] = a.off[l];
+    std::vector<double> hmean, hout;
+    for (long r0 = 0; r0 < R; r0 += chunk) {
+        const long rc_n = std::min(chunk, (long)R - r0), blocks = (rc_n + rb - 1) / rb;
+        if (mean) {
+            HIPCHK(h, hipMemcpyAsync(h->d_mkmm, mean + r0 * L, sizeof(double) * rc_n * L, hipMemcpyHostToDevice, ms));
+        } else if (r0 == 0) {   // the handle's own means for every realisation: the first chunk is the longest
+            hmean.resize((size_t)rc_n * L);
+            for (long r = 0; r < rc_n; ++r)
+                for (int l = 0; l < L; ++l) hmean[r * L + l] = h->mean_b[l];
+            HIPCHK(h, hipMemcpyAsync(h->d_mkmm, hmean.data(), sizeof(double) * rc_n * L, hipMemcpyHostToDevice, ms));
+        }
+        HIPCHK(h, hipMemcpyAsync(h->d_mkmy, Y + r0 * N, sizeof(double) * rc_n * N, hipMemcpyHostToDevice, ms));
+        pk.R = (int)rc_n; pk.blocks = (int)blocks;
+        hipError_t e = gpcc_markov_multi_pack_launch(pk, ms);
+        if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_multi_pack: %s", hipGetErrorString(e));
+        a.R = (int)rc_n; a.ldo = rc_n;
+        rc = markov_launch(h, "gpcc_markov_multi", MK_MULTI, M, (int)blocks, a.stage, markov_filter_lds(h),
+                           [&](const GpccMkLaunch &g) { return gpcc_markov_multi_launch(g, (int)blocks, a); });
+        if (rc) return rc;
+        // the chunk's results in one contiguous copy; a chunk that is not the whole of R is scattered into the caller's rows on the
+        // host.  The synchronisation also guards the buffers, which the next chunk overwrites
+        double *dst = rc_n == R ? loglik : (hout.resize((size_t)rc_n * M), hout.data());
+        HIPCHK(h, hipMemcpyAsync(dst, h->d_mkmo, sizeof(double) * rc_n * M, hipMemcpyDeviceToHost, ms));
+        HIPCHK(h, hipStreamSynchronize(ms));
+        if (dst != loglik)
+            for (long m = 0; m < M; ++m) memcpy(loglik + m * R + r0, dst + m * rc_n, sizeof(double) * rc_n);
+    }
+    HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
+    HIPCHK(h, hipStreamSynchronize(ms));
+    h->markov_count += (long)M * R;
     return 0;
 }
 

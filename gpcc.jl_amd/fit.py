@@ -291,6 +291,34 @@ def gpcc_grid(tarray, yarray, stdarray, *, kernel, candidatedelays, iterations, 
             obj.close()
 
 
+class RealisationDelays(collections.namedtuple("RealisationDelays", "prob map_index mean_delay")):
+    """realisation_delays' result: prob[R, G] (each realisation's getprobabilities over the grid), map_index[R] (its most probable
+    grid point) and mean_delay[R, L] (its posterior-mean delay, prob @ candidatedelays)."""
+
+
+def realisation_delays(objective, candidatedelays, alpha, rho, Y, logprior=None, center="own", probabilities=getprobabilities):
+    """The delay posterior of every flux realisation in Y over the grid candidatedelays (G, L), in ONE linear-time pass
+    (objective.loglik_markov_realisations) -> RealisationDelays(prob[R, G], map_index[R], mean_delay[R, L]).
+
+    alpha (G, L) and rho (G) are the per-delay fitted hyper-parameters of a GridFit of the ORIGINAL data (res.alpha, res.rho).  They are
+    FROZEN: nothing is refitted per realisation, and with marginalise_b the offsets' prior variances stay the original data's.  Row r of
+    prob is getprobabilities(loglik[:, r], logprior) of realisation r under the fitted model at each delay.  So with Y =
+    synthetic.flux_randomise(yarray, stdarray, R, seed) the scatter of mean_delay (or of candidatedelays[map_index]) is the
+    flux-randomisation scatter of the delay UNDER THE FITTED MODEL; it leaves out the scatter of the hyper-parameters' own fit, which a
+    refit per realisation (one gpcc_grid each) would add.  With parametric-bootstrap or null light curves as Y the same call gives a
+    false-alarm rate.  center: loglik_markov_realisations' ("own": each realisation's band means).  logprior: getprobabilities' second
+    argument (G).  probabilities: the function applied per realisation (default: getprobabilities)."""
+    cand = np.asarray(candidatedelays, np.float64)
+    cand = cand.reshape(len(cand), -1)
+    ll, info = objective.loglik_markov_realisations(Y, cand, alpha, rho, center=center)
+    if (np.asarray(info) != 0).any():
+        bad = int(np.flatnonzero(np.asarray(info) != 0)[0])
+        raise ValueError("realisation_delays: grid point %d has info = %d (loglik_markov_batch's codes)" % (bad, int(info[bad])))
+    R = ll.shape[1]
+    prob = np.stack([probabilities(ll[:, r]) if logprior is None else probabilities(ll[:, r], logprior) for r in range(R)])
+    return RealisationDelays(prob, np.argmax(prob, axis=1), prob @ cand)
+
+
 def _with_evidence(res, obj, cand, engine, evidence, rhomin, rhomax, max_rounds, g_tol, solver="dense"):
     if evidence is None:
         return res

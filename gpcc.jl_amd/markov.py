@@ -131,6 +131,106 @@ def loglik_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginali
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
+# Many flux realisations per parameter row (csrc/gpcc_markov_multi.hip.h, gpcc_loglik_markov_multi_batch), the same
+# algorithm in numpy.  In the filter of the module's docstring nothing but m, eps, eps^2 / S and m += P h eps / S reads a flux: the
+# merged order, A, P, S, log S and the gain depend on (tau, alpha, rho), the times and the error bars alone.  Per parameter row they are
+# computed once and R means (the columns of m) are driven through them.  The model is that of the data set the "handle" holds
+# (tarray, yarray, stdarray): with marginalise_b the offsets' prior variances are 100 var(yarray_l), NOT 100 var(Y_r).
+# ----------------------------------------------------------------------------------------------------------------------------------
+def _bands(tarray, Y):
+    """Y (a list of L arrays (R, N_l), or one (R, N) array in the bands' order) as a list of L arrays (R, N_l)."""
+    L = len(tarray)
+    Nl = [len(t) for t in tarray]
+    if not isinstance(Y, (list, tuple)):
+        Y = np.atleast_2d(np.asarray(Y, np.float64))
+        edges = np.concatenate([[0], np.cumsum(Nl)])
+        if Y.shape[1] != edges[-1]:
+            raise ValueError("Y must be (R, N) = (R, %d)" % edges[-1])
+        Y = [Y[:, edges[l]:edges[l + 1]] for l in range(L)]
+    Y = [np.atleast_2d(np.asarray(a, np.float64)) for a in Y]
+    R = Y[0].shape[0]
+    if len(Y) != L or any(a.shape != (R, n) for a, n in zip(Y, Nl)):
+        raise ValueError("Y must hold L arrays (R, N_l)")
+    return Y
+
+
+def band_means(tarray, Y):
+    """(R, L): each realisation's own band means."""
+    return np.stack([a.sum(axis=1) / a.shape[1] for a in _bands(tarray, Y)], axis=1)
+
+
+def realisation_residuals(tarray, Y, mean):
+    """Per band the residuals (R, N_l) of the realisations Y about mean (R, L), in the band's time-sorted order (prepare()'s); a
+    residual that is not finite becomes NaN."""
+    Y = _bands(tarray, Y)
+    mean = np.asarray(mean, np.float64).reshape(Y[0].shape[0], len(Y))
+    out = []
+    for l in range(len(Y)):
+        perm = np.argsort(np.asarray(tarray[l], np.float64), kind="stable")
+        r = (Y[l] - mean[:, l:l + 1])[:, perm]
+        out.append(np.where(np.isfinite(r), r, np.nan))
+    return out
+
+
+def _multi_pass(name, train, res, alpha, rho, p, n, vb):
+    """_pass over the training points alone with R means at once: train is _setup's, res[band][:, position] the realisations'
+    residuals.  -> (loglik[R], info); the flux-independent quantities of a step are computed once."""
+    ev = sorted(train, key=lambda e: e[:3])       # shifted time, then band, then position in the band: merge_order()'s order
+    R = res[0].shape[0]
+    Pinf = stationary(name, rho)
+    P = _prior(name, rho, p, n, vb)
+    m = np.zeros((n, R))
+    ll = np.zeros(R)
+    sprev = None
+    for step, (s, b, i, _, s2) in enumerate(ev, 1):
+        d = 0.0 if sprev is None else s - sprev
+        sprev = s
+        m, P = _propagate(name, m, P, Pinf, d, rho, p)
+        h = np.zeros(n)
+        h[0] = alpha[b]
+        if n > p:
+            h[p + b] = 1.0
+        Ph = P @ h
+        S = h @ Ph + s2
+        if not (S > 0.0 and math.isfinite(S)):
+            return np.full(R, math.nan), step
+        eps = res[b][:, i] - h @ m
+        ll -= 0.5 * (LOG2PI + math.log(S) + eps * eps / S)
+        m = m + np.outer(Ph, eps / S)
+        P = P - np.outer(Ph, Ph) / S
+        P = 0.5 * (P + P.T)
+    return ll, 0
+
+
+def loglik_realisations(kernel, tarray, yarray, stdarray, Y, delays, alpha, rho, marginalise_b=True, mean=None):
+    """(loglik[M, R], info[M]) of R flux realisations Y on the cadence and under the model of (tarray, yarray, stdarray):
+    Objective.loglik_markov_realisations' result.  loglik[m, r] = logpdf(MvNormal(Q mean_r, K_m), Y_r) with K_m built from the times,
+    stdarray, the kernel and -- with marginalise_b -- the prior variances 100 var(yarray_l).  Y: a list of L arrays (R, N_l) or one
+    (R, N) array; delays and alpha (M, L) or (L,), rho (M,) or a scalar.  mean: (R, L), the offset subtracted per realisation and band;
+    None: the band means of yarray (the handle's) for every realisation.  info: loglik()'s codes, of the row; such a row is NaN
+    throughout.  A flux that is not finite makes its own column NaN."""
+    L = len(tarray)
+    delays = np.asarray(delays, np.float64).reshape(-1, L)
+    alpha = np.asarray(alpha, np.float64).reshape(-1, L)
+    rho = np.asarray(rho, np.float64).reshape(-1)
+    res = None
+    out, infos = [], []
+    for g in range(len(rho)):
+        name, _, dg, ag, rg, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays[g], alpha[g], rho[g],
+                                                                   marginalise_b, codes_first=True)
+        if res is None:
+            Y = _bands(tarray, Y)
+            res = realisation_residuals(tarray, Y, np.tile(means, (Y[0].shape[0], 1)) if mean is None else mean)
+        if code:
+            ll, info = np.full(res[0].shape[0], math.nan), code
+        else:
+            ll, info = _multi_pass(name, train, res, ag, rg, p, n, vb)
+        out.append(ll)
+        infos.append(info)
+    return np.array(out), np.array(infos, dtype=np.int32)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
 # The gradient in linear time (csrc/gpcc_markov_grad.hip.h, DESIGN.md 4.17), the same algorithm in numpy: the filter's forward
 # sensitivities.  For one parameter theta the tangents (dm, dP) = d(m, P)/d theta are carried beside (m, P):
 #
@@ -1280,6 +1380,14 @@ class MarkovObjective:
         return loglik_batch(self.kernel, *self.data, delays, alpha, rho, self.marginalise_b)
 
     loglik_batch = loglik_markov_batch
+
+    def loglik_markov_realisations(self, Y, delays, alpha, rho, center="own"):
+        """Objective.loglik_markov_realisations' result: (loglik[M, R], info[M])."""
+        if isinstance(center, str):
+            if center not in ("own", "handle"):
+                raise ValueError('center must be "own", "handle" or an (R, L) array')
+            center = band_means(self.data[0], Y) if center == "own" else None
+        return loglik_realisations(self.kernel, *self.data, Y, delays, alpha, rho, self.marginalise_b, mean=center)
 
     def loglik_hess_hyper_markov_batch(self, delays, alpha, rho):
         """Objective.loglik_hess_hyper_markov_batch's result: (loglik[M], grad[M, 2L+1], hess[M, L+1, L+1], info[M])."""

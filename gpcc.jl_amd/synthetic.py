@@ -66,3 +66,19 @@ def default_hyperparameters(yarray):
     """Fixed hyper-parameters for fixed-hyper sweeps: alpha_l = var(y_l)
     (centre of sampleα, gpccfixdelay_marginaliseb.jl:188), rho = 3.5."""
     return np.array([np.var(y, ddof=1) for y in yarray]), RHO_TRUE
+
+
+def flux_randomise(yarray, stdarray, R, seed):
+    """R flux-randomised realisations of a data set on its own cadence: per band an (R, N_l) array y_l + sigma_l z, z standard normal,
+    every flux redrawn within its error bar (reverberation mapping's "flux randomisation").  Reproducible from the seed (numpy's PCG64;
+    the bands are drawn one after the other from one generator).  What Objective.loglik_markov_realisations and
+    fit.realisation_delays take as Y."""
+    R = int(R)
+    if R < 1:
+        raise ValueError("R >= 1")
+    rng = np.random.default_rng(seed)
+    out = []
+    for y, sd in zip(yarray, stdarray):
+        y, sd = np.asarray(y, np.float64).reshape(-1), np.asarray(sd, np.float64).reshape(-1)
+        out.append(y[None, :] + sd[None, :] * rng.standard_normal((R, len(y))))
+    return out

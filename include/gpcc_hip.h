@@ -153,6 +153,8 @@ int gpcc_multi_stats(gpcc_handle_t handle, double *compute_ms, double *gather_ms
  *                                     depend on it)
  *   markov_sample_chunk_draws 0       gpcc_sample_markov_batch: draws per chunk of its scratch; 0 = what fits 128 MiB in whole waves
  *                                     (results do not depend on it)
+ *   markov_multi_chunk       0        gpcc_loglik_markov_multi_batch: realisations per chunk of its scratch, rounded down to whole blocks;
+ *                                     0 = what fits 128 MiB (results do not depend on it)
  *   fp32_refine              1        fp32 handles: fp64 refinement of the quadratic forms
  *   fp32_guard               1        fp32 handles: evaluations whose pivot ratios exceed the limits are repeated in fp64
  *   fp32_assemble            1        fp32 handles: tiles inside one band pair are evaluated in fp32
@@ -167,7 +169,9 @@ int gpcc_multi_stats(gpcc_handle_t handle, double *compute_ms, double *gather_ms
  * "gather_width", "small_n_max" (383), "small_n_active", "small_n_count", "chain_count" (evaluations that took the persistent
  * launch so far), "chain_last_grid" (workgroups of the last one), "fp32_guard_count", "fp32_chain_count", "workspace_streams" / "workspace_slots" (what the workspace really holds: smaller than "streams" /
  * "slots_per_stream" only if the device's memory was short when it was allocated -- then gpcc_last_error carries a note; the
- * options themselves are never rewritten); "markov_tap_bytes" (the tap scratch of gpcc_predict_markov_batch, 0 before its first call). */
+ * options themselves are never rewritten); "markov_tap_bytes" (the tap scratch of gpcc_predict_markov_batch, 0 before its first call);
+ * "markov_multi_bytes" (the scratch of gpcc_loglik_markov_multi_batch, 0 before its first call) and "markov_multi_block" (the
+ * realisations a lane of that entry carries for this handle's kernel and b-mode; 0 where the entry refuses the handle). */
 int gpcc_set_option(gpcc_handle_t handle, const char *key, long value);
 long gpcc_get_option(gpcc_handle_t handle, const char *key);
 
@@ -218,7 +222,8 @@ int gpcc_loglik_batch(gpcc_handle_t handle, int M, const double *delays, const d
  * entry instead of a gpcc_loglik_batch (GPCC_ERR_UNSUPPORTED where this entry is); read-only "markov_count": evaluations so far.
  * Predictions, held-out scores and the offsets' posterior in linear time: the three entries below; the gradient in linear time:
  * gpcc_loglik_grad_markov_batch after them; the (alpha, rho) block of the Hessian is gpcc_loglik_hess_hyper_markov_batch, the full
- * Hessian (the rows of tau) gpcc_loglik_hess_markov_batch; the Fisher information gpcc_loglik_fisher_markov_batch.
+ * Hessian (the rows of tau) gpcc_loglik_hess_markov_batch; the Fisher information gpcc_loglik_fisher_markov_batch; many flux
+ * realisations per row in one pass (a second data axis) gpcc_loglik_markov_multi_batch.
  * Blocking. */
 int gpcc_loglik_markov_batch(gpcc_handle_t handle, int M, const double *delays, const double *alpha, const double *rho,
                              double *loglik, int *info);
@@ -393,6 +398,34 @@ int gpcc_loglik_hess_markov_batch(gpcc_handle_t h, int M, const double *delays, 
  * Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Blocking. */
 int gpcc_loglik_fisher_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                     double *loglik, double *grad, double *fisher, int *info);
+
+/* The log-likelihood of MANY FLUX REALISATIONS per parameter row in LINEAR TIME for the Markov kernels: the second data axis of
+ * gpcc_loglik_markov_batch (kernel: csrc/gpcc_markov_multi.hip.h) -- flux randomisation, parametric-bootstrap draws
+ * and null light curves on the handle's cadence.  Y: R x N row-major, each row in the order gpcc_create took y.  mean: R x L, the
+ * offset subtracted per realisation and band; NULL: the handle's band means (of the y it was created with) for every realisation.
+ * loglik: M x R row-major.  info: M entries.
+ *   THE MODEL IS THE HANDLE'S: its times, its sigma, its kernel, its b-mode and, with marginalise_b, ITS prior variances Sigma_b =
+ *   100 var(y_l) of the y it was created with.  loglik[m][r] = logpdf(MvNormal(Q mean_r, K_m), Y_r), Q the replication matrix that
+ *   repeats each band's offset once per point of that band, K_m = delayedCovariance + Sobs (+ B) built from the handle's constants:
+ *   nothing of K depends on r.  With marginalise_b a fresh handle made from Y_r would use 100 var(Y_r) where this entry uses the
+ *   handle's Sigma_b; without marginalise_b and with mean_r = the band means of Y_r the value is that fresh handle's (another order of
+ *   rounding, the same bar).
+ * info[m]: gpcc_loglik_markov_batch's codes (-1, -2, or the merged position j of the first predictive variance that is not positive
+ * and finite); they depend on the parameter row only, and a row with info != 0 is NaN in all its R entries.  A flux that is not
+ * finite makes its own column NaN and no other.
+ * Refusals: gpcc_loglik_markov_batch's (rbf, and marginalise_b with L > 4: GPCC_ERR_UNSUPPORTED before any device work);
+ * GPCC_ERR_ARGUMENT for R < 1 or a NULL Y.  M = 0 returns 0.
+ * Path: a pack kernel gathers Y through the handle's sort permutation, subtracts the means and writes the residuals point-major in
+ * blocks of RB realisations (read-only option "markov_multi_block": 8); then one lane per (row, block) carries the row's covariance
+ * recursion once and RB means through it.  No atomics: cell (m, r) is bitwise the same for any M, R, row order, order of the
+ * realisations and chunk.  It is not bitwise gpcc_loglik_markov_batch's value of the same data (another statement order); for a
+ * single data set that entry stays the route.
+ * Memory: handle-owned scratch for one chunk of realisations -- fluxes, packed residuals, results: 16 N + 8 M bytes a realisation --
+ * grown on demand, chunked to 128 MiB (option "markov_multi_chunk": realisations per chunk, rounded down to whole blocks, 0 = by the
+ * budget; read-only "markov_multi_bytes" reports the scratch); none of the N^2 workspace.  "markov_count" advances by M R.
+ * Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Blocking. */
+int gpcc_loglik_markov_multi_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                   int R, const double *Y, const double *mean, double *loglik, int *info);
 
 /* Same with DEVICE pointers, enqueued behind `stream` (a hipStream_t, NULL = default stream) and
  * joined back into it: asynchronous, outputs valid once `stream` has drained. */

@@ -284,6 +284,25 @@ function loglik_fisher_markov(h::Handle, delays::Matrix{Float64}, alpha::Matrix{
     return ll, grad, fisher, info
 end
 
+"the log-likelihood of R flux realisations per column (τ, α, ρ) in ONE linear-time pass (gpcc_loglik_markov_multi_batch: per column the
+filter's covariance recursion runs once and drives R means, DESIGN 4.23; OU, matern32, matern52) -> (ll R×M, info[M]).  Y: N×R, column
+r one realisation in the order the handle took y.  mean: L×R, the offset subtracted per realisation and band, or nothing: the handle's
+band means.  The model is the handle's: times, σ, kernel, b-mode and, with marginalise_b, the prior variances of the y it was created
+with.  info is loglik_markov's and depends on the column (τ, α, ρ) only; such a column is NaN for every realisation; a flux that is
+not finite makes its own realisation NaN.  Errors for rbf and for marginalise_b with more than 4 bands."
+function loglik_markov_realisations(h::Handle, Y::Matrix{Float64}, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64};
+                                    mean = nothing)
+    M, R = length(rho), size(Y, 2)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M) && R >= 1
+    @assert mean === nothing || size(mean) == (h.L, R)
+    ll, info = Matrix{Float64}(undef, R, M), Vector{Cint}(undef, M)         # C writes M×R row-major: R×M here
+    rc = ccall((:gpcc_loglik_markov_multi_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, R, Y, mean === nothing ? C_NULL : convert(Matrix{Float64}, mean), ll, info)
+    rc == 0 || error("gpcc_loglik_markov_multi_batch: " * lasterror(h.ptr))
+    return ll, info
+end
+
 "Laplace-marginalised evidence over α and ρ per delay (columns of delays, L×G), from (alpha0 L×G, rho0[G]), usually the fit's
 output.  Prior log-uniform in α and in ρ on [rhomin, rhomax]: log_evidence is log Z(τ) up to ONE additive constant shared by all
 delays -- use it only through getprobabilities (or differences).  -> (ll[G], alpha L×G, rho[G], log_evidence[G], cov (L+1)×(L+1)×G
