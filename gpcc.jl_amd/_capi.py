@@ -56,6 +56,8 @@ SIGNATURES = {
                                                        c_double_p, c_double_p, c_double_p, c_int_p]),
     "gpcc_loglik_markov_multi_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                                       ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "gpcc_loglik_markov_resampled_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p,
+                                                          ctypes.c_int, c_double_p, c_int_p, c_double_p, c_double_p, c_double_p, c_int_p]),
     "gpcc_loglik_hess_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                               c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
     "gpcc_loglik_hess_hyper_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,

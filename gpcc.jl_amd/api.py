@@ -347,6 +347,53 @@ class Objective:
                                                               _dp(mean) if mean is not None else None, _dp(ll), _ip(info)))
         return ll, info
 
+    def loglik_markov_resampled(self, Y, delays, alpha, rho, real, counts=None, center="own", sigma_b="own"):
+        """The linear-time objective of M rows that each carry their own (tau, alpha, rho) AND their own resampled data set on this
+        handle's cadence (gpcc_loglik_markov_resampled_batch; OU, matern32 and matern52 only) -> (loglik[M], info[M]): flux
+        randomisation with a refit per realisation, random subset selection, each realisation's own Sigma_b.  Y: the R realisations, a
+        list of L arrays (R, N_l) or one (R, N) array, each row in the order the handle took y.  real[m] in [0, R): the realisation of
+        row m.  counts: the multiplicities in Y's form (integers >= 0; 0 drops the point, n > 1 is the point once with sigma^2 / n), or
+        None: all 1.  loglik[m] is the value of a fresh Objective on the kept points of realisation real[m] with error bars sigma /
+        sqrt(count), when center and sigma_b are "own": each realisation's band means and 100 var (n - 1) over its distinct kept
+        points (ValueError if a band keeps fewer than 2 while marginalise_b is on).  "handle": the handle's band means / prior
+        variances; an (R, L) array is taken as given.  sigma_b is read with marginalise_b only.  A realisation that keeps no point
+        gives (0.0, 0).  info is loglik_markov_batch's, a positive value counted among the kept points.  A flux that is not finite
+        at a kept point makes the rows of that realisation NaN, and no other.  R is split across calls so that each fits option
+        "markov_resample_bytes_max" (16 N bytes a realisation); a row's value does not depend on the split, on M, R or any order.
+        ValueError: a real[m] outside [0, R), counts that are negative or of another shape.  rbf, or marginalise_b with more than
+        4 bands: GpccError (unsupported)."""
+        from . import markov
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        Y = self.realisations(Y)
+        R = Y.shape[0]
+        real = np.ascontiguousarray(np.atleast_1d(real), dtype=np.int32)
+        if real.shape != (M,) or (M and (real.min() < 0 or real.max() >= R)):
+            raise ValueError("real must hold one realisation in [0, R = %d) per row (M = %d)" % (R, M))
+        shape = [np.empty(int(n)) for n in self.Nl]
+        cnt = None
+        if counts is not None:
+            cnt = np.ascontiguousarray(np.concatenate(markov._counts(shape, counts, R), axis=1), dtype=np.int32)
+        mean, vb = markov.resample_arguments(shape, Y, cnt, center, sigma_b, self.marginalise_b)
+        ll = np.empty(M, dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        per = max(1, int(self.get_option("markov_resample_bytes_max")) // (16 * self.N))
+        for r0 in range(0, R, per):
+            r1 = min(R, r0 + per)
+            rows = np.arange(M) if per >= R else np.flatnonzero((real >= r0) & (real < r1))
+            if not len(rows):
+                continue
+            d, a, rh, rl = _d(delays[rows]), _d(alpha[rows]), _d(rho[rows]), np.ascontiguousarray(real[rows] - r0, dtype=np.int32)
+            yk = _d(Y[r0:r1])
+            ck = np.ascontiguousarray(cnt[r0:r1]) if cnt is not None else None
+            mk = _d(mean[r0:r1]) if mean is not None else None
+            vk = _d(vb[r0:r1]) if vb is not None else None
+            lk, ik = np.empty(len(rows), dtype=np.float64), np.zeros(len(rows), dtype=np.int32)
+            self._chk(_capi.load().gpcc_loglik_markov_resampled_batch(
+                self._h, len(rows), _dp(d), _dp(a), _dp(rh), _ip(rl), r1 - r0, _dp(yk), _ip(ck) if ck is not None else None,
+                _dp(mk) if mk is not None else None, _dp(vk) if vk is not None else None, _dp(lk), _ip(ik)))
+            ll[rows], info[rows] = lk, ik
+        return ll, info
+
     def predict_markov_batch(self, delays, alpha, rho, ttest, weights=None):
         """predict_batch in linear time (gpcc_predict_markov_batch: two Kalman filters and a combine per row, O(N + T); OU, matern32 and
         matern52 only) -> (mu[M, T], var[M, T], loglik[M], info[M], mix_mu[T], mix_var[T]), what predict_batch returns.  ttest need not

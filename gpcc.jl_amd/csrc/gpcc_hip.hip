@@ -17,6 +17,7 @@
 #include "gpcc_markov_hess_tau.hip.h"
 #include "gpcc_markov_fisher.hip.h"
 #include "gpcc_markov_multi.hip.h"
+#include "gpcc_markov_resample.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -274,6 +275,15 @@ struct gpcc_handle_s {
     int *d_mkmp = nullptr;
     long mkmy_cap = 0, mkmr_cap = 0, mkmm_cap = 0, mkmo_cap = 0, mkmp_cap = 0;
     int markov_multi_chunk = 0;          // option "markov_multi_chunk": realisations per chunk of gpcc_loglik_markov_multi_batch (0: by the scratch budget)
+    // linear-time log-likelihood of resampled data sets (gpcc_loglik_markov_resampled_batch): grown on demand -- the packed pairs
+    // {residual, variance} [R][N] (mkrv_cap pairs: the scratch the budget below governs) and what the pack kernel reads: the fluxes
+    // as the caller holds them (mkry_cap doubles), the multiplicities (mkrc_cap ints), the means and the offsets' prior variances
+    // (mkrm_cap doubles: both), the rows' realisations (mkrr_cap ints); the sort permutation (N ints, uploaded once)
+    double2 *d_mkrv = nullptr;
+    double *d_mkry = nullptr, *d_mkrm = nullptr;
+    int *d_mkrc = nullptr, *d_mkrr = nullptr, *d_mkrp = nullptr;
+    long mkrv_cap = 0, mkry_cap = 0, mkrm_cap = 0, mkrc_cap = 0, mkrr_cap = 0, mkrp_cap = 0;
+    long markov_resample_bytes_max = (long)512 << 20;   // option "markov_resample_bytes_max": the most the packed pairs of one call may take
     int laplace_markov = 0;              // option "laplace_markov": gpcc_laplace_evidence's rounds are gpcc_loglik_hess_hyper_markov_batch calls
     int markov_chunk_rows = 0;           // option "markov_chunk_rows": rows per chunk of gpcc_predict_markov_batch (0: by the scratch budget)
     // linear-time draws (gpcc_sample_markov_batch): grown on demand -- the combine's weights of a chunk of rows (mksw_cap doubles), the
@@ -591,6 +601,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_mkts); hipFree(h->d_mktb);
     hipFree(h->d_mkfs); hipFree(h->d_mkfb);
     hipFree(h->d_mkmy); hipFree(h->d_mkmr); hipFree(h->d_mkmm); hipFree(h->d_mkmo); hipFree(h->d_mkmp);
+    hipFree(h->d_mkrv); hipFree(h->d_mkry); hipFree(h->d_mkrm); hipFree(h->d_mkrc); hipFree(h->d_mkrr); hipFree(h->d_mkrp);
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
     hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
     hipFree(h->d_smean); hipFree(h->d_sdraw); hipFree(h->d_szeta); hipFree(h->d_slist); hipFree(h->d_soff);
@@ -706,6 +717,9 @@ extern "C" int gpcc_set_option(gpcc_handle_t h, const char *key, long v)
     } else if (!strcmp(key, "markov_multi_chunk")) {
         if (v < 0) return fail(h, GPCC_ERR_ARGUMENT, "markov_multi_chunk must be >= 0");
         h->markov_multi_chunk = (int)v;
+    } else if (!strcmp(key, "markov_resample_bytes_max")) {
+        if (v < 0) return fail(h, GPCC_ERR_ARGUMENT, "markov_resample_bytes_max must be >= 0");
+        h->markov_resample_bytes_max = v;
     } else if (!strcmp(key, "markov_sample_chunk_draws")) {
         if (v < 0) return fail(h, GPCC_ERR_ARGUMENT, "markov_sample_chunk_draws must be >= 0");
         h->markov_sample_chunk_draws = (int)v;
@@ -800,6 +814,15 @@ extern "C" long gpcc_get_option(gpcc_handle_t h, const char *key)
         const gpcc_handle_t q = primary(h);
         if (q->kernel_id == GPCC_KERNEL_RBF) return 0;   // realisations per lane of this handle's filter <P, NOFF>; 0: refused
         return gpcc_markov_multi_rb(q->kernel_id == GPCC_KERNEL_OU ? 1 : (q->kernel_id == GPCC_KERNEL_MATERN32 ? 2 : 3), q->mb ? q->L : 0);
+    }
+    if (!strcmp(key, "markov_resample_bytes_max")) return primary(h)->markov_resample_bytes_max;
+    if (!strcmp(key, "markov_resample_bytes") || !strcmp(key, "markov_resample_upload_bytes")) {
+        // (of the handle that computes: a multi-device handle's first device, an fp32 handle's fp64 twin)
+        gpcc_handle_t q = primary(h);
+        if (q->precision == GPCC_PRECISION_FP32) q = q->fb;
+        if (!q) return 0;
+        return !strcmp(key, "markov_resample_bytes") ? 16 * q->mkrv_cap
+                                                     : 8 * (q->mkry_cap + q->mkrm_cap) + 4 * (q->mkrc_cap + q->mkrr_cap + q->mkrp_cap);
     }
     if (!strcmp(key, "markov_sample_bytes")) return 8 * (h->mksw_cap + h->mksrt_cap + h->mksacc_cap) + 4 * h->mksi_cap;
     if (!strcmp(key, "fit_threads")) return h->fit_threads;
@@ -2162,7 +2185,7 @@ static void markov_fill_args(gpcc_handle_t h, int M, const double *dd, const dou
 }
 
 // the kernels with dynamic LDS, for gpcc_handle::mk_lds_raised
-enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI };
+enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI, MK_RESAMPLE };
 
 // The launch of every kernel of the filter, `name` in messages: one lane per row, `rows` rows along x and ny lanes per row along y.
 // The shape: one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy beyond; the light
@@ -2336,6 +2359,98 @@ extern "C" int gpcc_loglik_markov_multi_batch(gpcc_handle_t h, int M, const doub
     HIPCHK(h, hipMemcpyAsync(info, h->d_oinfo, sizeof(int) * M, hipMemcpyDeviceToHost, ms));
     HIPCHK(h, hipStreamSynchronize(ms));
     h->markov_count += (long)M * R;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The linear-time log-likelihood of rows with their own resampled data set (gpcc_loglik_markov_resampled_batch; kernel:
+// gpcc_markov_resample.hip.h): one lane per row, as gpcc_loglik_markov_batch, reading per step one packed pair
+// {residual, sigma^2 / count} of the row's realisation.  It needs what gpcc_loglik_markov_batch needs plus the buffers below, nothing
+// of the N^2 workspace.  Everything that can be refused is refused on the host before any device work.  The entry does not chunk (a
+// row may reference any realisation): a call whose packed pairs (16 N R bytes) exceed option "markov_resample_bytes_max" is refused,
+// and the callers split R.
+// ------------------------------------------------------------------------------------------
+extern "C" int gpcc_loglik_markov_resampled_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                                  const int *real, int R, const double *Y, const int *count, const double *mean,
+                                                  const double *sigma_b, double *loglik, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (M == 0) return 0;
+    if (R < 1) return fail(h, GPCC_ERR_ARGUMENT, "R=%d < 1", R);
+    if (!Y || !real) return fail(h, GPCC_ERR_ARGUMENT, "NULL %s", Y ? "real" : "Y");
+    if (!delays || !alpha || !rho || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    int rc = markov_refusals(h, "gpcc_loglik_markov_resampled_batch", "gpcc_loglik_batch on one handle per realisation");
+    if (rc) return rc;
+    const gpcc_handle_t q = primary(h);
+    {
+        const MarkovDims d = markov_dims(q);
+        if (!gpcc_mk_ships<GpccMkShipsResample>(d.p, d.noff))
+            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_markov_resampled_batch: the instantiation <%d, %d> (states of the process, "
+                                                 "offset states) does not ship; use gpcc_loglik_batch on one handle per realisation", d.p, d.noff);
+    }
+    const long N = q->N, budget = q->markov_resample_bytes_max;
+    if (16 * N * (long)R > budget)
+        return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_markov_resampled_batch: R=%d realisations of N=%ld points pack to %ld bytes, over "
+                                             "the limit markov_resample_bytes_max=%ld; split R across calls", R, N, 16 * N * (long)R, budget);
+    for (int m = 0; m < M; ++m)
+        if (real[m] < 0 || real[m] >= R) return fail(h, GPCC_ERR_ARGUMENT, "real[%d]=%d outside [0, R=%d)", m, real[m], R);
+    if (count)
+        for (long k = 0; k < N * (long)R; ++k)
+            if (count[k] < 0) return fail(h, GPCC_ERR_ARGUMENT, "count[%ld][%ld]=%d < 0", k / N, k % N, count[k]);
+    if (route_fp64(h, "linear-time log-likelihood of resampled data sets", rc, [&](gpcc_handle_t o) {
+            const long own = o->markov_resample_bytes_max;
+            o->markov_resample_bytes_max = budget;   // the caller's limit holds on the handle that computes
+            const int r2 = gpcc_loglik_markov_resampled_batch(o, M, delays, alpha, rho, real, R, Y, count, mean, sigma_b, loglik, info);
+            o->markov_resample_bytes_max = own;
+            return r2;
+        }))
+        return rc;
+    GPCC_ON_DEVICE(h, h->device);
+    const int L = h->L;
+    const long RN = N * (long)R, RL = (long)R * L;
+    double *dd, *da, *dr;
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
+        int g = grow_buf(h, &h->d_mkrv, &h->mkrv_cap, RN);
+        if (!g) g = grow_buf(h, &h->d_mkry, &h->mkry_cap, RN);
+        if (!g && count) g = grow_buf(h, &h->d_mkrc, &h->mkrc_cap, RN);
+        if (!g) g = grow_buf(h, &h->d_mkrm, &h->mkrm_cap, 2 * RL);
+        if (!g) g = grow_buf(h, &h->d_mkrr, &h->mkrr_cap, (long)M);
+        if (!g && !h->mkrp_cap) {
+            g = grow_buf(h, &h->d_mkrp, &h->mkrp_cap, N);
+            if (!g) HIPCHK(h, hipMemcpy(h->d_mkrp, h->mk_perm.data(), sizeof(int) * N, hipMemcpyHostToDevice));
+        }
+        return g;
+    });
+    if (rc) return rc;
+    const hipStream_t ms = h->main_stream;
+    // the means and the offsets' prior variances of every realisation, the handle's where the caller gives none: [R][L] | [R][L]
+    std::vector<double> hm((size_t)2 * RL);
+    const int noff = markov_dims(h).noff;
+    for (long r = 0; r < R; ++r)
+        for (int l = 0; l < L; ++l) {
+            hm[r * L + l] = mean ? mean[r * L + l] : h->mean_b[l];
+            hm[RL + r * L + l] = !noff ? 0.0 : (sigma_b ? sigma_b[r * L + l] : h->sigma_b[l]);
+        }
+    HIPCHK(h, hipMemcpyAsync(h->d_mkrm, hm.data(), sizeof(double) * 2 * RL, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_mkry, Y, sizeof(double) * RN, hipMemcpyHostToDevice, ms));
+    if (count) HIPCHK(h, hipMemcpyAsync(h->d_mkrc, count, sizeof(int) * RN, hipMemcpyHostToDevice, ms));
+    HIPCHK(h, hipMemcpyAsync(h->d_mkrr, real, sizeof(int) * M, hipMemcpyHostToDevice, ms));
+    GpccMarkovResampleArgs a;
+    markov_fill_args(h, M, dd, da, dr, a);
+    a.rv = h->d_mkrv; a.real = h->d_mkrr; a.sigb = h->d_mkrm + RL;
+    GpccMarkovResamplePackArgs pk;
+    pk.Y = h->d_mkry; pk.mean = h->d_mkrm; pk.sig2 = h->d_mk + 2 * N; pk.count = count ? h->d_mkrc : nullptr; pk.perm = h->d_mkrp;
+    pk.rv = h->d_mkrv; pk.total = RN; pk.N = (int)N; pk.L = L;
+    for (int l = 0; l <= GPCC_MARKOV_MAXL; ++l) pk.off[l] = a.off[l];
+    const hipError_t e = gpcc_markov_resample_pack_launch(pk, ms);
+    if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "gpcc_markov_resample_pack: %s", hipGetErrorString(e));
+    rc = markov_launch(h, "gpcc_markov_resample", MK_RESAMPLE, M, 1, a.stage, markov_filter_lds(h),
+                       [&](const GpccMkLaunch &g) { return gpcc_markov_resample_launch(g, a); });
+    if (rc) return rc;
+    rc = markov_finish(h, M, loglik, info);   // (its synchronisation also guards hm and the caller's arrays)
+    if (rc) return rc;
+    h->markov_count += M;
     return 0;
 }
 

@@ -1,9 +1,10 @@
 // gpcc_markov.hip.h -- the exact linear-time log-likelihood of the Markov kernels (OU, Matern-3/2, Matern-5/2) for gfx950:
 // gpcc_loglik_markov_batch of include/gpcc_hip.h; gpcc.jl_amd/markov.py is the same algorithm in numpy.  This file owns
 // the Kalman filter itself (gpcc_mk_init, gpcc_mk_transition, gpcc_mk_propagate, gpcc_mk_update) and the forward walk over the data
-// around it (GpccMkLane, gpcc_mk_open, gpcc_mk_next).  Eight kernels walk the data around the one step.  Five go forward once and share
-// this file's cursor: gpcc_markov_eval below, gpcc_markov_grad, gpcc_markov_hess, gpcc_markov_hess_tau and gpcc_markov_multi (their own
-// headers; gpcc_markov_multi carries many realisations' means through one covariance recursion and has its own update).  Three
+// around it (GpccMkLane, gpcc_mk_open, gpcc_mk_next).  Nine kernels walk the data around the one step.  Six go forward once and share
+// this file's cursor: gpcc_markov_eval below, gpcc_markov_grad, gpcc_markov_hess, gpcc_markov_hess_tau, gpcc_markov_multi and
+// gpcc_markov_resample (their own headers; gpcc_markov_multi carries many realisations' means through one covariance recursion and has
+// its own update; gpcc_markov_resample reads each lane's own resampled data and skips the points it drops).  Three
 // go forward and backward and share the cursor of gpcc_markov_pred.hip.h (GpccMkpLane, gpcc_mkp_next): gpcc_markov_taps there,
 // gpcc_markov_draw (gpcc_markov_sample.hip.h) and gpcc_markov_loo_taps (gpcc_markov_loo.hip.h).  The merged order -- the lowest band
 // first on ties, and each exception to it -- is written in those two places only.
@@ -221,7 +222,7 @@ __device__ __forceinline__ bool gpcc_mk_update(int b, double al, double r, doubl
     return ok;
 }
 
-// ---- the forward walk, shared by gpcc_markov_eval below, gpcc_markov_grad, gpcc_markov_hess, gpcc_markov_hess_tau and gpcc_markov_multi: what a lane
+// ---- the forward walk, shared by gpcc_markov_eval below, gpcc_markov_grad, gpcc_markov_hess, gpcc_markov_hess_tau, gpcc_markov_multi and gpcc_markov_resample: what a lane
 // keeps outside its registers, the kernel's prologue (gpcc_mk_open) and the choice of the next observation (gpcc_mk_next).  ARGS:
 // any argument struct with GpccMarkovArgs' fields ----
 
@@ -329,7 +330,7 @@ __global__ void __launch_bounds__(256) gpcc_markov_eval(const GpccMarkovArgs a)
     }
 }
 
-// ---- which <P, NOFF> ship, and their launch: once, for the eight families of the linear-time path ----
+// ---- which <P, NOFF> ship, and their launch: once, for the nine families of the linear-time path ----
 
 // What a family ships is a statement next to its kernel: a struct whose max_noff[P - 1] is the largest NOFF built for P states of the
 // process (every NOFF below it is built too).  The dispatch below instantiates exactly these, so the objects hold exactly these, and

@@ -319,6 +319,86 @@ def realisation_delays(objective, candidatedelays, alpha, rho, Y, logprior=None,
     return RealisationDelays(prob, np.argmax(prob, axis=1), prob @ cand)
 
 
+class RealisationRefits(collections.namedtuple("RealisationRefits", "loglikel alpha rho f_calls rounds delays start_loglikel")):
+    """realisation_refits' result: loglikel[R, G] (each realisation's refitted profile likelihood over the grid), alpha[R, G, L],
+    rho[R, G], f_calls, rounds, delays (the RealisationDelays of loglikel) and start_loglikel[R, G] (the value at the warm start as the
+    optimiser holds it, loglikel >= it; None with start=None)."""
+
+
+def realisation_refits(objective, candidatedelays, Y, counts=None, *, iterations, start=None, seed=1, numberofrestarts=1,
+                       initialrandom=5, rhomin=0.1, rhomax=20.0, logprior=None, probabilities=getprobabilities):
+    """FR/RSS with a REFIT PER REALISATION: fits (alpha, rho) at every row of candidatedelays (G, L) for every resampled data set
+    (Y, counts) on objective's cadence (synthetic.resample's result; counts None: all 1) -> RealisationRefits.  The lock-step
+    BatchedNelderMead of gpcc_grid's python engine runs over the problems (realisation, delay, restart); every optimiser round is ONE
+    objective.loglik_markov_resampled call (linear time: OU, matern32, matern52), each realisation under its own band means and, with
+    marginalise_b, its own offsets' prior variances.  objective: an Objective, or a markov.MarkovObjective (no GPU).
+
+    start=None: the reference's random candidates exactly as gpcc_grid draws them -- the same seed and the same draws for every
+    realisation and delay, scaled by each realisation's own band variances -- so that realisation r's result is that of
+    gpcc_grid(engine="python", solver="markov") on its reduced data set.  start=(alpha[G, L], rho[G]), usually a GridFit of the
+    original data (res.alpha, res.rho): every realisation starts Nelder-Mead at delay g from (alpha[g], rho[g]), with one restart and
+    no random candidates; rho is clipped into (rhomin, rhomax).  delays: getprobabilities per realisation over its refitted likelihoods
+    (logprior, probabilities: realisation_delays').  realisation_delays is the frozen route, one pass and no refit."""
+    from . import markov
+    cand = np.ascontiguousarray(np.asarray(candidatedelays, np.float64).reshape(len(candidatedelays), -1))
+    G, L = cand.shape
+    shape = [np.empty(int(n)) for n in objective.Nl] if hasattr(objective, "Nl") else objective.data[0]
+    Yb = markov._bands(shape, Y)
+    R = Yb[0].shape[0]
+    cb = markov._counts(shape, counts, R)
+    mb = bool(objective.marginalise_b)
+    mean, vb = markov.resample_constants(shape, Yb, cb, mb)
+    Yf = np.ascontiguousarray(np.concatenate(Yb, axis=1))
+    cf = None if counts is None else np.ascontiguousarray(np.concatenate(cb, axis=1))
+    if start is None:
+        K = int(numberofrestarts)
+        rg = np.random.default_rng(seed)
+        rho0 = rg.uniform(rhomin + 1e-3, rhomax - 1e-3, K) if K in (1, 2) else logrange(rhomin + 1e-3, rhomax - 1e-3, K)
+        vary = np.array([[np.var(Yb[l][r][cb[l][r] > 0], ddof=1) for l in range(L)] for r in range(R)])
+        cands = np.empty((R, K, initialrandom, L + 1))
+        for i in range(K):
+            for c in range(initialrandom):
+                u = rg.random(L) * (1.2 - 0.8) + 0.8
+                for r in range(R):
+                    cands[r, i, c, :L] = invmakepositive(vary[r] * u)
+                cands[:, i, c, L] = invtransformbetween(rho0[i], rhomin, rhomax)
+    else:
+        K = 1
+        a0 = np.asarray(start[0], np.float64).reshape(G, L)
+        r0 = np.clip(np.asarray(start[1], np.float64).reshape(G), rhomin + 1e-9 * (rhomax - rhomin), rhomax - 1e-9 * (rhomax - rhomin))
+        xs = np.concatenate([invmakepositive(np.maximum(a0 - 1e-8, 1e-300)), invtransformbetween(r0, rhomin, rhomax)[:, None]], axis=1)
+    P = R * G * K                                                        # problem p = (realisation, delay, restart), realisation-major
+
+    def unpack(X):
+        return makepositive(X[:, :L]) + 1e-8, transformbetween(X[:, L], rhomin, rhomax)
+
+    def negobj(pidx, X):
+        alpha, rho = unpack(X)
+        ll, info = objective.loglik_markov_resampled(Yf, cand[(pidx // K) % G], alpha, rho, pidx // (G * K), counts=cf, center=mean,
+                                                     sigma_b=vb)
+        return np.where(info == 0, -ll, np.inf)
+
+    extra_calls, extra_rounds, f_start = 0, 0, None
+    if start is None:
+        pid = np.repeat(np.arange(P), initialrandom)
+        Xc = cands[pid // (G * K), pid % K, np.tile(np.arange(initialrandom), P)]
+        f0 = negobj(pid, Xc).reshape(P, initialrandom)                   # argmin over the random candidates (:209)
+        x0 = Xc.reshape(P, initialrandom, L + 1)[np.arange(P), np.argmin(f0, axis=1)]
+        extra_calls, extra_rounds = P * initialrandom, 1
+    else:
+        x0 = np.tile(xs, (R, 1))
+        f_start = -negobj(np.arange(P), x0).reshape(R, G)
+    nm = BatchedNelderMead(x0, negobj, iterations=iterations, g_tol=1e-6)
+    xmin, fmin = nm.run()
+    fmin = fmin.reshape(R * G, K)
+    pick = np.argmin(fmin, axis=1)
+    a_sel, r_sel = unpack(xmin.reshape(R * G, K, L + 1)[np.arange(R * G), pick])
+    ll = -fmin[np.arange(R * G), pick].reshape(R, G)
+    prob = np.stack([probabilities(ll[r]) if logprior is None else probabilities(ll[r], logprior) for r in range(R)])
+    return RealisationRefits(ll, a_sel.reshape(R, G, L), r_sel.reshape(R, G), nm.f_calls + extra_calls, nm.rounds + extra_rounds,
+                             RealisationDelays(prob, np.argmax(prob, axis=1), prob @ cand), f_start)
+
+
 def _with_evidence(res, obj, cand, engine, evidence, rhomin, rhomax, max_rounds, g_tol, solver="dense"):
     if evidence is None:
         return res

@@ -231,6 +231,126 @@ def loglik_realisations(kernel, tarray, yarray, stdarray, Y, delays, alpha, rho,
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
+# Rows with their own resampled data set (csrc/gpcc_markov_resample.hip.h, gpcc_loglik_markov_resampled_batch), the
+# same algorithm in numpy.  A realisation is a flux vector on the cadence of (tarray, stdarray) and a multiplicity per point: a point
+# with count 0 is dropped, a point drawn n times is the point once with variance sigma^2 / n.  Row m has its own (tau, alpha, rho) and
+# the index real[m] of its realisation; its value is that of the reduced data set (the kept points, sigma / sqrt n).
+# ----------------------------------------------------------------------------------------------------------------------------------
+def _counts(tarray, counts, R):
+    """counts (None: all 1; a list of L arrays (R, N_l) or one (R, N) array) as a list of L integer arrays (R, N_l); negative: ValueError."""
+    if counts is None:
+        return [np.ones((R, len(t)), dtype=np.int64) for t in tarray]
+    c = [np.asarray(a) for a in _bands(tarray, counts)]
+    if c[0].shape[0] != R:
+        raise ValueError("counts must hold as many realisations as Y (%d)" % R)
+    if any((a < 0).any() or (a != np.floor(a)).any() for a in c):
+        raise ValueError("counts must be integers >= 0")
+    return [a.astype(np.int64) for a in c]
+
+
+def resample_constants(tarray, Y, counts=None, marginalise_b=True):
+    """(mean[R, L], sigma_b[R, L]) of R resampled data sets as prepare() computes them for each reduced data set: the band means and
+    100 var (n - 1) over a band's distinct kept points (count >= 1), unweighted; sigma_b is zeros without marginalise_b.  A band
+    that keeps no point has mean 0 (it subtracts from nothing).  ValueError: marginalise_b and a band with fewer than 2 kept points."""
+    Y = _bands(tarray, Y)
+    R, L = Y[0].shape[0], len(Y)
+    counts = _counts(tarray, counts, R)
+    mean, vb = np.zeros((R, L)), np.zeros((R, L))
+    for r in range(R):
+        for l in range(L):
+            y = Y[l][r][counts[l][r] > 0]
+            if marginalise_b and len(y) < 2:
+                raise ValueError("realisation %d keeps %d distinct points of band %d: marginalise_b needs at least 2 for the offset's "
+                                 "prior variance" % (r, len(y), l + 1))
+            if len(y):
+                mean[r, l] = y.sum() / len(y)
+            if marginalise_b:
+                vb[r, l] = 100.0 * (np.sum((y - mean[r, l]) ** 2) / (len(y) - 1))
+    return mean, vb
+
+
+def resample_arguments(tarray, Y, counts, center, sigma_b, marginalise_b):
+    """center and sigma_b of loglik_markov_resampled ("own", "handle" or an (R, L) array each) as (mean, sigma_b): an (R, L) array, or
+    None for the handle's.  "own": resample_constants' (its ValueError for a band with fewer than 2 kept points under marginalise_b
+    is raised only where sigma_b is "own")."""
+    R = _bands(tarray, Y)[0].shape[0]
+    L = len(tarray)
+    for name, v in (("center", center), ("sigma_b", sigma_b)):
+        if isinstance(v, str) and v not in ("own", "handle"):
+            raise ValueError('%s must be "own", "handle" or an (R, L) array' % name)
+    own = None
+    if (isinstance(center, str) and center == "own") or (isinstance(sigma_b, str) and sigma_b == "own"):
+        own = resample_constants(tarray, Y, counts, marginalise_b and isinstance(sigma_b, str) and sigma_b == "own")
+    out = []
+    for k, v in enumerate((center, sigma_b)):
+        if isinstance(v, str):
+            out.append(own[k] if v == "own" else None)
+        else:
+            a = np.ascontiguousarray(v, dtype=np.float64)
+            if a.shape != (R, L):
+                raise ValueError("%s must be (R, L) = (%d, %d)" % (("center", "sigma_b")[k], R, L))
+            out.append(a)
+    return out[0], out[1]
+
+
+def loglik_resampled(kernel, tarray, yarray, stdarray, Y, counts, real, delays, alpha, rho, marginalise_b=True, mean=None, sigma_b=None):
+    """(loglik[M], info[M]) of M rows (delays and alpha (M, L), rho (M)), row m scored on realisation real[m] of the R resampled data
+    sets (Y, counts) on the cadence of (tarray, stdarray): Objective.loglik_markov_resampled's result with mean and sigma_b given.
+    loglik[m] = logpdf(MvNormal(Q mean_r, K), Y_r[sel]), sel the points of r = real[m] with count >= 1, K from (tau, alpha, rho)_m on
+    t[sel] with variances sigma^2[sel] / count and, with marginalise_b, B from sigma_b[r].  Y: a list of L arrays (R, N_l) or one (R, N)
+    array; counts the same in integers, or None (all 1).  mean, sigma_b: (R, L); None: those of (tarray, yarray, stdarray), the
+    handle's.  A realisation that keeps no point gives (0.0, 0).  info: loglik()'s codes, the position counted among the kept points.
+    A flux that is not finite at a kept point makes the row NaN.  ValueError: a real[m] outside [0, R), negative counts."""
+    name = _name(kernel)
+    L = len(tarray)
+    Y = _bands(tarray, Y)
+    R = Y[0].shape[0]
+    counts = _counts(tarray, counts, R)
+    delays = np.asarray(delays, np.float64).reshape(-1, L)
+    alpha = np.asarray(alpha, np.float64).reshape(-1, L)
+    rho = np.asarray(rho, np.float64).reshape(-1)
+    real = np.asarray(real).reshape(-1)
+    if len(real) != len(rho) or (len(real) and (real.min() < 0 or real.max() >= R)):
+        raise ValueError("real must hold one realisation in [0, %d) per row" % R)
+    if marginalise_b and L > MAX_OFFSET_BANDS:
+        raise ValueError("marginalise_b with %d bands: the linear-time solver keeps at most %d offset states" % (L, MAX_OFFSET_BANDS))
+    _, _, _, hvb = prepare(tarray, yarray, stdarray, marginalise_b)
+    hmean = np.array([np.asarray(y, np.float64).sum() / len(y) for y in yarray])
+    mean = np.tile(hmean, (R, 1)) if mean is None else np.asarray(mean, np.float64).reshape(R, L)
+    vb = np.tile(hvb, (R, 1)) if sigma_b is None else np.asarray(sigma_b, np.float64).reshape(R, L)
+    if not marginalise_b:
+        vb = np.zeros((R, L))
+    p = _ORDER[name]
+    n = p + (L if marginalise_b else 0)
+    kept = {}
+
+    def points(r):
+        """the kept points of realisation r: [(band, position in the sorted band, time, residual, variance)]"""
+        if r not in kept:
+            out = []
+            for l in range(L):
+                t, sd = np.asarray(tarray[l], np.float64), np.asarray(stdarray[l], np.float64)
+                perm = np.argsort(t, kind="stable")
+                res = (Y[l][r] - mean[r, l])[perm]
+                res = np.where(np.isfinite(res), res, np.nan)
+                cnt, s2 = counts[l][r][perm], (sd * sd)[perm]
+                out += [(l, i, t[perm][i], res[i], s2[i] / cnt[i]) for i in range(len(t)) if cnt[i] > 0]
+            kept[r] = out
+        return kept[r]
+
+    ll, info = np.empty(len(rho)), np.zeros(len(rho), dtype=np.int32)
+    for m in range(len(rho)):
+        code = -1 if not np.all(alpha[m] > 0.0) else (-2 if rho[m] <= 0.0 else 0)
+        if code:
+            ll[m], info[m] = math.nan, code
+            continue
+        r = int(real[m])
+        train = [(t - delays[m, l], l, i, res, s2) for (l, i, t, res, s2) in points(r)]
+        ll[m], info[m] = _pass(name, train, [], alpha[m], float(rho[m]), p, n, vb[r])[:2]
+    return ll, info
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
 # The gradient in linear time (csrc/gpcc_markov_grad.hip.h, DESIGN.md 4.17), the same algorithm in numpy: the filter's forward
 # sensitivities.  For one parameter theta the tangents (dm, dP) = d(m, P)/d theta are carried beside (m, P):
 #
@@ -1388,6 +1508,11 @@ class MarkovObjective:
                 raise ValueError('center must be "own", "handle" or an (R, L) array')
             center = band_means(self.data[0], Y) if center == "own" else None
         return loglik_realisations(self.kernel, *self.data, Y, delays, alpha, rho, self.marginalise_b, mean=center)
+
+    def loglik_markov_resampled(self, Y, delays, alpha, rho, real, counts=None, center="own", sigma_b="own"):
+        """Objective.loglik_markov_resampled's result: (loglik[M], info[M])."""
+        mean, vb = resample_arguments(self.data[0], Y, counts, center, sigma_b, self.marginalise_b)
+        return loglik_resampled(self.kernel, *self.data, Y, counts, real, delays, alpha, rho, self.marginalise_b, mean=mean, sigma_b=vb)
 
     def loglik_hess_hyper_markov_batch(self, delays, alpha, rho):
         """Objective.loglik_hess_hyper_markov_batch's result: (loglik[M], grad[M, 2L+1], hess[M, L+1, L+1], info[M])."""

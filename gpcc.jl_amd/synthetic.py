@@ -82,3 +82,33 @@ def flux_randomise(yarray, stdarray, R, seed):
         y, sd = np.asarray(y, np.float64).reshape(-1), np.asarray(sd, np.float64).reshape(-1)
         out.append(y[None, :] + sd[None, :] * rng.standard_normal((R, len(y))))
     return out
+
+
+def resample(yarray, stdarray, R, seed, flux=True, subset=True):
+    """R resampled realisations of a data set on its own cadence, reverberation mapping's FR/RSS -> (Y, counts): per band an (R, N_l)
+    array of fluxes and an (R, N_l) integer array of multiplicities.  flux: flux_randomise's recipe, y_l + sigma_l z with z standard
+    normal (False: y_l unchanged).  subset: random subset selection -- per band N_l indices drawn with replacement, counts their
+    multiplicities (each band's counts sum to N_l; a point not drawn has count 0, a point drawn n times stands for error bar
+    sigma / sqrt n); a draw that leaves a band fewer than 2 distinct points is redrawn, so every band keeps at least 2 (False: counts
+    of 1).  Realisation r is drawn from its own generator (numpy's PCG64 seeded with (seed, r); per band first the fluxes, then the
+    indices): reproducible from the seed and the same in any R.  What Objective.loglik_markov_resampled and fit.realisation_refits
+    take as Y and counts."""
+    R = int(R)
+    if R < 1:
+        raise ValueError("R >= 1")
+    ys = [np.asarray(y, np.float64).reshape(-1) for y in yarray]
+    sds = [np.asarray(sd, np.float64).reshape(-1) for sd in stdarray]
+    if subset and any(len(y) < 2 for y in ys):
+        raise ValueError("random subset selection keeps at least 2 distinct points per band: a band has fewer")
+    Y = [np.empty((R, len(y))) for y in ys]
+    counts = [np.ones((R, len(y)), dtype=np.int64) for y in ys]
+    for r in range(R):
+        rng = np.random.default_rng([int(seed), r])
+        for l, (y, sd) in enumerate(zip(ys, sds)):
+            Y[l][r] = y + sd * rng.standard_normal(len(y)) if flux else y
+            while subset:
+                c = np.bincount(rng.integers(0, len(y), len(y)), minlength=len(y))
+                if np.count_nonzero(c) >= 2:
+                    counts[l][r] = c
+                    break
+    return Y, counts

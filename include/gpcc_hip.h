@@ -155,6 +155,8 @@ int gpcc_multi_stats(gpcc_handle_t handle, double *compute_ms, double *gather_ms
  *                                     (results do not depend on it)
  *   markov_multi_chunk       0        gpcc_loglik_markov_multi_batch: realisations per chunk of its scratch, rounded down to whole blocks;
  *                                     0 = what fits 128 MiB (results do not depend on it)
+ *   markov_resample_bytes_max 512 MiB gpcc_loglik_markov_resampled_batch: the most the packed data of one call (16 N R bytes) may take;
+ *                                     a larger call is refused with GPCC_ERR_UNSUPPORTED (the callers split R; >= 0)
  *   fp32_refine              1        fp32 handles: fp64 refinement of the quadratic forms
  *   fp32_guard               1        fp32 handles: evaluations whose pivot ratios exceed the limits are repeated in fp64
  *   fp32_assemble            1        fp32 handles: tiles inside one band pair are evaluated in fp32
@@ -171,7 +173,10 @@ int gpcc_multi_stats(gpcc_handle_t handle, double *compute_ms, double *gather_ms
  * "slots_per_stream" only if the device's memory was short when it was allocated -- then gpcc_last_error carries a note; the
  * options themselves are never rewritten); "markov_tap_bytes" (the tap scratch of gpcc_predict_markov_batch, 0 before its first call);
  * "markov_multi_bytes" (the scratch of gpcc_loglik_markov_multi_batch, 0 before its first call) and "markov_multi_block" (the
- * realisations a lane of that entry carries for this handle's kernel and b-mode; 0 where the entry refuses the handle). */
+ * realisations a lane of that entry carries for this handle's kernel and b-mode; 0 where the entry refuses the handle);
+ * "markov_resample_bytes" (the packed per-realisation data of gpcc_loglik_markov_resampled_batch, 16 N R bytes after one call, 0
+ * before the first) and "markov_resample_upload_bytes" (what its pack kernel reads: the fluxes, multiplicities, means, prior
+ * variances, the rows' realisations and the sort permutation as uploaded) -- both of the handle that computes. */
 int gpcc_set_option(gpcc_handle_t handle, const char *key, long value);
 long gpcc_get_option(gpcc_handle_t handle, const char *key);
 
@@ -223,7 +228,8 @@ int gpcc_loglik_batch(gpcc_handle_t handle, int M, const double *delays, const d
  * Predictions, held-out scores and the offsets' posterior in linear time: the three entries below; the gradient in linear time:
  * gpcc_loglik_grad_markov_batch after them; the (alpha, rho) block of the Hessian is gpcc_loglik_hess_hyper_markov_batch, the full
  * Hessian (the rows of tau) gpcc_loglik_hess_markov_batch; the Fisher information gpcc_loglik_fisher_markov_batch; many flux
- * realisations per row in one pass (a second data axis) gpcc_loglik_markov_multi_batch.
+ * realisations per row in one pass (a second data axis) gpcc_loglik_markov_multi_batch; rows with their own resampled data set
+ * (FR/RSS with refits) gpcc_loglik_markov_resampled_batch.
  * Blocking. */
 int gpcc_loglik_markov_batch(gpcc_handle_t handle, int M, const double *delays, const double *alpha, const double *rho,
                              double *loglik, int *info);
@@ -426,6 +432,35 @@ int gpcc_loglik_fisher_markov_batch(gpcc_handle_t h, int M, const double *delays
  * Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Blocking. */
 int gpcc_loglik_markov_multi_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                    int R, const double *Y, const double *mean, double *loglik, int *info);
+
+/* The log-likelihood of M rows that each carry their own (tau, alpha, rho) AND THEIR OWN RESAMPLED DATA SET on the handle's cadence,
+ * in LINEAR TIME for the Markov kernels (kernel: csrc/gpcc_markov_resample.hip.h): flux randomisation with a refit
+ * per realisation, random subset selection (FR/RSS) and, with marginalise_b, each realisation's own Sigma_b.
+ *   real: M entries, the realisation of row m, 0 <= real[m] < R.  Y: R x N row-major, each row in the order gpcc_create took y.
+ *   count: R x N multiplicities >= 0 in the same order, or NULL: all 1.  mean: R x L, or NULL: the handle's band means.
+ *   sigma_b: R x L, the offsets' prior variances, or NULL: the handle's; read only with marginalise_b.  loglik, info: M entries.
+ * SEMANTICS.  Let sel be the points of realisation r = real[m] with count >= 1.  loglik[m] = logpdf(MvNormal(Q mean_r, K), Y_r[sel]):
+ * K built from (tau, alpha, rho)_m on the handle's times t[sel] with the variances sigma^2[sel] / count and, with marginalise_b, B
+ * from sigma_b[r].  This is the value of a fresh handle created from the distinct selected points with error bars sigma / sqrt(n),
+ * when mean_r and sigma_b_r are that data set's band means and 100 var (n - 1); only the order of rounding differs.  A dropped point
+ * contributes nothing, not even its 1/2 log 2 pi; a realisation with no selected point gives 0.0 with info 0.
+ * info[m]: gpcc_loglik_markov_batch's codes; a positive j counts positions among the KEPT points in merged order, so it equals the
+ * fresh handle's code.  A flux that is not finite at a kept point makes the rows that reference that realisation NaN, and no other.
+ * With real[m] pointing to the handle's own y, count, mean and sigma_b NULL, the row is bitwise gpcc_loglik_markov_batch's.
+ * Refusals: gpcc_loglik_markov_batch's (rbf, and marginalise_b with L > 4: GPCC_ERR_UNSUPPORTED); GPCC_ERR_ARGUMENT for R < 1, a
+ * NULL Y or real, a real[m] outside [0, R), a negative count; GPCC_ERR_UNSUPPORTED, the message naming the limit, for a call whose
+ * packed data (16 N R bytes) exceeds option "markov_resample_bytes_max" (512 MiB) -- the entry does not chunk, since a row may
+ * reference any realisation: split R across calls.  All of them on the host, before any device work.  M = 0 returns 0.
+ * Path: a pack kernel gathers Y through the handle's sort permutation, subtracts the means and writes per (r, i) one 16-byte pair
+ * {residual, sigma^2_i / count}, a dropped point marked by a negative variance; then one lane per row walks the handle's shared merge
+ * and reads its realisation's pair at each step, skipping dropped points and forming the lag from the last kept point.  No atomics:
+ * a row's value is bitwise the same for any M, R, row order, position of its realisation in Y and split across calls.
+ * Memory: handle-owned scratch grown on demand -- the packed data ("markov_resample_bytes") and what the pack kernel reads
+ * ("markov_resample_upload_bytes": 12 N + 16 L bytes a realisation, 4 M for the rows); none of the N^2 workspace.  "markov_count"
+ * advances by M.  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Blocking. */
+int gpcc_loglik_markov_resampled_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                       const int *real, int R, const double *Y, const int *count, const double *mean,
+                                       const double *sigma_b, double *loglik, int *info);
 
 /* Same with DEVICE pointers, enqueued behind `stream` (a hipStream_t, NULL = default stream) and
  * joined back into it: asynchronous, outputs valid once `stream` has drained. */

@@ -303,6 +303,34 @@ function loglik_markov_realisations(h::Handle, Y::Matrix{Float64}, delays::Matri
     return ll, info
 end
 
+"the log-likelihood of M columns (τ, α, ρ) that each carry THEIR OWN RESAMPLED DATA SET on the handle's cadence, in one linear-time pass
+(gpcc_loglik_markov_resampled_batch, DESIGN 4.24; OU, matern32, matern52) -> (ll[M], info[M]): flux randomisation with a refit per
+realisation, random subset selection, each realisation's own Σ_b.  Y: N×R, column r one realisation in the order the handle took y.
+real[m] in 1:R: the realisation of column m.  counts: N×R multiplicities ≥ 0 (0 drops the point, n > 1 is the point once with σ²/n) or
+nothing: all 1.  mean, sigma_b: L×R -- each realisation's band means and offsets' prior variances (for the value of a fresh handle on
+the kept points: the means and 100 var (n - 1) of its distinct kept points) -- or nothing: the handle's.  A realisation that keeps no
+point gives 0.0.  info is loglik_markov's, a positive value counted among the kept points.  A flux that is not finite at a kept point
+makes the columns of that realisation NaN.  Errors for rbf, for marginalise_b with more than 4 bands, and for a call whose packed data
+(16 N R bytes) exceeds the option markov_resample_bytes_max: split R."
+function loglik_markov_resampled(h::Handle, Y::Matrix{Float64}, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64},
+                                 real::Vector{<:Integer}; counts = nothing, mean = nothing, sigma_b = nothing)
+    M, R = length(rho), size(Y, 2)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M) && length(real) == M && R >= 1
+    @assert all(1 .<= real .<= R)
+    @assert counts === nothing || (size(counts) == size(Y) && all(counts .>= 0))
+    @assert mean === nothing || size(mean) == (h.L, R)
+    @assert sigma_b === nothing || size(sigma_b) == (h.L, R)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    rc = ccall((:gpcc_loglik_markov_resampled_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Cint, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, convert(Vector{Cint}, real .- 1), R, Y,
+               counts === nothing ? C_NULL : convert(Matrix{Cint}, counts), mean === nothing ? C_NULL : convert(Matrix{Float64}, mean),
+               sigma_b === nothing ? C_NULL : convert(Matrix{Float64}, sigma_b), ll, info)
+    rc == 0 || error("gpcc_loglik_markov_resampled_batch: " * lasterror(h.ptr))
+    return ll, info
+end
+
 "Laplace-marginalised evidence over α and ρ per delay (columns of delays, L×G), from (alpha0 L×G, rho0[G]), usually the fit's
 output.  Prior log-uniform in α and in ρ on [rhomin, rhomax]: log_evidence is log Z(τ) up to ONE additive constant shared by all
 delays -- use it only through getprobabilities (or differences).  -> (ll[G], alpha L×G, rho[G], log_evidence[G], cov (L+1)×(L+1)×G

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Registers, spills and scratch of every kernel in csrc/libgpcc_hip.so (the gfx950 code objects inside the fat binary: roc-obj-ls /
 roc-obj-extract + llvm-readelf --notes).  Prints the kernels that spill or use scratch, and the totals.
-  python tools/kernel_resources.py [library] [--all]"""
+  python tools/kernel_resources.py [library] [--all] [--match=TEXT]
+--match=TEXT: only the kernels whose name holds TEXT, all of them listed (a family's log under profiles/markov/, e.g.
+--match=gpcc_markov_resample > profiles/markov/kernel_resources_resample.log)."""
 import os
 import re
 import subprocess
 import sys
 import tempfile
 
+match = next((a[len("--match="):] for a in sys.argv[1:] if a.startswith("--match=")), None)
 lib = next((a for a in sys.argv[1:] if not a.startswith("--")), os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gpcc.jl_amd", "csrc", "libgpcc_hip.so"))
 show_all = "--all" in sys.argv
 readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
@@ -59,6 +62,9 @@ with tempfile.TemporaryDirectory() as td:
 demangle = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), capture_output=True, text=True).stdout.splitlines()
 for r, d in zip(rows, demangle):
     r["pretty"] = d.split("(")[0]
+if match is not None:
+    rows = [r for r in rows if match in r["pretty"]]
+    show_all = True
 bad = [r for r in rows if r.get("vgpr_spill_count", 0) or r.get("private_segment_fixed_size", 0)]
 print("%d kernels in %d gfx950 code objects of %s (%.1f MB)" % (len(rows), len(uris), os.path.basename(lib), os.path.getsize(lib) / 1e6))
 for r in (rows if show_all else bad):
