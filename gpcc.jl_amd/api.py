@@ -182,6 +182,7 @@ class Objective:
         assert np.array_equal(Nl, Ny) and np.array_equal(Nl, Ns), "band lengths differ between t, y, sigma"
         self.L, self.Nl, self.N = L, Nl.copy(), int(Nl.sum())
         self.yflat = y.copy()     # the fluxes in the order they were handed over (the leave-one-out residuals are taken against them)
+        self.sflat = s.copy()     # the error bars in the same order (fit.gpcc_grid_noise scales the excess variance by their mean square)
         self.marginalise_b = bool(marginalise_b)
         self.device = int(device)
         lib = _capi.load()
@@ -547,6 +548,49 @@ class Objective:
         info = np.zeros(M, dtype=np.int32)
         self._chk(_capi.load().gpcc_loglik_grad_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _dp(grad),
                                                              _ip(info)))
+        return ll, grad, info
+
+    def _noise(self, M, x, name):
+        """kappa or nu of the noise entries as a contiguous (M, L) array, or None: an (M, L) array, or (L,) broadcast over the rows."""
+        if x is None:
+            return None
+        x = np.asarray(x, dtype=np.float64)
+        if x.shape == (self.L,):
+            x = np.broadcast_to(x, (M, self.L))
+        if x.shape != (M, self.L):
+            raise ValueError("%s must be (M, L) = (%d, %d), (L,) or None" % (name, M, self.L))
+        return _d(x)
+
+    def loglik_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
+        """The linear-time objective of M rows that each carry their own (tau, alpha, rho) AND their own noise model
+        (gpcc_loglik_noise_markov_batch; OU, matern32 and matern52 only) -> (loglik[M], info[M]): point i of band l is observed with
+        the variance kappa_l^2 sigma_i^2 + nu_l, kappa >= 0 the scale of the reported error bars, nu >= 0 an excess variance.  kappa,
+        nu: (M, L), (L,) broadcast, or None (all 1 / all 0).  loglik[m] is the value of a fresh Objective on fit.effective_std(sigma,
+        kappa[m], nu[m]); at kappa = 1, nu = 0 loglik and info are bitwise loglik_markov_batch's.  info as loglik_markov_batch and,
+        after -1 and -2, -3: a kappa or nu of the row is negative or not finite.  rbf, or marginalise_b with more than 4 bands:
+        GpccError (unsupported)."""
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        kappa, nu = self._noise(M, kappa, "kappa"), self._noise(M, nu, "nu")
+        ll = np.empty(M, dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        self._chk(_capi.load().gpcc_loglik_noise_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho),
+                                                              _dp(kappa) if kappa is not None else None,
+                                                              _dp(nu) if nu is not None else None, _dp(ll), _ip(info)))
+        return ll, info
+
+    def loglik_grad_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
+        """loglik_markov_noise_batch and its gradient (gpcc_loglik_grad_noise_markov_batch: forward sensitivities, one lane per (row,
+        parameter)) -> (loglik[M], grad[M, 4L+1], info[M]), a row of grad being [alpha_1..L, rho, tau_1..L, kappa_1..L, nu_1..L]: the
+        first 2L+1 entries as loglik_grad_markov_batch, d/d kappa_l and d/d nu_l behind them.  loglik and info are
+        loglik_markov_noise_batch's; a row of grad is NaN where info != 0."""
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        kappa, nu = self._noise(M, kappa, "kappa"), self._noise(M, nu, "nu")
+        ll = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, 4 * self.L + 1), dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        self._chk(_capi.load().gpcc_loglik_grad_noise_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho),
+                                                                   _dp(kappa) if kappa is not None else None,
+                                                                   _dp(nu) if nu is not None else None, _dp(ll), _dp(grad), _ip(info)))
         return ll, grad, info
 
     def loglik_hess_batch(self, delays, alpha, rho):

@@ -18,6 +18,7 @@
 #include "gpcc_markov_fisher.hip.h"
 #include "gpcc_markov_multi.hip.h"
 #include "gpcc_markov_resample.hip.h"
+#include "gpcc_markov_noise.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -283,6 +284,10 @@ struct gpcc_handle_s {
     double *d_mkry = nullptr, *d_mkrm = nullptr;
     int *d_mkrc = nullptr, *d_mkrr = nullptr, *d_mkrp = nullptr;
     long mkrv_cap = 0, mkry_cap = 0, mkrm_cap = 0, mkrc_cap = 0, mkrr_cap = 0, mkrp_cap = 0;
+    // linear-time log-likelihood and gradient under a per-row noise model (gpcc_loglik_noise_markov_batch and its gradient): the rows'
+    // kappa | nu (2 M L doubles), the per-slot results [slots][M] and the rows [M][4L + 1], grown on demand
+    double *d_mknp = nullptr, *d_mkns = nullptr, *d_mkng = nullptr;
+    long mknp_cap = 0, mkns_cap = 0, mkng_cap = 0;
     long markov_resample_bytes_max = (long)512 << 20;   // option "markov_resample_bytes_max": the most the packed pairs of one call may take
     int laplace_markov = 0;              // option "laplace_markov": gpcc_laplace_evidence's rounds are gpcc_loglik_hess_hyper_markov_batch calls
     int markov_chunk_rows = 0;           // option "markov_chunk_rows": rows per chunk of gpcc_predict_markov_batch (0: by the scratch budget)
@@ -601,6 +606,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_mkts); hipFree(h->d_mktb);
     hipFree(h->d_mkfs); hipFree(h->d_mkfb);
     hipFree(h->d_mkmy); hipFree(h->d_mkmr); hipFree(h->d_mkmm); hipFree(h->d_mkmo); hipFree(h->d_mkmp);
+    hipFree(h->d_mknp); hipFree(h->d_mkns); hipFree(h->d_mkng);
     hipFree(h->d_mkrv); hipFree(h->d_mkry); hipFree(h->d_mkrm); hipFree(h->d_mkrc); hipFree(h->d_mkrr); hipFree(h->d_mkrp);
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
     hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
@@ -2185,7 +2191,7 @@ static void markov_fill_args(gpcc_handle_t h, int M, const double *dd, const dou
 }
 
 // the kernels with dynamic LDS, for gpcc_handle::mk_lds_raised
-enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI, MK_RESAMPLE };
+enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI, MK_RESAMPLE, MK_NOISE, MK_NOISE_GRAD };
 
 // The launch of every kernel of the filter, `name` in messages: one lane per row, `rows` rows along x and ny lanes per row along y.
 // The shape: one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy beyond; the light
@@ -2834,6 +2840,127 @@ extern "C" int gpcc_loglik_grad_markov_batch(gpcc_handle_t h, int M, const doubl
     rc = markov_grad_enqueue(h, M, dd, da, dr, grad);
     if (rc) return rc;
     return markov_finish(h, M, loglik, info);
+}
+
+// ------------------------------------------------------------------------------------------
+// The linear-time log-likelihood and gradient of rows with their own noise model (gpcc_loglik_noise_markov_batch,
+// gpcc_loglik_grad_noise_markov_batch; kernels: gpcc_markov_noise.hip.h): point i of band l of row m is observed with
+// the variance kappa_{m,l}^2 sigma_i^2 + nu_{m,l}.  One lane per row (value) or per (row, slot) (gradient), as gpcc_loglik_markov_batch
+// and gpcc_loglik_grad_markov_batch; they need what those need plus the rows' kappa and nu, the slots and the rows below.
+// ------------------------------------------------------------------------------------------
+// the dynamic LDS of the family: the light curves, the lanes' cursors and their kappa^2, nu
+static auto markov_noise_lds(gpcc_handle_t h)
+{
+    return [h](int thr, bool st) { return gpcc_markov_noise_lds_bytes(h->N, h->L, thr, st); };
+}
+
+// the rows' kappa | nu staged in d_mknp on main_stream (NULL: all 1 / all 0, from a host copy that lives in this function only: the
+// stream is drained before it goes, so that no return of the caller, an error's included, leaves a copy reading freed memory), and
+// the family's arguments beside the filter's
+static int markov_noise_stage(gpcc_handle_t h, int M, const double *kappa, const double *nu, GpccMarkovNoiseArgs &a)
+{
+    const long ML = (long)M * h->L;
+    if (!kappa || !nu) {
+        std::vector<double> hold((size_t)2 * ML, 0.0);
+        for (long k = 0; k < ML; ++k) hold[k] = kappa ? kappa[k] : 1.0;
+        if (nu) std::copy(nu, nu + ML, hold.begin() + ML);
+        const hipError_t e = hipMemcpyAsync(h->d_mknp, hold.data(), sizeof(double) * 2 * ML, hipMemcpyHostToDevice, h->main_stream);
+        const hipError_t e2 = hipStreamSynchronize(h->main_stream);
+        HIPCHK(h, e);
+        HIPCHK(h, e2);
+    } else {
+        HIPCHK(h, hipMemcpyAsync(h->d_mknp, kappa, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_mknp + ML, nu, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
+    }
+    a.kappa = h->d_mknp; a.nu = h->d_mknp + ML;
+    a.slot = h->d_mkns; a.grad = h->d_mkng; a.twice = markov_dims(h).p == 1;
+    return 0;
+}
+
+static int markov_noise_ships(gpcc_handle_t h, const char *who, const char *dense)
+{
+    const MarkovDims d = markov_dims(primary(h));
+    if (!gpcc_mk_ships<GpccMkShipsNoise>(d.p, d.noff))
+        return fail(h, GPCC_ERR_UNSUPPORTED, "%s: the instantiation <%d, %d> (states of the process, offset states) does not ship; use %s",
+                    who, d.p, d.noff, dense);
+    return 0;
+}
+
+// gpcc_markov_noise_eval over the M staged rows: loglik and info left in d_out / d_oinfo
+static int markov_noise_eval_launch(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, GpccMarkovNoiseArgs &a)
+{
+    markov_fill_args(h, M, dd, da, dr, a);
+    return markov_launch(h, "gpcc_markov_noise_eval", MK_NOISE, M, 1, a.stage, markov_noise_lds(h),
+                         [&](const GpccMkLaunch &g) { return gpcc_markov_noise_launch(g, a); });
+}
+
+extern "C" int gpcc_loglik_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                              const double *kappa, const double *nu, double *loglik, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (M == 0) return 0;
+    if (!delays || !alpha || !rho || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    const char *dense = "gpcc_loglik_batch on a handle created with the error bars sqrt(kappa^2 sigma^2 + nu)";
+    int rc = markov_refusals(h, "gpcc_loglik_noise_markov_batch", dense);
+    if (!rc) rc = markov_noise_ships(h, "gpcc_loglik_noise_markov_batch", dense);
+    if (rc) return rc;
+    if (route_fp64(h, "linear-time log-likelihood under a noise model", rc,
+                   [&](gpcc_handle_t o) { return gpcc_loglik_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, loglik, info); }))
+        return rc;
+    GPCC_ON_DEVICE(h, h->device);
+    double *dd, *da, *dr;
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] { return grow_buf(h, &h->d_mknp, &h->mknp_cap, 2L * M * h->L); });
+    if (rc) return rc;
+    GpccMarkovNoiseArgs a;
+    rc = markov_noise_stage(h, M, kappa, nu, a);
+    if (rc) return rc;
+    rc = markov_noise_eval_launch(h, M, dd, da, dr, a);
+    if (rc) return rc;
+    rc = markov_finish(h, M, loglik, info);   // (its synchronisation also guards the caller's arrays)
+    if (rc) return rc;
+    h->markov_count += M;
+    return 0;
+}
+
+extern "C" int gpcc_loglik_grad_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                                   const double *kappa, const double *nu, double *loglik, double *grad, int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (M == 0) return 0;
+    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    const char *dense = "gpcc_loglik_grad_batch on a handle created with the error bars sqrt(kappa^2 sigma^2 + nu)";
+    int rc = markov_refusals(h, "gpcc_loglik_grad_noise_markov_batch", dense);
+    if (!rc) rc = markov_noise_ships(h, "gpcc_loglik_grad_noise_markov_batch", dense);
+    if (rc) return rc;
+    if (route_fp64(h, "linear-time gradient under a noise model", rc, [&](gpcc_handle_t o) {
+            return gpcc_loglik_grad_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, loglik, grad, info);
+        }))
+        return rc;
+    GPCC_ON_DEVICE(h, h->device);
+    const int L = h->L, W = 4 * L + 1, slots = gpcc_markov_noise_slots(L, markov_dims(h).p == 1);
+    double *dd, *da, *dr;
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
+        int g = grow_buf(h, &h->d_mknp, &h->mknp_cap, 2L * M * L);
+        if (!g) g = grow_buf(h, &h->d_mkns, &h->mkns_cap, (long)slots * M);
+        if (!g) g = grow_buf(h, &h->d_mkng, &h->mkng_cap, (long)W * M);
+        return g;
+    });
+    if (rc) return rc;
+    GpccMarkovNoiseArgs a;
+    rc = markov_noise_stage(h, M, kappa, nu, a);
+    if (rc) return rc;
+    rc = markov_noise_eval_launch(h, M, dd, da, dr, a);
+    if (rc) return rc;
+    rc = markov_slots_launch(h, "gpcc_markov_noise_grad", MK_NOISE_GRAD, M, dd, da, dr, slots, a, markov_noise_lds(h),
+                             gpcc_markov_noise_grad_launch);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(grad, h->d_mkng, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
+    rc = markov_finish(h, M, loglik, info);
+    if (rc) return rc;
+    h->markov_count += M;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------

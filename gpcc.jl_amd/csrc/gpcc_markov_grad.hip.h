@@ -260,7 +260,9 @@ __device__ __forceinline__ void gpcc_mkg_update(int b, double al, bool dh, doubl
 }
 
 // one lane's walk: KIND of slot, tb: the band of an alpha or tau slot, rb / rr: the band whose rank among ties is rr instead of its
-// index (rb = -1: none), handed to gpcc_mk_next<true>
+// index (rb = -1: none), handed to gpcc_mk_next<true>.  gpcc_mkn_walk of gpcc_markov_noise.hip.h is this walk statement by statement,
+// on the mapped variance kappa^2 sigma^2 + nu in place of p.s2: a change here is made there as well (tests/test_gpu_markov_noise.py
+// reports whether the two are still bitwise the same at kappa = 1, nu = 0)
 template <int P, int NOFF, int KIND>
 __device__ __forceinline__ double gpcc_mkg_walk(const GpccMarkovGradArgs &a, const GpccMkLane &ln, int tb, int rb, int rr)
 {

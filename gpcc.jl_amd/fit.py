@@ -399,6 +399,101 @@ def realisation_refits(objective, candidatedelays, Y, counts=None, *, iterations
                              RealisationDelays(prob, np.argmax(prob, axis=1), prob @ cand), f_start)
 
 
+def effective_std(stdarray, kappa, nu):
+    """The error bars sqrt(kappa_l^2 sigma_l^2 + nu_l) of the noise model of Objective.loglik_markov_noise_batch, as a list of L
+    arrays: kappa and nu scalars or (L,).  A fresh Objective or Predictor on them is the route to predictions, leave-one-out scores,
+    Hessians, the Laplace evidence and draws under a fitted noise model (its loglik_markov_batch is loglik_markov_noise_batch's value)."""
+    L = len(stdarray)
+    kappa = np.broadcast_to(np.asarray(kappa, np.float64), (L,))
+    nu = np.broadcast_to(np.asarray(nu, np.float64), (L,))
+    return [np.sqrt(kappa[l] ** 2 * np.asarray(stdarray[l], np.float64) ** 2 + nu[l]) for l in range(L)]
+
+
+class NoiseGridFit(collections.namedtuple("NoiseGridFit", "loglikel alpha rho kappa nu f_calls rounds start_loglikel")):
+    """gpcc_grid_noise's result: loglikel[G] (the profile likelihood over the grid with the noise model fitted beside alpha and rho),
+    alpha[G, L], rho[G], kappa[G, L], nu[G, L], f_calls, rounds and start_loglikel[G] (the value at the warm start as the optimiser
+    holds it, loglikel >= it; None with start=None)."""
+
+
+def gpcc_grid_noise(objective, candidatedelays, *, iterations, noise="both", shared=False, start=None, seed=1, numberofrestarts=1,
+                    initialrandom=5, rhomin=0.1, rhomax=20.0, kappa=1.0, nu=0.0):
+    """gpcc_grid with a NOISE MODEL fitted beside (alpha, rho) at every row of candidatedelays (G, L): point i of band l has the
+    variance kappa_l^2 sigma_i^2 + nu_l -> NoiseGridFit.  Built like realisation_refits: the lock-step
+    BatchedNelderMead over the problems (delay, restart), every optimiser round ONE objective.loglik_markov_noise_batch call (linear
+    time: OU, matern32, matern52).  objective: an Objective, or a markov.MarkovObjective (no GPU).
+
+    noise: "scale" fits kappa, "excess" fits nu, "both" both; the part not fitted stays at the `kappa` / `nu` argument (a scalar or
+    (L,)).  shared=True fits one kappa and / or one nu for all bands.  kappa=0.0, noise="excess", shared=True is the model of the
+    reference's unused src/UNUSED/gpccfixdelay_globalnoiseterm.jl, up to the scale of nu.  The optimiser's variables: kappa =
+    makepositive(x); nu_l = makepositive(x) mean(sigma_l^2), so that x is dimensionless.
+
+    start=None: the random candidates -- alpha and rho exactly gpcc_grid's draws (the same seed gives the same ones), kappa from
+    U(0.8, 1.2) and nu from U(0, 1) mean(sigma_l^2), drawn after them.  start=(alpha[G, L], rho[G]), usually a GridFit of the plain
+    model: Nelder-Mead starts at delay g from (alpha[g], rho[g], kappa = 1, nu = 0.1 mean(sigma_l^2)) with one restart and no
+    candidates; rho is clipped into (rhomin, rhomax)."""
+    if noise not in ("scale", "excess", "both"):
+        raise ValueError('noise must be "scale", "excess" or "both", got %r' % (noise,))
+    cand = np.ascontiguousarray(np.asarray(candidatedelays, np.float64).reshape(len(candidatedelays), -1))
+    G, L = cand.shape
+    edges = np.concatenate([[0], np.cumsum(objective.Nl if hasattr(objective, "Nl") else [len(t) for t in objective.data[0]])])
+    vary = np.array([np.var(objective.yflat[edges[l]:edges[l + 1]], ddof=1) for l in range(L)])
+    ms2 = np.array([np.mean(objective.sflat[edges[l]:edges[l + 1]] ** 2) for l in range(L)])
+    kfix = np.broadcast_to(np.asarray(kappa, np.float64), (L,))
+    vfix = np.broadcast_to(np.asarray(nu, np.float64), (L,))
+    nk = 0 if noise == "excess" else (1 if shared else L)                # the optimiser's kappa and nu variables
+    nv = 0 if noise == "scale" else (1 if shared else L)
+    n = L + 1 + nk + nv
+
+    def unpack(X):
+        kap = np.broadcast_to(makepositive(X[:, L + 1:L + 1 + nk]), (len(X), L)) if nk else np.tile(kfix, (len(X), 1))
+        exc = np.broadcast_to(makepositive(X[:, L + 1 + nk:]), (len(X), L)) * ms2 if nv else np.tile(vfix, (len(X), 1))
+        return makepositive(X[:, :L]) + 1e-8, transformbetween(X[:, L], rhomin, rhomax), kap, exc
+
+    if start is None:
+        K = int(numberofrestarts)
+        rg = np.random.default_rng(seed)
+        rho0 = rg.uniform(rhomin + 1e-3, rhomax - 1e-3, K) if K in (1, 2) else logrange(rhomin + 1e-3, rhomax - 1e-3, K)
+        cands = np.empty((K, initialrandom, n))
+        for i in range(K):
+            for c in range(initialrandom):
+                cands[i, c, :L] = invmakepositive(vary * (rg.random(L) * (1.2 - 0.8) + 0.8))
+                cands[i, c, L] = invtransformbetween(rho0[i], rhomin, rhomax)
+        for i in range(K):                                               # after gpcc_grid's draws, so that those stay gpcc_grid's
+            for c in range(initialrandom):
+                cands[i, c, L + 1:L + 1 + nk] = invmakepositive(rg.random(nk) * (1.2 - 0.8) + 0.8)
+                cands[i, c, L + 1 + nk:] = invmakepositive(np.maximum(rg.random(nv), 1e-12))
+    else:
+        K = 1
+        a0 = np.asarray(start[0], np.float64).reshape(G, L)
+        r0 = np.clip(np.asarray(start[1], np.float64).reshape(G), rhomin + 1e-9 * (rhomax - rhomin), rhomax - 1e-9 * (rhomax - rhomin))
+        xs = np.concatenate([invmakepositive(np.maximum(a0 - 1e-8, 1e-300)), invtransformbetween(r0, rhomin, rhomax)[:, None],
+                             np.full((G, nk), float(invmakepositive(1.0))), np.full((G, nv), float(invmakepositive(0.1)))], axis=1)
+    P = G * K                                                            # problem p = (delay p // K, restart p % K)
+
+    def negobj(pidx, X):
+        alpha, rho, kap, exc = unpack(X)
+        ll, info = objective.loglik_markov_noise_batch(cand[pidx // K], alpha, rho, kap, exc)
+        return np.where(info == 0, -ll, np.inf)
+
+    extra_calls, extra_rounds, f_start = 0, 0, None
+    if start is None:
+        pid = np.repeat(np.arange(P), initialrandom)
+        Xc = cands[np.tile(np.repeat(np.arange(K), initialrandom), G), np.tile(np.arange(initialrandom), P)]
+        f0 = negobj(pid, Xc).reshape(P, initialrandom)                   # argmin over the random candidates
+        x0 = Xc.reshape(P, initialrandom, n)[np.arange(P), np.argmin(f0, axis=1)]
+        extra_calls, extra_rounds = P * initialrandom, 1
+    else:
+        x0 = xs
+        f_start = -negobj(np.arange(P), x0)
+    nm = BatchedNelderMead(x0, negobj, iterations=iterations, g_tol=1e-6)
+    xmin, fmin = nm.run()
+    fmin = fmin.reshape(G, K)
+    pick = np.argmin(fmin, axis=1)
+    a_sel, r_sel, k_sel, v_sel = unpack(xmin.reshape(G, K, n)[np.arange(G), pick])
+    return NoiseGridFit(-fmin[np.arange(G), pick], a_sel, r_sel, np.array(k_sel), np.array(v_sel), nm.f_calls + extra_calls,
+                        nm.rounds + extra_rounds, f_start)
+
+
 def _with_evidence(res, obj, cand, engine, evidence, rhomin, rhomax, max_rounds, g_tol, solver="dense"):
     if evidence is None:
         return res

@@ -508,6 +508,166 @@ def loglik_grad_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marg
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
+# A noise model per row (csrc/gpcc_markov_noise.hip.h, gpcc_loglik_noise_markov_batch and its gradient), the same
+# algorithm in numpy.  Point i of band l is observed with the variance v_i = kappa_l^2 sigma_i^2 + nu_l: kappa >= 0 scales the reported
+# error bars, nu >= 0 is an excess variance; kappa = 1, nu = 0 is loglik()'s model.  The band means and the offsets' prior variances
+# depend on y only and stay those of (tarray, yarray, stdarray), so the value is loglik()'s on the error bars sqrt(v_i).  Value and the
+# alpha, rho, tau entries of the gradient are _pass and _grad_pass on the mapped variances.  A noise parameter of band l moves the
+# observation variance alone: dvar = [band_i = l] (2 kappa_l sigma_i^2 or 1) enters dS, and nothing else has a direct term -- no dA, no
+# dPinf, no dh, the merged order merge_order()'s (_noise_pass).  Codes: loglik()'s, then -3: a kappa or nu negative or not finite.
+# ----------------------------------------------------------------------------------------------------------------------------------
+def _noise_setup(L, kappa, nu):
+    """kappa and nu as (L,) arrays (None: ones / zeros) and the code -3 (one of them negative or not finite) or 0."""
+    kappa = np.ones(L) if kappa is None else np.asarray(kappa, np.float64).reshape(L)
+    nu = np.zeros(L) if nu is None else np.asarray(nu, np.float64).reshape(L)
+    ok = np.all(np.isfinite(kappa)) and np.all(np.isfinite(nu)) and np.all(kappa >= 0.0) and np.all(nu >= 0.0)
+    return kappa, nu, (0 if ok else -3)
+
+
+def _noise_train(train, kappa, nu, slip=None):
+    """_setup's training observations with the mapped variance in place of sigma^2, and the reported sigma^2 as a sixth entry."""
+    k2 = kappa * kappa
+    ex = nu * k2 if slip == "nu_scaled" else nu
+    return [(s, b, i, r, k2[b] * s2 + ex[b], s2) for (s, b, i, r, s2) in train]
+
+
+def _noise_pass(name, ntrain, alpha, rho, p, n, vb, kind, band, kappa, slip=None):
+    """d loglik / d kappa_band (kind "kappa") or d nu_band ("nu") by the tangent recursion over _noise_train's observations: _grad_pass
+    without dA, dPinf and dh, plus dvar in dS.  slip: loglik_grad_noise()'s."""
+    ev = sorted(ntrain, key=lambda e: e[:3])
+    Pinf = stationary(name, rho)
+    P = _prior(name, rho, p, n, vb)
+    dP = np.zeros((n, n))
+    m, dm = np.zeros(n), np.zeros(n)
+    dll, sprev = 0.0, None
+    for (s, b, _, r, v, s2) in ev:
+        d = 0.0 if sprev is None else s - sprev
+        sprev = s
+        A = transition(name, d, rho)
+        D = P[:p, :p] - Pinf
+        dm[:p] = A @ dm[:p]
+        dP[:p, :p] = A @ dP[:p, :p] @ A.T
+        dP[:p, p:] = A @ dP[:p, p:]
+        dP[p:, :p] = dP[:p, p:].T
+        m[:p] = A @ m[:p]
+        P[:p, :p] = A @ D @ A.T + Pinf
+        P[:p, p:] = A @ P[:p, p:]
+        P[p:, :p] = P[:p, p:].T
+        h = np.zeros(n)
+        h[0] = alpha[b]
+        if n > p:
+            h[p + b] = 1.0
+        dvar = 0.0
+        if b == band or slip == "noise_all_bands":
+            dvar = 1.0 if kind == "nu" else (s2 if slip == "kappa_linear" else 2.0 * kappa[band] * s2)
+        Ph = P @ h
+        dPh = dP @ h
+        S = h @ Ph + v
+        if not (S > 0.0 and math.isfinite(S)):
+            return math.nan
+        dS = h @ dPh + dvar
+        eps = r - h @ m
+        deps = -(h @ dm)
+        g = eps / S
+        dg = (deps - g * dS) / S
+        dll -= 0.5 * (dS / S + 2.0 * g * deps - g * g * dS)
+        dm = dm + dPh * g + Ph * dg
+        m = m + Ph * g
+        dP = dP - (np.outer(dPh, Ph) + np.outer(Ph, dPh)) / S + np.outer(Ph, Ph) * (dS / (S * S))
+        P = P - np.outer(Ph, Ph) / S
+        P = 0.5 * (P + P.T)
+        dP = 0.5 * (dP + dP.T)
+    return dll
+
+
+def loglik_noise(kernel, tarray, yarray, stdarray, delays, alpha, rho, kappa=None, nu=None, marginalise_b=True, _slip=None):
+    """(loglik, info) of one (tau, alpha, rho, kappa, nu): loglik() with the variances kappa_l^2 sigma_i^2 + nu_l, a row of
+    Objective.loglik_markov_noise_batch.  kappa, nu: (L,) or None (ones / zeros: then the numbers are loglik()'s exactly).  info:
+    loglik()'s codes and, after -1 and -2, -3: a kappa or nu negative or not finite.  _slip (tests only): "nu_scaled" (nu multiplied
+    by kappa^2)."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b,
+                                                                       codes_first=True)
+    kappa, nu, ncode = _noise_setup(L, kappa, nu)
+    code = code or ncode
+    if code:
+        return math.nan, code
+    ll, info, _, _, _, _ = _pass(name, [e[:5] for e in _noise_train(train, kappa, nu, _slip)], [], alpha, rho, p, n, vb)
+    return ll, info
+
+
+def loglik_grad_noise(kernel, tarray, yarray, stdarray, delays, alpha, rho, kappa=None, nu=None, marginalise_b=True, _slip=None):
+    """(loglik, grad[4L+1], info): loglik_noise() and its gradient [d/dalpha_1..L, d/drho, d/dtau_1..L, d/dkappa_1..L, d/dnu_1..L], a row
+    of Objective.loglik_grad_markov_noise_batch.  The first 2L+1 entries are loglik_grad()'s on the mapped variances (exactly its
+    numbers at kappa = 1, nu = 0).  grad is NaN where info != 0.  _slip (tests only) injects one mistake: "kappa_linear" (dvar/dkappa
+    = sigma^2 instead of 2 kappa sigma^2), "noise_all_bands" (dvar on every band, not band l alone), "nu_scaled" (nu multiplied by
+    kappa^2 in the variance)."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b,
+                                                                       codes_first=True)
+    kappa, nu, ncode = _noise_setup(L, kappa, nu)
+    code = code or ncode
+    nan = np.full(4 * L + 1, math.nan)
+    if code:
+        return math.nan, nan, code
+    ntrain = _noise_train(train, kappa, nu, _slip)
+    mapped = [e[:5] for e in ntrain]
+    ll, info, _, _, _, _ = _pass(name, mapped, [], alpha, rho, p, n, vb)
+    if info:
+        return math.nan, nan, info
+    grad = np.empty(4 * L + 1)
+    for l in range(L):
+        grad[l] = _grad_pass(name, mapped, alpha, rho, p, n, vb, "alpha", l)
+    grad[L] = _grad_pass(name, mapped, alpha, rho, p, n, vb, "rho")
+    for l in range(L):
+        if name == "OU":
+            first = _grad_pass(name, mapped, alpha, rho, p, n, vb, "tau", l, rank=-1)
+            last = _grad_pass(name, mapped, alpha, rho, p, n, vb, "tau", l, rank=L)
+            grad[L + 1 + l] = 0.5 * (first + last)
+        else:
+            grad[L + 1 + l] = _grad_pass(name, mapped, alpha, rho, p, n, vb, "tau", l)
+    for l in range(L):
+        grad[2 * L + 1 + l] = _noise_pass(name, ntrain, alpha, rho, p, n, vb, "kappa", l, kappa, slip=_slip)
+        grad[3 * L + 1 + l] = _noise_pass(name, ntrain, alpha, rho, p, n, vb, "nu", l, kappa, slip=_slip)
+    return ll, grad, 0
+
+
+def _noise_rows(L, M, x):
+    """kappa or nu of M rows: (M, L), (L,) broadcast, or None for every row."""
+    if x is None:
+        return [None] * M
+    x = np.asarray(x, np.float64)
+    if x.shape == (L,):
+        x = np.broadcast_to(x, (M, L))
+    if x.shape != (M, L):
+        raise ValueError("kappa and nu must be (M, L) = (%d, %d), (L,) or None" % (M, L))
+    return x
+
+
+def loglik_noise_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, kappa=None, nu=None, marginalise_b=True):
+    """loglik_noise over M rows -> (loglik[M], info[M]): Objective.loglik_markov_noise_batch's shape."""
+    L = len(tarray)
+    delays = np.asarray(delays, np.float64).reshape(-1, L)
+    alpha = np.asarray(alpha, np.float64).reshape(-1, L)
+    rho = np.asarray(rho, np.float64).reshape(-1)
+    kappa, nu = _noise_rows(L, len(rho), kappa), _noise_rows(L, len(rho), nu)
+    out = [loglik_noise(kernel, tarray, yarray, stdarray, delays[i], alpha[i], rho[i], kappa[i], nu[i], marginalise_b)
+           for i in range(len(rho))]
+    return np.array([o[0] for o in out]), np.array([o[1] for o in out], dtype=np.int32)
+
+
+def loglik_grad_noise_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, kappa=None, nu=None, marginalise_b=True):
+    """loglik_grad_noise over M rows -> (loglik[M], grad[M, 4L+1], info[M]): Objective.loglik_grad_markov_noise_batch's shape."""
+    L = len(tarray)
+    delays = np.asarray(delays, np.float64).reshape(-1, L)
+    alpha = np.asarray(alpha, np.float64).reshape(-1, L)
+    rho = np.asarray(rho, np.float64).reshape(-1)
+    kappa, nu = _noise_rows(L, len(rho), kappa), _noise_rows(L, len(rho), nu)
+    out = [loglik_grad_noise(kernel, tarray, yarray, stdarray, delays[i], alpha[i], rho[i], kappa[i], nu[i], marginalise_b)
+           for i in range(len(rho))]
+    return (np.array([o[0] for o in out]), np.array([o[1] for o in out]).reshape(-1, 4 * L + 1),
+            np.array([o[2] for o in out], dtype=np.int32))
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
 # The (alpha, rho) block of the Hessian in linear time (csrc/gpcc_markov_hess.hip.h, DESIGN.md 4.18), the same algorithm in numpy: the
 # filter's second-order forward sensitivities.  For a pair (a, b) of theta = (alpha_1..alpha_L, rho) four sets are carried: (m, P),
 # (m_a, P_a), (m_b, P_b), (m_ab, P_ab).  For alpha and rho the merged order is fixed and no kink is crossed: no tie convention.
@@ -1495,6 +1655,7 @@ class MarkovObjective:
         self.data = (tarray, yarray, stdarray)
         self.kernel, self.marginalise_b, self.L = _name(kernel), bool(marginalise_b), len(tarray)
         self.yflat = np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in yarray])
+        self.sflat = np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in stdarray])
 
     def loglik_markov_batch(self, delays, alpha, rho):
         return loglik_batch(self.kernel, *self.data, delays, alpha, rho, self.marginalise_b)
@@ -1513,6 +1674,14 @@ class MarkovObjective:
         """Objective.loglik_markov_resampled's result: (loglik[M], info[M])."""
         mean, vb = resample_arguments(self.data[0], Y, counts, center, sigma_b, self.marginalise_b)
         return loglik_resampled(self.kernel, *self.data, Y, counts, real, delays, alpha, rho, self.marginalise_b, mean=mean, sigma_b=vb)
+
+    def loglik_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
+        """Objective.loglik_markov_noise_batch's result: (loglik[M], info[M])."""
+        return loglik_noise_batch(self.kernel, *self.data, delays, alpha, rho, kappa, nu, self.marginalise_b)
+
+    def loglik_grad_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
+        """Objective.loglik_grad_markov_noise_batch's result: (loglik[M], grad[M, 4L+1], info[M])."""
+        return loglik_grad_noise_batch(self.kernel, *self.data, delays, alpha, rho, kappa, nu, self.marginalise_b)
 
     def loglik_hess_hyper_markov_batch(self, delays, alpha, rho):
         """Objective.loglik_hess_hyper_markov_batch's result: (loglik[M], grad[M, 2L+1], hess[M, L+1, L+1], info[M])."""

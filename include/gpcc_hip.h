@@ -462,6 +462,36 @@ int gpcc_loglik_markov_resampled_batch(gpcc_handle_t h, int M, const double *del
                                        const int *real, int R, const double *Y, const int *count, const double *mean,
                                        const double *sigma_b, double *loglik, int *info);
 
+/* The log-likelihood, and its gradient, of M rows that each carry their own (tau, alpha, rho) AND THEIR OWN NOISE MODEL, in LINEAR
+ * TIME for the Markov kernels (kernels: csrc/gpcc_markov_noise.hip.h).  Point i of band l of row m is observed with
+ * the variance
+ *     v_i = kappa[m][l]^2 sigma_i^2 + nu[m][l]     kappa >= 0: the scale of the reported error bars; nu >= 0: an excess variance, flux^2
+ * kappa = 1, nu = 0 is the model of every other entry; kappa = 0 and one nu for all bands is K + sigma^2 I + B of the reference's
+ * src/UNUSED/gpccfixdelay_globalnoiseterm.jl:137-147, which fits that sigma^2 as one more Nelder-Mead parameter.  The band means and
+ * Sigma_b depend on y only and stay the handle's.
+ *   kappa, nu: M x L row-major each; NULL: all 1 (kappa), all 0 (nu).  loglik, info: M entries.
+ *   grad: M rows of 4L+1 doubles [d/d alpha_1..L, d/d rho, d/d tau_1..L, d/d kappa_1..L, d/d nu_1..L]; the first 2L+1 follow
+ *   gpcc_loglik_grad_markov_batch's conventions (OU at a tie: the mean of the one-sided derivatives); a row is NaN where info != 0.
+ * SEMANTICS.  loglik[m] is the value gpcc_loglik_markov_batch returns on a fresh handle created with the error bars
+ * sqrt(kappa_l^2 sigma_i^2 + nu_l); only the order of rounding differs.  With kappa = 1, nu = 0 (or both NULL) loglik and info are
+ * BITWISE gpcc_loglik_markov_batch's: kappa^2 sigma^2 + nu is one fma, which returns sigma^2 exactly.
+ * info[m]: gpcc_loglik_markov_batch's codes and, after them in precedence (-1: some alpha <= 0, -2: rho <= 0), -3: some kappa or nu of
+ * the row is negative or not finite -- loglik NaN, the gradient row NaN, no other row touched.  A positive j keeps its meaning (with
+ * kappa = 0, nu = 0 a band has no noise at all, and two points that tie in shifted time give the position of the second).
+ * Refusals: gpcc_loglik_markov_batch's (GPCC_ERR_UNSUPPORTED: rbf; marginalise_b with L > 4).  M = 0 returns 0.
+ * Path: one lane per row (value), one lane per (row, slot) (gradient: L alpha, one rho, L tau (OU: 2L), L kappa, L nu slots, then a
+ * small kernel that writes the rows); a lane's kappa^2 and nu sit in LDS beside its cursors, 44 L bytes a lane instead of 28 L, and
+ * the light curves are staged in LDS while they fit beside that.  The gradient's value and info come from the value kernel inside
+ * the same call.  No atomics: a row's bits depend on that row alone, whatever M, the row order, the launch shape and the options.
+ * Memory: gpcc_loglik_markov_batch's, plus 16 M L bytes for kappa and nu and, for the gradient, 8 M bytes per slot and 8 M (4L + 1)
+ * bytes, grown on demand; none of the N^2 workspace.  "markov_count" advances by M.  Always fp64 (an fp32 handle on its fp64 twin);
+ * a multi-device handle computes on device_ids[0].  Predictions, held-out scores, Hessians and draws under a fitted noise model: a
+ * fresh handle on those error bars.  Blocking. */
+int gpcc_loglik_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                   const double *kappa, const double *nu, double *loglik, int *info);
+int gpcc_loglik_grad_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                        const double *kappa, const double *nu, double *loglik, double *grad, int *info);
+
 /* Same with DEVICE pointers, enqueued behind `stream` (a hipStream_t, NULL = default stream) and
  * joined back into it: asynchronous, outputs valid once `stream` has drained. */
 int gpcc_loglik_batch_device(gpcc_handle_t handle, int M, const double *d_delays,

@@ -192,6 +192,40 @@ function loglik_grad_markov(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Fl
     return ll, grad, info
 end
 
+"loglik_markov_batch of M rows that each carry their own NOISE MODEL (gpcc_loglik_noise_markov_batch, DESIGN 4.25; OU, matern32,
+matern52): point i of band l of row m has the variance kappa[l, m]^2 σ_i^2 + nu[l, m] -> (ll[M], info[M]).  kappa, nu: L×M, or nothing
+(all 1 / all 0: then ll and info are bitwise loglik_markov_batch's).  ll[m] is the value of a fresh handle on the error bars
+sqrt(kappa^2 σ^2 + nu); kappa = 0 with one nu for all bands is K + σ²I + B of src/UNUSED/gpccfixdelay_globalnoiseterm.jl:137-147.
+info = -3 (after -1, -2): a kappa or nu of the row is negative or not finite."
+function loglik_markov_noise(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64},
+                             kappa::Union{Nothing,Matrix{Float64}} = nothing, nu::Union{Nothing,Matrix{Float64}} = nothing)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    @assert (kappa === nothing || size(kappa) == (h.L, M)) && (nu === nothing || size(nu) == (h.L, M))
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    rc = ccall((:gpcc_loglik_noise_markov_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, kappa === nothing ? C_NULL : kappa, nu === nothing ? C_NULL : nu, ll, info)
+    rc == 0 || error("gpcc_loglik_noise_markov_batch: " * lasterror(h.ptr))
+    return ll, info
+end
+
+"loglik_markov_noise and its gradient (gpcc_loglik_grad_noise_markov_batch): (ll[M], grad (4L+1)×M, info[M]), a column of grad being
+[α_1..α_L, ρ, τ_1..τ_L, kappa_1..kappa_L, nu_1..nu_L]; NaN where info != 0."
+function loglik_grad_markov_noise(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64},
+                                  kappa::Union{Nothing,Matrix{Float64}} = nothing, nu::Union{Nothing,Matrix{Float64}} = nothing)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    @assert (kappa === nothing || size(kappa) == (h.L, M)) && (nu === nothing || size(nu) == (h.L, M))
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    grad = Matrix{Float64}(undef, 4h.L + 1, M)                            # column-major (4L+1)×M == row-major M×(4L+1)
+    rc = ccall((:gpcc_loglik_grad_noise_markov_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, kappa === nothing ? C_NULL : kappa, nu === nothing ? C_NULL : nu, ll, grad, info)
+    rc == 0 || error("gpcc_loglik_grad_noise_markov_batch: " * lasterror(h.ptr))
+    return ll, grad, info
+end
+
 "objective, gradient, Hessian and expected (Fisher) information for M triples: (ll[M], grad (2L+1)×M, hess and fisher
 (2L+1)×(2L+1)×M, info[M]) in [α_1..α_L, ρ, τ_1..τ_L] order, symmetric blocks, NaN where info != 0; fisher = 1/2 tr(K⁻¹D_iK⁻¹D_j)."
 function loglik_hess_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
