@@ -16,7 +16,9 @@ to the posterior variance by subtraction, so every predictive variance S = alpha
 the fp64 transition matrix, eps alpha^2, i.e. up to eps alpha^2 / sigma^2 relative, accumulated over the N steps; the sum of
 (log S + eps_i^2 / S) / 2, whose second part is about |loglik|, moves by up to 2 N eps alpha^2 / sigma^2 |loglik|.  (The same filter
 run in extended precision on the fp64 transition matrices shows the same error: it is the rounding of A, not of the recursion.  Seen
-at rho = 300, where neighbouring points are correlated to 1 - 1e-7.)"""
+at rho = 300, where neighbouring points are correlated to 1 - 1e-7.)
+
+Not covered here -- lambda x lag below 1e-3, rho above 300, four and eight bands, three bands tied on one time: tests/_markov_regime_cases.py."""
 import itertools
 
 import numpy as np
