@@ -8,5 +8,5 @@ from ._capi import GpccError  # noqa: F401
 from .api import (KERNELS, OU, Kernel, Objective, PosDefException, build_info, delayedCovariance,  # noqa: F401
                   getprobabilities, matern32, matern52, mvnormal_logpdf, rbf, selftest)
 from .distributed import shard_bounds, sharded_grid_fit, sharded_loglik  # noqa: F401
-from .fit import (CVGrid, DelayAveragedPredictor, GridFit, LooScores, NoiseGridFit, Predictor, RealisationDelays, RealisationRefits, cvindices, delay_covariance, gpcc, gpcc_grid,  # noqa: F401,E402
-                  effective_std, gpcc_grid_noise, laplace_covariance, performcv, performcv_grid, realisation_delays, realisation_refits, singlegp, uniformpriordelay, unpack_grad, unpack_hessian)
+from .fit import (CVGrid, DelayAveragedPredictor, GridFit, LooScores, NoiseEvidence, NoiseGridFit, Predictor, RealisationDelays, RealisationRefits, cvindices, delay_covariance, gpcc, gpcc_grid,  # noqa: F401,E402
+                  effective_std, gpcc_grid_noise, laplace_covariance, noise_evidence, performcv, performcv_grid, realisation_delays, realisation_refits, singlegp, uniformpriordelay, unpack_grad, unpack_hessian)

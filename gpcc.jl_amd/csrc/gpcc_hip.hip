@@ -19,6 +19,7 @@
 #include "gpcc_markov_multi.hip.h"
 #include "gpcc_markov_resample.hip.h"
 #include "gpcc_markov_noise.hip.h"
+#include "gpcc_markov_noise_hess.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -288,6 +289,10 @@ struct gpcc_handle_s {
     // kappa | nu (2 M L doubles), the per-slot results [slots][M] and the rows [M][4L + 1], grown on demand
     double *d_mknp = nullptr, *d_mkns = nullptr, *d_mkng = nullptr;
     long mknp_cap = 0, mkns_cap = 0, mkng_cap = 0;
+    // linear-time Hessian under a per-row noise model (gpcc_loglik_hess_noise_markov_batch): the per-pair results [pair slots][M] and the
+    // blocks [M][(3L + 1)^2], grown on demand
+    double *d_mknhs = nullptr, *d_mknhb = nullptr;
+    long mknhs_cap = 0, mknhb_cap = 0;
     long markov_resample_bytes_max = (long)512 << 20;   // option "markov_resample_bytes_max": the most the packed pairs of one call may take
     int laplace_markov = 0;              // option "laplace_markov": gpcc_laplace_evidence's rounds are gpcc_loglik_hess_hyper_markov_batch calls
     int markov_chunk_rows = 0;           // option "markov_chunk_rows": rows per chunk of gpcc_predict_markov_batch (0: by the scratch budget)
@@ -607,6 +612,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_mkfs); hipFree(h->d_mkfb);
     hipFree(h->d_mkmy); hipFree(h->d_mkmr); hipFree(h->d_mkmm); hipFree(h->d_mkmo); hipFree(h->d_mkmp);
     hipFree(h->d_mknp); hipFree(h->d_mkns); hipFree(h->d_mkng);
+    hipFree(h->d_mknhs); hipFree(h->d_mknhb);
     hipFree(h->d_mkrv); hipFree(h->d_mkry); hipFree(h->d_mkrm); hipFree(h->d_mkrc); hipFree(h->d_mkrr); hipFree(h->d_mkrp);
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
     hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
@@ -2191,7 +2197,7 @@ static void markov_fill_args(gpcc_handle_t h, int M, const double *dd, const dou
 }
 
 // the kernels with dynamic LDS, for gpcc_handle::mk_lds_raised
-enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI, MK_RESAMPLE, MK_NOISE, MK_NOISE_GRAD };
+enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI, MK_RESAMPLE, MK_NOISE, MK_NOISE_GRAD, MK_NOISE_HESS };
 
 // The launch of every kernel of the filter, `name` in messages: one lane per row, `rows` rows along x and ny lanes per row along y.
 // The shape: one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy beyond; the light
@@ -2923,6 +2929,33 @@ extern "C" int gpcc_loglik_noise_markov_batch(gpcc_handle_t h, int M, const doub
     return 0;
 }
 
+// the gradient's buffers for M rows under a noise model, and its launches over the M staged rows: the rows' kappa | nu staged,
+// gpcc_markov_noise_eval (loglik and info left in d_out / d_oinfo), gpcc_markov_noise_grad and its finish kernel, the rows copied to
+// `grad` behind them.  gpcc_loglik_hess_noise_markov_batch shares both, so its value, info and gradient are this entry's bitwise
+static int markov_noise_grad_grow(gpcc_handle_t h, int M)
+{
+    const int L = h->L, slots = gpcc_markov_noise_slots(L, markov_dims(h).p == 1);
+    int g = grow_buf(h, &h->d_mknp, &h->mknp_cap, 2L * M * L);
+    if (!g) g = grow_buf(h, &h->d_mkns, &h->mkns_cap, (long)slots * M);
+    if (!g) g = grow_buf(h, &h->d_mkng, &h->mkng_cap, (long)(4 * L + 1) * M);
+    return g;
+}
+
+static int markov_noise_grad_enqueue(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, const double *kappa,
+                                     const double *nu, double *grad, GpccMarkovNoiseArgs &a)
+{
+    const int L = h->L, W = 4 * L + 1, slots = gpcc_markov_noise_slots(L, markov_dims(h).p == 1);
+    int rc = markov_noise_stage(h, M, kappa, nu, a);
+    if (rc) return rc;
+    rc = markov_noise_eval_launch(h, M, dd, da, dr, a);
+    if (rc) return rc;
+    rc = markov_slots_launch(h, "gpcc_markov_noise_grad", MK_NOISE_GRAD, M, dd, da, dr, slots, a, markov_noise_lds(h),
+                             gpcc_markov_noise_grad_launch);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(grad, h->d_mkng, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
+    return 0;
+}
+
 extern "C" int gpcc_loglik_grad_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                                    const double *kappa, const double *nu, double *loglik, double *grad, int *info)
 {
@@ -2939,24 +2972,68 @@ extern "C" int gpcc_loglik_grad_noise_markov_batch(gpcc_handle_t h, int M, const
         }))
         return rc;
     GPCC_ON_DEVICE(h, h->device);
-    const int L = h->L, W = 4 * L + 1, slots = gpcc_markov_noise_slots(L, markov_dims(h).p == 1);
+    double *dd, *da, *dr;
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] { return markov_noise_grad_grow(h, M); });
+    if (rc) return rc;
+    GpccMarkovNoiseArgs a;
+    rc = markov_noise_grad_enqueue(h, M, dd, da, dr, kappa, nu, grad, a);
+    if (rc) return rc;
+    rc = markov_finish(h, M, loglik, info);
+    if (rc) return rc;
+    h->markov_count += M;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The linear-time Hessian of rows with their own noise model over [alpha_1..L, rho, kappa_1..L, nu_1..L]
+// (gpcc_loglik_hess_noise_markov_batch; kernel: gpcc_markov_noise_hess.hip.h): the filter's second-order forward
+// sensitivities with variance tangents, one lane per (row, pair slot).  Value, info and gradient come from the noise gradient entry's
+// launches inside the same call (bitwise gpcc_loglik_grad_noise_markov_batch's by construction); it needs what that entry needs plus
+// the pair slots and the blocks, nothing of the N^2 workspace.
+// ------------------------------------------------------------------------------------------
+extern "C" int gpcc_loglik_hess_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                                   const double *kappa, const double *nu, double *loglik, double *grad, double *hess,
+                                                   int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (M == 0) return 0;
+    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    const char *dense = "gpcc_loglik_hess_hyper_batch on a handle created with the error bars sqrt(kappa^2 sigma^2 + nu) (effective_std)";
+    int rc = markov_refusals(h, "gpcc_loglik_hess_noise_markov_batch", dense);
+    if (!rc) rc = markov_noise_ships(h, "gpcc_loglik_hess_noise_markov_batch", dense);
+    if (rc) return rc;
+    {
+        const MarkovDims d = markov_dims(primary(h));
+        if (!gpcc_mk_ships<GpccMkShipsNoiseHess>(d.p, d.noff))
+            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_hess_noise_markov_batch: the instantiation <%d, %d> (states of the process, "
+                        "offset states) needs scratch memory and does not ship; use %s", d.p, d.noff, dense);
+    }
+    if (route_fp64(h, "linear-time Hessian under a noise model", rc, [&](gpcc_handle_t o) {
+            return gpcc_loglik_hess_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, loglik, grad, hess, info);
+        }))
+        return rc;
+    GPCC_ON_DEVICE(h, h->device);
+    const int L = h->L, n = 3 * L + 1, slots = gpcc_markov_noise_hess_slots(L);
     double *dd, *da, *dr;
     rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
-        int g = grow_buf(h, &h->d_mknp, &h->mknp_cap, 2L * M * L);
-        if (!g) g = grow_buf(h, &h->d_mkns, &h->mkns_cap, (long)slots * M);
-        if (!g) g = grow_buf(h, &h->d_mkng, &h->mkng_cap, (long)W * M);
+        int g = markov_noise_grad_grow(h, M);
+        if (!g && hess) g = grow_buf(h, &h->d_mknhs, &h->mknhs_cap, (long)slots * M);
+        if (!g && hess) g = grow_buf(h, &h->d_mknhb, &h->mknhb_cap, (long)n * n * M);
         return g;
     });
     if (rc) return rc;
     GpccMarkovNoiseArgs a;
-    rc = markov_noise_stage(h, M, kappa, nu, a);
+    rc = markov_noise_grad_enqueue(h, M, dd, da, dr, kappa, nu, grad, a);
     if (rc) return rc;
-    rc = markov_noise_eval_launch(h, M, dd, da, dr, a);
-    if (rc) return rc;
-    rc = markov_slots_launch(h, "gpcc_markov_noise_grad", MK_NOISE_GRAD, M, dd, da, dr, slots, a, markov_noise_lds(h),
-                             gpcc_markov_noise_grad_launch);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(grad, h->d_mkng, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
+    if (hess) {
+        GpccMarkovNoiseHessArgs b;
+        b.kappa = a.kappa; b.nu = a.nu; b.slot = h->d_mknhs; b.hess = h->d_mknhb;
+        rc = markov_slots_launch(h, "gpcc_markov_noise_hess", MK_NOISE_HESS, M, dd, da, dr, slots, b, markov_noise_lds(h),
+                                 gpcc_markov_noise_hess_launch);
+        if (rc) return rc;
+        HIPCHK(h, hipMemcpyAsync(hess, h->d_mknhb, sizeof(double) * n * n * M, hipMemcpyDeviceToHost, h->main_stream));
+    }
     rc = markov_finish(h, M, loglik, info);
     if (rc) return rc;
     h->markov_count += M;

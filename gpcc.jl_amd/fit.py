@@ -494,6 +494,29 @@ def gpcc_grid_noise(objective, candidatedelays, *, iterations, noise="both", sha
                         nm.rounds + extra_rounds, f_start)
 
 
+class NoiseEvidence(collections.namedtuple("NoiseEvidence", "loglik alpha rho kappa nu log_evidence cov info rounds pinned")):
+    """noise_evidence's result: the mode at every delay (loglik[G], alpha[G, L], rho[G], kappa[G, L], nu[G, L]), log_evidence[G] up to
+    one constant shared by all delays, cov[G, n, n] in the variables u of laplace.laplace_evidence_noise, info[G] (0, or laplace's
+    codes), rounds[G] and pinned[G, n]: the one-sided variables (kappa, w) that ended on a bound with the gradient pointing out."""
+
+
+def noise_evidence(objective, candidatedelays, noisefit, *, noise="both", shared=False, kappa=1.0, nu=0.0, rhomin=0.1, rhomax=20.0,
+                   max_rounds=50, g_tol=1e-6, **bounds):
+    """The Laplace-marginalised evidence over (alpha, rho, kappa, nu) at every row of candidatedelays, started at a NoiseGridFit
+    (gpcc_grid_noise's result, with the same noise, shared, kappa, nu, rhomin and rhomax) -> NoiseEvidence: laplace.laplace_evidence_noise
+    with the fit as the start.  getprobabilities(result.log_evidence) is the delay posterior with the hyper-parameters AND the noise
+    model integrated out, where the fit's profile likelihood only maximises over them.  objective: an Objective (the rounds are
+    gpcc_loglik_hess_noise_markov_batch calls) or a markov.MarkovObjective (no GPU).  The part of the noise model that is not fitted
+    stays at `kappa` / `nu`.  bounds: kappamin, kappamax, wmin, wmax of laplace_evidence_noise."""
+    cand = np.ascontiguousarray(np.asarray(candidatedelays, np.float64).reshape(len(candidatedelays), -1))
+    G, L = cand.shape
+    kap0 = np.asarray(noisefit.kappa, np.float64).reshape(G, L) if noise != "excess" else np.broadcast_to(np.asarray(kappa, np.float64), (G, L))
+    exc0 = np.asarray(noisefit.nu, np.float64).reshape(G, L) if noise != "scale" else np.broadcast_to(np.asarray(nu, np.float64), (G, L))
+    return NoiseEvidence(*laplace.laplace_evidence_noise(objective, cand, noisefit.alpha, noisefit.rho, kap0, exc0, noise=noise,
+                                                         shared=shared, rhomin=rhomin, rhomax=rhomax, max_rounds=max_rounds,
+                                                         g_tol=g_tol, **bounds))
+
+
 def _with_evidence(res, obj, cand, engine, evidence, rhomin, rhomax, max_rounds, g_tol, solver="dense"):
     if evidence is None:
         return res

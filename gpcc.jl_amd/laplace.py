@@ -91,9 +91,17 @@ def hyper_to_u(theta, gt, Ht):
 
 class BatchedNewton:
     """Maximise l for P problems of dimension n.  fbatch(pidx, U) -> (val[K], grad[K, n], hess[K, n, n]) for the rows of U (K, n),
-    row i belonging to problem pidx[i]; a non-finite value = rejected point.  lo, hi: the box (n each, None = unbounded)."""
+    row i belonging to problem pidx[i]; a non-finite value = rejected point.  lo, hi: the box (n each, None = unbounded).
 
-    def __init__(self, u0, fbatch, max_rounds=50, g_tol=1e-6, lo=None, hi=None):
+    one_sided: indices of variables that may END on a bound.  A variable that finishes fixed at a bound with the gradient pointing out
+    (|g_k| > g_tol) makes the problem ON_BOUND; a one-sided one is PINNED instead: it is left out of -H and of the 1/2 log 2 pi count
+    and contributes -log|g_k|, the leading-order boundary Laplace term (the integral of exp(-|g_k| x) over x >= 0), so that
+        log Z = f + (n_free / 2) log 2 pi - 1/2 log det(-H_free) - sum over the pinned k of log|g_k|,
+    info stays 0, `pinned` [P][n] says which, and cov holds the inverse of -H_free with zero rows and columns for the pinned variables.
+    Evidences with different pinned sets are comparable only to the order of that approximation.  With the empty default every step
+    and every result is what it was."""
+
+    def __init__(self, u0, fbatch, max_rounds=50, g_tol=1e-6, lo=None, hi=None, one_sided=()):
         self.u0 = np.array(u0, dtype=np.float64)
         self.P, self.n = self.u0.shape
         self.fbatch = fbatch
@@ -103,6 +111,8 @@ class BatchedNewton:
         self.f_calls = 0
         self.batches = 0
         self.trace = []   # (pidx list, U rows) of every batch, in order
+        self.one_sided = frozenset(int(k) for k in one_sided)
+        self.pinned = [[False] * self.n for _ in range(self.P)]
 
     def _fixed(self, p, k):
         uk, gk = self.u[p][k], self.g[p][k]
@@ -138,8 +148,45 @@ class BatchedNewton:
             lam = 1e-3 * s if lam == 0.0 else lam * 10.0
         return None
 
+    def _finish_pinned(self, p, pin):
+        """_finish(p, 0) with the one-sided variables `pin` fixed at a bound with an outward gradient."""
+        n = self.n
+        free = [k for k in range(n) if k not in pin]
+        m = len(free)
+        A = [-self.H[p][i * n + j] for i in free for j in free]
+        Lc = chol(m, A)
+        cov = [0.0 if Lc is not None else float("nan")] * (n * n)
+        if Lc is not None:
+            ci = chol_inverse(m, Lc)
+            for a, i in enumerate(free):
+                for b, j in enumerate(free):
+                    cov[i * n + j] = ci[a * m + b]
+        self.cov[p] = cov
+        code = 0
+        for k in free:
+            if self._fixed(p, k) and abs(self.g[p][k]) > self.g_tol:
+                code = ON_BOUND
+        if code == 0 and Lc is None:
+            code = NOT_MAXIMUM
+        self.info[p] = code
+        if code == 0:
+            hl = 0.0
+            for k in range(m):
+                hl = hl + math.log(Lc[k * m + k])
+            for k in pin:
+                hl = hl + math.log(abs(self.g[p][k]))
+                self.pinned[p][k] = True
+            self.logz[p] = self.f[p] + 0.5 * float(m) * LOG2PI - hl
+        else:
+            self.logz[p] = float("nan")
+
     def _finish(self, p, code):
         n = self.n
+        if code == 0 and self.one_sided:
+            pin = [k for k in sorted(self.one_sided) if self._fixed(p, k) and abs(self.g[p][k]) > self.g_tol]
+            if pin:
+                self._finish_pinned(p, pin)
+                return
         A = [-v for v in self.H[p]]
         Lc = chol(n, A)
         self.cov[p] = chol_inverse(n, Lc) if Lc is not None else [float("nan")] * (n * n)
@@ -281,3 +328,109 @@ def laplace_evidence(objective, delays, alpha0, rho0, rhomin=0.1, rhomax=20.0, m
     rho = np.array([math.exp(float(u[g, L])) for g in range(G)])
     info = np.where((info == BAD_START) & (start_info != 0), start_info, info).astype(np.int32)
     return f, alpha, rho, logz, cov, info, rounds
+
+
+NOISE_KINDS = ("scale", "excess", "both")
+
+
+def noise_variables(L, ms2, noise="both", shared=False):
+    """The variables of laplace_evidence_noise and their map to theta = [alpha_1..L, rho, kappa_1..L, nu_1..L]: (nk, nv, J) with nk
+    kappa variables and nv variables w (nu_l = w mean(sigma_l^2)), and J [3L+1, n] the constant Jacobian d theta / d x of
+    x = [alpha, rho, kappa variables, w variables]: rows and columns of the block are selected by it, summed where a variable is
+    shared, and the rows of nu scaled by mean(sigma_l^2)."""
+    if noise not in NOISE_KINDS:
+        raise ValueError('noise must be "scale", "excess" or "both", got %r' % (noise,))
+    nk = 0 if noise == "excess" else (1 if shared else L)
+    nv = 0 if noise == "scale" else (1 if shared else L)
+    n = L + 1 + nk + nv
+    J = np.zeros((3 * L + 1, n))
+    for i in range(L + 1):
+        J[i, i] = 1.0
+    for l in range(L):
+        if nk:
+            J[L + 1 + l, L + 1 + (0 if shared else l)] = 1.0
+        if nv:
+            J[2 * L + 1 + l, L + 1 + nk + (0 if shared else l)] = float(ms2[l])
+    return nk, nv, J
+
+
+def noise_to_x(J, grad_row, hess):
+    """(g_x, H_x) of one row: grad_row the entry's [alpha, rho, tau, kappa, nu] row (4L+1), hess its (3L+1)^2 block."""
+    L = (J.shape[0] - 1) // 3
+    gt = np.concatenate([np.asarray(grad_row, np.float64)[:L + 1], np.asarray(grad_row, np.float64)[2 * L + 1:]])
+    return J.T @ gt, J.T @ np.asarray(hess, np.float64) @ J
+
+
+def band_mean_sigma2(objective):
+    """mean(sigma_l^2) per band of an Objective or a markov.MarkovObjective: the unit of gpcc_grid_noise's dimensionless w."""
+    edges = np.concatenate([[0], np.cumsum(objective.Nl if hasattr(objective, "Nl") else [len(t) for t in objective.data[0]])])
+    return np.array([np.mean(objective.sflat[edges[l]:edges[l + 1]] ** 2) for l in range(len(edges) - 1)])
+
+
+def laplace_evidence_noise(objective, delays, alpha0, rho0, kappa0, nu0, *, noise="both", shared=False, rhomin=0.1, rhomax=20.0,
+                           kappamin=0.1, kappamax=10.0, wmin=1e-4, wmax=1e2, max_rounds=50, g_tol=1e-6):
+    """The Laplace-marginalised evidence at every delay under a FITTED NOISE MODEL v_i = kappa_l^2 sigma_i^2 + nu_l: the
+    lock-step damped Newton polish of laplace_evidence over objective.loglik_hess_markov_noise_batch (an Objective's, in linear time on
+    the device, or a markov.MarkovObjective's, without a GPU) -> (loglik, alpha, rho, kappa, nu, log_evidence, cov, info, rounds, pinned).
+
+    Variables u: log alpha_l, log rho, log kappa (L of them, or one when shared) and log w with nu_l = w mean(sigma_l^2) (L, or one when
+    shared), gpcc_grid_noise's dimensionless variable.  noise: "scale" fits kappa, "excess" fits w, "both" both; the part that is not
+    fitted stays at kappa0 / nu0 and has no variable.  alpha0 [G, L], rho0 [G], kappa0, nu0 [G, L] (or (L,)): the start, usually a
+    NoiseGridFit; with shared=True band 1's kappa0 and nu0 / mean(sigma^2) start the shared variable.  The chain rule is on the host:
+    rows and columns of the entry's (3L+1)^2 block are selected (summed for a shared variable), then theta = exp(u) as in hyper_to_u.
+
+    Prior: flat in u -- alpha and rho as laplace_evidence, kappa on [kappamin, kappamax], w on [wmin, wmax]; the constant is shared by
+    all delays, so only differences of log_evidence mean anything.
+
+    ONE-SIDED VARIABLES.  Clean data puts w at its lower bound with the gradient pointing out.  kappa and w are one-sided
+    (BatchedNewton): such a variable is pinned -- left out of -H and of the 1/2 log 2 pi count, contributing -log|g_k| instead, the
+    leading-order boundary Laplace term -- info stays 0 and pinned[G, n] says which.  Evidences of delays with different pinned sets
+    are comparable only to the order of that approximation.  alpha and rho keep ON_BOUND.  cov [G, n, n] is the covariance in u, with
+    zero rows and columns for the pinned variables."""
+    delays = np.ascontiguousarray(np.atleast_2d(delays), dtype=np.float64)
+    G, L = delays.shape
+    ms2 = band_mean_sigma2(objective)
+    nk, nv, J = noise_variables(L, ms2, noise, shared)
+    n = L + 1 + nk + nv
+    alpha0 = np.asarray(alpha0, dtype=np.float64).reshape(G, L)
+    rho0 = np.asarray(rho0, dtype=np.float64).reshape(G)
+    kappa0 = np.broadcast_to(np.asarray(kappa0, dtype=np.float64), (G, L))
+    nu0 = np.broadcast_to(np.asarray(nu0, dtype=np.float64), (G, L))
+    lo = [-INF] * L + [math.log(rhomin)] + [math.log(kappamin)] * nk + [math.log(wmin)] * nv
+    hi = [INF] * L + [math.log(rhomax)] + [math.log(kappamax)] * nk + [math.log(wmax)] * nv
+
+    def safe_log(v, floor):
+        return math.log(max(float(v), floor))
+
+    u0 = np.array([[math.log(float(alpha0[g, l])) for l in range(L)] + [math.log(float(rho0[g]))]
+                   + [safe_log(kappa0[g, l], kappamin) for l in range(nk)]
+                   + [safe_log(nu0[g, l] / ms2[l], wmin) for l in range(nv)] for g in range(G)])
+    start_info = np.zeros(G, dtype=np.int32)
+    first = [True]
+
+    def unpack(U, rows):
+        K = len(U)
+        x = np.array([[math.exp(float(U[i, k])) for k in range(n)] for i in range(K)]).reshape(K, n)
+        kap = np.array(kappa0[rows]) if not nk else np.broadcast_to(x[:, L + 1:L + 1 + nk], (K, L)).copy()
+        exc = np.array(nu0[rows]) if not nv else np.broadcast_to(x[:, L + 1 + nk:], (K, L)) * ms2
+        return x, x[:, :L].copy(), x[:, L].copy(), kap, exc
+
+    def fb(pidx, U):
+        x, a, r, kap, exc = unpack(U, pidx)
+        ll, grad, hess, info = objective.loglik_hess_markov_noise_batch(delays[pidx], a, r, kap, exc)
+        if first[0]:
+            start_info[pidx] = info
+            first[0] = False
+        val = np.where(info == 0, ll, np.nan)
+        gu = np.empty((len(pidx), n))
+        Hu = np.empty((len(pidx), n, n))
+        for i in range(len(pidx)):
+            gx, Hx = noise_to_x(J, grad[i], hess[i])
+            gu[i], Hu[i] = hyper_to_u(x[i], gx, Hx)
+        return val, gu, Hu
+
+    nt = BatchedNewton(u0, fb, max_rounds=max_rounds, g_tol=g_tol, lo=lo, hi=hi, one_sided=range(L + 1, n))
+    u, f, logz, cov, info, rounds = nt.run()
+    _, alpha, rho, kappa, nu = unpack(u, np.arange(G))
+    info = np.where((info == BAD_START) & (start_info != 0), start_info, info).astype(np.int32)
+    return f, alpha, rho, kappa, nu, logz, cov, info, rounds, np.array(nt.pinned, dtype=bool).reshape(G, n)

@@ -920,6 +920,149 @@ def loglik_hess_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marg
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
+# The Hessian under a noise model per row (csrc/gpcc_markov_noise_hess.hip.h, gpcc_loglik_hess_noise_markov_batch), the
+# same algorithm in numpy, over theta = [alpha_1..alpha_L, rho, kappa_1..kappa_L, nu_1..nu_L], n = 3L + 1.  A pair of alpha and rho is
+# _hess_pass on the mapped variances.  A pair with a noise parameter (_noise_hess_pass) is _hess_pass's recursion with _noise_pass's
+# tangent in it: for kappa_l or nu_l the prior's, the transition's and the stationary tangent are zero and there is no h-tangent; at an
+# observation of band l the variance moves by dvar = 2 kappa_l sigma_i^2 (kappa) or 1 (nu), and by d2var = 2 sigma_i^2 on the pair
+# (kappa_l, kappa_l) alone:  S_a += dvar_a,  S_b += dvar_b,  S_ab += d2var,  and everything behind S, S_a, S_b, S_ab is _hess_pass's.
+# A (rho, noise) pair forms A_rho and Pinf_rho only; a noise noise pair on two bands is not zero: the filter couples the bands.
+# ----------------------------------------------------------------------------------------------------------------------------------
+def _noise_hess_pass(name, ntrain, alpha, rho, p, n, vb, a, b, kappa, slip=None):
+    """d2 loglik / d theta_a d theta_b for a <= b in 0..3L with b a noise parameter (b > L), over _noise_train's observations in
+    merge_order()'s order.  slip: loglik_hess_noise()'s."""
+    L = len(alpha)
+    ev = sorted(ntrain, key=lambda e: e[:3])
+    ra = a == L
+    na = a > L
+
+    def noise(q):       # (band, is_nu) of a noise index
+        return ((q - L - 1) % L, q > 2 * L)
+
+    (banda, nua) = noise(a) if na else (a if a < L else -1, False)
+    bandb, nub = noise(b)
+    zero = np.zeros((p, p))
+    Pinf = stationary(name, rho)
+    Qa = stationary_drho(name, rho) if ra else zero
+    P = _prior(name, rho, p, n, vb)
+    Pa, Pb, Pab = np.zeros((n, n)), np.zeros((n, n)), np.zeros((n, n))
+    Pa[:p, :p] = Qa
+    m, ma, mb, mab = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
+    kfac = 1.0 if slip == "kappa_linear" else 2.0
+    hll, sprev = 0.0, None
+    for (s, band, _, r, v, s2) in ev:
+        d = 0.0 if sprev is None else s - sprev
+        sprev = s
+        A = transition(name, d, rho)
+        Aa = transition_drho(name, d, rho) if (ra and slip != "rho_noise_no_dA") else zero
+        X = slice(0, p)
+        D, Da, Db, Dab = P[X, X] - Pinf, Pa[X, X] - Qa, Pb[X, X], Pab[X, X]
+        # A_b = 0, A_ab = 0, Pinf_b = Pinf_ab = 0: _hess_pass's step without those terms
+        mab[X] = Aa @ mb[X] + A @ mab[X]
+        Pab[X, X] = Aa @ Db @ A.T + A @ Db @ Aa.T + A @ Dab @ A.T
+        Pab[X, p:] = Aa @ Pb[X, p:] + A @ Pab[X, p:]
+        Pab[p:, X] = Pab[X, p:].T
+        ma[X], mb[X] = Aa @ m[X] + A @ ma[X], A @ mb[X]
+        Pa[X, X] = Aa @ D @ A.T + A @ Da @ A.T + A @ D @ Aa.T + Qa
+        Pb[X, X] = A @ Db @ A.T
+        Pa[X, p:], Pb[X, p:] = Aa @ P[X, p:] + A @ Pa[X, p:], A @ Pb[X, p:]
+        Pa[p:, X], Pb[p:, X] = Pa[X, p:].T, Pb[X, p:].T
+        m[X] = A @ m[X]
+        P[X, X] = A @ D @ A.T + Pinf
+        P[X, p:] = A @ P[X, p:]
+        P[p:, X] = P[X, p:].T
+
+        h, ha = np.zeros(n), np.zeros(n)
+        h[0] = alpha[band]
+        if n > p:
+            h[p + band] = 1.0
+        ha[0] = float(a < L and band == a)
+        dva = 0.0
+        if na and band == banda:
+            dva = 1.0 if nua else kfac * kappa[banda] * s2
+        dvb = 0.0
+        if band == bandb:
+            dvb = 1.0 if nub else kfac * kappa[bandb] * s2
+        d2v = 2.0 * s2 if (a == b and not nub and band == bandb and slip != "no_d2kappa") else 0.0
+        Ph = P @ h
+        Pha, Phb = Pa @ h + P @ ha, Pb @ h
+        Phab = Pab @ h + Pb @ ha
+        S = h @ Ph + v
+        if not (S > 0.0 and math.isfinite(S)):
+            return math.nan
+        Sa, Sb = ha @ Ph + h @ Pha + dva, h @ Phb + dvb
+        Sab = h @ Phab + ha @ Phb + d2v
+        eps = r - h @ m
+        ea, eb = -(ha @ m) - h @ ma, -(h @ mb)
+        eab = -(h @ mab) - ha @ mb
+        inv = 1.0 / S
+        g = eps * inv
+        ga, gb = (ea - g * Sa) * inv, (eb - g * Sb) * inv
+        gab = (eab - ga * Sb - gb * Sa - g * Sab) * inv
+        SaSb = (Sa - dva) * (Sb - dvb) if slip == "dvar_one_side" else Sa * Sb      # the S_a S_b cross terms of the second tangent
+        hll -= 0.5 * (Sab * inv - SaSb * inv * inv + 2.0 * ea * eb * inv + 2.0 * g * eab - 2.0 * g * inv * (ea * Sb + eb * Sa)
+                      - g * g * Sab + 2.0 * g * g * SaSb * inv)
+        k = Ph * inv
+        ka, kb = Pha * inv - k * (inv * Sa), Phb * inv - k * (inv * Sb)
+        kab = Phab * inv - Pha * (inv * inv * Sb) - Phb * (inv * inv * Sa) - k * (inv * Sab) + k * (2.0 * inv * inv * SaSb)
+        mab = mab + Phab * g + Pha * gb + Phb * ga + Ph * gab
+        ma, mb = ma + Pha * g + Ph * ga, mb + Phb * g + Ph * gb
+        m = m + Ph * g
+        Pab = Pab - np.outer(kab, Ph) - np.outer(ka, Phb) - np.outer(kb, Pha) - np.outer(k, Phab)
+        Pa = Pa - np.outer(ka, Ph) - np.outer(k, Pha)
+        Pb = Pb - np.outer(kb, Ph) - np.outer(k, Phb)
+        P = P - np.outer(k, Ph)
+        P, Pa, Pb, Pab = (0.5 * (Z + Z.T) for Z in (P, Pa, Pb, Pab))
+    return hll
+
+
+def loglik_hess_noise(kernel, tarray, yarray, stdarray, delays, alpha, rho, kappa=None, nu=None, marginalise_b=True, _slip=None):
+    """(loglik, grad[4L+1], hess[3L+1, 3L+1], info) of one (tau, alpha, rho, kappa, nu): loglik_grad_noise()'s value, row and info, and the
+    Hessian over [alpha_1..alpha_L, rho, kappa_1..kappa_L, nu_1..nu_L] by the filter's second-order forward sensitivities with the
+    variance's tangents, each pair computed once and mirrored: Objective.loglik_hess_markov_noise_batch's row.  The leading (L+1) x (L+1)
+    block is loglik_hess_hyper()'s on the error bars sqrt(kappa_l^2 sigma_i^2 + nu_l).  grad and hess are NaN where info != 0.
+    _slip (tests only) injects one mistake: "no_d2kappa" (the 2 sigma^2 term of (kappa_l, kappa_l) left out), "dvar_one_side" (dvar
+    enters S_a, S_b but not the S_a S_b cross terms of the second tangent), "kappa_linear" (dvar = kappa sigma^2 instead of
+    2 kappa sigma^2), "noise_noise_diag_only" (noise pairs on two bands set to zero), "rho_noise_no_dA" (the (rho, noise) pairs walked
+    without A_rho)."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b,
+                                                                       codes_first=True)
+    W = 3 * L + 1
+    ll, grad, info = loglik_grad_noise(kernel, tarray, yarray, stdarray, delays, alpha, rho, kappa, nu, marginalise_b)
+    hess = np.full((W, W), math.nan)
+    if info:
+        return ll, grad, hess, info
+    kappa, nu, _ = _noise_setup(L, kappa, nu)
+    ntrain = _noise_train(train, kappa, nu)
+    mapped = [e[:5] for e in ntrain]
+    for a in range(W):
+        for b in range(a, W):
+            if b <= L:
+                v = _hess_pass(name, mapped, alpha, rho, p, n, vb, a, b)
+            elif _slip == "noise_noise_diag_only" and a > L and (a - L - 1) % L != (b - L - 1) % L:
+                v = 0.0
+            else:
+                v = _noise_hess_pass(name, ntrain, alpha, rho, p, n, vb, a, b, kappa, slip=_slip)
+            hess[a, b] = hess[b, a] = v
+    return ll, grad, hess, 0
+
+
+def loglik_hess_noise_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, kappa=None, nu=None, marginalise_b=True):
+    """loglik_hess_noise over M rows -> (loglik[M], grad[M, 4L+1], hess[M, 3L+1, 3L+1], info[M]): Objective.loglik_hess_markov_noise_batch's
+    shape."""
+    L = len(tarray)
+    W = 3 * L + 1
+    delays = np.asarray(delays, np.float64).reshape(-1, L)
+    alpha = np.asarray(alpha, np.float64).reshape(-1, L)
+    rho = np.asarray(rho, np.float64).reshape(-1)
+    kappa, nu = _noise_rows(L, len(rho), kappa), _noise_rows(L, len(rho), nu)
+    out = [loglik_hess_noise(kernel, tarray, yarray, stdarray, delays[i], alpha[i], rho[i], kappa[i], nu[i], marginalise_b)
+           for i in range(len(rho))]
+    return (np.array([o[0] for o in out]), np.array([o[1] for o in out]).reshape(-1, 4 * L + 1),
+            np.array([o[2] for o in out]).reshape(-1, W, W), np.array([o[3] for o in out], dtype=np.int32))
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
 # The Fisher information in linear time (csrc/gpcc_markov_fisher.hip.h, DESIGN.md 4.22), the same algorithm in numpy.  The expectation
 # of -l_ab over the data of the model at theta: the innovation eps_k is independent of the past with variance S_k, its tangent
 # eps_a = -h_a'm - h'm_a depends on the past only, so
@@ -1682,6 +1825,10 @@ class MarkovObjective:
     def loglik_grad_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
         """Objective.loglik_grad_markov_noise_batch's result: (loglik[M], grad[M, 4L+1], info[M])."""
         return loglik_grad_noise_batch(self.kernel, *self.data, delays, alpha, rho, kappa, nu, self.marginalise_b)
+
+    def loglik_hess_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
+        """Objective.loglik_hess_markov_noise_batch's result: (loglik[M], grad[M, 4L+1], hess[M, 3L+1, 3L+1], info[M])."""
+        return loglik_hess_noise_batch(self.kernel, *self.data, delays, alpha, rho, kappa, nu, self.marginalise_b)
 
     def loglik_hess_hyper_markov_batch(self, delays, alpha, rho):
         """Objective.loglik_hess_hyper_markov_batch's result: (loglik[M], grad[M, 2L+1], hess[M, L+1, L+1], info[M])."""

@@ -492,6 +492,29 @@ int gpcc_loglik_noise_markov_batch(gpcc_handle_t h, int M, const double *delays,
 int gpcc_loglik_grad_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                         const double *kappa, const double *nu, double *loglik, double *grad, int *info);
 
+/* The Hessian of that log-likelihood over the fitted parameters of a row,
+ *     theta = [alpha_1..alpha_L, rho, kappa_1..kappa_L, nu_1..nu_L],   n = 3L + 1,
+ * in LINEAR TIME (kernel: csrc/gpcc_markov_noise_hess.hip.h): the filter's second-order forward sensitivities with the
+ * variance's tangents (d v_i / d kappa_l = 2 kappa_l sigma_i^2, d v_i / d nu_l = 1 on band l, d2 v_i / d kappa_l^2 = 2 sigma_i^2), exact.
+ *   grad: M rows of 4L+1 doubles, gpcc_loglik_grad_noise_markov_batch's layout.  loglik, grad and info are BITWISE that entry's: they
+ *   come from its launches inside the same call.
+ *   hess: M row-major n x n blocks in the order of theta (the delays have no rows in it), bitwise symmetric; NULL: the call IS the
+ *   gradient entry.  kappa = nu = NULL: kappa = 1, nu = 0.  A row's leading (L+1) x (L+1) block is the block
+ *   gpcc_loglik_hess_hyper_markov_batch returns on a fresh handle created with the error bars sqrt(kappa_l^2 sigma_i^2 + nu_l); only the
+ *   order of rounding differs.
+ * info, precedence (-1, -2, -3, j > 0), refusals and M = 0: gpcc_loglik_grad_noise_markov_batch's; a row with info != 0 has a NaN block
+ * and touches no other row.  Besides: GPCC_ERR_UNSUPPORTED before any device work for an instantiation that the compiler cannot keep
+ * out of scratch memory (Matern-5/2 with four bands and marginalised offsets, as gpcc_loglik_hess_hyper_markov_batch); the way round is
+ * gpcc_loglik_hess_hyper_batch on a handle created with the effective error bars, which gives the (alpha, rho) block at a fixed noise
+ * model.
+ * Path: one lane per (row, pair slot a <= b), n (n + 1) / 2 slots, then a small kernel that writes both halves of the blocks.  No
+ * atomics: a row's bits depend on that row alone, whatever M, the row order, the launch shape and the options.
+ * Memory: the gradient entry's, plus 8 M bytes per slot and 8 M n^2 bytes, grown on demand; none of the N^2 workspace.  "markov_count"
+ * advances by M.  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Not here: the rows
+ * of tau under a noise model and the Fisher information in kappa, nu.  Blocking. */
+int gpcc_loglik_hess_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                        const double *kappa, const double *nu, double *loglik, double *grad, double *hess, int *info);
+
 /* Same with DEVICE pointers, enqueued behind `stream` (a hipStream_t, NULL = default stream) and
  * joined back into it: asynchronous, outputs valid once `stream` has drained. */
 int gpcc_loglik_batch_device(gpcc_handle_t handle, int M, const double *d_delays,

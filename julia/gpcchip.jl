@@ -226,6 +226,22 @@ function loglik_grad_markov_noise(h::Handle, delays::Matrix{Float64}, alpha::Mat
     return ll, grad, info
 end
 
+"loglik_grad_markov_noise and the Hessian over [α_1..α_L, ρ, kappa_1..kappa_L, nu_1..nu_L] (gpcc_loglik_hess_noise_markov_batch, DESIGN
+4.26): (ll[M], grad (4L+1)×M, hess (3L+1)×(3L+1)×M, info[M]); symmetric blocks, NaN where info != 0; ll, grad, info bitwise the gradient's."
+function loglik_hess_markov_noise(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64},
+                                  kappa::Union{Nothing,Matrix{Float64}} = nothing, nu::Union{Nothing,Matrix{Float64}} = nothing)
+    M, n = length(rho), 3h.L + 1
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    @assert (kappa === nothing || size(kappa) == (h.L, M)) && (nu === nothing || size(nu) == (h.L, M))
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    grad, hess = Matrix{Float64}(undef, 4h.L + 1, M), Array{Float64}(undef, n, n, M)
+    rc = ccall((:gpcc_loglik_hess_noise_markov_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, kappa === nothing ? C_NULL : kappa, nu === nothing ? C_NULL : nu, ll, grad, hess, info)
+    rc == 0 || error("gpcc_loglik_hess_noise_markov_batch: " * lasterror(h.ptr))
+    return ll, grad, hess, info
+end
+
 "objective, gradient, Hessian and expected (Fisher) information for M triples: (ll[M], grad (2L+1)×M, hess and fisher
 (2L+1)×(2L+1)×M, info[M]) in [α_1..α_L, ρ, τ_1..τ_L] order, symmetric blocks, NaN where info != 0; fisher = 1/2 tr(K⁻¹D_iK⁻¹D_j)."
 function loglik_hess_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
