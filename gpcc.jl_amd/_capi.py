@@ -64,6 +64,8 @@ SIGNATURES = {
                                                            c_double_p, c_double_p, c_double_p, c_int_p]),
     "gpcc_loglik_hess_noise_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
                                                            c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "gpcc_loglik_hess_full_noise_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
+                                                                c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
     "gpcc_loglik_hess_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,
                                               c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
     "gpcc_loglik_hess_hyper_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p,

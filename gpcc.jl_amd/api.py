@@ -613,6 +613,29 @@ class Objective:
                                                                    _ip(info)))
         return ll, grad, hess, info
 
+    def loglik_hess_full_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
+        """loglik_grad_markov_noise_batch and the FULL Hessian, the delays included, over the gradient row's order [alpha_1..L, rho,
+        tau_1..L, kappa_1..L, nu_1..L] in linear time (gpcc_loglik_hess_full_noise_markov_batch: the rows of tau by second-order forward
+        sensitivities, one lane per (row, pair with a tau)) -> (loglik[M], grad[M, 4L+1], hess[M, 4L+1, 4L+1], info[M]).  loglik, grad
+        and info are bitwise loglik_grad_markov_noise_batch's; the sub-block on the indices {0..L, 2L+1..4L} is bitwise
+        loglik_hess_markov_noise_batch's; the leading (2L+1) x (2L+1) block is loglik_hess_markov_batch's of a fresh Objective on
+        fit.effective_std(sigma, kappa[m], nu[m]).  hess is bitwise symmetric and NaN where info != 0.  On an OU row where two points of
+        different bands have exactly equal shifted times every entry with a tau index is NaN and info stays 0; with one band the tau
+        entries are exact zeros.  rbf, marginalise_b with more than 4 bands, or matern52 with marginalise_b and 4 bands: GpccError
+        (unsupported)."""
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        kappa, nu = self._noise(M, kappa, "kappa"), self._noise(M, nu, "nu")
+        n = 4 * self.L + 1
+        ll = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, n), dtype=np.float64)
+        hess = np.empty((M, n, n), dtype=np.float64)
+        info = np.zeros(M, dtype=np.int32)
+        self._chk(_capi.load().gpcc_loglik_hess_full_noise_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho),
+                                                                        _dp(kappa) if kappa is not None else None,
+                                                                        _dp(nu) if nu is not None else None, _dp(ll), _dp(grad),
+                                                                        _dp(hess), _ip(info)))
+        return ll, grad, hess, info
+
     def loglik_hess_batch(self, delays, alpha, rho):
         """objective, gradient, Hessian and expected (Fisher) information for M (tau, alpha, rho) triples -> (loglik[M],
         grad[M, P], hess[M, P, P], fisher[M, P, P], info[M]), P = 2L+1 in a gradient row's order [alpha_1..alpha_L, rho,

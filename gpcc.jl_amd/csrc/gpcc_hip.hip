@@ -20,6 +20,7 @@
 #include "gpcc_markov_resample.hip.h"
 #include "gpcc_markov_noise.hip.h"
 #include "gpcc_markov_noise_hess.hip.h"
+#include "gpcc_markov_noise_hess_tau.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -293,6 +294,10 @@ struct gpcc_handle_s {
     // blocks [M][(3L + 1)^2], grown on demand
     double *d_mknhs = nullptr, *d_mknhb = nullptr;
     long mknhs_cap = 0, mknhb_cap = 0;
+    // its rows of tau (gpcc_loglik_hess_full_noise_markov_batch): the per-pair results [pair slots with a tau][M] and the blocks
+    // [M][(4L + 1)^2], grown on demand
+    double *d_mknts = nullptr, *d_mkntb = nullptr;
+    long mknts_cap = 0, mkntb_cap = 0;
     long markov_resample_bytes_max = (long)512 << 20;   // option "markov_resample_bytes_max": the most the packed pairs of one call may take
     int laplace_markov = 0;              // option "laplace_markov": gpcc_laplace_evidence's rounds are gpcc_loglik_hess_hyper_markov_batch calls
     int markov_chunk_rows = 0;           // option "markov_chunk_rows": rows per chunk of gpcc_predict_markov_batch (0: by the scratch budget)
@@ -613,6 +618,7 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_mkmy); hipFree(h->d_mkmr); hipFree(h->d_mkmm); hipFree(h->d_mkmo); hipFree(h->d_mkmp);
     hipFree(h->d_mknp); hipFree(h->d_mkns); hipFree(h->d_mkng);
     hipFree(h->d_mknhs); hipFree(h->d_mknhb);
+    hipFree(h->d_mknts); hipFree(h->d_mkntb);
     hipFree(h->d_mkrv); hipFree(h->d_mkry); hipFree(h->d_mkrm); hipFree(h->d_mkrc); hipFree(h->d_mkrr); hipFree(h->d_mkrp);
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
     hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
@@ -2197,7 +2203,7 @@ static void markov_fill_args(gpcc_handle_t h, int M, const double *dd, const dou
 }
 
 // the kernels with dynamic LDS, for gpcc_handle::mk_lds_raised
-enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI, MK_RESAMPLE, MK_NOISE, MK_NOISE_GRAD, MK_NOISE_HESS };
+enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI, MK_RESAMPLE, MK_NOISE, MK_NOISE_GRAD, MK_NOISE_HESS, MK_NOISE_HESS_TAU };
 
 // The launch of every kernel of the filter, `name` in messages: one lane per row, `rows` rows along x and ny lanes per row along y.
 // The shape: one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy beyond; the light
@@ -3033,6 +3039,69 @@ extern "C" int gpcc_loglik_hess_noise_markov_batch(gpcc_handle_t h, int M, const
                                  gpcc_markov_noise_hess_launch);
         if (rc) return rc;
         HIPCHK(h, hipMemcpyAsync(hess, h->d_mknhb, sizeof(double) * n * n * M, hipMemcpyDeviceToHost, h->main_stream));
+    }
+    rc = markov_finish(h, M, loglik, info);
+    if (rc) return rc;
+    h->markov_count += M;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The linear-time full Hessian of rows with their own noise model over [alpha_1..L, rho, tau_1..L, kappa_1..L, nu_1..L], the gradient
+// row's order (gpcc_loglik_hess_full_noise_markov_batch; kernel: gpcc_markov_noise_hess_tau.hip.h): the rows of tau by
+// the same second-order forward sensitivities, one lane per (row, pair slot with a tau).  Value, info, gradient and the
+// [alpha, rho, kappa, nu] block come from gpcc_loglik_hess_noise_markov_batch's launches inside the same call (bitwise that entry's by
+// construction); it needs what that entry needs plus the new slots and the full blocks, nothing of the N^2 workspace.
+// ------------------------------------------------------------------------------------------
+extern "C" int gpcc_loglik_hess_full_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                                        const double *kappa, const double *nu, double *loglik, double *grad, double *hess,
+                                                        int *info)
+{
+    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
+    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
+    if (M == 0) return 0;
+    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    const char *dense = "gpcc_loglik_hess_batch on a handle created with the error bars sqrt(kappa^2 sigma^2 + nu) (effective_std)";
+    int rc = markov_refusals(h, "gpcc_loglik_hess_full_noise_markov_batch", dense);
+    if (!rc) rc = markov_noise_ships(h, "gpcc_loglik_hess_full_noise_markov_batch", dense);
+    if (rc) return rc;
+    {
+        const MarkovDims d = markov_dims(primary(h));
+        if (!gpcc_mk_ships<GpccMkShipsNoiseHess>(d.p, d.noff) || !gpcc_mk_ships<GpccMkShipsNoiseHessTau>(d.p, d.noff))
+            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_hess_full_noise_markov_batch: the instantiation <%d, %d> (states of the process, "
+                        "offset states) needs scratch memory and does not ship; use %s", d.p, d.noff, dense);
+    }
+    if (route_fp64(h, "linear-time full Hessian under a noise model", rc, [&](gpcc_handle_t o) {
+            return gpcc_loglik_hess_full_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, loglik, grad, hess, info);
+        }))
+        return rc;
+    GPCC_ON_DEVICE(h, h->device);
+    const int L = h->L, n = 3 * L + 1, W = 4 * L + 1, slots = gpcc_markov_noise_hess_slots(L), tslots = gpcc_markov_noise_hess_tau_slots(L);
+    double *dd, *da, *dr;
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
+        int g = markov_noise_grad_grow(h, M);
+        if (!g && hess) g = grow_buf(h, &h->d_mknhs, &h->mknhs_cap, (long)slots * M);
+        if (!g && hess) g = grow_buf(h, &h->d_mknhb, &h->mknhb_cap, (long)n * n * M);
+        if (!g && hess) g = grow_buf(h, &h->d_mknts, &h->mknts_cap, (long)tslots * M);
+        if (!g && hess) g = grow_buf(h, &h->d_mkntb, &h->mkntb_cap, (long)W * W * M);
+        return g;
+    });
+    if (rc) return rc;
+    GpccMarkovNoiseArgs a;
+    rc = markov_noise_grad_enqueue(h, M, dd, da, dr, kappa, nu, grad, a);
+    if (rc) return rc;
+    if (hess) {
+        GpccMarkovNoiseHessArgs b;
+        b.kappa = a.kappa; b.nu = a.nu; b.slot = h->d_mknhs; b.hess = h->d_mknhb;
+        rc = markov_slots_launch(h, "gpcc_markov_noise_hess", MK_NOISE_HESS, M, dd, da, dr, slots, b, markov_noise_lds(h),
+                                 gpcc_markov_noise_hess_launch);
+        if (rc) return rc;
+        GpccMarkovNoiseHessTauArgs c;
+        c.kappa = a.kappa; c.nu = a.nu; c.slot = h->d_mknts; c.noise = h->d_mknhb; c.hess = h->d_mkntb;
+        rc = markov_slots_launch(h, "gpcc_markov_noise_hess_tau", MK_NOISE_HESS_TAU, M, dd, da, dr, tslots, c, markov_noise_lds(h),
+                                 gpcc_markov_noise_hess_tau_launch);
+        if (rc) return rc;
+        HIPCHK(h, hipMemcpyAsync(hess, h->d_mkntb, sizeof(double) * W * W * M, hipMemcpyDeviceToHost, h->main_stream));
     }
     rc = markov_finish(h, M, loglik, info);
     if (rc) return rc;

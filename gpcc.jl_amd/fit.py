@@ -112,7 +112,7 @@ def laplace_covariance(H, free, L=None):
     return cov, True
 
 
-def delay_covariance(objective, delays, alpha, rho, free=None, solver="dense", curvature="hessian"):
+def delay_covariance(objective, delays, alpha, rho, free=None, solver="dense", curvature="hessian", kappa=None, nu=None, noise_free=None):
     """The Laplace covariance of the delays (and hyper-parameters) at one point (delays[L], alpha[L], rho): one Hessian call over
     [alpha_1..alpha_L, rho, tau_1..tau_L] -- objective.loglik_hess_batch (solver "dense") or objective.loglik_hess_markov_batch (solver
     "markov": linear time, OU / matern32 / matern52; Objective's or markov.MarkovObjective's) -- then
@@ -122,7 +122,23 @@ def delay_covariance(objective, delays, alpha, rho, free=None, solver="dense", c
     "dense" there) or when -H_ff is not positive definite.  ValueError for another solver, or for a `free` that holds every delay.
     curvature="fisher": the expected (Fisher) information I in place of -H, cov = (I_ff)^-1 -- positive semi-definite at any point, not
     only at a maximum, and independent of the fluxes (a cadence's forecast) -- from objective.loglik_hess_batch's Fisher matrix (solver
-    "dense") or objective.loglik_fisher_markov_batch (solver "markov"); the same ok rules."""
+    "dense") or objective.loglik_fisher_markov_batch (solver "markov"); the same ok rules.
+    kappa, nu (each (L,) or None; both None: everything above, unchanged): the point carries a noise model, point i of band l observed
+    with the variance kappa_l^2 sigma_i^2 + nu_l (None beside a given one: ones / zeros).  The Hessian is then
+    objective.loglik_hess_full_markov_noise_batch's over [alpha_1..L, rho, tau_1..L, kappa_1..L, nu_1..L] (DESIGN.md 4.27), so the delay's
+    variance carries the (tau, kappa) and (tau, nu) couplings that a noise model frozen into the error bars drops; solver must be
+    "markov" and curvature "hessian" (ValueError otherwise: the Fisher information in kappa, nu does not exist yet).  `free` indexes that
+    4L+1 order and defaults to every alpha, rho, tau_2..tau_L and the noise parameters of `noise_free`, a boolean mask of 2L
+    (kappa_1..L, nu_1..L) whose default is kappa_l > 0 and nu_l > 0: a parameter on its lower bound is not at an interior maximum and
+    is left out, the way laplace.BatchedNewton pins it.  The same ok rules and the same ValueError for a `free` that holds every delay.
+    At a stationary point the delay block of cov does not depend on how the nuisance parameters are parametrised (kappa or log kappa,
+    nu or sqrt(nu): the Hessian transforms as J'HJ there, and the block of the inverse over the untransformed delays is unchanged)."""
+    noise = kappa is not None or nu is not None
+    if noise and solver != "markov":
+        raise ValueError("kappa / nu need solver='markov', got %r: the dense path has no noise model (the Fisher information in kappa, nu "
+                         "does not exist yet either)" % (solver,))
+    if noise and curvature != "hessian":
+        raise ValueError("kappa / nu need curvature='hessian', got %r: the Fisher information in kappa, nu does not exist yet" % (curvature,))
     if solver not in ("dense", "markov"):
         raise ValueError("solver must be 'dense' or 'markov', got %r" % (solver,))
     if curvature not in ("hessian", "fisher"):
@@ -131,13 +147,23 @@ def delay_covariance(objective, delays, alpha, rho, free=None, solver="dense", c
     L = delays.shape[1]
     alpha = np.asarray(alpha, dtype=np.float64).reshape(1, L)
     rho = np.asarray(rho, dtype=np.float64).reshape(1)
+    if noise:
+        kappa = np.ones((1, L)) if kappa is None else np.asarray(kappa, dtype=np.float64).reshape(1, L)
+        nu = np.zeros((1, L)) if nu is None else np.asarray(nu, dtype=np.float64).reshape(1, L)
+        if free is None:
+            if noise_free is None:
+                noise_free = np.concatenate([kappa[0] > 0.0, nu[0] > 0.0])
+            noise_free = np.asarray(noise_free, dtype=bool).reshape(2 * L)
+            free = list(range(L + 1)) + list(range(L + 2, 2 * L + 1)) + [2 * L + 1 + int(k) for k in np.flatnonzero(noise_free)]
     if free is None:
         free = list(range(L + 1)) + list(range(L + 2, 2 * L + 1))
     free = np.asarray(free)
     idx = np.flatnonzero(free) if free.dtype == bool else free.astype(int).ravel()
     if set(range(L + 1, 2 * L + 1)) <= set(idx.tolist()):
         raise ValueError("free holds every delay: a common shift of all delays leaves the likelihood unchanged, fix at least one")
-    if curvature == "fisher":
+    if noise:
+        _, _, hess, info = objective.loglik_hess_full_markov_noise_batch(delays, alpha, rho, kappa, nu)
+    elif curvature == "fisher":
         if solver == "markov":
             _, _, fisher, info = objective.loglik_fisher_markov_batch(delays, alpha, rho)
         else:

@@ -1063,6 +1063,158 @@ def loglik_hess_noise_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
+# The rows of tau of the Hessian under a noise model per row (csrc/gpcc_markov_noise_hess_tau.hip.h,
+# gpcc_loglik_hess_full_noise_markov_batch), the same algorithm in numpy, over the gradient row's order
+# theta = [alpha_1..alpha_L, rho, tau_1..tau_L, kappa_1..kappa_L, nu_1..nu_L], n = 4L + 1.  An (alpha, tau), (rho, tau) or (tau, tau)
+# pair is _hess_pass on the mapped variances.  A (tau_l, noise) pair (_noise_tau_hess_pass) carries the noise tangent a of
+# _noise_hess_pass (no tangent of A, of Pinf, of the prior or of h; dvar in S_a) and the tau tangent b of _hess_pass (A_b = c_l F A):
+#   step     A_a = A_ab = 0, so  m_ab <- A_b m_a + A m_ab,  P_ab,xx <- A_b D_a A' + A D_a A_b' + A D_ab A',  P_ab,xb <- A_b P_a,xb + A P_ab,xb:
+#            the second tangent moves as the tau tangent of the "state" (m_a, P_a) with a zero stationary part; no cross term
+#   update   h_a = h_b = 0, S_a += dvar, nothing in S_b and S_ab
+# On an OU row with a cross-band tie in shifted time the pair has no second derivative: NaN, as every pair with a tau.
+# ----------------------------------------------------------------------------------------------------------------------------------
+NOISE_HESS_FULL_SLIPS = ("tau_noise_no_dvar", "tau_noise_as_state", "plain_variance", "tau_noise_own_band")
+
+
+def _noise_tau_hess_pass(name, ntrain, alpha, rho, p, n, vb, tl, q, kappa, slip=None):
+    """d2 loglik / d tau_tl d theta_q for a noise parameter q of the 3L + 1 order of _noise_hess_pass (q > L: kappa_1..L, nu_1..L), over
+    _noise_train's observations in merge_order()'s order.  NaN on an OU row with a cross-band tie.  slip: loglik_hess_full_noise()'s."""
+    L = len(alpha)
+    ev = sorted(ntrain, key=lambda e: e[:3])
+    banda, nua = (q - L - 1) % L, q > 2 * L
+    zero = np.zeros((p, p))
+    Pinf = stationary(name, rho)
+    F = companion(name, rho)
+    P = _prior(name, rho, p, n, vb)
+    Pa, Pb, Pab = np.zeros((n, n)), np.zeros((n, n)), np.zeros((n, n))
+    m, ma, mb, mab = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
+    hll, sprev, bprev = 0.0, None, -1
+    for (s, band, _, r, v, s2) in ev:
+        d = 0.0 if sprev is None else s - sprev
+        if name == "OU" and sprev is not None and d == 0.0 and band != bprev:
+            return math.nan
+        cb = 0.0 if sprev is None else -float(band == tl) + float(bprev == tl)
+        sprev, bprev = s, band
+        A = transition(name, d, rho)
+        Ab = cb * (F @ A) if cb != 0.0 else zero
+        X = slice(0, p)
+        D, Da, Db, Dab = P[X, X] - Pinf, Pa[X, X], Pb[X, X], Pab[X, X]
+        if slip == "tau_noise_as_state":      # the tau tangent of the state, not of (m_a, P_a)
+            mab[X] = Ab @ m[X] + A @ mab[X]
+            Pab[X, X] = Ab @ D @ A.T + A @ D @ Ab.T + A @ Dab @ A.T
+            Pab[X, p:] = Ab @ P[X, p:] + A @ Pab[X, p:]
+        else:
+            mab[X] = Ab @ ma[X] + A @ mab[X]
+            Pab[X, X] = Ab @ Da @ A.T + A @ Da @ Ab.T + A @ Dab @ A.T
+            Pab[X, p:] = Ab @ Pa[X, p:] + A @ Pab[X, p:]
+        Pab[p:, X] = Pab[X, p:].T
+        ma[X], mb[X] = A @ ma[X], Ab @ m[X] + A @ mb[X]
+        Pa[X, X] = A @ Da @ A.T
+        Pb[X, X] = Ab @ D @ A.T + A @ Db @ A.T + A @ D @ Ab.T
+        Pa[X, p:], Pb[X, p:] = A @ Pa[X, p:], Ab @ P[X, p:] + A @ Pb[X, p:]
+        Pa[p:, X], Pb[p:, X] = Pa[X, p:].T, Pb[X, p:].T
+        m[X] = A @ m[X]
+        P[X, X] = A @ D @ A.T + Pinf
+        P[X, p:] = A @ P[X, p:]
+        P[p:, X] = P[X, p:].T
+
+        h = np.zeros(n)
+        h[0] = alpha[band]
+        if n > p:
+            h[p + band] = 1.0
+        dva = 0.0
+        if band == banda:
+            dva = 1.0 if nua else 2.0 * kappa[banda] * s2
+        Ph, Pha, Phb, Phab = P @ h, Pa @ h, Pb @ h, Pab @ h
+        S = h @ Ph + v
+        if not (S > 0.0 and math.isfinite(S)):
+            return math.nan
+        Sa1, Sb, Sab = h @ Pha + dva, h @ Phb, h @ Phab             # Sa1: the first-order update's S_a
+        Sa = h @ Pha if slip == "tau_noise_no_dvar" else Sa1        # the second-order update's
+        eps = r - h @ m
+        ea, eb, eab = -(h @ ma), -(h @ mb), -(h @ mab)
+        inv = 1.0 / S
+        g = eps * inv
+        ga, gb, ga1 = (ea - g * Sa) * inv, (eb - g * Sb) * inv, (ea - g * Sa1) * inv
+        gab = (eab - ga * Sb - gb * Sa - g * Sab) * inv
+        hll -= 0.5 * (Sab * inv - Sa * Sb * inv * inv + 2.0 * ea * eb * inv + 2.0 * g * eab - 2.0 * g * inv * (ea * Sb + eb * Sa)
+                      - g * g * Sab + 2.0 * g * g * Sa * Sb * inv)
+        k = Ph * inv
+        ka, kb, ka1 = Pha * inv - k * (inv * Sa), Phb * inv - k * (inv * Sb), Pha * inv - k * (inv * Sa1)
+        kab = Phab * inv - Pha * (inv * inv * Sb) - Phb * (inv * inv * Sa) - k * (inv * Sab) + k * (2.0 * inv * inv * Sa * Sb)
+        mab = mab + Phab * g + Pha * gb + Phb * ga + Ph * gab
+        ma, mb = ma + Pha * g + Ph * ga1, mb + Phb * g + Ph * gb
+        m = m + Ph * g
+        Pab = Pab - np.outer(kab, Ph) - np.outer(ka, Phb) - np.outer(kb, Pha) - np.outer(k, Phab)
+        Pa = Pa - np.outer(ka1, Ph) - np.outer(k, Pha)
+        Pb = Pb - np.outer(kb, Ph) - np.outer(k, Phb)
+        P = P - np.outer(k, Ph)
+        P, Pa, Pb, Pab = (0.5 * (Z + Z.T) for Z in (P, Pa, Pb, Pab))
+    return hll
+
+
+def loglik_hess_full_noise(kernel, tarray, yarray, stdarray, delays, alpha, rho, kappa=None, nu=None, marginalise_b=True, pairs=None,
+                           _slip=None):
+    """(loglik, grad[4L+1], hess[4L+1, 4L+1], info) of one (tau, alpha, rho, kappa, nu): loglik_grad_noise()'s value, row and info, and the
+    full Hessian over the gradient row's order [alpha_1..L, rho, tau_1..L, kappa_1..L, nu_1..L], each pair computed once and mirrored:
+    Objective.loglik_hess_full_markov_noise_batch's row.  The sub-block on the indices {0..L, 2L+1..4L} is loglik_hess_noise()'s exactly;
+    the leading (2L+1) x (2L+1) block is loglik_hess()'s on the error bars sqrt(kappa_l^2 sigma_i^2 + nu_l).  grad and hess are NaN where
+    info != 0.  On an OU row with a cross-band tie in shifted time every entry with a tau index is NaN and info stays 0; with one band
+    the tau entries are exact zeros.  pairs: an iterable of (a, b) in the 4L+1 order that restricts the work to those entries (either
+    order); the others come back NaN.
+    _slip (tests only) injects one mistake: "tau_noise_no_dvar" (the noise tangent's dvar left out of the second-order update of a
+    (tau, noise) pair), "tau_noise_as_state" (the (tau, noise) second tangent propagated from the state instead of from the noise
+    tangent), "plain_variance" (the (alpha, tau), (rho, tau) and (tau, tau) pairs walked on sigma^2 instead of kappa^2 sigma^2 + nu),
+    "tau_noise_own_band" (a (tau_l, noise_m) pair formed for l == m only, the others zero)."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b,
+                                                                       codes_first=True)
+    W, T, K = 4 * L + 1, L + 1, 2 * L + 1
+    ll, grad, info = loglik_grad_noise(kernel, tarray, yarray, stdarray, delays, alpha, rho, kappa, nu, marginalise_b)
+    hess = np.full((W, W), math.nan)
+    if info:
+        return ll, grad, hess, info
+    kappa, nu, _ = _noise_setup(L, kappa, nu)
+    ntrain = _noise_train(train, kappa, nu)
+    mapped = [e[:5] for e in ntrain]
+    want = None if pairs is None else {(min(a, b), max(a, b)) for (a, b) in pairs}
+    for a in range(W):
+        for b in range(a, W):
+            if want is not None and (a, b) not in want:
+                continue
+            ta, tb = T <= a < K, T <= b < K
+            if not ta and not tb:           # [alpha, rho, kappa, nu]: loglik_hess_noise()'s pair in its 3L + 1 order
+                qa, qb = (a if a < T else a - L), (b if b < T else b - L)
+                if qb <= L:
+                    v = _hess_pass(name, mapped, alpha, rho, p, n, vb, qa, qb)
+                else:
+                    v = _noise_hess_pass(name, ntrain, alpha, rho, p, n, vb, qa, qb, kappa)
+            elif b < K:                     # (alpha, tau), (rho, tau), (tau, tau): _hess_pass's order is this one's first 2L + 1
+                v = _hess_pass(name, train if _slip == "plain_variance" else mapped, alpha, rho, p, n, vb, a, b)
+            else:                           # (tau_l, noise): a is the tau
+                if _slip == "tau_noise_own_band" and (a - T) != (b - K) % L:
+                    v = 0.0
+                else:
+                    v = _noise_tau_hess_pass(name, ntrain, alpha, rho, p, n, vb, a - T, b - L, kappa, slip=_slip)
+            hess[a, b] = hess[b, a] = v
+    return ll, grad, hess, 0
+
+
+def loglik_hess_full_noise_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, kappa=None, nu=None, marginalise_b=True, pairs=None):
+    """loglik_hess_full_noise over M rows -> (loglik[M], grad[M, 4L+1], hess[M, 4L+1, 4L+1], info[M]):
+    Objective.loglik_hess_full_markov_noise_batch's shape."""
+    L = len(tarray)
+    W = 4 * L + 1
+    delays = np.asarray(delays, np.float64).reshape(-1, L)
+    alpha = np.asarray(alpha, np.float64).reshape(-1, L)
+    rho = np.asarray(rho, np.float64).reshape(-1)
+    kappa, nu = _noise_rows(L, len(rho), kappa), _noise_rows(L, len(rho), nu)
+    out = [loglik_hess_full_noise(kernel, tarray, yarray, stdarray, delays[i], alpha[i], rho[i], kappa[i], nu[i], marginalise_b, pairs)
+           for i in range(len(rho))]
+    return (np.array([o[0] for o in out]), np.array([o[1] for o in out]).reshape(-1, W),
+            np.array([o[2] for o in out]).reshape(-1, W, W), np.array([o[3] for o in out], dtype=np.int32))
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
 # The Fisher information in linear time (csrc/gpcc_markov_fisher.hip.h, DESIGN.md 4.22), the same algorithm in numpy.  The expectation
 # of -l_ab over the data of the model at theta: the innovation eps_k is independent of the past with variance S_k, its tangent
 # eps_a = -h_a'm - h'm_a depends on the past only, so
@@ -1829,6 +1981,10 @@ class MarkovObjective:
     def loglik_hess_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
         """Objective.loglik_hess_markov_noise_batch's result: (loglik[M], grad[M, 4L+1], hess[M, 3L+1, 3L+1], info[M])."""
         return loglik_hess_noise_batch(self.kernel, *self.data, delays, alpha, rho, kappa, nu, self.marginalise_b)
+
+    def loglik_hess_full_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
+        """Objective.loglik_hess_full_markov_noise_batch's result: (loglik[M], grad[M, 4L+1], hess[M, 4L+1, 4L+1], info[M])."""
+        return loglik_hess_full_noise_batch(self.kernel, *self.data, delays, alpha, rho, kappa, nu, self.marginalise_b)
 
     def loglik_hess_hyper_markov_batch(self, delays, alpha, rho):
         """Objective.loglik_hess_hyper_markov_batch's result: (loglik[M], grad[M, 2L+1], hess[M, L+1, L+1], info[M])."""

@@ -510,10 +510,35 @@ int gpcc_loglik_grad_noise_markov_batch(gpcc_handle_t h, int M, const double *de
  * Path: one lane per (row, pair slot a <= b), n (n + 1) / 2 slots, then a small kernel that writes both halves of the blocks.  No
  * atomics: a row's bits depend on that row alone, whatever M, the row order, the launch shape and the options.
  * Memory: the gradient entry's, plus 8 M bytes per slot and 8 M n^2 bytes, grown on demand; none of the N^2 workspace.  "markov_count"
- * advances by M.  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Not here: the rows
- * of tau under a noise model and the Fisher information in kappa, nu.  Blocking. */
+ * advances by M.  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  The rows of tau
+ * under a noise model: gpcc_loglik_hess_full_noise_markov_batch below.  Not here: the Fisher information in kappa, nu.  Blocking. */
 int gpcc_loglik_hess_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                         const double *kappa, const double *nu, double *loglik, double *grad, double *hess, int *info);
+
+/* The FULL Hessian of that log-likelihood, the delays included, over the gradient row's order
+ *     theta = [alpha_1..alpha_L, rho, tau_1..tau_L, kappa_1..kappa_L, nu_1..nu_L],   n = 4L + 1,
+ * in LINEAR TIME (kernel: csrc/gpcc_markov_noise_hess_tau.hip.h): the rows of tau by the same second-order forward
+ * sensitivities -- the (alpha, tau), (rho, tau) and (tau, tau) pairs are gpcc_loglik_hess_markov_batch's recursion on the variances
+ * kappa_l^2 sigma_i^2 + nu_l, the (tau, kappa) and (tau, nu) pairs carry a noise tangent and a tau tangent.  Exact.
+ *   hess: M row-major n x n blocks in the order of theta, bitwise symmetric; NULL: the call IS the gradient entry
+ *   (gpcc_loglik_grad_noise_markov_batch).  kappa / nu NULL: 1 / 0.
+ *   loglik, grad and info are BITWISE gpcc_loglik_grad_noise_markov_batch's, and the sub-block on the indices {0..L, 2L+1..4L} is BITWISE
+ *   gpcc_loglik_hess_noise_markov_batch's: both come from those entries' launches inside the same call.  The leading (2L+1) x (2L+1)
+ *   block is what gpcc_loglik_hess_markov_batch returns on a fresh handle created with the error bars sqrt(kappa_l^2 sigma_i^2 + nu_l);
+ *   only the order of rounding differs.
+ * TIES: gpcc_loglik_hess_markov_batch's contract.  On an OU row where two points of different bands have exactly equal shifted times
+ * every entry with a tau index is NaN, the (tau, kappa) and (tau, nu) entries included; info stays 0; value, gradient and the
+ * [alpha, rho, kappa, nu] sub-block are untouched.  Matern-3/2 and -5/2 are exact at ties.  With L = 1 the tau entries are exact zeros.
+ * info, precedence (-1, -2, -3, j > 0), refusals (GPCC_ERR_UNSUPPORTED before any device work for Matern-5/2 with four bands and
+ * marginalised offsets) and M = 0: gpcc_loglik_hess_noise_markov_batch's; a row with info != 0 has a NaN block and touches no other row.
+ * Path: that entry's launches, then one lane per (row, pair slot with a tau), 3 L^2 + L + L (L + 1) / 2 slots, then a small kernel
+ * that writes the blocks.  No atomics: a row's bits depend on that row alone, whatever M, the row order, the launch shape and the
+ * options.
+ * Memory: that entry's, plus 8 M bytes per new slot and 8 M n^2 bytes, grown on demand; none of the N^2 workspace.  "markov_count"
+ * advances by M.  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle computes on device_ids[0].  Not here: the Fisher
+ * information in kappa, nu.  Blocking. */
+int gpcc_loglik_hess_full_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                             const double *kappa, const double *nu, double *loglik, double *grad, double *hess, int *info);
 
 /* Same with DEVICE pointers, enqueued behind `stream` (a hipStream_t, NULL = default stream) and
  * joined back into it: asynchronous, outputs valid once `stream` has drained. */

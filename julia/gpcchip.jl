@@ -242,6 +242,23 @@ function loglik_hess_markov_noise(h::Handle, delays::Matrix{Float64}, alpha::Mat
     return ll, grad, hess, info
 end
 
+"loglik_grad_markov_noise and the full Hessian, the delays included, over [α_1..α_L, ρ, τ_1..τ_L, kappa_1..kappa_L, nu_1..nu_L]
+(gpcc_loglik_hess_full_noise_markov_batch, DESIGN 4.27): (ll[M], grad (4L+1)×M, hess (4L+1)×(4L+1)×M, info[M]); symmetric blocks, NaN
+where info != 0; on an OU row with a cross-band tie the entries with a τ index are NaN; ll, grad, info bitwise the gradient's."
+function loglik_hess_full_markov_noise(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64},
+                                       kappa::Union{Nothing,Matrix{Float64}} = nothing, nu::Union{Nothing,Matrix{Float64}} = nothing)
+    M, n = length(rho), 4h.L + 1
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    @assert (kappa === nothing || size(kappa) == (h.L, M)) && (nu === nothing || size(nu) == (h.L, M))
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    grad, hess = Matrix{Float64}(undef, n, M), Array{Float64}(undef, n, n, M)
+    rc = ccall((:gpcc_loglik_hess_full_noise_markov_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, kappa === nothing ? C_NULL : kappa, nu === nothing ? C_NULL : nu, ll, grad, hess, info)
+    rc == 0 || error("gpcc_loglik_hess_full_noise_markov_batch: " * lasterror(h.ptr))
+    return ll, grad, hess, info
+end
+
 "objective, gradient, Hessian and expected (Fisher) information for M triples: (ll[M], grad (2L+1)×M, hess and fisher
 (2L+1)×(2L+1)×M, info[M]) in [α_1..α_L, ρ, τ_1..τ_L] order, symmetric blocks, NaN where info != 0; fisher = 1/2 tr(K⁻¹D_iK⁻¹D_j)."
 function loglik_hess_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
