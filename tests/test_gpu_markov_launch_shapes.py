@@ -119,6 +119,57 @@ def test_rows_do_not_depend_on_the_launch_shape(problem, entry, wpw):
             assert np.array_equal(x[sl], y, equal_nan=True), (problem, entry, M, r0, k)
 
 
+# ---- staged against unstaged light curves for the same row ---------------------------------------------------------------------------
+STAGING_NL = [600] * 8
+LDS_MAX = 156 * 1024                              # GPCC_MARKOV_LDS_MAX (gpcc_markov.hip.h)
+# entry -> (the call, bytes per lane and band beside the staged light curves (GPCC_MARKOV_LANE_BYTES, + GPCC_MARKOV_NOISE_LANE_BYTES),
+#           ny of the entry's widest kernel)
+STAGING_ENTRIES = {
+    "loglik": (lambda obj, d, a, r, kap, nu: obj.loglik_markov_batch(d, a, r), 28, lambda L, ou: 1),
+    "noise": (lambda obj, d, a, r, kap, nu: obj.loglik_markov_noise_batch(d, a, r, kap, nu), 44, lambda L, ou: 1),
+    "grad": (lambda obj, d, a, r, kap, nu: obj.loglik_grad_markov_batch(d, a, r), 28, ENTRIES["grad"][1]),
+}
+
+
+def _lds_bytes(N, L, threads, lane_bytes):
+    """gpcc_markov_lds_bytes / gpcc_markov_noise_lds_bytes with the light curves staged."""
+    return 24 * N + lane_bytes * L * threads
+
+
+@pytest.mark.parametrize("entry", list(STAGING_ENTRIES))
+@pytest.mark.parametrize("kernel", ["OU", "matern32"])
+def test_rows_do_not_depend_on_staging(kernel, entry):
+    """Eight bands of 600 points (N = 4800), fixed offsets: beside the lanes' part of a workgroup of 64 lanes the light curves fit the LDS
+    and are staged; beside that of 256 lanes they do not and come through the caches (markov_launch decides it from the workgroup's
+    size, which it takes from the batch's).  A batch that runs four waves per workgroup, bitwise against the same rows in calls of at
+    most 64 rows: "a row's bits depend on the row alone" also across the two sources of the light curves.  The two preconditions are
+    asserted from the headers' formulas, so that the test fails if the constants move instead of comparing staged with staged."""
+    call, lane_bytes, ny_of = STAGING_ENTRIES[entry]
+    L, N, C = len(STAGING_NL), sum(STAGING_NL), _cus()
+    assert _lds_bytes(N, L, 64, lane_bytes) <= LDS_MAX < _lds_bytes(N, L, 256, lane_bytes)          # 64 lanes stage, 256 do not ...
+    assert lane_bytes * L * 256 <= LDS_MAX                                                       # ... and still launch
+    ny = ny_of(L, kernel == "OU")
+    M = next(m for m in range(1, 1 << 30, 256) if (m + 63) // 64 * ny > 2 * C)                   # M % 256 == 1: the last row alone
+    assert M % 256 == 1 and (M + 63) // 64 * ny > 2 * C and (M - 256 + 63) // 64 * ny <= 2 * C, (M, ny, C)
+    t, y, s, _ = MC.lightcurves(STAGING_NL, seed=31 + L, kind="plain")
+    delays, alpha, rho = _rows(L, M, seed=M + ny)
+    rg = np.random.default_rng(M)
+    kappa, nu = rg.uniform(0.5, 2.0, (M, L)), rg.uniform(0.0, 0.05, (M, L))
+    with gpcc_amd.Objective(t, y, s, KERN[kernel], marginalise_b=False) as obj:
+        big = call(obj, delays, alpha, rho, kappa, nu)
+        info = big[-1]
+        assert info[M - 1] != 0 and (info[:M - 1] == 0).all()                                    # the failing row alone
+        assert all(np.isnan(x[M - 1]).all() for x in big[:-1]) and all(np.isfinite(x[:M - 1]).all() for x in big[:-1])
+        nb = (M + 255) // 256
+        for r0, n in [(0, 64), (M - 1, 1), (max(nb // 2, 1) * 256 - 32, 64)]:                    # the last: across a workgroup border
+            assert 0 <= r0 and r0 + n <= M
+            sl = slice(r0, r0 + n)
+            small = call(obj, delays[sl], alpha[sl], rho[sl], kappa[sl], nu[sl])
+            assert len(small) == len(big)
+            for k, (x, z) in enumerate(zip(big, small)):
+                assert np.array_equal(x[sl], z, equal_nan=True), (kernel, entry, M, r0, k)
+
+
 @pytest.mark.parametrize("wpw", [4, 2])
 @pytest.mark.parametrize("problem", list(PROBLEMS))
 def test_draws_do_not_depend_on_the_launch_shape(problem, wpw):
