@@ -2997,6 +2997,28 @@ extern "C" int gpcc_loglik_grad_noise_markov_batch(gpcc_handle_t h, int M, const
 // launches inside the same call (bitwise gpcc_loglik_grad_noise_markov_batch's by construction); it needs what that entry needs plus
 // the pair slots and the blocks, nothing of the N^2 workspace.
 // ------------------------------------------------------------------------------------------
+// the block's buffers for M rows on top of the noise gradient's, and its launches over the M staged rows: the noise gradient's, then
+// (with_hess) gpcc_markov_noise_hess and its finish kernel, the blocks left in d_mknhb.  gpcc_loglik_hess_full_noise_markov_batch
+// shares both
+static int markov_noise_hess_grow(gpcc_handle_t h, int M, bool with_hess)
+{
+    const int n = 3 * h->L + 1;
+    int g = markov_noise_grad_grow(h, M);
+    if (!g && with_hess) g = grow_buf(h, &h->d_mknhs, &h->mknhs_cap, (long)gpcc_markov_noise_hess_slots(h->L) * M);
+    return (g || !with_hess) ? g : grow_buf(h, &h->d_mknhb, &h->mknhb_cap, (long)n * n * M);
+}
+
+static int markov_noise_hess_enqueue(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, const double *kappa,
+                                     const double *nu, double *grad, bool with_hess, GpccMarkovNoiseArgs &a)
+{
+    const int rc = markov_noise_grad_enqueue(h, M, dd, da, dr, kappa, nu, grad, a);
+    if (rc || !with_hess) return rc;
+    GpccMarkovNoiseHessArgs b;
+    b.kappa = a.kappa; b.nu = a.nu; b.slot = h->d_mknhs; b.hess = h->d_mknhb;
+    return markov_slots_launch(h, "gpcc_markov_noise_hess", MK_NOISE_HESS, M, dd, da, dr, gpcc_markov_noise_hess_slots(h->L), b,
+                               markov_noise_lds(h), gpcc_markov_noise_hess_launch);
+}
+
 extern "C" int gpcc_loglik_hess_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                                    const double *kappa, const double *nu, double *loglik, double *grad, double *hess,
                                                    int *info)
@@ -3020,26 +3042,14 @@ extern "C" int gpcc_loglik_hess_noise_markov_batch(gpcc_handle_t h, int M, const
         }))
         return rc;
     GPCC_ON_DEVICE(h, h->device);
-    const int L = h->L, n = 3 * L + 1, slots = gpcc_markov_noise_hess_slots(L);
+    const int n = 3 * h->L + 1;
     double *dd, *da, *dr;
-    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
-        int g = markov_noise_grad_grow(h, M);
-        if (!g && hess) g = grow_buf(h, &h->d_mknhs, &h->mknhs_cap, (long)slots * M);
-        if (!g && hess) g = grow_buf(h, &h->d_mknhb, &h->mknhb_cap, (long)n * n * M);
-        return g;
-    });
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] { return markov_noise_hess_grow(h, M, hess != nullptr); });
     if (rc) return rc;
     GpccMarkovNoiseArgs a;
-    rc = markov_noise_grad_enqueue(h, M, dd, da, dr, kappa, nu, grad, a);
+    rc = markov_noise_hess_enqueue(h, M, dd, da, dr, kappa, nu, grad, hess != nullptr, a);
     if (rc) return rc;
-    if (hess) {
-        GpccMarkovNoiseHessArgs b;
-        b.kappa = a.kappa; b.nu = a.nu; b.slot = h->d_mknhs; b.hess = h->d_mknhb;
-        rc = markov_slots_launch(h, "gpcc_markov_noise_hess", MK_NOISE_HESS, M, dd, da, dr, slots, b, markov_noise_lds(h),
-                                 gpcc_markov_noise_hess_launch);
-        if (rc) return rc;
-        HIPCHK(h, hipMemcpyAsync(hess, h->d_mknhb, sizeof(double) * n * n * M, hipMemcpyDeviceToHost, h->main_stream));
-    }
+    if (hess) HIPCHK(h, hipMemcpyAsync(hess, h->d_mknhb, sizeof(double) * n * n * M, hipMemcpyDeviceToHost, h->main_stream));
     rc = markov_finish(h, M, loglik, info);
     if (rc) return rc;
     h->markov_count += M;
@@ -3076,26 +3086,18 @@ extern "C" int gpcc_loglik_hess_full_noise_markov_batch(gpcc_handle_t h, int M, 
         }))
         return rc;
     GPCC_ON_DEVICE(h, h->device);
-    const int L = h->L, n = 3 * L + 1, W = 4 * L + 1, slots = gpcc_markov_noise_hess_slots(L), tslots = gpcc_markov_noise_hess_tau_slots(L);
+    const int W = 4 * h->L + 1, tslots = gpcc_markov_noise_hess_tau_slots(h->L);
     double *dd, *da, *dr;
     rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
-        int g = markov_noise_grad_grow(h, M);
-        if (!g && hess) g = grow_buf(h, &h->d_mknhs, &h->mknhs_cap, (long)slots * M);
-        if (!g && hess) g = grow_buf(h, &h->d_mknhb, &h->mknhb_cap, (long)n * n * M);
+        int g = markov_noise_hess_grow(h, M, hess != nullptr);
         if (!g && hess) g = grow_buf(h, &h->d_mknts, &h->mknts_cap, (long)tslots * M);
-        if (!g && hess) g = grow_buf(h, &h->d_mkntb, &h->mkntb_cap, (long)W * W * M);
-        return g;
+        return (g || !hess) ? g : grow_buf(h, &h->d_mkntb, &h->mkntb_cap, (long)W * W * M);
     });
     if (rc) return rc;
     GpccMarkovNoiseArgs a;
-    rc = markov_noise_grad_enqueue(h, M, dd, da, dr, kappa, nu, grad, a);
+    rc = markov_noise_hess_enqueue(h, M, dd, da, dr, kappa, nu, grad, hess != nullptr, a);
     if (rc) return rc;
     if (hess) {
-        GpccMarkovNoiseHessArgs b;
-        b.kappa = a.kappa; b.nu = a.nu; b.slot = h->d_mknhs; b.hess = h->d_mknhb;
-        rc = markov_slots_launch(h, "gpcc_markov_noise_hess", MK_NOISE_HESS, M, dd, da, dr, slots, b, markov_noise_lds(h),
-                                 gpcc_markov_noise_hess_launch);
-        if (rc) return rc;
         GpccMarkovNoiseHessTauArgs c;
         c.kappa = a.kappa; c.nu = a.nu; c.slot = h->d_mknts; c.noise = h->d_mknhb; c.hess = h->d_mkntb;
         rc = markov_slots_launch(h, "gpcc_markov_noise_hess_tau", MK_NOISE_HESS_TAU, M, dd, da, dr, tslots, c, markov_noise_lds(h),

@@ -161,7 +161,8 @@ __device__ __forceinline__ void gpcc_mkf_moment(const double (&Q)[P][P], const d
         }
 }
 
-// Ph = C h, dPh = dC h + C dh, S = h'Ph + sigma^2, dS = dh'Ph + h'dPh: gpcc_mkg_update's, statement by statement
+// Ph = C h, dPh = dC h + C dh, S = h'Ph + sigma^2, dS = dh'Ph + h'dPh: the statements that open gpcc_mkg_update, repeated
+// here because this walk needs the four values themselves
 template <int P, int NOFF>
 __device__ __forceinline__ void gpcc_mkf_gain(int b, double al, bool dh, double s2, const double (&C)[P + NOFF][P + NOFF],
                                               const double (&dC)[P + NOFF][P + NOFF], double (&Ph)[P + NOFF], double (&dPh)[P + NOFF],

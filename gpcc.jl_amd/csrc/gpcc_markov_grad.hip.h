@@ -29,12 +29,26 @@
 // before (bprev) for the lags' tangents.  The primal recursion is the one filter step of gpcc_markov.hip.h, called once.  Per-slot
 // results go to slot[slot][row], so a wave's stores coalesce.  Lanes beyond M compute row M - 1 again and store nothing.  No atomics,
 // no communication between lanes.
+//
+// ONE WALK, TWO KERNELS.  gpcc_mkg_walk is a template on the lane's noise policy (below): gpcc_markov_grad instantiates it on
+// GpccMkPlain, gpcc_markov_noise_grad (gpcc_markov_noise.hip.h) on a lane with its own kappa and nu for its alpha, rho and tau slots.
+// gpcc_mkg_update has the kind GPCC_MKG_NOISE for the tangent by a kappa or a nu, which the second-order walks carry as well.
 #pragma once
 #include "gpcc_markov.hip.h"
 
 #define GPCC_MKG_ALPHA 0
 #define GPCC_MKG_RHO 1
 #define GPCC_MKG_TAU 2
+#define GPCC_MKG_NOISE 3   /* a kappa or a nu of gpcc_markov_noise.hip.h: moves as an alpha's tangent, its update has dvar in place of dh */
+
+// THE NOISE POLICY of a walk: the variance a lane observes a point of band b with, from the handle's sigma_i^2.  Every derivative walk of
+// this path (gpcc_mkg_walk, gpcc_mkh_walk, gpcc_mkt_walk) is a template on it and has one definition.  A plain lane holds nothing and
+// sees sigma_i^2 itself; a lane with a noise model of its own is gpcc_markov_noise.hip.h's GpccMknLane (kappa_b^2 sigma_i^2 + nu_b).
+// `noise` says at compile time whether variance tangents exist at all: where it is false no statement of a walk has an operand for them
+struct GpccMkPlain {
+    static constexpr bool noise = false;
+    __device__ __forceinline__ double var(const GpccMkLane &, int, double s2) const { return s2; }
+};
 
 // GpccMarkovArgs' fields under the same names (the host fills both through one template) and the slots
 struct GpccMarkovGradArgs {
@@ -113,8 +127,8 @@ __device__ __forceinline__ void gpcc_mkg_dstationary(double lam, double lam2, do
     }
 }
 
-// the tangent of gpcc_mk_propagate, from the state BEFORE it.  KIND: GPCC_MKG_ALPHA has neither dA nor dPinf, GPCC_MKG_TAU has dA
-// where `ad`, GPCC_MKG_RHO has both
+// the tangent of gpcc_mk_propagate, from the state BEFORE it.  KIND: GPCC_MKG_ALPHA and GPCC_MKG_NOISE have neither dA nor dPinf,
+// GPCC_MKG_TAU has dA where `ad`, GPCC_MKG_RHO has both
 template <int P, int NOFF, int KIND>
 __device__ __forceinline__ void gpcc_mkg_propagate(const double (&A)[P][P], const double (&Ad)[P][P], bool ad, const double (&Q)[P][P],
                                                    const double (&Qd)[P][P], const double (&mu)[P + NOFF],
@@ -169,7 +183,7 @@ __device__ __forceinline__ void gpcc_mkg_propagate(const double (&A)[P][P], cons
 #pragma unroll
         for (int i2 = 0; i2 < P; ++i2) dC[i2][P + c] = t1[i2];
     }
-    if constexpr (KIND != GPCC_MKG_ALPHA) {
+    if constexpr (KIND == GPCC_MKG_RHO || KIND == GPCC_MKG_TAU) {
         if (ad) {
             // the dA terms: dmu += dA mu, dC_xx += dA D A' + (dA D A')', dC_xb += dA C_xb
             double T[P][P], W[P][P];
@@ -216,10 +230,12 @@ __device__ __forceinline__ void gpcc_mkg_propagate(const double (&A)[P][P], cons
 }
 
 // the tangent of gpcc_mk_update, from the state BEFORE it (after the propagation).  dh: this observation's h moves with the lane's alpha
+// (GPCC_MKG_ALPHA reads it).  dvar: the tangent of this observation's variance, [b == l] (2 kappa_l sigma_i^2 or 1) for the kappa or nu
+// of band l (GPCC_MKG_NOISE reads it): it enters through dS alone, no other kind has an operand for it
 template <int P, int NOFF, int KIND>
 __device__ __forceinline__ void gpcc_mkg_update(int b, double al, bool dh, double r, double s2, const double (&mu)[P + NOFF],
                                                 const double (&C)[P + NOFF][P + NOFF], double (&dmu)[P + NOFF],
-                                                double (&dC)[P + NOFF][P + NOFF], double &dll)
+                                                double (&dC)[P + NOFF][P + NOFF], double &dll, double dvar = 0.0)
 {
     constexpr int NS = P + NOFF;
     double Ph[NS], dPh[NS];
@@ -234,7 +250,8 @@ __device__ __forceinline__ void gpcc_mkg_update(int b, double al, bool dh, doubl
         Ph[i2] = acc;
         dPh[i2] = dacc;       // dC h so far
     }
-    double S = al * Ph[0] + s2, hm = al * mu[0], dS = al * dPh[0], dhm = al * dmu[0];
+    // (dvar in its place among the four, in one expression with the product, as s2 is in S's: a compile-time choice, never a + 0.0)
+    double S = al * Ph[0] + s2, hm = al * mu[0], dS = KIND == GPCC_MKG_NOISE ? al * dPh[0] + dvar : al * dPh[0], dhm = al * dmu[0];
 #pragma unroll
     for (int c = 0; c < NOFF; ++c) {
         S += (b == c) ? Ph[P + c] : 0.0;
@@ -260,11 +277,10 @@ __device__ __forceinline__ void gpcc_mkg_update(int b, double al, bool dh, doubl
 }
 
 // one lane's walk: KIND of slot, tb: the band of an alpha or tau slot, rb / rr: the band whose rank among ties is rr instead of its
-// index (rb = -1: none), handed to gpcc_mk_next<true>.  gpcc_mkn_walk of gpcc_markov_noise.hip.h is this walk statement by statement,
-// on the mapped variance kappa^2 sigma^2 + nu in place of p.s2: a change here is made there as well (tests/test_gpu_markov_noise.py
-// reports whether the two are still bitwise the same at kappa = 1, nu = 0)
-template <int P, int NOFF, int KIND>
-__device__ __forceinline__ double gpcc_mkg_walk(const GpccMarkovGradArgs &a, const GpccMkLane &ln, int tb, int rb, int rr)
+// index (rb = -1: none), handed to gpcc_mk_next<true>.  nz: the lane's noise policy.  The alpha, rho and tau slots of gpcc_markov_grad
+// (GpccMkPlain) and of gpcc_markov_noise_grad (GpccMknLane) are this one walk; ARGS is the kernel's, read by the cursor as it is there
+template <int P, int NOFF, int KIND, class ARGS, class NZ>
+__device__ __forceinline__ double gpcc_mkg_walk(const ARGS &a, const GpccMkLane &ln, const NZ &nz, int tb, int rb, int rr)
 {
     constexpr int NS = P + NOFF;
     const double rho = ln.rho;
@@ -286,7 +302,7 @@ __device__ __forceinline__ double gpcc_mkg_walk(const GpccMarkovGradArgs &a, con
     for (int j = 0; j < a.N; ++j) {
         const GpccMkPoint p = gpcc_mk_next<true>(a, ln, j, sprev, rb, rr);
         const int b = p.b;
-        const double d = p.d;
+        const double d = p.d, s2 = nz.var(ln, b, p.s2);
 
         double A[P][P], Ad[P][P];
         gpcc_mk_transition<P>(lam, lam2, d, A);
@@ -307,8 +323,8 @@ __device__ __forceinline__ double gpcc_mkg_walk(const GpccMarkovGradArgs &a, con
         bprev = b;
         gpcc_mkg_propagate<P, NOFF, KIND>(A, Ad, ad, Q, Qd, mu, C, dmu, dC);
         gpcc_mk_propagate<P, NOFF>(A, Q, mu, C);
-        gpcc_mkg_update<P, NOFF, KIND>(b, p.al, KIND == GPCC_MKG_ALPHA && b == tb, p.r, p.s2, mu, C, dmu, dC, dll);
-        gpcc_mk_update<P, NOFF>(b, p.al, p.r, p.s2, mu, C, ll);
+        gpcc_mkg_update<P, NOFF, KIND>(b, p.al, KIND == GPCC_MKG_ALPHA && b == tb, p.r, s2, mu, C, dmu, dC, dll);
+        gpcc_mk_update<P, NOFF>(b, p.al, p.r, s2, mu, C, ll);
     }
     return dll;
 }
@@ -324,12 +340,12 @@ __global__ void __launch_bounds__(256) gpcc_markov_grad(const GpccMarkovGradArgs
     const int slot = blockIdx.y;
     double dll;
     if (slot < L) {
-        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_ALPHA>(a, ln, slot, -1, 0);
+        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_ALPHA>(a, ln, GpccMkPlain(), slot, -1, 0);
     } else if (slot == L) {
-        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_RHO>(a, ln, -1, -1, 0);
+        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_RHO>(a, ln, GpccMkPlain(), -1, -1, 0);
     } else {
         const int q = slot - L - 1, tb = a.twice ? q >> 1 : q;
-        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_TAU>(a, ln, tb, a.twice ? tb : -1, (q & 1) ? L : -1);
+        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_TAU>(a, ln, GpccMkPlain(), tb, a.twice ? tb : -1, (q & 1) ? L : -1);
     }
     if (ln.valid) a.slot[(long)slot * a.M + ln.row] = dll;
 }

@@ -19,6 +19,11 @@
 //            ll_ab -= (S_ab / S - S_a S_b / S^2 + 2 eps_a eps_b / S + 2 g eps_ab - 2 g (eps_a S_b + eps_b S_a) / S - g^2 S_ab
 //                      + 2 g^2 S_a S_b / S) / 2,  then the second tangents of mu += Ph g and C -= k Ph', k = Ph / S
 //
+// ONE WALK, TWO KERNELS.  gpcc_mkh_walk and gpcc_mkh_update are templates on the lane's noise policy (gpcc_markov_grad.hip.h).
+// gpcc_markov_hess instantiates them on GpccMkPlain over the four kinds of pair of alpha and rho; gpcc_markov_noise_hess
+// (gpcc_markov_noise_hess.hip.h) on a lane with its own kappa and nu, over those four and the four kinds with a noise parameter, whose
+// variance tangents enter S_a, S_b and S_ab.  In the plain instantiation no statement has an operand for a variance tangent.
+//
 // NOT HERE.  The Fisher information (its expectation needs another recursion) stays with gpcc_loglik_hess_batch /
 // gpcc_loglik_hess_hyper_batch.  The rows of tau are gpcc_markov_hess_tau.hip.h's (gpcc_loglik_hess_markov_batch), built from these pieces.
 //
@@ -38,6 +43,11 @@
 #define GPCC_MKH_AA_OFF 1    /* (alpha_l, alpha_m), l < m */
 #define GPCC_MKH_AR 2        /* (alpha_l, rho) */
 #define GPCC_MKH_RR 3        /* (rho, rho) */
+/* the kinds that only a lane with a noise model has (gpcc_markov_noise_hess.hip.h instantiates them) */
+#define GPCC_MKNH_AN 4       /* (alpha_l, kappa_m or nu_m) */
+#define GPCC_MKNH_RN 5       /* (rho, kappa_m or nu_m) */
+#define GPCC_MKNH_NN_DIAG 6  /* (kappa_l, kappa_l), (nu_l, nu_l) */
+#define GPCC_MKNH_NN_OFF 7   /* two different noise parameters, of one band or of two */
 
 // GpccMarkovArgs' fields under the same names (the host fills them through one template), the slots and the blocks
 struct GpccMarkovHessArgs {
@@ -154,13 +164,15 @@ __device__ __forceinline__ void gpcc_mkh_cross(const double (&A)[P][P], const do
 }
 
 // the second tangent of gpcc_mk_update, from the state and the two tangents BEFORE it (after the propagation).  ha, hb: this
-// observation's h moves with the pair's first / second parameter (an alpha of its band).  A diagonal pair passes its tangent twice
-template <int P, int NOFF>
-__device__ __forceinline__ void gpcc_mkh_update(int b, double al, bool ha, bool hb, double r, double s2, const double (&mu)[P + NOFF],
-                                                const double (&C)[P + NOFF][P + NOFF], const double (&mua)[P + NOFF],
-                                                const double (&Ca)[P + NOFF][P + NOFF], const double (&mub)[P + NOFF],
-                                                const double (&Cb)[P + NOFF][P + NOFF], double (&muab)[P + NOFF],
-                                                double (&Cab)[P + NOFF][P + NOFF], double &hll)
+// observation's h moves with the pair's first / second parameter (an alpha of its band).  A diagonal pair passes its tangent twice.
+// NOISE: the lane carries a noise model, and the tangents of this observation's variance by the pair's parameters enter S_a, S_b and
+// S_ab (dva, dvb, d2v; a noise parameter has no h-tangent).  Without one the three are not read: no statement has an operand for them
+template <int P, int NOFF, bool NOISE>
+__device__ __forceinline__ void gpcc_mkh_update(int b, double al, bool ha, bool hb, double dva, double dvb, double d2v, double r, double s2,
+                                                const double (&mu)[P + NOFF], const double (&C)[P + NOFF][P + NOFF],
+                                                const double (&mua)[P + NOFF], const double (&Ca)[P + NOFF][P + NOFF],
+                                                const double (&mub)[P + NOFF], const double (&Cb)[P + NOFF][P + NOFF],
+                                                double (&muab)[P + NOFF], double (&Cab)[P + NOFF][P + NOFF], double &hll)
 {
     constexpr int NS = P + NOFF;
     double Ph[NS], Pha[NS], Phb[NS], Phab[NS];
@@ -181,6 +193,11 @@ __device__ __forceinline__ void gpcc_mkh_update(int b, double al, bool ha, bool 
         Phab[i2] = accab + (hb ? a0 : 0.0) + (ha ? b0 : 0.0);
     }
     double S = al * Ph[0] + s2, Sa = al * Pha[0], Sb = al * Phb[0], Sab = al * Phab[0];
+    if constexpr (NOISE) {      // each one expression: the product and the variance's tangent contract as S's does
+        Sa = al * Pha[0] + dva;
+        Sb = al * Phb[0] + dvb;
+        Sab = al * Phab[0] + d2v;
+    }
     double hm = al * mu[0], hma = al * mua[0], hmb = al * mub[0], hmab = al * muab[0];
 #pragma unroll
     for (int c = 0; c < NOFF; ++c) {
@@ -213,14 +230,31 @@ __device__ __forceinline__ void gpcc_mkh_update(int b, double al, bool ha, bool 
     }
 }
 
-// one lane's walk over the merged observations for the pair (pa, pb) of kind PAIR (pa, pb: the bands of its alphas)
-template <int P, int NOFF, int PAIR>
-__device__ __forceinline__ double gpcc_mkh_walk(const GpccMarkovHessArgs &a, const GpccMkLane &ln, int pa, int pb)
+// what a lane knows of one parameter of its pair: the band (of an alpha, kappa or nu; -1: rho) and, for a noise parameter, whether it
+// is a nu and the factor of sigma_i^2 in a kappa's dvar (2 kappa).  A plain kernel's pairs read the band alone
+struct GpccMkhParam {
+    int band;
+    bool is_nu;
+    double dk;
+};
+
+// one lane's walk over the merged observations for the pair (pa, pb) of kind PAIR, every observation's variance being the noise policy's
+// (nz.var).  gpcc_markov_hess instantiates the four kinds of alpha and rho on GpccMkPlain; gpcc_markov_noise_hess all eight on
+// GpccMknLane.  A noise tangent has no tangent of the prior, of A or of Pinf and no h-tangent: it is propagated as an alpha's with a
+// zero A-tangent, and the variance's tangents dva, dvb, d2v enter the updates instead; on (rho, noise) the second tangent moves as the
+// rho tangent of the noise "state", the way (alpha, rho)'s moves.  ARGS is the kernel's, read by the cursor as it is there
+template <int P, int NOFF, int PAIR, class ARGS, class NZ>
+__device__ __forceinline__ double gpcc_mkh_walk(const ARGS &a, const GpccMkLane &ln, const NZ &nz, const GpccMkhParam pa, const GpccMkhParam pb)
 {
+    static_assert(NZ::noise || PAIR <= GPCC_MKH_RR, "a pair with a kappa or a nu needs a lane with a noise model");
     constexpr int NS = P + NOFF;
-    constexpr bool DIAG = PAIR == GPCC_MKH_AA_DIAG || PAIR == GPCC_MKH_RR;
-    constexpr bool RHO = PAIR == GPCC_MKH_AR || PAIR == GPCC_MKH_RR;      // some tangent of A is formed
-    constexpr int KA = PAIR == GPCC_MKH_RR ? GPCC_MKG_RHO : GPCC_MKG_ALPHA, KB = RHO ? GPCC_MKG_RHO : GPCC_MKG_ALPHA;
+    constexpr bool DIAG = PAIR == GPCC_MKH_AA_DIAG || PAIR == GPCC_MKH_RR || PAIR == GPCC_MKNH_NN_DIAG;
+    constexpr bool RHO = PAIR == GPCC_MKH_AR || PAIR == GPCC_MKH_RR || PAIR == GPCC_MKNH_RN;      // some tangent of A is formed
+    constexpr bool NA = PAIR == GPCC_MKNH_NN_DIAG || PAIR == GPCC_MKNH_NN_OFF;                    // the first parameter is a noise parameter
+    constexpr bool NB = NA || PAIR == GPCC_MKNH_AN || PAIR == GPCC_MKNH_RN;                       // the second one is
+    constexpr bool RA = PAIR == GPCC_MKH_RR || PAIR == GPCC_MKNH_RN, RB = PAIR == GPCC_MKH_AR || PAIR == GPCC_MKH_RR;   // ... is rho
+    constexpr int KA = NA ? GPCC_MKG_NOISE : (RA ? GPCC_MKG_RHO : GPCC_MKG_ALPHA);
+    constexpr int KB = NB ? GPCC_MKG_NOISE : (RB ? GPCC_MKG_RHO : GPCC_MKG_ALPHA);
     const double rho = ln.rho;
     double lam, lam2, Q[P][P], mu[NS], C[NS][NS];
     gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
@@ -248,8 +282,8 @@ __device__ __forceinline__ double gpcc_mkh_walk(const GpccMarkovHessArgs &a, con
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
             const bool xx = i < P && j < P;
-            Ca[i][j] = (KA == GPCC_MKG_RHO && xx) ? Qr[i < P ? i : 0][j < P ? j : 0] : 0.0;
-            if constexpr (!DIAG) Cb[i][j] = (KB == GPCC_MKG_RHO && xx) ? Qr[i < P ? i : 0][j < P ? j : 0] : 0.0;
+            Ca[i][j] = (RA && xx) ? Qr[i < P ? i : 0][j < P ? j : 0] : 0.0;
+            if constexpr (!DIAG) Cb[i][j] = (RB && xx) ? Qr[i < P ? i : 0][j < P ? j : 0] : 0.0;
             Cab[i][j] = (PAIR == GPCC_MKH_RR && xx) ? Qrr[i < P ? i : 0][j < P ? j : 0] : 0.0;
         }
     }
@@ -258,7 +292,12 @@ __device__ __forceinline__ double gpcc_mkh_walk(const GpccMarkovHessArgs &a, con
     for (int j = 0; j < a.N; ++j) {
         const GpccMkPoint p = gpcc_mk_next<false>(a, ln, j, sprev);
         const int b = p.b;
-        const double d = p.d, al = p.al, r = p.r, s2 = p.s2;
+        const double d = p.d, al = p.al, r = p.r, s2 = nz.var(ln, b, p.s2);
+        // the variance's tangents at this observation (read by the updates of a lane with a noise model only)
+        double dva = 0.0, dvb = 0.0, d2v = 0.0;
+        if constexpr (NA) dva = (b == pa.band) ? (pa.is_nu ? 1.0 : pa.dk * p.s2) : 0.0;
+        if constexpr (NB) dvb = (b == pb.band) ? (pb.is_nu ? 1.0 : pb.dk * p.s2) : 0.0;
+        if constexpr (PAIR == GPCC_MKNH_NN_DIAG) d2v = (b == pa.band && !pa.is_nu) ? 2.0 * p.s2 : 0.0;
 
         double A[P][P], Ar[P][P], Arr[P][P];
         gpcc_mk_transition<P>(lam, lam2, d, A);
@@ -276,17 +315,19 @@ __device__ __forceinline__ double gpcc_mkh_walk(const GpccMarkovHessArgs &a, con
             gpcc_mkh_cross<P, NOFF>(A, Ar, Q, Qr, C, mua, Ca, muab, Cab);
         } else if constexpr (PAIR == GPCC_MKH_AR) {
             gpcc_mkg_propagate<P, NOFF, GPCC_MKG_RHO>(A, Ar, true, Z, Z, mua, Ca, muab, Cab);
+        } else if constexpr (PAIR == GPCC_MKNH_RN) {
+            gpcc_mkg_propagate<P, NOFF, GPCC_MKG_RHO>(A, Ar, true, Z, Z, mub, Cb, muab, Cab);
         } else {
             gpcc_mkg_propagate<P, NOFF, GPCC_MKG_ALPHA>(A, Z, false, Q, Z, mu, C, muab, Cab);
         }
-        gpcc_mkg_propagate<P, NOFF, KA>(A, Ar, KA == GPCC_MKG_RHO, Q, Qr, mu, C, mua, Ca);
-        if constexpr (!DIAG) gpcc_mkg_propagate<P, NOFF, KB>(A, Ar, KB == GPCC_MKG_RHO, Q, Qr, mu, C, mub, Cb);
+        gpcc_mkg_propagate<P, NOFF, KA>(A, Ar, RA, Q, Qr, mu, C, mua, Ca);
+        if constexpr (!DIAG) gpcc_mkg_propagate<P, NOFF, KB>(A, Ar, RB, Q, Qr, mu, C, mub, Cb);
         gpcc_mk_propagate<P, NOFF>(A, Q, mu, C);
         // the update, in the same order
-        const bool ha = KA == GPCC_MKG_ALPHA && b == pa, hb = KB == GPCC_MKG_ALPHA && b == pb;
-        gpcc_mkh_update<P, NOFF>(b, al, ha, hb, r, s2, mu, C, mua, Ca, mub, Cb, muab, Cab, hll);
-        gpcc_mkg_update<P, NOFF, KA>(b, al, ha, r, s2, mu, C, mua, Ca, dll);
-        if constexpr (!DIAG) gpcc_mkg_update<P, NOFF, KB>(b, al, hb, r, s2, mu, C, mub, Cb, dll);
+        const bool ha = !RA && !NA && b == pa.band, hb = !RB && !NB && b == pb.band;
+        gpcc_mkh_update<P, NOFF, NZ::noise>(b, al, ha, hb, dva, dvb, d2v, r, s2, mu, C, mua, Ca, mub, Cb, muab, Cab, hll);
+        gpcc_mkg_update<P, NOFF, KA>(b, al, ha, r, s2, mu, C, mua, Ca, dll, dva);
+        if constexpr (!DIAG) gpcc_mkg_update<P, NOFF, KB>(b, al, hb, r, s2, mu, C, mub, Cb, dll, dvb);
         gpcc_mk_update<P, NOFF>(b, al, r, s2, mu, C, ll);
     }
     return hll;
@@ -307,15 +348,16 @@ __global__ void __launch_bounds__(256) gpcc_markov_hess(const GpccMarkovHessArgs
         ++pa;
     }
     const int pb = pa + rest;
+    const GpccMkhParam qa = {pa, false, 0.0}, qb = {pb, false, 0.0}, qr = {-1, false, 0.0};
     double hll;
     if (pa == L)
-        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_RR>(a, ln, -1, -1);
+        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_RR>(a, ln, GpccMkPlain(), qr, qr);
     else if (pb == L)
-        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AR>(a, ln, pa, -1);
+        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AR>(a, ln, GpccMkPlain(), qa, qr);
     else if (pa == pb)
-        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AA_DIAG>(a, ln, pa, pa);
+        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AA_DIAG>(a, ln, GpccMkPlain(), qa, qa);
     else
-        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AA_OFF>(a, ln, pa, pb);
+        hll = gpcc_mkh_walk<P, NOFF, GPCC_MKH_AA_OFF>(a, ln, GpccMkPlain(), qa, qb);
     if (ln.valid) a.slot[(long)slot * a.M + ln.row] = hll;
 }
 

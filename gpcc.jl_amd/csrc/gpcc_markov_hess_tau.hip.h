@@ -17,6 +17,10 @@
 // gpcc_mkt_cross off it.  A tau tangent of A is formed only on the steps next to a point of its band.  The update is gpcc_mkh_update
 // (h_a = e_1 for an alpha of the observed band only).
 //
+// ONE WALK, TWO KERNELS.  gpcc_mkt_walk is a template on the lane's noise policy (gpcc_markov_grad.hip.h): gpcc_markov_hess_tau
+// instantiates it on GpccMkPlain over the four kinds of pair below; gpcc_markov_noise_hess_tau (gpcc_markov_noise_hess_tau.hip.h) on a lane
+// with its own kappa and nu, over those four and (tau, kappa or nu), whose first tangent is a noise tangent (gpcc_markov_hess.hip.h).
+//
 // TIES.  Matern-3/2 and -5/2 are twice differentiable at zero lag: the fixed-order second tangent is the derivative, there is no tie
 // convention.  OU is not: on a row where two points of different bands have exactly equal shifted times -- a step with d == 0 and
 // band != bprev after the first -- no second derivative by tau exists, and gpcc_loglik_hess_batch's convention there (k_ss = 1 / rho^2,
@@ -39,6 +43,7 @@
 #define GPCC_MKT_RT 1        /* (rho, tau_l) */
 #define GPCC_MKT_TT_DIAG 2   /* (tau_l, tau_l) */
 #define GPCC_MKT_TT_OFF 3    /* (tau_l, tau_m), l < m */
+#define GPCC_MKNT_TN 8       /* (tau_l, kappa_m or nu_m): a lane with a noise model only (gpcc_markov_noise_hess_tau.hip.h instantiates it) */
 
 // GpccMarkovArgs' fields under the same names (the host fills them through one template), the slots and the blocks
 struct GpccMarkovHessTauArgs {
@@ -133,14 +138,19 @@ __device__ __forceinline__ void gpcc_mkt_cross(const double (&A)[P][P], const do
         }
 }
 
-// one lane's walk over the merged observations for a pair of kind PAIR.  pa: the band of the pair's alpha (GPCC_MKT_AT), ta: of its
-// first tau (GPCC_MKT_TT_OFF), tb: of its (second) tau.  NaN on an OU row with a cross-band tie
-template <int P, int NOFF, int PAIR>
-__device__ __forceinline__ double gpcc_mkt_walk(const GpccMarkovHessTauArgs &a, const GpccMkLane &ln, int pa, int ta, int tb)
+// one lane's walk over the merged observations for a pair of kind PAIR, every observation's variance being the noise policy's (nz.var).
+// pa: the band of the pair's alpha (GPCC_MKT_AT), ta: of its first tau (GPCC_MKT_TT_OFF), tb: of its (second) tau; for GPCC_MKNT_TN tb is
+// the band of the tau and pn the noise parameter, which no other kind reads.  gpcc_markov_hess_tau instantiates the four kinds without a
+// noise parameter on GpccMkPlain; gpcc_markov_noise_hess_tau all five on GpccMknLane.  ARGS is the kernel's, read by the cursor as it is
+// there.  NaN on an OU row with a cross-band tie
+template <int P, int NOFF, int PAIR, class ARGS, class NZ>
+__device__ __forceinline__ double gpcc_mkt_walk(const ARGS &a, const GpccMkLane &ln, const NZ &nz, int pa, int ta, int tb, const GpccMkhParam pn)
 {
+    static_assert(NZ::noise || PAIR != GPCC_MKNT_TN, "a pair with a kappa or a nu needs a lane with a noise model");
     constexpr int NS = P + NOFF;
     constexpr bool DIAG = PAIR == GPCC_MKT_TT_DIAG;
-    constexpr int KA = PAIR == GPCC_MKT_AT ? GPCC_MKG_ALPHA : (PAIR == GPCC_MKT_RT ? GPCC_MKG_RHO : GPCC_MKG_TAU);
+    constexpr bool TN = PAIR == GPCC_MKNT_TN;
+    constexpr int KA = TN ? GPCC_MKG_NOISE : (PAIR == GPCC_MKT_AT ? GPCC_MKG_ALPHA : (PAIR == GPCC_MKT_RT ? GPCC_MKG_RHO : GPCC_MKG_TAU));
     const double rho = ln.rho;
     double lam, lam2, Q[P][P], mu[NS], C[NS][NS];
     gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
@@ -176,16 +186,19 @@ __device__ __forceinline__ double gpcc_mkt_walk(const GpccMarkovHessTauArgs &a, 
     for (int j = 0; j < a.N; ++j) {
         const GpccMkPoint p = gpcc_mk_next<false>(a, ln, j, sprev);
         const int b = p.b;
-        const double d = p.d, al = p.al, r = p.r, s2 = p.s2;
+        const double d = p.d, al = p.al, r = p.r, s2 = nz.var(ln, b, p.s2);
         if constexpr (P == 1) tie = tie || (j > 0 && d == 0.0 && b != bprev);
+        // the variance's tangent by the pair's noise parameter at this observation (read by the updates of a lane with a noise model only)
+        double dva = 0.0;
+        if constexpr (TN) dva = (b == pn.band) ? (pn.is_nu ? 1.0 : pn.dk * p.s2) : 0.0;
         // the lags' tangents by the pair's taus
         const int cb = (j == 0) ? 0 : (int)(bprev == tb) - (int)(b == tb);
         const int ca = (PAIR != GPCC_MKT_TT_OFF || j == 0) ? 0 : (int)(bprev == ta) - (int)(b == ta);
         bprev = b;
         const bool adb = cb != 0;
 
-        // A, the first tangent of A by the pair's first parameter where it is not its tau (Aa: A_rho or A_tau_a), by its tau (Ab), and
-        // the second (Aab)
+        // A, the first tangent of A by the pair's first parameter where it is not its tau (Aa: A_rho or A_tau_a; zero for an alpha or
+        // a noise parameter), by its tau (Ab), and the second (Aab)
         double A[P][P], Aa[P][P], Ab[P][P], Aab[P][P];
         gpcc_mk_transition<P>(lam, lam2, d, A);
         gpcc_mkg_dtransition_lag<P>(lam, lam2, (double)cb, A, Ab);
@@ -210,10 +223,10 @@ __device__ __forceinline__ double gpcc_mkt_walk(const GpccMarkovHessTauArgs &a, 
                 for (int k = 0; k < P; ++k) Aa[i2][k] = Aab[i2][k] = 0.0;
         }
         // the step: the second tangent from the state and the tangents before it, then the tangents, then the state.  An (alpha, tau)
-        // pair's second tangent is the tau tangent of (mu_alpha, C_alpha), whose stationary part is zero; the others' that of the
-        // state with A_ab, plus the terms in the first tangents of A
+        // and a (tau, noise) pair's second tangent is the tau tangent of (mu_a, C_a), whose stationary part is zero; the others' that
+        // of the state with A_ab, plus the terms in the first tangents of A
         {
-            constexpr bool AT = PAIR == GPCC_MKT_AT;
+            constexpr bool AT = PAIR == GPCC_MKT_AT || TN;
             const double(&smu)[NS] = AT ? mua : mu;
             const double(&sC)[NS][NS] = AT ? Ca : C;
             const double(&sQ)[P][P] = AT ? Z : Q;
@@ -222,7 +235,7 @@ __device__ __forceinline__ double gpcc_mkt_walk(const GpccMarkovHessTauArgs &a, 
         }
         if constexpr (DIAG) {
             if (adb) gpcc_mkh_cross<P, NOFF>(A, Ab, Q, Z, C, mua, Ca, muab, Cab);
-        } else if constexpr (PAIR != GPCC_MKT_AT) {
+        } else if constexpr (PAIR == GPCC_MKT_RT || PAIR == GPCC_MKT_TT_OFF) {
             if (ada || adb) gpcc_mkt_cross<P, NOFF>(A, Aa, Ab, Q, Qr, C, mua, Ca, mub, Cb, muab, Cab);
         }
         {
@@ -233,8 +246,8 @@ __device__ __forceinline__ double gpcc_mkt_walk(const GpccMarkovHessTauArgs &a, 
         gpcc_mk_propagate<P, NOFF>(A, Q, mu, C);
         // the update, in the same order
         const bool ha = PAIR == GPCC_MKT_AT && b == pa;
-        gpcc_mkh_update<P, NOFF>(b, al, ha, false, r, s2, mu, C, mua, Ca, mub, Cb, muab, Cab, hll);
-        gpcc_mkg_update<P, NOFF, KA>(b, al, ha, r, s2, mu, C, mua, Ca, dll);
+        gpcc_mkh_update<P, NOFF, NZ::noise>(b, al, ha, false, dva, 0.0, 0.0, r, s2, mu, C, mua, Ca, mub, Cb, muab, Cab, hll);
+        gpcc_mkg_update<P, NOFF, KA>(b, al, ha, r, s2, mu, C, mua, Ca, dll, dva);
         if constexpr (!DIAG) gpcc_mkg_update<P, NOFF, GPCC_MKG_TAU>(b, al, false, r, s2, mu, C, mub, Cb, dll);
         gpcc_mk_update<P, NOFF>(b, al, r, s2, mu, C, ll);
     }
@@ -250,14 +263,15 @@ __global__ void __launch_bounds__(256) gpcc_markov_hess_tau(const GpccMarkovHess
 
     // the pair of this workgroup (uniform)
     const int slot = blockIdx.y;
+    const GpccMkhParam none = {-1, false, 0.0};
     double hll;
     if (slot < L * L) {
-        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_AT>(a, ln, slot / L, -1, slot % L);
+        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_AT>(a, ln, GpccMkPlain(), slot / L, -1, slot % L, none);
     } else if (slot < L * L + L) {
-        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_RT>(a, ln, -1, -1, slot - L * L);
+        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_RT>(a, ln, GpccMkPlain(), -1, -1, slot - L * L, none);
     } else if (slot < L * L + 2 * L) {
         const int l = slot - L * L - L;
-        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_TT_DIAG>(a, ln, -1, l, l);
+        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_TT_DIAG>(a, ln, GpccMkPlain(), -1, l, l, none);
     } else {
         // (tau_l, tau_m), l < m, rows of the strict upper triangle one after the other
         int ta = 0, rest = slot - L * L - 2 * L;
@@ -265,7 +279,7 @@ __global__ void __launch_bounds__(256) gpcc_markov_hess_tau(const GpccMarkovHess
             rest -= L - 1 - ta;
             ++ta;
         }
-        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_TT_OFF>(a, ln, -1, ta, ta + 1 + rest);
+        hll = gpcc_mkt_walk<P, NOFF, GPCC_MKT_TT_OFF>(a, ln, GpccMkPlain(), -1, ta, ta + 1 + rest, none);
     }
     if (ln.valid) a.slot[(long)slot * a.M + ln.row] = hll;
 }

@@ -13,12 +13,16 @@
 // A kappa or nu that is negative or not finite: info = -3, after -1 (alpha) and -2 (rho).
 //
 // gpcc_markov_noise_grad<P, NOFF>: ONE LANE PER (ROW, PARAMETER SLOT), the slot being blockIdx.y as in gpcc_markov_grad: L alpha, one
-// rho, L tau (OU: 2L, the first / last pair), then L kappa and L nu.  The alpha, rho and tau slots are gpcc_markov_grad's walk on s2'
-// (a copy of gpcc_mkg_walk that differs in the one statement: the existing kernel's instantiations stay as they are).  A NOISE SLOT of
-// band l is the easiest tangent of all: no dA, no dPinf, no dh, the lowest-band-first order; the observation variance alone moves,
+// rho, L tau (OU: 2L, the first / last pair), then L kappa and L nu.  The alpha, rho and tau slots are gpcc_mkg_walk itself, instantiated
+// on this header's noise policy (GpccMknLane: every observation's variance is s2') where gpcc_markov_grad instantiates it on GpccMkPlain.
+// A NOISE SLOT of band l is the easiest tangent of all: no dA, no dPinf, no dh, the lowest-band-first order; the observation variance
+// alone moves,
 //     dvar = [b == l] (2 kappa_l sigma_i^2  or  1)
-// and enters the update's tangent through dS only.  With dmu, dC the tangents before the update, (dS, dhm, dPh) as gpcc_mkg_update
-// forms them and dS += dvar, everything after is gpcc_mkg_update's.  Its propagate is gpcc_mkg_propagate<P, NOFF, GPCC_MKG_ALPHA>.
+// and enters the update's tangent through dS only: gpcc_mkg_update<.., GPCC_MKG_NOISE>.  Its propagate is an alpha's
+// (gpcc_mkg_propagate<P, NOFF, GPCC_MKG_ALPHA>).
+//
+// WHAT IS HERE is what the noise model alone has: the policy, the Args struct, the slot count, the LDS behind the shared region, the
+// noise slot's walk and the two kernels' slot decoding.
 #pragma once
 #include "gpcc_markov_grad.hip.h"
 
@@ -47,10 +51,17 @@ static inline size_t gpcc_markov_noise_lds_bytes(int N, int L, int threads, bool
     return gpcc_markov_lds_bytes(N, L, threads, stage) + (size_t)GPCC_MARKOV_NOISE_LANE_BYTES * L * threads;
 }
 
-// a lane's noise model: kappa^2 and nu in LDS, [band][thread] (kappa itself is not kept: a kappa slot reads its one from the row again)
+// a lane's noise model: kappa^2 and nu in LDS, [band][thread] (kappa itself is not kept: a kappa slot reads its one from the row again).
+// It is the noise policy (gpcc_markov_grad.hip.h, beside GpccMkPlain) that the derivative walks of the noise kernels are instantiated on
 struct GpccMknLane {
+    static constexpr bool noise = true;
     double *sk2, *snu;                     // LDS, [band][thread]
     int info;                              // gpcc_mk_load_row's, or -3
+    // the variance the lane sees at a point of band b
+    __device__ __forceinline__ double var(const GpccMkLane &ln, int b, double s2) const
+    {
+        return fma(sk2[b * ln.nthr + ln.tid], s2, snu[b * ln.nthr + ln.tid]);
+    }
 };
 
 // the family's prologue behind gpcc_mk_open: carves its part of the LDS after the shared region (which ends at the cursors, L nthr
@@ -74,12 +85,6 @@ __device__ __forceinline__ GpccMknLane gpcc_mkn_open(const ARGS &a, const GpccMk
     return nl;
 }
 
-// the variance a lane sees at a point of band b
-__device__ __forceinline__ double gpcc_mkn_var(const GpccMkLane &ln, const GpccMknLane &nl, int b, double s2)
-{
-    return fma(nl.sk2[b * ln.nthr + ln.tid], s2, nl.snu[b * ln.nthr + ln.tid]);
-}
-
 template <int P, int NOFF>
 __global__ void __launch_bounds__(256) gpcc_markov_noise_eval(const GpccMarkovNoiseArgs a)
 {
@@ -98,7 +103,7 @@ __global__ void __launch_bounds__(256) gpcc_markov_noise_eval(const GpccMarkovNo
         double A[P][P];
         gpcc_mk_transition<P>(lam, lam2, p.d, A);
         gpcc_mk_propagate<P, NOFF>(A, Q, mu, C);
-        const bool ok = gpcc_mk_update<P, NOFF>(p.b, p.al, p.r, gpcc_mkn_var(ln, nl, p.b, p.s2), mu, C, ll);
+        const bool ok = gpcc_mk_update<P, NOFF>(p.b, p.al, p.r, nl.var(ln, p.b, p.s2), mu, C, ll);
         info = (info == 0 && !ok) ? j + 1 : info;   // first predictive variance that is not positive and finite
     }
     if (ln.valid) {
@@ -107,96 +112,8 @@ __global__ void __launch_bounds__(256) gpcc_markov_noise_eval(const GpccMarkovNo
     }
 }
 
-// gpcc_mkg_walk on the mapped variance (the alpha, rho and tau slots): that walk, statement by statement, with p.s2 replaced
-template <int P, int NOFF, int KIND>
-__device__ __forceinline__ double gpcc_mkn_walk(const GpccMarkovNoiseArgs &a, const GpccMkLane &ln, const GpccMknLane &nl, int tb, int rb,
-                                                int rr)
-{
-    constexpr int NS = P + NOFF;
-    const double rho = ln.rho;
-    double lam, lam2, Q[P][P], mu[NS], C[NS][NS];
-    gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
-    double Qd[P][P], dmu[NS], dC[NS][NS];
-    const double dlam = -lam / rho;
-    gpcc_mkg_dstationary<P>(lam, lam2, KIND == GPCC_MKG_RHO ? dlam : 0.0, Qd);
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        dmu[i] = 0.0;
-#pragma unroll
-        for (int j = 0; j < NS; ++j) dC[i][j] = (KIND == GPCC_MKG_RHO && i < P && j < P) ? Qd[i][j] : 0.0;
-    }
-
-    double ll = 0.0, dll = 0.0, sprev = 0.0;
-    int bprev = -1;
-    for (int j = 0; j < a.N; ++j) {
-        const GpccMkPoint p = gpcc_mk_next<true>(a, ln, j, sprev, rb, rr);
-        const int b = p.b;
-        const double d = p.d, s2 = gpcc_mkn_var(ln, nl, b, p.s2);
-
-        double A[P][P], Ad[P][P];
-        gpcc_mk_transition<P>(lam, lam2, d, A);
-        bool ad = false;
-        if constexpr (KIND == GPCC_MKG_RHO) {
-            ad = true;
-            gpcc_mkg_dtransition_rate<P>(lam, lam2, d, dlam, Ad);
-        } else if constexpr (KIND == GPCC_MKG_TAU) {
-            const int dd = (j == 0) ? 0 : (int)(bprev == tb) - (int)(b == tb);
-            ad = dd != 0;
-            gpcc_mkg_dtransition_lag<P>(lam, lam2, (double)dd, A, Ad);
-        } else {
-#pragma unroll
-            for (int i2 = 0; i2 < P; ++i2)
-#pragma unroll
-                for (int k = 0; k < P; ++k) Ad[i2][k] = 0.0;
-        }
-        bprev = b;
-        gpcc_mkg_propagate<P, NOFF, KIND>(A, Ad, ad, Q, Qd, mu, C, dmu, dC);
-        gpcc_mk_propagate<P, NOFF>(A, Q, mu, C);
-        gpcc_mkg_update<P, NOFF, KIND>(b, p.al, KIND == GPCC_MKG_ALPHA && b == tb, p.r, s2, mu, C, dmu, dC, dll);
-        gpcc_mk_update<P, NOFF>(b, p.al, p.r, s2, mu, C, ll);
-    }
-    return dll;
-}
-
-// the tangent of gpcc_mk_update for a noise slot, from the state BEFORE it: gpcc_mkg_update without dh, plus dvar in dS
-template <int P, int NOFF>
-__device__ __forceinline__ void gpcc_mkn_update(int b, double al, double dvar, double r, double s2, const double (&mu)[P + NOFF],
-                                                const double (&C)[P + NOFF][P + NOFF], double (&dmu)[P + NOFF],
-                                                double (&dC)[P + NOFF][P + NOFF], double &dll)
-{
-    constexpr int NS = P + NOFF;
-    double Ph[NS], dPh[NS];
-#pragma unroll
-    for (int i2 = 0; i2 < NS; ++i2) {
-        double acc = al * GPCC_MK_SYM(C, i2, 0), dacc = al * GPCC_MK_SYM(dC, i2, 0);
-#pragma unroll
-        for (int c = 0; c < NOFF; ++c) {
-            acc += (b == c) ? GPCC_MK_SYM(C, i2, P + c) : 0.0;
-            dacc += (b == c) ? GPCC_MK_SYM(dC, i2, P + c) : 0.0;
-        }
-        Ph[i2] = acc;
-        dPh[i2] = dacc;
-    }
-    double S = al * Ph[0] + s2, hm = al * mu[0], dS = al * dPh[0] + dvar, dhm = al * dmu[0];
-#pragma unroll
-    for (int c = 0; c < NOFF; ++c) {
-        S += (b == c) ? Ph[P + c] : 0.0;
-        hm += (b == c) ? mu[P + c] : 0.0;
-        dS += (b == c) ? dPh[P + c] : 0.0;
-        dhm += (b == c) ? dmu[P + c] : 0.0;
-    }
-    const double inv = 1.0 / S, g = (r - hm) * inv, dg = (-dhm - g * dS) * inv;
-    dll -= 0.5 * (dS * inv - 2.0 * g * dhm - g * g * dS);
-#pragma unroll
-    for (int i2 = 0; i2 < NS; ++i2) {
-        dmu[i2] += dPh[i2] * g + Ph[i2] * dg;
-        const double ki = Ph[i2] * inv, dki = dPh[i2] * inv - ki * inv * dS;
-#pragma unroll
-        for (int k = i2; k < NS; ++k) dC[i2][k] -= dki * Ph[k] + ki * dPh[k];
-    }
-}
-
-// a noise slot's walk: tb its band; a kappa slot has dvar = dk sigma^2 with dk = 2 kappa_tb, a nu slot (is_nu) dvar = 1
+// a noise slot's walk, the one walk that only a lane with a noise model has: tb its band; a kappa slot has dvar = dk sigma^2 with
+// dk = 2 kappa_tb, a nu slot (is_nu) dvar = 1.  Its tangent is propagated as an alpha's and updated by gpcc_mkg_update<.., GPCC_MKG_NOISE>
 template <int P, int NOFF>
 __device__ __forceinline__ double gpcc_mkn_walk_noise(const GpccMarkovNoiseArgs &a, const GpccMkLane &ln, const GpccMknLane &nl, int tb,
                                                       bool is_nu, double dk)
@@ -220,13 +137,13 @@ __device__ __forceinline__ double gpcc_mkn_walk_noise(const GpccMarkovNoiseArgs 
     for (int j = 0; j < a.N; ++j) {
         const GpccMkPoint p = gpcc_mk_next<false>(a, ln, j, sprev);
         const int b = p.b;
-        const double s2 = gpcc_mkn_var(ln, nl, b, p.s2);
+        const double s2 = nl.var(ln, b, p.s2);
         const double dvar = (b == tb) ? (is_nu ? 1.0 : dk * p.s2) : 0.0;
         double A[P][P];
         gpcc_mk_transition<P>(lam, lam2, p.d, A);
         gpcc_mkg_propagate<P, NOFF, GPCC_MKG_ALPHA>(A, Zd, false, Q, Zd, mu, C, dmu, dC);
         gpcc_mk_propagate<P, NOFF>(A, Q, mu, C);
-        gpcc_mkn_update<P, NOFF>(b, p.al, dvar, p.r, s2, mu, C, dmu, dC, dll);
+        gpcc_mkg_update<P, NOFF, GPCC_MKG_NOISE>(b, p.al, false, p.r, s2, mu, C, dmu, dC, dll, dvar);
         gpcc_mk_update<P, NOFF>(b, p.al, p.r, s2, mu, C, ll);
     }
     return dll;
@@ -244,12 +161,12 @@ __global__ void __launch_bounds__(256) gpcc_markov_noise_grad(const GpccMarkovNo
     const int slot = blockIdx.y;
     double dll;
     if (slot < L) {
-        dll = gpcc_mkn_walk<P, NOFF, GPCC_MKG_ALPHA>(a, ln, nl, slot, -1, 0);
+        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_ALPHA>(a, ln, nl, slot, -1, 0);
     } else if (slot == L) {
-        dll = gpcc_mkn_walk<P, NOFF, GPCC_MKG_RHO>(a, ln, nl, -1, -1, 0);
+        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_RHO>(a, ln, nl, -1, -1, 0);
     } else if (slot < L + 1 + ntau) {
         const int q = slot - L - 1, tb = a.twice ? q >> 1 : q;
-        dll = gpcc_mkn_walk<P, NOFF, GPCC_MKG_TAU>(a, ln, nl, tb, a.twice ? tb : -1, (q & 1) ? L : -1);
+        dll = gpcc_mkg_walk<P, NOFF, GPCC_MKG_TAU>(a, ln, nl, tb, a.twice ? tb : -1, (q & 1) ? L : -1);
     } else {
         const int q = slot - L - 1 - ntau, tb = q < L ? q : q - L;
         const long m_ = ln.valid ? ln.row : a.M - 1;
