@@ -288,6 +288,19 @@ class Objective:
             raise ValueError("delays and alpha must be (M, L) = (%d, %d)" % (M, self.L))
         return M, delays, alpha, rho
 
+    def _markov(self, symbol, delays, alpha, rho, shapes, noise=None):
+        """The linear-time value or derivative entry `symbol` -> (loglik[M], one array (M,) + shape per shape of shapes, info[M]).
+        noise: (kappa, nu) of a noise entry, which takes them behind rho (_noise); None for a plain entry."""
+        M, delays, alpha, rho = self._params(delays, alpha, rho)
+        params = [delays, alpha, rho]
+        if noise is not None:
+            params += [self._noise(M, noise[0], "kappa"), self._noise(M, noise[1], "nu")]
+        ll = np.empty(M, dtype=np.float64)
+        out = [np.empty((M,) + shape, dtype=np.float64) for shape in shapes]
+        info = np.zeros(M, dtype=np.int32)
+        self._chk(getattr(_capi.load(), symbol)(self._h, M, *[_dp(x) if x is not None else None for x in params + [ll] + out], _ip(info)))
+        return (ll, *out, info)
+
     def loglik_batch(self, delays, alpha, rho):
         """objective for M (tau, alpha, rho) triples -> (loglik[M], info[M]).  info follows LAPACK
         potrf (>0: not positive definite, loglik NaN); -1: alpha <= 0; -2: rho <= 0."""
@@ -301,11 +314,7 @@ class Objective:
         """The same objective in linear time (gpcc_loglik_markov_batch: a Kalman filter over the observations merged by shifted time;
         OU, matern32 and matern52 only) -> (loglik[M], info[M]).  info as loglik_batch, a positive value being the merged position of
         the first predictive variance that is not positive.  rbf, or marginalise_b with more than 4 bands: GpccError (unsupported)."""
-        M, delays, alpha, rho = self._params(delays, alpha, rho)
-        ll = np.empty(M, dtype=np.float64)
-        info = np.zeros(M, dtype=np.int32)
-        self._chk(_capi.load().gpcc_loglik_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _ip(info)))
-        return ll, info
+        return self._markov("gpcc_loglik_markov_batch", delays, alpha, rho, [])
 
     def realisations(self, Y):
         """Y of loglik_markov_realisations as one (R, N) array: a list of L arrays (R, N_l) side by side, or the (R, N) array itself."""
@@ -542,13 +551,7 @@ class Objective:
         (row, parameter); OU, matern32 and matern52 only) -> (loglik[M], grad[M, 2L+1], info[M]).  loglik and info are bitwise
         loglik_markov_batch's; a row of grad is NaN where info != 0.  rbf, or marginalise_b with more than 4 bands: GpccError
         (unsupported)."""
-        M, delays, alpha, rho = self._params(delays, alpha, rho)
-        ll = np.empty(M, dtype=np.float64)
-        grad = np.empty((M, 2 * self.L + 1), dtype=np.float64)
-        info = np.zeros(M, dtype=np.int32)
-        self._chk(_capi.load().gpcc_loglik_grad_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _dp(grad),
-                                                             _ip(info)))
-        return ll, grad, info
+        return self._markov("gpcc_loglik_grad_markov_batch", delays, alpha, rho, [(2 * self.L + 1,)])
 
     def _noise(self, M, x, name):
         """kappa or nu of the noise entries as a contiguous (M, L) array, or None: an (M, L) array, or (L,) broadcast over the rows."""
@@ -569,29 +572,14 @@ class Objective:
         kappa[m], nu[m]); at kappa = 1, nu = 0 loglik and info are bitwise loglik_markov_batch's.  info as loglik_markov_batch and,
         after -1 and -2, -3: a kappa or nu of the row is negative or not finite.  rbf, or marginalise_b with more than 4 bands:
         GpccError (unsupported)."""
-        M, delays, alpha, rho = self._params(delays, alpha, rho)
-        kappa, nu = self._noise(M, kappa, "kappa"), self._noise(M, nu, "nu")
-        ll = np.empty(M, dtype=np.float64)
-        info = np.zeros(M, dtype=np.int32)
-        self._chk(_capi.load().gpcc_loglik_noise_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho),
-                                                              _dp(kappa) if kappa is not None else None,
-                                                              _dp(nu) if nu is not None else None, _dp(ll), _ip(info)))
-        return ll, info
+        return self._markov("gpcc_loglik_noise_markov_batch", delays, alpha, rho, [], noise=(kappa, nu))
 
     def loglik_grad_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
         """loglik_markov_noise_batch and its gradient (gpcc_loglik_grad_noise_markov_batch: forward sensitivities, one lane per (row,
         parameter)) -> (loglik[M], grad[M, 4L+1], info[M]), a row of grad being [alpha_1..L, rho, tau_1..L, kappa_1..L, nu_1..L]: the
         first 2L+1 entries as loglik_grad_markov_batch, d/d kappa_l and d/d nu_l behind them.  loglik and info are
         loglik_markov_noise_batch's; a row of grad is NaN where info != 0."""
-        M, delays, alpha, rho = self._params(delays, alpha, rho)
-        kappa, nu = self._noise(M, kappa, "kappa"), self._noise(M, nu, "nu")
-        ll = np.empty(M, dtype=np.float64)
-        grad = np.empty((M, 4 * self.L + 1), dtype=np.float64)
-        info = np.zeros(M, dtype=np.int32)
-        self._chk(_capi.load().gpcc_loglik_grad_noise_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho),
-                                                                   _dp(kappa) if kappa is not None else None,
-                                                                   _dp(nu) if nu is not None else None, _dp(ll), _dp(grad), _ip(info)))
-        return ll, grad, info
+        return self._markov("gpcc_loglik_grad_noise_markov_batch", delays, alpha, rho, [(4 * self.L + 1,)], noise=(kappa, nu))
 
     def loglik_hess_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
         """loglik_grad_markov_noise_batch and the Hessian over [alpha_1..L, rho, kappa_1..L, nu_1..L] in linear time
@@ -600,18 +588,8 @@ class Objective:
         loglik_grad_markov_noise_batch's; hess is bitwise symmetric and NaN where info != 0; the delays have no rows in it.  A row's
         leading (L+1) x (L+1) block is loglik_hess_hyper_markov_batch's of a fresh Objective on fit.effective_std(sigma, kappa[m],
         nu[m]).  rbf, marginalise_b with more than 4 bands, or matern52 with marginalise_b and 4 bands: GpccError (unsupported)."""
-        M, delays, alpha, rho = self._params(delays, alpha, rho)
-        kappa, nu = self._noise(M, kappa, "kappa"), self._noise(M, nu, "nu")
         n = 3 * self.L + 1
-        ll = np.empty(M, dtype=np.float64)
-        grad = np.empty((M, 4 * self.L + 1), dtype=np.float64)
-        hess = np.empty((M, n, n), dtype=np.float64)
-        info = np.zeros(M, dtype=np.int32)
-        self._chk(_capi.load().gpcc_loglik_hess_noise_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho),
-                                                                   _dp(kappa) if kappa is not None else None,
-                                                                   _dp(nu) if nu is not None else None, _dp(ll), _dp(grad), _dp(hess),
-                                                                   _ip(info)))
-        return ll, grad, hess, info
+        return self._markov("gpcc_loglik_hess_noise_markov_batch", delays, alpha, rho, [(4 * self.L + 1,), (n, n)], noise=(kappa, nu))
 
     def loglik_hess_full_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
         """loglik_grad_markov_noise_batch and the FULL Hessian, the delays included, over the gradient row's order [alpha_1..L, rho,
@@ -623,18 +601,8 @@ class Objective:
         different bands have exactly equal shifted times every entry with a tau index is NaN and info stays 0; with one band the tau
         entries are exact zeros.  rbf, marginalise_b with more than 4 bands, or matern52 with marginalise_b and 4 bands: GpccError
         (unsupported)."""
-        M, delays, alpha, rho = self._params(delays, alpha, rho)
-        kappa, nu = self._noise(M, kappa, "kappa"), self._noise(M, nu, "nu")
         n = 4 * self.L + 1
-        ll = np.empty(M, dtype=np.float64)
-        grad = np.empty((M, n), dtype=np.float64)
-        hess = np.empty((M, n, n), dtype=np.float64)
-        info = np.zeros(M, dtype=np.int32)
-        self._chk(_capi.load().gpcc_loglik_hess_full_noise_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho),
-                                                                        _dp(kappa) if kappa is not None else None,
-                                                                        _dp(nu) if nu is not None else None, _dp(ll), _dp(grad),
-                                                                        _dp(hess), _ip(info)))
-        return ll, grad, hess, info
+        return self._markov("gpcc_loglik_hess_full_noise_markov_batch", delays, alpha, rho, [(n,), (n, n)], noise=(kappa, nu))
 
     def loglik_hess_batch(self, delays, alpha, rho):
         """objective, gradient, Hessian and expected (Fisher) information for M (tau, alpha, rho) triples -> (loglik[M],
@@ -673,15 +641,8 @@ class Objective:
         hess[M, L+1, L+1], info[M]).  loglik, grad and info are bitwise loglik_grad_markov_batch's; hess is bitwise symmetric and NaN where
         info != 0.  The Fisher information in linear time: loglik_fisher_markov_batch.  The rows of tau: loglik_hess_markov_batch.
         rbf, or marginalise_b with more than 4 bands: GpccError (unsupported)."""
-        M, delays, alpha, rho = self._params(delays, alpha, rho)
         P, n = 2 * self.L + 1, self.L + 1
-        ll = np.empty(M, dtype=np.float64)
-        grad = np.empty((M, P), dtype=np.float64)
-        hess = np.empty((M, n, n), dtype=np.float64)
-        info = np.zeros(M, dtype=np.int32)
-        self._chk(_capi.load().gpcc_loglik_hess_hyper_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _dp(grad),
-                                                                   _dp(hess), _ip(info)))
-        return ll, grad, hess, info
+        return self._markov("gpcc_loglik_hess_hyper_markov_batch", delays, alpha, rho, [(P,), (n, n)])
 
     def loglik_hess_markov_batch(self, delays, alpha, rho):
         """The full Hessian in linear time (gpcc_loglik_hess_markov_batch: loglik_hess_hyper_markov_batch's launches, and the rows of
@@ -693,15 +654,8 @@ class Objective:
         use loglik_hess_batch for OU on a grid of delays that collides with the cadence.  The Matern kernels are exact at ties.  The
         Fisher information in linear time: loglik_fisher_markov_batch.  rbf, marginalise_b with more than 4 bands, or matern52 with marginalise_b and 4 bands:
         GpccError (unsupported)."""
-        M, delays, alpha, rho = self._params(delays, alpha, rho)
         P = 2 * self.L + 1
-        ll = np.empty(M, dtype=np.float64)
-        grad = np.empty((M, P), dtype=np.float64)
-        hess = np.empty((M, P, P), dtype=np.float64)
-        info = np.zeros(M, dtype=np.int32)
-        self._chk(_capi.load().gpcc_loglik_hess_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _dp(grad),
-                                                             _dp(hess), _ip(info)))
-        return ll, grad, hess, info
+        return self._markov("gpcc_loglik_hess_markov_batch", delays, alpha, rho, [(P,), (P, P)])
 
     def loglik_fisher_markov_batch(self, delays, alpha, rho):
         """The expected (Fisher) information in linear time (gpcc_loglik_fisher_markov_batch: the Kalman filter carrying the second
@@ -712,15 +666,8 @@ class Objective:
         exactly equal shifted times every entry with a tau index is NaN while info stays 0 and the (alpha, rho) block is exact -- use
         loglik_hess_batch's Fisher information there.  The Matern kernels are exact at ties.  rbf, marginalise_b with more than 4
         bands, or matern52 with marginalise_b and 4 bands: GpccError (unsupported)."""
-        M, delays, alpha, rho = self._params(delays, alpha, rho)
         P = 2 * self.L + 1
-        ll = np.empty(M, dtype=np.float64)
-        grad = np.empty((M, P), dtype=np.float64)
-        fisher = np.empty((M, P, P), dtype=np.float64)
-        info = np.zeros(M, dtype=np.int32)
-        self._chk(_capi.load().gpcc_loglik_fisher_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(ll), _dp(grad),
-                                                               _dp(fisher), _ip(info)))
-        return ll, grad, fisher, info
+        return self._markov("gpcc_loglik_fisher_markov_batch", delays, alpha, rho, [(P,), (P, P)])
 
     def laplace_evidence(self, delays, alpha0, rho0, rhomin=0.1, rhomax=20.0, max_rounds=50, g_tol=1e-6, solver="dense"):
         """The Laplace-marginalised evidence over alpha and rho per row of delays (G, L), from (alpha0[G, L], rho0[G]) (usually

@@ -125,6 +125,13 @@ struct MultiWorker {
     }
 };
 
+// the two buffers of a stage of a linear-time value or derivative entry (MarkovStage), grown on demand: the per-slot results
+// [slots][M] and the rows [M][width]
+struct MarkovBufs {
+    double *slot = nullptr, *rows = nullptr;
+    long slot_cap = 0, rows_cap = 0;
+};
+
 struct gpcc_handle_s {
     int device = 0;
     int L = 0, N = 0, Np = 0, nt = 0, kernel_id = 0, mb = 1, precision = 0;
@@ -258,19 +265,9 @@ struct gpcc_handle_s {
     double *d_mkt = nullptr, *d_mktap = nullptr, *d_mkmu = nullptr, *d_mkvar = nullptr, *d_mkmix = nullptr, *d_mkw = nullptr, *d_mkaux = nullptr;
     int *d_mkti = nullptr, *d_mkauxi = nullptr;
     long mkt_cap = 0, mkti_cap = 0, mktap_cap = 0, mkmu_cap = 0, mkvar_cap = 0, mkmix_cap = 0, mkw_cap = 0, mkaux_cap = 0, mkauxi_cap = 0;
-    // linear-time gradient (gpcc_loglik_grad_markov_batch): the per-slot results [slots][M] and the rows [M][2L + 1], grown on demand
-    double *d_mkgs = nullptr, *d_mkgr = nullptr;
-    long mkgs_cap = 0, mkgr_cap = 0;
-    // linear-time Hessian block (gpcc_loglik_hess_hyper_markov_batch): the per-pair results [pair slots][M] and the blocks [M][(L + 1)^2]
-    double *d_mkhs = nullptr, *d_mkhb = nullptr;
-    long mkhs_cap = 0, mkhb_cap = 0;
-    // linear-time rows of tau of the Hessian (gpcc_loglik_hess_markov_batch): the per-pair results [tau pair slots][M] and the blocks
-    // [M][(2L + 1)^2]
-    double *d_mkts = nullptr, *d_mktb = nullptr;
-    long mkts_cap = 0, mktb_cap = 0;
-    // linear-time Fisher information (gpcc_loglik_fisher_markov_batch): the per-pair results [pair slots][M] and the blocks [M][(2L + 1)^2]
-    double *d_mkfs = nullptr, *d_mkfb = nullptr;
-    long mkfs_cap = 0, mkfb_cap = 0;
+    // linear-time gradient, Hessian block, rows of tau of the Hessian and Fisher information: the buffers of the stages mks_grad,
+    // mks_hess, mks_hess_tau and mks_fisher, which state their sizes
+    MarkovBufs mkg, mkh, mkt, mkf;
     // linear-time log-likelihood of many realisations (gpcc_loglik_markov_multi_batch): grown on demand, for one chunk of realisations --
     // the fluxes as the caller holds them (mkmy_cap doubles), their packed residuals (mkmr_cap), the means (mkmm_cap), the chunk's
     // results [M][chunk] (mkmo_cap) and the sort permutation (N ints, uploaded once)
@@ -286,18 +283,9 @@ struct gpcc_handle_s {
     double *d_mkry = nullptr, *d_mkrm = nullptr;
     int *d_mkrc = nullptr, *d_mkrr = nullptr, *d_mkrp = nullptr;
     long mkrv_cap = 0, mkry_cap = 0, mkrm_cap = 0, mkrc_cap = 0, mkrr_cap = 0, mkrp_cap = 0;
-    // linear-time log-likelihood and gradient under a per-row noise model (gpcc_loglik_noise_markov_batch and its gradient): the rows'
-    // kappa | nu (2 M L doubles), the per-slot results [slots][M] and the rows [M][4L + 1], grown on demand
-    double *d_mknp = nullptr, *d_mkns = nullptr, *d_mkng = nullptr;
-    long mknp_cap = 0, mkns_cap = 0, mkng_cap = 0;
-    // linear-time Hessian under a per-row noise model (gpcc_loglik_hess_noise_markov_batch): the per-pair results [pair slots][M] and the
-    // blocks [M][(3L + 1)^2], grown on demand
-    double *d_mknhs = nullptr, *d_mknhb = nullptr;
-    long mknhs_cap = 0, mknhb_cap = 0;
-    // its rows of tau (gpcc_loglik_hess_full_noise_markov_batch): the per-pair results [pair slots with a tau][M] and the blocks
-    // [M][(4L + 1)^2], grown on demand
-    double *d_mknts = nullptr, *d_mkntb = nullptr;
-    long mknts_cap = 0, mkntb_cap = 0;
+    // the same under a per-row noise model: the buffers of the stages mks_noise_eval (rows: the rows' kappa | nu, 2 M L doubles; no
+    // slots), mks_noise_grad, mks_noise_hess and mks_noise_hess_tau
+    MarkovBufs mkn, mkng, mknh, mknt;
     long markov_resample_bytes_max = (long)512 << 20;   // option "markov_resample_bytes_max": the most the packed pairs of one call may take
     int laplace_markov = 0;              // option "laplace_markov": gpcc_laplace_evidence's rounds are gpcc_loglik_hess_hyper_markov_batch calls
     int markov_chunk_rows = 0;           // option "markov_chunk_rows": rows per chunk of gpcc_predict_markov_batch (0: by the scratch budget)
@@ -611,14 +599,8 @@ extern "C" int gpcc_destroy(gpcc_handle_t h)
     hipFree(h->d_mkt); hipFree(h->d_mktap); hipFree(h->d_mkmu); hipFree(h->d_mkvar); hipFree(h->d_mkmix); hipFree(h->d_mkw);
     hipFree(h->d_mkaux); hipFree(h->d_mkti); hipFree(h->d_mkauxi);
     hipFree(h->d_mksw); hipFree(h->d_mksrt); hipFree(h->d_mksacc); hipFree(h->d_mksi);
-    hipFree(h->d_mkgs); hipFree(h->d_mkgr);
-    hipFree(h->d_mkhs); hipFree(h->d_mkhb);
-    hipFree(h->d_mkts); hipFree(h->d_mktb);
-    hipFree(h->d_mkfs); hipFree(h->d_mkfb);
+    for (MarkovBufs *b : {&h->mkg, &h->mkh, &h->mkt, &h->mkf, &h->mkn, &h->mkng, &h->mknh, &h->mknt}) { hipFree(b->slot); hipFree(b->rows); }
     hipFree(h->d_mkmy); hipFree(h->d_mkmr); hipFree(h->d_mkmm); hipFree(h->d_mkmo); hipFree(h->d_mkmp);
-    hipFree(h->d_mknp); hipFree(h->d_mkns); hipFree(h->d_mkng);
-    hipFree(h->d_mknhs); hipFree(h->d_mknhb);
-    hipFree(h->d_mknts); hipFree(h->d_mkntb);
     hipFree(h->d_mkrv); hipFree(h->d_mkry); hipFree(h->d_mkrm); hipFree(h->d_mkrc); hipFree(h->d_mkrr); hipFree(h->d_mkrp);
     hipFree(h->d_cand); hipFree(h->d_ggrad); hipFree(h->d_hout); hipFree(h->d_pw);
     hipFree(h->d_xhld); hipFree(h->d_xw); hipFree(h->d_xmix); hipFree(h->d_xscr); hipFree(h->d_xscri);
@@ -2231,60 +2213,134 @@ static int markov_launch(gpcc_handle_t h, const char *name, MarkovKernel kernel,
 }
 
 // the dynamic LDS of the kernels that stage the light curves alone
+static size_t markov_filter_lds_bytes(gpcc_handle_t h, int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); }
 static auto markov_filter_lds(gpcc_handle_t h)
 {
-    return [h](int thr, bool st) { return gpcc_markov_lds_bytes(h->N, h->L, thr, st); };
+    return [h](int thr, bool st) { return markov_filter_lds_bytes(h, thr, st); };
 }
 
-// gpcc_markov_eval over the M staged rows: loglik and info left in d_out / d_oinfo
-static int markov_eval_launch(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr)
+// ------------------------------------------------------------------------------------------
+// The driver of the nine value and derivative entries (plain: value, gradient, Hessian block, full Hessian, Fisher information; under a
+// per-row noise model: value, gradient, Hessian, full Hessian).  An entry is a MarkovEntry -- its names, its refusals, its stages --
+// that markov_entry() runs; a stage is one kernel with its finish kernel, stated once as a MarkovStage beside the first entry that
+// lists it.  Every stage reads the loglik and info the family's value stage left in d_out / d_oinfo, so a longer list returns the
+// shorter one's value, info, gradient and block bitwise by construction.
+// ------------------------------------------------------------------------------------------
+// a call's M rows as a stage sees them: staged at dd, da, dr; kappa, nu: the caller's arrays of a noise entry (host; NULL: all 1 / 0)
+struct MarkovRun {
+    gpcc_handle_t h;
+    int M;
+    const double *dd, *da, *dr, *kappa, *nu;
+};
+
+struct MarkovStage {
+    const char *name;                                           // the kernel's name in messages
+    MarkovKernel kernel;
+    int (*slots)(gpcc_handle_t h);                              // lanes per row, each with a result in slot (nullptr: one lane, no slot buffer)
+    MarkovBufs gpcc_handle_s::*bufs;                            // its buffers (nullptr: none, it leaves loglik and info in d_out / d_oinfo)
+    int (*width)(int L);                                        // the doubles per row of rows
+    size_t (*lds)(gpcc_handle_t h, int threads, bool staged);   // its dynamic LDS: markov_launch's lds_bytes
+    int (*launch)(const MarkovRun &r, const MarkovStage &s);    // fills its Args beyond markov_fill_args, then markov_stage_launch
+};
+
+// a stage's buffers for M rows
+static int markov_stage_grow(gpcc_handle_t h, int M, const MarkovStage &s)
 {
-    GpccMarkovArgs a;
-    markov_fill_args(h, M, dd, da, dr, a);
-    return markov_launch(h, "gpcc_markov_eval", MK_EVAL, M, 1, a.stage, markov_filter_lds(h),
-                         [&](const GpccMkLaunch &g) { return gpcc_markov_launch(g, a); });
+    if (!s.bufs) return 0;
+    MarkovBufs &b = h->*s.bufs;
+    const int g = s.slots ? grow_buf(h, &b.slot, &b.slot_cap, (long)s.slots(h) * M) : 0;
+    return g ? g : grow_buf(h, &b.rows, &b.rows_cap, (long)s.width(h->L) * M);
 }
 
-// a derivative kernel (gradient, Hessian block, Hessian's rows of tau, Fisher information) and its finish kernel over the M staged
-// rows, one lane per (row, slot); a holds the kernel's own fields, the filter's are filled here.  lds_bytes: markov_launch's
-template <typename ARGS, typename LdsBytes, typename Launch>
-static int markov_slots_launch(gpcc_handle_t h, const char *name, MarkovKernel kernel, int M, const double *dd, const double *da,
-                               const double *dr, int slots, ARGS &a, LdsBytes &&lds_bytes, Launch &&launch)
-{
-    markov_fill_args(h, M, dd, da, dr, a);
-    return markov_launch(h, name, kernel, M, slots, a.stage, lds_bytes, [&](const GpccMkLaunch &g) { return launch(g, slots, a); });
-}
-
-// ... for the kernels that stage the light curves alone
+// a stage's kernel (and finish kernel) over the M staged rows, one lane per (row, slot): a holds the kernel's own fields, the filter's
+// are filled here; launch(g, slots, a): the family's launch function
 template <typename ARGS, typename Launch>
-static int markov_slots_launch(gpcc_handle_t h, const char *name, MarkovKernel kernel, int M, const double *dd, const double *da,
-                               const double *dr, int slots, ARGS &a, Launch &&launch)
+static int markov_stage_launch(const MarkovRun &r, const MarkovStage &s, ARGS &a, Launch &&launch)
 {
-    return markov_slots_launch(h, name, kernel, M, dd, da, dr, slots, a, markov_filter_lds(h), launch);
+    const int slots = s.slots ? s.slots(r.h) : 1;
+    markov_fill_args(r.h, r.M, r.dd, r.da, r.dr, a);
+    return markov_launch(r.h, s.name, s.kernel, r.M, slots, a.stage, [&](int thr, bool st) { return s.lds(r.h, thr, st); },
+                         [&](const GpccMkLaunch &g) { return launch(g, slots, a); });
 }
 
-extern "C" int gpcc_loglik_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
-                                        double *loglik, int *info)
+// an instantiation <P, NOFF> an entry needs; scratch: the refusal says "needs scratch memory and does not ship", not "does not ship"
+struct MarkovShips {
+    bool (*ships)(int p, int noff);
+    bool scratch;
+};
+
+// a stage of an entry; out: where the caller wants the stage's rows (NULL: they stay on the device, for the next stage)
+struct MarkovStep {
+    const MarkovStage *stage;
+    double *out;
+};
+
+struct MarkovEntry {
+    const char *name, *dense;   // the entry, and the dense entry its refusals send the caller to
+    const char *what;           // the call in an fp32 handle's message (route_fp64)
+    bool pointers;              // every pointer the entry requires is non-NULL (a block's pointer is not required)
+    const MarkovShips *ships;   // the nships instantiations this call needs, refused in this order
+    int nships;
+    const MarkovStep *steps;    // the nsteps stages of this call in launch order: without its block, an entry lists the gradient's
+    int nsteps;
+    const double *kappa, *nu;   // MarkovRun's
+    bool counts;                // a good call adds M to markov_count (the value entries and the noise family: as found)
+};
+
+// reissue(o): the same call on handle o (route_fp64's call)
+template <typename Reissue>
+static int markov_entry(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, double *loglik, int *info,
+                        const MarkovEntry &e, Reissue &&reissue)
 {
     if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
     if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
     if (M == 0) return 0;
-    if (!delays || !alpha || !rho || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
-    int rc = markov_refusals(h, "gpcc_loglik_markov_batch", "gpcc_loglik_batch");
+    if (!e.pointers) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    int rc = markov_refusals(h, e.name, e.dense);
     if (rc) return rc;
-    if (route_fp64(h, "linear-time log-likelihood", rc,
-                   [&](gpcc_handle_t o) { return gpcc_loglik_markov_batch(o, M, delays, alpha, rho, loglik, info); }))
-        return rc;
+    const MarkovDims d = markov_dims(primary(h));
+    for (int i = 0; i < e.nships; ++i)
+        if (!e.ships[i].ships(d.p, d.noff))
+            return fail(h, GPCC_ERR_UNSUPPORTED, "%s: the instantiation <%d, %d> (states of the process, offset states) %sdoes not ship; use %s",
+                        e.name, d.p, d.noff, e.ships[i].scratch ? "needs scratch memory and " : "", e.dense);
+    if (route_fp64(h, e.what, rc, reissue)) return rc;
     GPCC_ON_DEVICE(h, h->device);
+    MarkovRun r = {h, M, nullptr, nullptr, nullptr, e.kappa, e.nu};
     double *dd, *da, *dr;
-    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [] { return 0; });
+    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {   // every listed stage's buffers, ahead of anything enqueued
+        int g = 0;
+        for (int i = 0; i < e.nsteps && !g; ++i) g = markov_stage_grow(h, M, *e.steps[i].stage);
+        return g;
+    });
     if (rc) return rc;
-    rc = markov_eval_launch(h, M, dd, da, dr);
+    r.dd = dd; r.da = da; r.dr = dr;
+    for (int i = 0; i < e.nsteps; ++i) {
+        const MarkovStage &s = *e.steps[i].stage;
+        rc = s.launch(r, s);
+        if (rc) return rc;
+        if (e.steps[i].out)
+            HIPCHK(h, hipMemcpyAsync(e.steps[i].out, (h->*s.bufs).rows, sizeof(double) * s.width(h->L) * M, hipMemcpyDeviceToHost, h->main_stream));
+    }
+    rc = markov_finish(h, M, loglik, info);   // (its synchronisation also guards the caller's arrays, kappa and nu among them)
     if (rc) return rc;
-    rc = markov_finish(h, M, loglik, info);
-    if (rc) return rc;
-    h->markov_count += M;
+    if (e.counts) h->markov_count += M;
     return 0;
+}
+
+static const MarkovStage mks_eval = {   // loglik and info of the M rows, left in d_out / d_oinfo
+    "gpcc_markov_eval", MK_EVAL, nullptr, nullptr, nullptr, markov_filter_lds_bytes, [](const MarkovRun &r, const MarkovStage &s) {
+        GpccMarkovArgs a;
+        return markov_stage_launch(r, s, a, [](const GpccMkLaunch &g, int, const GpccMarkovArgs &a) { return gpcc_markov_launch(g, a); });
+    }};
+
+extern "C" int gpcc_loglik_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                        double *loglik, int *info)
+{
+    const MarkovStep steps[] = {{&mks_eval, nullptr}};
+    return markov_entry(h, M, delays, alpha, rho, loglik, info,
+                        {"gpcc_loglik_markov_batch", "gpcc_loglik_batch", "linear-time log-likelihood", delays && alpha && rho && loglik && info,
+                         nullptr, 0, steps, 1, nullptr, nullptr, /* counts */ true},
+                        [&](gpcc_handle_t o) { return gpcc_loglik_markov_batch(o, M, delays, alpha, rho, loglik, info); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2808,455 +2864,258 @@ extern "C" int gpcc_posterior_offsets_markov_batch(gpcc_handle_t h, int M, const
 
 // ------------------------------------------------------------------------------------------
 // The linear-time gradient of the Markov kernels (gpcc_loglik_grad_markov_batch; kernel: gpcc_markov_grad.hip.h): the
-// filter's forward sensitivities, one lane per (row, parameter slot).  Value and info come from a gpcc_markov_eval launch of the same
-// call (bitwise gpcc_loglik_markov_batch's by construction); it needs what that entry needs plus the slots and the rows.
+// filter's forward sensitivities, one lane per (row, parameter slot; OU: two per tau_l).
 // ------------------------------------------------------------------------------------------
-// the gradient's buffers for M rows, and its launches over the M staged rows: gpcc_markov_eval (loglik and info left in d_out / d_oinfo),
-// gpcc_markov_grad and its finish kernel, the rows copied to `grad` behind them.  gpcc_loglik_hess_hyper_markov_batch shares both
-static int markov_grad_grow(gpcc_handle_t h, int M)
-{
-    const int slots = gpcc_markov_grad_slots(h->L, markov_dims(h).p == 1);
-    const int g = grow_buf(h, &h->d_mkgs, &h->mkgs_cap, (long)slots * M);
-    return g ? g : grow_buf(h, &h->d_mkgr, &h->mkgr_cap, (long)(2 * h->L + 1) * M);
-}
-
-static int markov_grad_enqueue(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, double *grad)
-{
-    const int W = 2 * h->L + 1, twice = markov_dims(h).p == 1, slots = gpcc_markov_grad_slots(h->L, twice != 0);
-    int rc = markov_eval_launch(h, M, dd, da, dr);
-    if (rc) return rc;
-    GpccMarkovGradArgs a;
-    a.slot = h->d_mkgs; a.grad = h->d_mkgr; a.twice = twice;
-    rc = markov_slots_launch(h, "gpcc_markov_grad", MK_GRAD, M, dd, da, dr, slots, a, gpcc_markov_grad_launch);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(grad, h->d_mkgr, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
-    return 0;
-}
+static const MarkovStage mks_grad = {   // rows: the gradients [M][2L + 1]
+    "gpcc_markov_grad", MK_GRAD, [](gpcc_handle_t h) { return gpcc_markov_grad_slots(h->L, markov_dims(h).p == 1); }, &gpcc_handle_s::mkg,
+    [](int L) { return 2 * L + 1; }, markov_filter_lds_bytes, [](const MarkovRun &r, const MarkovStage &s) {
+        GpccMarkovGradArgs a;
+        a.slot = r.h->mkg.slot; a.grad = r.h->mkg.rows; a.twice = markov_dims(r.h).p == 1;
+        return markov_stage_launch(r, s, a, gpcc_markov_grad_launch);
+    }};
 
 extern "C" int gpcc_loglik_grad_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                              double *loglik, double *grad, int *info)
 {
-    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
-    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
-    if (M == 0) return 0;
-    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
-    int rc = markov_refusals(h, "gpcc_loglik_grad_markov_batch", "gpcc_loglik_grad_batch");
-    if (rc) return rc;
-    if (route_fp64(h, "linear-time gradient", rc,
-                   [&](gpcc_handle_t o) { return gpcc_loglik_grad_markov_batch(o, M, delays, alpha, rho, loglik, grad, info); }))
-        return rc;
-    GPCC_ON_DEVICE(h, h->device);
-    double *dd, *da, *dr;
-    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] { return markov_grad_grow(h, M); });
-    if (rc) return rc;
-    rc = markov_grad_enqueue(h, M, dd, da, dr, grad);
-    if (rc) return rc;
-    return markov_finish(h, M, loglik, info);
+    const MarkovStep steps[] = {{&mks_eval, nullptr}, {&mks_grad, grad}};
+    return markov_entry(h, M, delays, alpha, rho, loglik, info,
+                        {"gpcc_loglik_grad_markov_batch", "gpcc_loglik_grad_batch", "linear-time gradient",
+                         delays && alpha && rho && loglik && grad && info, nullptr, 0, steps, 2, nullptr, nullptr, /* counts */ false},
+                        [&](gpcc_handle_t o) { return gpcc_loglik_grad_markov_batch(o, M, delays, alpha, rho, loglik, grad, info); });
 }
 
 // ------------------------------------------------------------------------------------------
 // The linear-time log-likelihood and gradient of rows with their own noise model (gpcc_loglik_noise_markov_batch,
 // gpcc_loglik_grad_noise_markov_batch; kernels: gpcc_markov_noise.hip.h): point i of band l of row m is observed with
 // the variance kappa_{m,l}^2 sigma_i^2 + nu_{m,l}.  One lane per row (value) or per (row, slot) (gradient), as gpcc_loglik_markov_batch
-// and gpcc_loglik_grad_markov_batch; they need what those need plus the rows' kappa and nu, the slots and the rows below.
+// and gpcc_loglik_grad_markov_batch.
 // ------------------------------------------------------------------------------------------
 // the dynamic LDS of the family: the light curves, the lanes' cursors and their kappa^2, nu
-static auto markov_noise_lds(gpcc_handle_t h)
-{
-    return [h](int thr, bool st) { return gpcc_markov_noise_lds_bytes(h->N, h->L, thr, st); };
-}
+static size_t markov_noise_lds_bytes(gpcc_handle_t h, int thr, bool st) { return gpcc_markov_noise_lds_bytes(h->N, h->L, thr, st); }
 
-// the rows' kappa | nu staged in d_mknp on main_stream (NULL: all 1 / all 0, from a host copy that lives in this function only: the
-// stream is drained before it goes, so that no return of the caller, an error's included, leaves a copy reading freed memory), and
-// the family's arguments beside the filter's
-static int markov_noise_stage(gpcc_handle_t h, int M, const double *kappa, const double *nu, GpccMarkovNoiseArgs &a)
+// the rows' kappa | nu staged in mkn.rows on main_stream (NULL: all 1 / all 0, from a host copy that lives in this function only: the
+// stream is drained before it goes, so that no return of the caller, an error's included, leaves a copy reading freed memory)
+static int markov_noise_stage(const MarkovRun &r)
 {
-    const long ML = (long)M * h->L;
-    if (!kappa || !nu) {
+    const gpcc_handle_t h = r.h;
+    const long ML = (long)r.M * h->L;
+    double *d_np = h->mkn.rows;
+    if (!r.kappa || !r.nu) {
         std::vector<double> hold((size_t)2 * ML, 0.0);
-        for (long k = 0; k < ML; ++k) hold[k] = kappa ? kappa[k] : 1.0;
-        if (nu) std::copy(nu, nu + ML, hold.begin() + ML);
-        const hipError_t e = hipMemcpyAsync(h->d_mknp, hold.data(), sizeof(double) * 2 * ML, hipMemcpyHostToDevice, h->main_stream);
+        for (long k = 0; k < ML; ++k) hold[k] = r.kappa ? r.kappa[k] : 1.0;
+        if (r.nu) std::copy(r.nu, r.nu + ML, hold.begin() + ML);
+        const hipError_t e = hipMemcpyAsync(d_np, hold.data(), sizeof(double) * 2 * ML, hipMemcpyHostToDevice, h->main_stream);
         const hipError_t e2 = hipStreamSynchronize(h->main_stream);
         HIPCHK(h, e);
         HIPCHK(h, e2);
     } else {
-        HIPCHK(h, hipMemcpyAsync(h->d_mknp, kappa, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
-        HIPCHK(h, hipMemcpyAsync(h->d_mknp + ML, nu, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
+        HIPCHK(h, hipMemcpyAsync(d_np, r.kappa, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
+        HIPCHK(h, hipMemcpyAsync(d_np + ML, r.nu, sizeof(double) * ML, hipMemcpyHostToDevice, h->main_stream));
     }
-    a.kappa = h->d_mknp; a.nu = h->d_mknp + ML;
-    a.slot = h->d_mkns; a.grad = h->d_mkng; a.twice = markov_dims(h).p == 1;
     return 0;
 }
 
-static int markov_noise_ships(gpcc_handle_t h, const char *who, const char *dense)
+// the staged kappa and nu in a kernel's Args; the value's and the gradient's Args whole (one struct: the value kernel reads no slot)
+template <typename ARGS>
+static void markov_noise_args(const MarkovRun &r, ARGS &a)
 {
-    const MarkovDims d = markov_dims(primary(h));
-    if (!gpcc_mk_ships<GpccMkShipsNoise>(d.p, d.noff))
-        return fail(h, GPCC_ERR_UNSUPPORTED, "%s: the instantiation <%d, %d> (states of the process, offset states) does not ship; use %s",
-                    who, d.p, d.noff, dense);
-    return 0;
+    a.kappa = r.h->mkn.rows; a.nu = a.kappa + (long)r.M * r.h->L;
 }
 
-// gpcc_markov_noise_eval over the M staged rows: loglik and info left in d_out / d_oinfo
-static int markov_noise_eval_launch(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, GpccMarkovNoiseArgs &a)
+static GpccMarkovNoiseArgs markov_noise_grad_args(const MarkovRun &r)
 {
-    markov_fill_args(h, M, dd, da, dr, a);
-    return markov_launch(h, "gpcc_markov_noise_eval", MK_NOISE, M, 1, a.stage, markov_noise_lds(h),
-                         [&](const GpccMkLaunch &g) { return gpcc_markov_noise_launch(g, a); });
+    GpccMarkovNoiseArgs a;
+    markov_noise_args(r, a);
+    a.slot = r.h->mkng.slot; a.grad = r.h->mkng.rows; a.twice = markov_dims(r.h).p == 1;
+    return a;
 }
+
+static const MarkovStage mks_noise_eval = {   // rows: the rows' kappa | nu [2][M][L], staged here; loglik and info left in d_out / d_oinfo
+    "gpcc_markov_noise_eval", MK_NOISE, nullptr, &gpcc_handle_s::mkn, [](int L) { return 2 * L; }, markov_noise_lds_bytes,
+    [](const MarkovRun &r, const MarkovStage &s) {
+        const int rc = markov_noise_stage(r);
+        if (rc) return rc;
+        GpccMarkovNoiseArgs a = markov_noise_grad_args(r);
+        return markov_stage_launch(r, s, a,
+                                   [](const GpccMkLaunch &g, int, const GpccMarkovNoiseArgs &a) { return gpcc_markov_noise_launch(g, a); });
+    }};
+
+static const MarkovStage mks_noise_grad = {   // rows: the gradients [M][4L + 1]
+    "gpcc_markov_noise_grad", MK_NOISE_GRAD, [](gpcc_handle_t h) { return gpcc_markov_noise_slots(h->L, markov_dims(h).p == 1); },
+    &gpcc_handle_s::mkng, [](int L) { return 4 * L + 1; }, markov_noise_lds_bytes, [](const MarkovRun &r, const MarkovStage &s) {
+        GpccMarkovNoiseArgs a = markov_noise_grad_args(r);
+        return markov_stage_launch(r, s, a, gpcc_markov_noise_grad_launch);
+    }};
+
+// what the noise entries refuse, in this order (the Hessian lists two, the full Hessian all three)
+static const MarkovShips markov_noise_ships[] = {{gpcc_mk_ships<GpccMkShipsNoise>, false}, {gpcc_mk_ships<GpccMkShipsNoiseHess>, true},
+                                                 {gpcc_mk_ships<GpccMkShipsNoiseHessTau>, true}};
 
 extern "C" int gpcc_loglik_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                               const double *kappa, const double *nu, double *loglik, int *info)
 {
-    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
-    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
-    if (M == 0) return 0;
-    if (!delays || !alpha || !rho || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
-    const char *dense = "gpcc_loglik_batch on a handle created with the error bars sqrt(kappa^2 sigma^2 + nu)";
-    int rc = markov_refusals(h, "gpcc_loglik_noise_markov_batch", dense);
-    if (!rc) rc = markov_noise_ships(h, "gpcc_loglik_noise_markov_batch", dense);
-    if (rc) return rc;
-    if (route_fp64(h, "linear-time log-likelihood under a noise model", rc,
-                   [&](gpcc_handle_t o) { return gpcc_loglik_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, loglik, info); }))
-        return rc;
-    GPCC_ON_DEVICE(h, h->device);
-    double *dd, *da, *dr;
-    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] { return grow_buf(h, &h->d_mknp, &h->mknp_cap, 2L * M * h->L); });
-    if (rc) return rc;
-    GpccMarkovNoiseArgs a;
-    rc = markov_noise_stage(h, M, kappa, nu, a);
-    if (rc) return rc;
-    rc = markov_noise_eval_launch(h, M, dd, da, dr, a);
-    if (rc) return rc;
-    rc = markov_finish(h, M, loglik, info);   // (its synchronisation also guards the caller's arrays)
-    if (rc) return rc;
-    h->markov_count += M;
-    return 0;
-}
-
-// the gradient's buffers for M rows under a noise model, and its launches over the M staged rows: the rows' kappa | nu staged,
-// gpcc_markov_noise_eval (loglik and info left in d_out / d_oinfo), gpcc_markov_noise_grad and its finish kernel, the rows copied to
-// `grad` behind them.  gpcc_loglik_hess_noise_markov_batch shares both, so its value, info and gradient are this entry's bitwise
-static int markov_noise_grad_grow(gpcc_handle_t h, int M)
-{
-    const int L = h->L, slots = gpcc_markov_noise_slots(L, markov_dims(h).p == 1);
-    int g = grow_buf(h, &h->d_mknp, &h->mknp_cap, 2L * M * L);
-    if (!g) g = grow_buf(h, &h->d_mkns, &h->mkns_cap, (long)slots * M);
-    if (!g) g = grow_buf(h, &h->d_mkng, &h->mkng_cap, (long)(4 * L + 1) * M);
-    return g;
-}
-
-static int markov_noise_grad_enqueue(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, const double *kappa,
-                                     const double *nu, double *grad, GpccMarkovNoiseArgs &a)
-{
-    const int L = h->L, W = 4 * L + 1, slots = gpcc_markov_noise_slots(L, markov_dims(h).p == 1);
-    int rc = markov_noise_stage(h, M, kappa, nu, a);
-    if (rc) return rc;
-    rc = markov_noise_eval_launch(h, M, dd, da, dr, a);
-    if (rc) return rc;
-    rc = markov_slots_launch(h, "gpcc_markov_noise_grad", MK_NOISE_GRAD, M, dd, da, dr, slots, a, markov_noise_lds(h),
-                             gpcc_markov_noise_grad_launch);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(grad, h->d_mkng, sizeof(double) * W * M, hipMemcpyDeviceToHost, h->main_stream));
-    return 0;
+    const MarkovStep steps[] = {{&mks_noise_eval, nullptr}};
+    return markov_entry(h, M, delays, alpha, rho, loglik, info,
+                        {"gpcc_loglik_noise_markov_batch", "gpcc_loglik_batch on a handle created with the error bars sqrt(kappa^2 sigma^2 + nu)",
+                         "linear-time log-likelihood under a noise model", delays && alpha && rho && loglik && info, markov_noise_ships, 1,
+                         steps, 1, kappa, nu, /* counts */ true},
+                        [&](gpcc_handle_t o) { return gpcc_loglik_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, loglik, info); });
 }
 
 extern "C" int gpcc_loglik_grad_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                                    const double *kappa, const double *nu, double *loglik, double *grad, int *info)
 {
-    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
-    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
-    if (M == 0) return 0;
-    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
-    const char *dense = "gpcc_loglik_grad_batch on a handle created with the error bars sqrt(kappa^2 sigma^2 + nu)";
-    int rc = markov_refusals(h, "gpcc_loglik_grad_noise_markov_batch", dense);
-    if (!rc) rc = markov_noise_ships(h, "gpcc_loglik_grad_noise_markov_batch", dense);
-    if (rc) return rc;
-    if (route_fp64(h, "linear-time gradient under a noise model", rc, [&](gpcc_handle_t o) {
-            return gpcc_loglik_grad_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, loglik, grad, info);
-        }))
-        return rc;
-    GPCC_ON_DEVICE(h, h->device);
-    double *dd, *da, *dr;
-    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] { return markov_noise_grad_grow(h, M); });
-    if (rc) return rc;
-    GpccMarkovNoiseArgs a;
-    rc = markov_noise_grad_enqueue(h, M, dd, da, dr, kappa, nu, grad, a);
-    if (rc) return rc;
-    rc = markov_finish(h, M, loglik, info);
-    if (rc) return rc;
-    h->markov_count += M;
-    return 0;
+    const MarkovStep steps[] = {{&mks_noise_eval, nullptr}, {&mks_noise_grad, grad}};
+    return markov_entry(h, M, delays, alpha, rho, loglik, info,
+                        {"gpcc_loglik_grad_noise_markov_batch",
+                         "gpcc_loglik_grad_batch on a handle created with the error bars sqrt(kappa^2 sigma^2 + nu)",
+                         "linear-time gradient under a noise model", delays && alpha && rho && loglik && grad && info, markov_noise_ships, 1,
+                         steps, 2, kappa, nu, /* counts */ true},
+                        [&](gpcc_handle_t o) {
+                            return gpcc_loglik_grad_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, loglik, grad, info);
+                        });
 }
 
 // ------------------------------------------------------------------------------------------
 // The linear-time Hessian of rows with their own noise model over [alpha_1..L, rho, kappa_1..L, nu_1..L]
 // (gpcc_loglik_hess_noise_markov_batch; kernel: gpcc_markov_noise_hess.hip.h): the filter's second-order forward
-// sensitivities with variance tangents, one lane per (row, pair slot).  Value, info and gradient come from the noise gradient entry's
-// launches inside the same call (bitwise gpcc_loglik_grad_noise_markov_batch's by construction); it needs what that entry needs plus
-// the pair slots and the blocks, nothing of the N^2 workspace.
+// sensitivities with variance tangents, one lane per (row, pair slot).  hess NULL: the noise gradient entry's stages alone.
 // ------------------------------------------------------------------------------------------
-// the block's buffers for M rows on top of the noise gradient's, and its launches over the M staged rows: the noise gradient's, then
-// (with_hess) gpcc_markov_noise_hess and its finish kernel, the blocks left in d_mknhb.  gpcc_loglik_hess_full_noise_markov_batch
-// shares both
-static int markov_noise_hess_grow(gpcc_handle_t h, int M, bool with_hess)
-{
-    const int n = 3 * h->L + 1;
-    int g = markov_noise_grad_grow(h, M);
-    if (!g && with_hess) g = grow_buf(h, &h->d_mknhs, &h->mknhs_cap, (long)gpcc_markov_noise_hess_slots(h->L) * M);
-    return (g || !with_hess) ? g : grow_buf(h, &h->d_mknhb, &h->mknhb_cap, (long)n * n * M);
-}
-
-static int markov_noise_hess_enqueue(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, const double *kappa,
-                                     const double *nu, double *grad, bool with_hess, GpccMarkovNoiseArgs &a)
-{
-    const int rc = markov_noise_grad_enqueue(h, M, dd, da, dr, kappa, nu, grad, a);
-    if (rc || !with_hess) return rc;
-    GpccMarkovNoiseHessArgs b;
-    b.kappa = a.kappa; b.nu = a.nu; b.slot = h->d_mknhs; b.hess = h->d_mknhb;
-    return markov_slots_launch(h, "gpcc_markov_noise_hess", MK_NOISE_HESS, M, dd, da, dr, gpcc_markov_noise_hess_slots(h->L), b,
-                               markov_noise_lds(h), gpcc_markov_noise_hess_launch);
-}
+static const MarkovStage mks_noise_hess = {   // rows: the blocks [M][(3L + 1)^2]
+    "gpcc_markov_noise_hess", MK_NOISE_HESS, [](gpcc_handle_t h) { return gpcc_markov_noise_hess_slots(h->L); }, &gpcc_handle_s::mknh,
+    [](int L) { return (3 * L + 1) * (3 * L + 1); }, markov_noise_lds_bytes, [](const MarkovRun &r, const MarkovStage &s) {
+        GpccMarkovNoiseHessArgs a;
+        markov_noise_args(r, a);
+        a.slot = r.h->mknh.slot; a.hess = r.h->mknh.rows;
+        return markov_stage_launch(r, s, a, gpcc_markov_noise_hess_launch);
+    }};
 
 extern "C" int gpcc_loglik_hess_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                                    const double *kappa, const double *nu, double *loglik, double *grad, double *hess,
                                                    int *info)
 {
-    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
-    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
-    if (M == 0) return 0;
-    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
-    const char *dense = "gpcc_loglik_hess_hyper_batch on a handle created with the error bars sqrt(kappa^2 sigma^2 + nu) (effective_std)";
-    int rc = markov_refusals(h, "gpcc_loglik_hess_noise_markov_batch", dense);
-    if (!rc) rc = markov_noise_ships(h, "gpcc_loglik_hess_noise_markov_batch", dense);
-    if (rc) return rc;
-    {
-        const MarkovDims d = markov_dims(primary(h));
-        if (!gpcc_mk_ships<GpccMkShipsNoiseHess>(d.p, d.noff))
-            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_hess_noise_markov_batch: the instantiation <%d, %d> (states of the process, "
-                        "offset states) needs scratch memory and does not ship; use %s", d.p, d.noff, dense);
-    }
-    if (route_fp64(h, "linear-time Hessian under a noise model", rc, [&](gpcc_handle_t o) {
-            return gpcc_loglik_hess_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, loglik, grad, hess, info);
-        }))
-        return rc;
-    GPCC_ON_DEVICE(h, h->device);
-    const int n = 3 * h->L + 1;
-    double *dd, *da, *dr;
-    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] { return markov_noise_hess_grow(h, M, hess != nullptr); });
-    if (rc) return rc;
-    GpccMarkovNoiseArgs a;
-    rc = markov_noise_hess_enqueue(h, M, dd, da, dr, kappa, nu, grad, hess != nullptr, a);
-    if (rc) return rc;
-    if (hess) HIPCHK(h, hipMemcpyAsync(hess, h->d_mknhb, sizeof(double) * n * n * M, hipMemcpyDeviceToHost, h->main_stream));
-    rc = markov_finish(h, M, loglik, info);
-    if (rc) return rc;
-    h->markov_count += M;
-    return 0;
+    const MarkovStep steps[] = {{&mks_noise_eval, nullptr}, {&mks_noise_grad, grad}, {&mks_noise_hess, hess}};
+    return markov_entry(h, M, delays, alpha, rho, loglik, info,
+                        {"gpcc_loglik_hess_noise_markov_batch",
+                         "gpcc_loglik_hess_hyper_batch on a handle created with the error bars sqrt(kappa^2 sigma^2 + nu) (effective_std)",
+                         "linear-time Hessian under a noise model", delays && alpha && rho && loglik && grad && info, markov_noise_ships, 2,
+                         steps, hess ? 3 : 2, kappa, nu, /* counts */ true},
+                        [&](gpcc_handle_t o) {
+                            return gpcc_loglik_hess_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, loglik, grad, hess, info);
+                        });
 }
 
 // ------------------------------------------------------------------------------------------
 // The linear-time full Hessian of rows with their own noise model over [alpha_1..L, rho, tau_1..L, kappa_1..L, nu_1..L], the gradient
 // row's order (gpcc_loglik_hess_full_noise_markov_batch; kernel: gpcc_markov_noise_hess_tau.hip.h): the rows of tau by
-// the same second-order forward sensitivities, one lane per (row, pair slot with a tau).  Value, info, gradient and the
-// [alpha, rho, kappa, nu] block come from gpcc_loglik_hess_noise_markov_batch's launches inside the same call (bitwise that entry's by
-// construction); it needs what that entry needs plus the new slots and the full blocks, nothing of the N^2 workspace.
+// the same second-order forward sensitivities, one lane per (row, pair slot with a tau), around the [alpha, rho, kappa, nu] block that
+// mks_noise_hess left on the device.  hess NULL: the noise gradient entry's stages alone.
 // ------------------------------------------------------------------------------------------
+static const MarkovStage mks_noise_hess_tau = {   // rows: the full blocks [M][(4L + 1)^2]
+    "gpcc_markov_noise_hess_tau", MK_NOISE_HESS_TAU, [](gpcc_handle_t h) { return gpcc_markov_noise_hess_tau_slots(h->L); },
+    &gpcc_handle_s::mknt, [](int L) { return (4 * L + 1) * (4 * L + 1); }, markov_noise_lds_bytes,
+    [](const MarkovRun &r, const MarkovStage &s) {
+        GpccMarkovNoiseHessTauArgs a;
+        markov_noise_args(r, a);
+        a.slot = r.h->mknt.slot; a.noise = r.h->mknh.rows; a.hess = r.h->mknt.rows;
+        return markov_stage_launch(r, s, a, gpcc_markov_noise_hess_tau_launch);
+    }};
+
 extern "C" int gpcc_loglik_hess_full_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                                         const double *kappa, const double *nu, double *loglik, double *grad, double *hess,
                                                         int *info)
 {
-    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
-    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
-    if (M == 0) return 0;
-    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
-    const char *dense = "gpcc_loglik_hess_batch on a handle created with the error bars sqrt(kappa^2 sigma^2 + nu) (effective_std)";
-    int rc = markov_refusals(h, "gpcc_loglik_hess_full_noise_markov_batch", dense);
-    if (!rc) rc = markov_noise_ships(h, "gpcc_loglik_hess_full_noise_markov_batch", dense);
-    if (rc) return rc;
-    {
-        const MarkovDims d = markov_dims(primary(h));
-        if (!gpcc_mk_ships<GpccMkShipsNoiseHess>(d.p, d.noff) || !gpcc_mk_ships<GpccMkShipsNoiseHessTau>(d.p, d.noff))
-            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_hess_full_noise_markov_batch: the instantiation <%d, %d> (states of the process, "
-                        "offset states) needs scratch memory and does not ship; use %s", d.p, d.noff, dense);
-    }
-    if (route_fp64(h, "linear-time full Hessian under a noise model", rc, [&](gpcc_handle_t o) {
-            return gpcc_loglik_hess_full_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, loglik, grad, hess, info);
-        }))
-        return rc;
-    GPCC_ON_DEVICE(h, h->device);
-    const int W = 4 * h->L + 1, tslots = gpcc_markov_noise_hess_tau_slots(h->L);
-    double *dd, *da, *dr;
-    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
-        int g = markov_noise_hess_grow(h, M, hess != nullptr);
-        if (!g && hess) g = grow_buf(h, &h->d_mknts, &h->mknts_cap, (long)tslots * M);
-        return (g || !hess) ? g : grow_buf(h, &h->d_mkntb, &h->mkntb_cap, (long)W * W * M);
-    });
-    if (rc) return rc;
-    GpccMarkovNoiseArgs a;
-    rc = markov_noise_hess_enqueue(h, M, dd, da, dr, kappa, nu, grad, hess != nullptr, a);
-    if (rc) return rc;
-    if (hess) {
-        GpccMarkovNoiseHessTauArgs c;
-        c.kappa = a.kappa; c.nu = a.nu; c.slot = h->d_mknts; c.noise = h->d_mknhb; c.hess = h->d_mkntb;
-        rc = markov_slots_launch(h, "gpcc_markov_noise_hess_tau", MK_NOISE_HESS_TAU, M, dd, da, dr, tslots, c, markov_noise_lds(h),
-                                 gpcc_markov_noise_hess_tau_launch);
-        if (rc) return rc;
-        HIPCHK(h, hipMemcpyAsync(hess, h->d_mkntb, sizeof(double) * W * W * M, hipMemcpyDeviceToHost, h->main_stream));
-    }
-    rc = markov_finish(h, M, loglik, info);
-    if (rc) return rc;
-    h->markov_count += M;
-    return 0;
+    const MarkovStep steps[] = {{&mks_noise_eval, nullptr}, {&mks_noise_grad, grad}, {&mks_noise_hess, nullptr}, {&mks_noise_hess_tau, hess}};
+    return markov_entry(h, M, delays, alpha, rho, loglik, info,
+                        {"gpcc_loglik_hess_full_noise_markov_batch",
+                         "gpcc_loglik_hess_batch on a handle created with the error bars sqrt(kappa^2 sigma^2 + nu) (effective_std)",
+                         "linear-time full Hessian under a noise model", delays && alpha && rho && loglik && grad && info,
+                         markov_noise_ships, 3, steps, hess ? 4 : 2, kappa, nu, /* counts */ true},
+                        [&](gpcc_handle_t o) {
+                            return gpcc_loglik_hess_full_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, loglik, grad, hess, info);
+                        });
 }
 
 // ------------------------------------------------------------------------------------------
 // The linear-time (alpha, rho) block of the Hessian of the Markov kernels (gpcc_loglik_hess_hyper_markov_batch; kernel:
-// gpcc_markov_hess.hip.h): the filter's second-order forward sensitivities, one lane per (row, pair slot).  Value, info
-// and gradient come from the gradient entry's launches inside the same call (bitwise gpcc_loglik_grad_markov_batch's by construction);
-// it needs what that entry needs plus the pair slots and the blocks, nothing of the N^2 workspace.
+// gpcc_markov_hess.hip.h): the filter's second-order forward sensitivities, one lane per (row, pair slot).  hess NULL:
+// the gradient entry's stages alone.
 // ------------------------------------------------------------------------------------------
-// the block's buffers for M rows on top of the gradient's, and its launches over the M staged rows: the gradient's, then (with_hess)
-// gpcc_markov_hess and its finish kernel, the blocks left in d_mkhb.  gpcc_loglik_hess_markov_batch shares both
-static int markov_hess_hyper_grow(gpcc_handle_t h, int M, bool with_hess)
-{
-    const int n = h->L + 1;
-    int g = markov_grad_grow(h, M);
-    if (!g && with_hess) g = grow_buf(h, &h->d_mkhs, &h->mkhs_cap, (long)gpcc_markov_hess_slots(h->L) * M);
-    return (g || !with_hess) ? g : grow_buf(h, &h->d_mkhb, &h->mkhb_cap, (long)n * n * M);
-}
+static const MarkovStage mks_hess = {   // rows: the blocks [M][(L + 1)^2]
+    "gpcc_markov_hess", MK_HESS, [](gpcc_handle_t h) { return gpcc_markov_hess_slots(h->L); }, &gpcc_handle_s::mkh,
+    [](int L) { return (L + 1) * (L + 1); }, markov_filter_lds_bytes, [](const MarkovRun &r, const MarkovStage &s) {
+        GpccMarkovHessArgs a;
+        a.slot = r.h->mkh.slot; a.hess = r.h->mkh.rows;
+        return markov_stage_launch(r, s, a, gpcc_markov_hess_launch);
+    }};
 
-static int markov_hess_hyper_enqueue(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, double *grad, bool with_hess)
-{
-    const int rc = markov_grad_enqueue(h, M, dd, da, dr, grad);
-    if (rc || !with_hess) return rc;
-    GpccMarkovHessArgs a;
-    a.slot = h->d_mkhs; a.hess = h->d_mkhb;
-    return markov_slots_launch(h, "gpcc_markov_hess", MK_HESS, M, dd, da, dr, gpcc_markov_hess_slots(h->L), a, gpcc_markov_hess_launch);
-}
+// what both plain Hessian entries refuse, with or without hess
+static const MarkovShips markov_hess_ships[] = {{gpcc_mk_ships<GpccMkShipsHess>, true}};
 
 extern "C" int gpcc_loglik_hess_hyper_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                                    double *loglik, double *grad, double *hess, int *info)
 {
-    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
-    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
-    if (M == 0) return 0;
-    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
-    int rc = markov_refusals(h, "gpcc_loglik_hess_hyper_markov_batch", "gpcc_loglik_hess_hyper_batch");
-    if (rc) return rc;
-    {
-        const MarkovDims d = markov_dims(primary(h));
-        if (!gpcc_mk_ships<GpccMkShipsHess>(d.p, d.noff))
-            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_hess_hyper_markov_batch: the instantiation <%d, %d> (states of the process, "
-                        "offset states) needs scratch memory and does not ship; use gpcc_loglik_hess_hyper_batch", d.p, d.noff);
-    }
-    if (route_fp64(h, "linear-time Hessian block", rc,
-                   [&](gpcc_handle_t o) { return gpcc_loglik_hess_hyper_markov_batch(o, M, delays, alpha, rho, loglik, grad, hess, info); }))
-        return rc;
-    GPCC_ON_DEVICE(h, h->device);
-    double *dd, *da, *dr;
-    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] { return markov_hess_hyper_grow(h, M, hess != nullptr); });
-    if (rc) return rc;
-    rc = markov_hess_hyper_enqueue(h, M, dd, da, dr, grad, hess != nullptr);
-    if (rc) return rc;
-    if (hess) HIPCHK(h, hipMemcpyAsync(hess, h->d_mkhb, sizeof(double) * (h->L + 1) * (h->L + 1) * M, hipMemcpyDeviceToHost, h->main_stream));
-    return markov_finish(h, M, loglik, info);
+    const MarkovStep steps[] = {{&mks_eval, nullptr}, {&mks_grad, grad}, {&mks_hess, hess}};
+    return markov_entry(h, M, delays, alpha, rho, loglik, info,
+                        {"gpcc_loglik_hess_hyper_markov_batch", "gpcc_loglik_hess_hyper_batch", "linear-time Hessian block",
+                         delays && alpha && rho && loglik && grad && info, markov_hess_ships, 1,
+                         steps, hess ? 3 : 2, nullptr, nullptr, /* counts */ false},
+                        [&](gpcc_handle_t o) { return gpcc_loglik_hess_hyper_markov_batch(o, M, delays, alpha, rho, loglik, grad, hess, info); });
 }
 
 // ------------------------------------------------------------------------------------------
 // The linear-time full Hessian of the Markov kernels (gpcc_loglik_hess_markov_batch; kernel: gpcc_markov_hess_tau.hip.h, DESIGN.md
-// 4.21): the rows of tau by the same second-order forward sensitivities, one lane per (row, pair slot with a tau).  Value, info,
-// gradient and the leading (alpha, rho) block come from gpcc_loglik_hess_hyper_markov_batch's launches inside the same call (bitwise
-// that entry's by construction); it needs what that entry needs plus the new slots and the full blocks, nothing of the N^2 workspace.
+// 4.21): the rows of tau by the same second-order forward sensitivities, one lane per (row, pair slot with a tau), around the leading
+// (alpha, rho) block that mks_hess left on the device.  hess NULL: the gradient entry's stages alone.
 // ------------------------------------------------------------------------------------------
+static const MarkovStage mks_hess_tau = {   // rows: the full blocks [M][(2L + 1)^2]
+    "gpcc_markov_hess_tau", MK_HESS_TAU, [](gpcc_handle_t h) { return gpcc_markov_hess_tau_slots(h->L); }, &gpcc_handle_s::mkt,
+    [](int L) { return (2 * L + 1) * (2 * L + 1); }, markov_filter_lds_bytes, [](const MarkovRun &r, const MarkovStage &s) {
+        GpccMarkovHessTauArgs a;
+        a.slot = r.h->mkt.slot; a.hyper = r.h->mkh.rows; a.hess = r.h->mkt.rows;
+        return markov_stage_launch(r, s, a, gpcc_markov_hess_tau_launch);
+    }};
+
 extern "C" int gpcc_loglik_hess_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                              double *loglik, double *grad, double *hess, int *info)
 {
-    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
-    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
-    if (M == 0) return 0;
-    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
-    int rc = markov_refusals(h, "gpcc_loglik_hess_markov_batch", "gpcc_loglik_hess_batch");
-    if (rc) return rc;
-    {
-        const MarkovDims d = markov_dims(primary(h));
-        if (!gpcc_mk_ships<GpccMkShipsHess>(d.p, d.noff))
-            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_hess_markov_batch: the instantiation <%d, %d> (states of the process, "
-                        "offset states) needs scratch memory and does not ship; use gpcc_loglik_hess_batch", d.p, d.noff);
-    }
-    if (route_fp64(h, "linear-time Hessian", rc,
-                   [&](gpcc_handle_t o) { return gpcc_loglik_hess_markov_batch(o, M, delays, alpha, rho, loglik, grad, hess, info); }))
-        return rc;
-    GPCC_ON_DEVICE(h, h->device);
-    const int W = 2 * h->L + 1, slots = gpcc_markov_hess_tau_slots(h->L);
-    double *dd, *da, *dr;
-    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
-        int g = markov_hess_hyper_grow(h, M, hess != nullptr);
-        if (!g && hess) g = grow_buf(h, &h->d_mkts, &h->mkts_cap, (long)slots * M);
-        return (g || !hess) ? g : grow_buf(h, &h->d_mktb, &h->mktb_cap, (long)W * W * M);
-    });
-    if (rc) return rc;
-    rc = markov_hess_hyper_enqueue(h, M, dd, da, dr, grad, hess != nullptr);
-    if (rc) return rc;
-    if (hess) {
-        GpccMarkovHessTauArgs a;
-        a.slot = h->d_mkts; a.hyper = h->d_mkhb; a.hess = h->d_mktb;
-        rc = markov_slots_launch(h, "gpcc_markov_hess_tau", MK_HESS_TAU, M, dd, da, dr, slots, a, gpcc_markov_hess_tau_launch);
-        if (rc) return rc;
-        HIPCHK(h, hipMemcpyAsync(hess, h->d_mktb, sizeof(double) * W * W * M, hipMemcpyDeviceToHost, h->main_stream));
-    }
-    return markov_finish(h, M, loglik, info);
+    const MarkovStep steps[] = {{&mks_eval, nullptr}, {&mks_grad, grad}, {&mks_hess, nullptr}, {&mks_hess_tau, hess}};
+    return markov_entry(h, M, delays, alpha, rho, loglik, info,
+                        {"gpcc_loglik_hess_markov_batch", "gpcc_loglik_hess_batch", "linear-time Hessian",
+                         delays && alpha && rho && loglik && grad && info, markov_hess_ships, 1,
+                         steps, hess ? 4 : 2, nullptr, nullptr, /* counts */ false},
+                        [&](gpcc_handle_t o) { return gpcc_loglik_hess_markov_batch(o, M, delays, alpha, rho, loglik, grad, hess, info); });
 }
 
 // ------------------------------------------------------------------------------------------
 // The linear-time Fisher information of the Markov kernels (gpcc_loglik_fisher_markov_batch; kernel: gpcc_markov_fisher.hip.h, DESIGN.md
-// 4.22): the second moments of the filter's means and of their tangents, one lane per (row, pair slot).  Value, info and gradient come
-// from the gradient entry's launches inside the same call (bitwise gpcc_loglik_grad_markov_batch's by construction); it needs what that
-// entry needs plus the pair slots and the blocks, nothing of the N^2 workspace.
+// 4.22): the second moments of the filter's means and of their tangents, one lane per (row, pair slot).  fisher NULL: the gradient
+// entry's stages alone, and no refusal of its own (the Hessian entries refuse with or without their block).
 // ------------------------------------------------------------------------------------------
+static const MarkovStage mks_fisher = {   // rows: the blocks [M][(2L + 1)^2]
+    "gpcc_markov_fisher", MK_FISHER, [](gpcc_handle_t h) { return gpcc_markov_fisher_slots(h->L); }, &gpcc_handle_s::mkf,
+    [](int L) { return (2 * L + 1) * (2 * L + 1); },
+    // (the instantiations that keep D in LDS take that much more per lane: fewer points are staged beside it)
+    [](gpcc_handle_t h, int thr, bool st) {
+        const MarkovDims d = markov_dims(h);
+        return markov_filter_lds_bytes(h, thr, st) + gpcc_markov_fisher_lds_extra(d.p, d.noff, thr);
+    },
+    [](const MarkovRun &r, const MarkovStage &s) {
+        GpccMarkovFisherArgs a;
+        a.slot = r.h->mkf.slot; a.fisher = r.h->mkf.rows;
+        return markov_stage_launch(r, s, a, gpcc_markov_fisher_launch);
+    }};
+
 extern "C" int gpcc_loglik_fisher_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                                double *loglik, double *grad, double *fisher, int *info)
 {
-    if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
-    if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
-    if (M == 0) return 0;
-    if (!delays || !alpha || !rho || !loglik || !grad || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
-    int rc = markov_refusals(h, "gpcc_loglik_fisher_markov_batch", "gpcc_loglik_hess_batch");
-    if (rc) return rc;
-    if (fisher) {
-        const MarkovDims d = markov_dims(primary(h));
-        if (!gpcc_mk_ships<GpccMkShipsFisher>(d.p, d.noff))
-            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_fisher_markov_batch: the instantiation <%d, %d> (states of the process, "
-                        "offset states) needs scratch memory and does not ship; use gpcc_loglik_hess_batch", d.p, d.noff);
-    }
-    if (route_fp64(h, "linear-time Fisher information", rc,
-                   [&](gpcc_handle_t o) { return gpcc_loglik_fisher_markov_batch(o, M, delays, alpha, rho, loglik, grad, fisher, info); }))
-        return rc;
-    GPCC_ON_DEVICE(h, h->device);
-    const int W = 2 * h->L + 1, slots = gpcc_markov_fisher_slots(h->L);
-    double *dd, *da, *dr;
-    rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
-        int g = markov_grad_grow(h, M);
-        if (!g && fisher) g = grow_buf(h, &h->d_mkfs, &h->mkfs_cap, (long)slots * M);
-        return (g || !fisher) ? g : grow_buf(h, &h->d_mkfb, &h->mkfb_cap, (long)W * W * M);
-    });
-    if (rc) return rc;
-    rc = markov_grad_enqueue(h, M, dd, da, dr, grad);
-    if (rc) return rc;
-    if (fisher) {
-        GpccMarkovFisherArgs a;
-        a.slot = h->d_mkfs; a.fisher = h->d_mkfb;
-        // (the instantiations that keep D in LDS take that much more per lane: fewer points are staged beside it)
-        const MarkovDims d = markov_dims(h);
-        const auto lds = [h, d](int thr, bool st) {
-            return gpcc_markov_lds_bytes(h->N, h->L, thr, st) + gpcc_markov_fisher_lds_extra(d.p, d.noff, thr);
-        };
-        rc = markov_slots_launch(h, "gpcc_markov_fisher", MK_FISHER, M, dd, da, dr, slots, a, lds, gpcc_markov_fisher_launch);
-        if (rc) return rc;
-        HIPCHK(h, hipMemcpyAsync(fisher, h->d_mkfb, sizeof(double) * W * W * M, hipMemcpyDeviceToHost, h->main_stream));
-    }
-    return markov_finish(h, M, loglik, info);
+    static const MarkovShips ships[] = {{gpcc_mk_ships<GpccMkShipsFisher>, true}};
+    const MarkovStep steps[] = {{&mks_eval, nullptr}, {&mks_grad, grad}, {&mks_fisher, fisher}};
+    return markov_entry(h, M, delays, alpha, rho, loglik, info,
+                        {"gpcc_loglik_fisher_markov_batch", "gpcc_loglik_hess_batch", "linear-time Fisher information",
+                         delays && alpha && rho && loglik && grad && info, ships, fisher ? 1 : 0,
+                         steps, fisher ? 3 : 2, nullptr, nullptr, /* counts */ false},
+                        [&](gpcc_handle_t o) { return gpcc_loglik_fisher_markov_batch(o, M, delays, alpha, rho, loglik, grad, fisher, info); });
 }
 
 // ------------------------------------------------------------------------------------------
