@@ -58,6 +58,9 @@ SIGNATURES = {
                                                       ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p]),
     "gpcc_loglik_markov_resampled_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p,
                                                           ctypes.c_int, c_double_p, c_int_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "gpcc_loglik_grad_markov_resampled_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p,
+                                                               ctypes.c_int, c_double_p, c_int_p, c_double_p, c_double_p, c_double_p,
+                                                               c_double_p, c_int_p]),
     "gpcc_loglik_noise_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
                                                       c_double_p, c_double_p, c_int_p]),
     "gpcc_loglik_grad_noise_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p,

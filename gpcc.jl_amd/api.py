@@ -372,6 +372,20 @@ class Objective:
         "markov_resample_bytes_max" (16 N bytes a realisation); a row's value does not depend on the split, on M, R or any order.
         ValueError: a real[m] outside [0, R), counts that are negative or of another shape.  rbf, or marginalise_b with more than
         4 bands: GpccError (unsupported)."""
+        return self._markov_resampled(Y, delays, alpha, rho, real, counts, center, sigma_b, False)[::2]
+
+    def loglik_grad_markov_resampled(self, Y, delays, alpha, rho, real, counts=None, center="own", sigma_b="own"):
+        """loglik_markov_resampled and its exact gradient in linear time (gpcc_loglik_grad_markov_resampled_batch; OU, matern32 and
+        matern52 only) -> (loglik[M], grad[M, 2L+1], info[M]), grad[m] = [d/dalpha_1..L, d/drho, d/dtau_1..L] of loglik[m]: the
+        gradient a fresh Objective on the kept points of realisation real[m] returns from loglik_grad_markov_batch, the band means and
+        Sigma_b being constants of the data.  The arguments, their handling, the split of R across calls and every ValueError are
+        loglik_markov_resampled's; loglik and info are bitwise its results.  A row with info != 0 has a NaN gradient; a realisation
+        that keeps no point gives 0.0 and a zero gradient; for OU an exact tie in shifted time between two kept points of different
+        bands gives the mean of the one-sided derivatives (a tie with a dropped point is no tie)."""
+        return self._markov_resampled(Y, delays, alpha, rho, real, counts, center, sigma_b, True)
+
+    def _markov_resampled(self, Y, delays, alpha, rho, real, counts, center, sigma_b, want_grad):
+        """loglik_markov_resampled's and loglik_grad_markov_resampled's argument handling and calls -> (loglik, grad or None, info)."""
         from . import markov
         M, delays, alpha, rho = self._params(delays, alpha, rho)
         Y = self.realisations(Y)
@@ -384,7 +398,9 @@ class Objective:
         if counts is not None:
             cnt = np.ascontiguousarray(np.concatenate(markov._counts(shape, counts, R), axis=1), dtype=np.int32)
         mean, vb = markov.resample_arguments(shape, Y, cnt, center, sigma_b, self.marginalise_b)
+        W = 2 * self.L + 1
         ll = np.empty(M, dtype=np.float64)
+        grad = np.empty((M, W), dtype=np.float64) if want_grad else None
         info = np.zeros(M, dtype=np.int32)
         per = max(1, int(self.get_option("markov_resample_bytes_max")) // (16 * self.N))
         for r0 in range(0, R, per):
@@ -398,11 +414,16 @@ class Objective:
             mk = _d(mean[r0:r1]) if mean is not None else None
             vk = _d(vb[r0:r1]) if vb is not None else None
             lk, ik = np.empty(len(rows), dtype=np.float64), np.zeros(len(rows), dtype=np.int32)
-            self._chk(_capi.load().gpcc_loglik_markov_resampled_batch(
-                self._h, len(rows), _dp(d), _dp(a), _dp(rh), _ip(rl), r1 - r0, _dp(yk), _ip(ck) if ck is not None else None,
-                _dp(mk) if mk is not None else None, _dp(vk) if vk is not None else None, _dp(lk), _ip(ik)))
+            args = (self._h, len(rows), _dp(d), _dp(a), _dp(rh), _ip(rl), r1 - r0, _dp(yk), _ip(ck) if ck is not None else None,
+                    _dp(mk) if mk is not None else None, _dp(vk) if vk is not None else None, _dp(lk))
+            if want_grad:
+                gk = np.empty((len(rows), W), dtype=np.float64)
+                self._chk(_capi.load().gpcc_loglik_grad_markov_resampled_batch(*args, _dp(gk), _ip(ik)))
+                grad[rows] = gk
+            else:
+                self._chk(_capi.load().gpcc_loglik_markov_resampled_batch(*args, _ip(ik)))
             ll[rows], info[rows] = lk, ik
-        return ll, info
+        return ll, grad, info
 
     def predict_markov_batch(self, delays, alpha, rho, ttest, weights=None):
         """predict_batch in linear time (gpcc_predict_markov_batch: two Kalman filters and a combine per row, O(N + T); OU, matern32 and

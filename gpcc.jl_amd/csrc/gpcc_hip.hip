@@ -18,6 +18,7 @@
 #include "gpcc_markov_fisher.hip.h"
 #include "gpcc_markov_multi.hip.h"
 #include "gpcc_markov_resample.hip.h"
+#include "gpcc_markov_resample_grad.hip.h"
 #include "gpcc_markov_noise.hip.h"
 #include "gpcc_markov_noise_hess.hip.h"
 #include "gpcc_markov_noise_hess_tau.hip.h"
@@ -2185,7 +2186,7 @@ static void markov_fill_args(gpcc_handle_t h, int M, const double *dd, const dou
 }
 
 // the kernels with dynamic LDS, for gpcc_handle::mk_lds_raised
-enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI, MK_RESAMPLE, MK_NOISE, MK_NOISE_GRAD, MK_NOISE_HESS, MK_NOISE_HESS_TAU };
+enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI, MK_RESAMPLE, MK_RESAMPLE_GRAD, MK_NOISE, MK_NOISE_GRAD, MK_NOISE_HESS, MK_NOISE_HESS_TAU };
 
 // The launch of every kernel of the filter, `name` in messages: one lane per row, `rows` rows along x and ny lanes per row along y.
 // The shape: one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy beyond; the light
@@ -2437,45 +2438,52 @@ extern "C" int gpcc_loglik_markov_multi_batch(gpcc_handle_t h, int M, const doub
 }
 
 // ------------------------------------------------------------------------------------------
-// The linear-time log-likelihood of rows with their own resampled data set (gpcc_loglik_markov_resampled_batch; kernel:
-// gpcc_markov_resample.hip.h): one lane per row, as gpcc_loglik_markov_batch, reading per step one packed pair
-// {residual, sigma^2 / count} of the row's realisation.  It needs what gpcc_loglik_markov_batch needs plus the buffers below, nothing
-// of the N^2 workspace.  Everything that can be refused is refused on the host before any device work.  The entry does not chunk (a
-// row may reference any realisation): a call whose packed pairs (16 N R bytes) exceed option "markov_resample_bytes_max" is refused,
-// and the callers split R.
+// The linear-time log-likelihood of rows with their own resampled data set and its gradient (gpcc_loglik_markov_resampled_batch,
+// gpcc_loglik_grad_markov_resampled_batch; kernels: gpcc_markov_resample.hip.h, DESIGN.md 4.24, gpcc_markov_resample_grad.hip.h,
+// DESIGN.md 4.28): one lane per row (the gradient: per row and parameter slot), as gpcc_loglik_markov_batch and
+// gpcc_loglik_grad_markov_batch, reading per step one packed pair {residual, sigma^2 / count} of the row's realisation.  They need what
+// gpcc_loglik_markov_batch needs plus the buffers below (the gradient: and the buffers of the plain gradient's stage, mkg), nothing of
+// the N^2 workspace.  Everything that can be refused is refused on the host before any device work.  The entries do not chunk (a row
+// may reference any realisation): a call whose packed pairs (16 N R bytes) exceed option "markov_resample_bytes_max" is refused, and the
+// callers split R.  Both entries are markov_resampled(), `who` the entry's name in messages: one set of checks, one pack, one value
+// kernel -- so the gradient entry's loglik and info are the value entry's bitwise by construction -- and with want_grad the gradient
+// kernel and gpcc_markov_grad's finish kernel behind them.  The per-realisation data source does not fit MarkovRun, so the pair runs
+// beside markov_entry() and not through it.
 // ------------------------------------------------------------------------------------------
-extern "C" int gpcc_loglik_markov_resampled_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
-                                                  const int *real, int R, const double *Y, const int *count, const double *mean,
-                                                  const double *sigma_b, double *loglik, int *info)
+static int markov_resampled(gpcc_handle_t h, const char *who, int M, const double *delays, const double *alpha, const double *rho,
+                            const int *real, int R, const double *Y, const int *count, const double *mean, const double *sigma_b,
+                            double *loglik, bool want_grad, double *grad, int *info)
 {
     if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
     if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
     if (M == 0) return 0;
     if (R < 1) return fail(h, GPCC_ERR_ARGUMENT, "R=%d < 1", R);
     if (!Y || !real) return fail(h, GPCC_ERR_ARGUMENT, "NULL %s", Y ? "real" : "Y");
-    if (!delays || !alpha || !rho || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
-    int rc = markov_refusals(h, "gpcc_loglik_markov_resampled_batch", "gpcc_loglik_batch on one handle per realisation");
+    if (!delays || !alpha || !rho || !loglik || !info || (want_grad && !grad)) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
+    int rc = markov_refusals(h, who, want_grad ? "gpcc_loglik_grad_batch on one handle per realisation" : "gpcc_loglik_batch on one handle per realisation");
     if (rc) return rc;
     const gpcc_handle_t q = primary(h);
     {
         const MarkovDims d = markov_dims(q);
-        if (!gpcc_mk_ships<GpccMkShipsResample>(d.p, d.noff))
-            return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_markov_resampled_batch: the instantiation <%d, %d> (states of the process, "
-                                                 "offset states) does not ship; use gpcc_loglik_batch on one handle per realisation", d.p, d.noff);
+        if (!gpcc_mk_ships<GpccMkShipsResample>(d.p, d.noff) || (want_grad && !gpcc_mk_ships<GpccMkShipsResampleGrad>(d.p, d.noff)))
+            return fail(h, GPCC_ERR_UNSUPPORTED, "%s: the instantiation <%d, %d> (states of the process, "
+                                                 "offset states) does not ship; use %s on one handle per realisation", who, d.p, d.noff,
+                        want_grad ? "gpcc_loglik_grad_batch" : "gpcc_loglik_batch");
     }
     const long N = q->N, budget = q->markov_resample_bytes_max;
     if (16 * N * (long)R > budget)
-        return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loglik_markov_resampled_batch: R=%d realisations of N=%ld points pack to %ld bytes, over "
-                                             "the limit markov_resample_bytes_max=%ld; split R across calls", R, N, 16 * N * (long)R, budget);
+        return fail(h, GPCC_ERR_UNSUPPORTED, "%s: R=%d realisations of N=%ld points pack to %ld bytes, over "
+                                             "the limit markov_resample_bytes_max=%ld; split R across calls", who, R, N, 16 * N * (long)R, budget);
     for (int m = 0; m < M; ++m)
         if (real[m] < 0 || real[m] >= R) return fail(h, GPCC_ERR_ARGUMENT, "real[%d]=%d outside [0, R=%d)", m, real[m], R);
     if (count)
         for (long k = 0; k < N * (long)R; ++k)
             if (count[k] < 0) return fail(h, GPCC_ERR_ARGUMENT, "count[%ld][%ld]=%d < 0", k / N, k % N, count[k]);
-    if (route_fp64(h, "linear-time log-likelihood of resampled data sets", rc, [&](gpcc_handle_t o) {
+    if (route_fp64(h, want_grad ? "linear-time gradient of resampled data sets" : "linear-time log-likelihood of resampled data sets", rc,
+                   [&](gpcc_handle_t o) {
             const long own = o->markov_resample_bytes_max;
             o->markov_resample_bytes_max = budget;   // the caller's limit holds on the handle that computes
-            const int r2 = gpcc_loglik_markov_resampled_batch(o, M, delays, alpha, rho, real, R, Y, count, mean, sigma_b, loglik, info);
+            const int r2 = markov_resampled(o, who, M, delays, alpha, rho, real, R, Y, count, mean, sigma_b, loglik, want_grad, grad, info);
             o->markov_resample_bytes_max = own;
             return r2;
         }))
@@ -2483,6 +2491,8 @@ extern "C" int gpcc_loglik_markov_resampled_batch(gpcc_handle_t h, int M, const 
     GPCC_ON_DEVICE(h, h->device);
     const int L = h->L;
     const long RN = N * (long)R, RL = (long)R * L;
+    const MarkovDims dims = markov_dims(h);
+    const int slots = gpcc_markov_grad_slots(L, dims.p == 1), W = 2 * L + 1;
     double *dd, *da, *dr;
     rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
         int g = grow_buf(h, &h->d_mkrv, &h->mkrv_cap, RN);
@@ -2494,13 +2504,15 @@ extern "C" int gpcc_loglik_markov_resampled_batch(gpcc_handle_t h, int M, const 
             g = grow_buf(h, &h->d_mkrp, &h->mkrp_cap, N);
             if (!g) HIPCHK(h, hipMemcpy(h->d_mkrp, h->mk_perm.data(), sizeof(int) * N, hipMemcpyHostToDevice));
         }
+        if (!g && want_grad) g = grow_buf(h, &h->mkg.slot, &h->mkg.slot_cap, (long)slots * M);
+        if (!g && want_grad) g = grow_buf(h, &h->mkg.rows, &h->mkg.rows_cap, (long)W * M);
         return g;
     });
     if (rc) return rc;
     const hipStream_t ms = h->main_stream;
     // the means and the offsets' prior variances of every realisation, the handle's where the caller gives none: [R][L] | [R][L]
     std::vector<double> hm((size_t)2 * RL);
-    const int noff = markov_dims(h).noff;
+    const int noff = dims.noff;
     for (long r = 0; r < R; ++r)
         for (int l = 0; l < L; ++l) {
             hm[r * L + l] = mean ? mean[r * L + l] : h->mean_b[l];
@@ -2522,10 +2534,36 @@ extern "C" int gpcc_loglik_markov_resampled_batch(gpcc_handle_t h, int M, const 
     rc = markov_launch(h, "gpcc_markov_resample", MK_RESAMPLE, M, 1, a.stage, markov_filter_lds(h),
                        [&](const GpccMkLaunch &g) { return gpcc_markov_resample_launch(g, a); });
     if (rc) return rc;
+    if (want_grad) {   // the slots, then the rows [M][2L + 1] from them and from the value kernel's info
+        GpccMarkovResampleGradArgs ga;
+        markov_fill_args(h, M, dd, da, dr, ga);
+        ga.slot = h->mkg.slot; ga.grad = h->mkg.rows; ga.twice = dims.p == 1;
+        ga.rv = a.rv; ga.real = a.real; ga.sigb = a.sigb;
+        rc = markov_launch(h, "gpcc_markov_resample_grad", MK_RESAMPLE_GRAD, M, slots, ga.stage, markov_filter_lds(h),
+                           [&](const GpccMkLaunch &g) { return gpcc_markov_resample_grad_launch(g, slots, ga); });
+        if (rc) return rc;
+        HIPCHK(h, hipMemcpyAsync(grad, h->mkg.rows, sizeof(double) * W * M, hipMemcpyDeviceToHost, ms));
+    }
     rc = markov_finish(h, M, loglik, info);   // (its synchronisation also guards hm and the caller's arrays)
     if (rc) return rc;
     h->markov_count += M;
     return 0;
+}
+
+extern "C" int gpcc_loglik_markov_resampled_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                                  const int *real, int R, const double *Y, const int *count, const double *mean,
+                                                  const double *sigma_b, double *loglik, int *info)
+{
+    return markov_resampled(h, "gpcc_loglik_markov_resampled_batch", M, delays, alpha, rho, real, R, Y, count, mean, sigma_b, loglik, false,
+                            nullptr, info);
+}
+
+extern "C" int gpcc_loglik_grad_markov_resampled_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                                       const int *real, int R, const double *Y, const int *count, const double *mean,
+                                                       const double *sigma_b, double *loglik, double *grad, int *info)
+{
+    return markov_resampled(h, "gpcc_loglik_grad_markov_resampled_batch", M, delays, alpha, rho, real, R, Y, count, mean, sigma_b, loglik,
+                            true, grad, info);
 }
 
 // ------------------------------------------------------------------------------------------

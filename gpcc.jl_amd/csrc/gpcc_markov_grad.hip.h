@@ -30,8 +30,10 @@
 // results go to slot[slot][row], so a wave's stores coalesce.  Lanes beyond M compute row M - 1 again and store nothing.  No atomics,
 // no communication between lanes.
 //
-// ONE WALK, TWO KERNELS.  gpcc_mkg_walk is a template on the lane's noise policy (below): gpcc_markov_grad instantiates it on
-// GpccMkPlain, gpcc_markov_noise_grad (gpcc_markov_noise.hip.h) on a lane with its own kappa and nu for its alpha, rho and tau slots.
+// ONE WALK, THREE KERNELS.  gpcc_mkg_walk is a template on the lane's noise policy and on its data policy (both below):
+// gpcc_markov_grad instantiates it on GpccMkPlain and GpccMkOwnData, gpcc_markov_noise_grad (gpcc_markov_noise.hip.h) on a lane with its
+// own kappa and nu for its alpha, rho and tau slots, gpcc_markov_resample_grad (gpcc_markov_resample_grad.hip.h) on a lane that reads
+// its own resampled data set and skips the points it drops.
 // gpcc_mkg_update has the kind GPCC_MKG_NOISE for the tangent by a kappa or a nu, which the second-order walks carry as well.
 #pragma once
 #include "gpcc_markov.hip.h"
@@ -48,6 +50,21 @@
 struct GpccMkPlain {
     static constexpr bool noise = false;
     __device__ __forceinline__ double var(const GpccMkLane &, int, double s2) const { return s2; }
+};
+
+// THE DATA POLICY of the first-order walk: what a lane observes at the point the cursor took.  take() hands over the residual, the
+// variance (before the noise policy), the lag from the lane's last observation and whether this is its first; kept false: the point is
+// not in the lane's data set and the walk does nothing at it.  The handle's own data: gpcc_mk_next's r, s2 and d as they are, never a
+// skip, no state -- after inlining the statements of the walk have the operands they had without a policy.  `resampled` says at compile
+// time whose Sigma_b the prior state takes: the kernel's argument or the policy's own (gpcc_markov_resample_grad.hip.h, GpccMkrData)
+struct GpccMkObs {
+    double r, s2, d;
+    bool first, kept;
+};
+
+struct GpccMkOwnData {
+    static constexpr bool resampled = false;
+    __device__ __forceinline__ GpccMkObs take(const GpccMkLane &, const GpccMkPoint &p, int j, double) { return {p.r, p.s2, p.d, j == 0, true}; }
 };
 
 // GpccMarkovArgs' fields under the same names (the host fills both through one template) and the slots
@@ -277,15 +294,20 @@ __device__ __forceinline__ void gpcc_mkg_update(int b, double al, bool dh, doubl
 }
 
 // one lane's walk: KIND of slot, tb: the band of an alpha or tau slot, rb / rr: the band whose rank among ties is rr instead of its
-// index (rb = -1: none), handed to gpcc_mk_next<true>.  nz: the lane's noise policy.  The alpha, rho and tau slots of gpcc_markov_grad
-// (GpccMkPlain) and of gpcc_markov_noise_grad (GpccMknLane) are this one walk; ARGS is the kernel's, read by the cursor as it is there
-template <int P, int NOFF, int KIND, class ARGS, class NZ>
-__device__ __forceinline__ double gpcc_mkg_walk(const ARGS &a, const GpccMkLane &ln, const NZ &nz, int tb, int rb, int rr)
+// index (rb = -1: none), handed to gpcc_mk_next<true>.  nz: the lane's noise policy, dt: its data policy (the walk's own copy: a policy
+// may keep state from one observation to the next).  The alpha, rho and tau slots of gpcc_markov_grad (GpccMkPlain, GpccMkOwnData), of
+// gpcc_markov_noise_grad (GpccMknLane) and of gpcc_markov_resample_grad (GpccMkrData) are this one walk; ARGS is the kernel's, read by
+// the cursor as it is there
+template <int P, int NOFF, int KIND, class ARGS, class NZ, class DT = GpccMkOwnData>
+__device__ __forceinline__ double gpcc_mkg_walk(const ARGS &a, const GpccMkLane &ln, const NZ &nz, int tb, int rb, int rr, DT dt = DT())
 {
     constexpr int NS = P + NOFF;
     const double rho = ln.rho;
     double lam, lam2, Q[P][P], mu[NS], C[NS][NS];
-    gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
+    if constexpr (DT::resampled)
+        gpcc_mk_init<P, NOFF>(rho, dt.sigma_b, lam, lam2, Q, mu, C);
+    else
+        gpcc_mk_init<P, NOFF>(rho, a.sigma_b, lam, lam2, Q, mu, C);
     // the tangents: zero, except the rho lane's prior state (dPinf)
     double Qd[P][P], dmu[NS], dC[NS][NS];
     const double dlam = -lam / rho;
@@ -300,9 +322,11 @@ __device__ __forceinline__ double gpcc_mkg_walk(const ARGS &a, const GpccMkLane 
     double ll = 0.0, dll = 0.0, sprev = 0.0;
     int bprev = -1;
     for (int j = 0; j < a.N; ++j) {
-        const GpccMkPoint p = gpcc_mk_next<true>(a, ln, j, sprev, rb, rr);
+        const GpccMkPoint p = gpcc_mk_next<true>(a, ln, j, sprev, rb, rr);   // (leaves the point's shifted time in sprev)
         const int b = p.b;
-        const double d = p.d, s2 = nz.var(ln, b, p.s2);
+        const GpccMkObs o = dt.take(ln, p, j, sprev);
+        if (!o.kept) continue;   // not in the lane's data: bprev stays the band of its last observation
+        const double d = o.d, s2 = nz.var(ln, b, o.s2);
 
         double A[P][P], Ad[P][P];
         gpcc_mk_transition<P>(lam, lam2, d, A);
@@ -311,7 +335,7 @@ __device__ __forceinline__ double gpcc_mkg_walk(const ARGS &a, const GpccMkLane 
             ad = true;
             gpcc_mkg_dtransition_rate<P>(lam, lam2, d, dlam, Ad);
         } else if constexpr (KIND == GPCC_MKG_TAU) {
-            const int dd = (j == 0) ? 0 : (int)(bprev == tb) - (int)(b == tb);
+            const int dd = o.first ? 0 : (int)(bprev == tb) - (int)(b == tb);
             ad = dd != 0;
             gpcc_mkg_dtransition_lag<P>(lam, lam2, (double)dd, A, Ad);
         } else {
@@ -323,8 +347,8 @@ __device__ __forceinline__ double gpcc_mkg_walk(const ARGS &a, const GpccMkLane 
         bprev = b;
         gpcc_mkg_propagate<P, NOFF, KIND>(A, Ad, ad, Q, Qd, mu, C, dmu, dC);
         gpcc_mk_propagate<P, NOFF>(A, Q, mu, C);
-        gpcc_mkg_update<P, NOFF, KIND>(b, p.al, KIND == GPCC_MKG_ALPHA && b == tb, p.r, s2, mu, C, dmu, dC, dll);
-        gpcc_mk_update<P, NOFF>(b, p.al, p.r, s2, mu, C, ll);
+        gpcc_mkg_update<P, NOFF, KIND>(b, p.al, KIND == GPCC_MKG_ALPHA && b == tb, o.r, s2, mu, C, dmu, dC, dll);
+        gpcc_mk_update<P, NOFF>(b, p.al, o.r, s2, mu, C, ll);
     }
     return dll;
 }
@@ -353,3 +377,5 @@ __global__ void __launch_bounds__(256) gpcc_markov_grad(const GpccMarkovGradArgs
 // ---- launches (gpcc_markov_grad_inst.hip: an object of its own) ----
 // grid (g.blocks, slots) of gpcc_markov_grad<g.p, g.noff>, then the finish kernel over the M rows
 hipError_t gpcc_markov_grad_launch(const GpccMkLaunch &g, int slots, const GpccMarkovGradArgs &a);
+// the finish kernel alone, over the M rows of a: the rows [M][2L + 1] from the slots, for a family that fills gpcc_markov_grad's slots
+hipError_t gpcc_markov_grad_finish_launch(hipStream_t s, const GpccMarkovGradArgs &a);

@@ -22,12 +22,16 @@ static __global__ void __launch_bounds__(64) gpcc_markov_grad_finish(const GpccM
     }
 }
 
+hipError_t gpcc_markov_grad_finish_launch(hipStream_t s, const GpccMarkovGradArgs &a)
+{
+    gpcc_markov_grad_finish<<<dim3((a.M + 63) / 64), dim3(64), 0, s>>>(a);
+    return hipGetLastError();
+}
+
 hipError_t gpcc_markov_grad_launch(const GpccMkLaunch &g, int slots, const GpccMarkovGradArgs &a)
 {
     const hipError_t e = gpcc_mk_dispatch<GpccMkShipsAll>(g.p, g.noff, [&](auto P, auto NOFF) {
         return gpcc_mk_launch_kernel(gpcc_markov_grad<P(), NOFF()>, g, slots, a);
     });
-    if (e != hipSuccess) return e;
-    gpcc_markov_grad_finish<<<dim3((a.M + 63) / 64), dim3(64), 0, g.s>>>(a);
-    return hipGetLastError();
+    return e != hipSuccess ? e : gpcc_markov_grad_finish_launch(g.s, a);
 }

@@ -19,6 +19,7 @@ import numpy as np
 
 from . import laplace
 from .api import Objective, PosDefException, getprobabilities, mvnormal_logpdf
+from .bfgs import BatchedBFGS
 from .neldermead import BatchedNelderMead
 
 
@@ -348,11 +349,17 @@ def realisation_delays(objective, candidatedelays, alpha, rho, Y, logprior=None,
 class RealisationRefits(collections.namedtuple("RealisationRefits", "loglikel alpha rho f_calls rounds delays start_loglikel")):
     """realisation_refits' result: loglikel[R, G] (each realisation's refitted profile likelihood over the grid), alpha[R, G, L],
     rho[R, G], f_calls, rounds, delays (the RealisationDelays of loglikel) and start_loglikel[R, G] (the value at the warm start as the
-    optimiser holds it, loglikel >= it; None with start=None)."""
+    optimiser holds it, loglikel >= it; None with start=None).  Beside the fields, two attributes that realisation_refits sets on its
+    result (copies made through the tuple, _replace or pickle fall back to None): x[R, G, L + 1], the returned cells in the
+    optimiser's coordinates, alpha = makepositive(x[..., :L]) + 1e-8 and rho = transformbetween(x[..., L], rhomin, rhomax), what
+    unpack_grad takes; converged[R, G], with optimiser="bfgs" whether the gradient of the cell's run fell to g_tol, None with
+    "neldermead", which has no such test."""
+    x = None
+    converged = None
 
 
 def realisation_refits(objective, candidatedelays, Y, counts=None, *, iterations, start=None, seed=1, numberofrestarts=1,
-                       initialrandom=5, rhomin=0.1, rhomax=20.0, logprior=None, probabilities=getprobabilities):
+                       initialrandom=5, rhomin=0.1, rhomax=20.0, logprior=None, probabilities=getprobabilities, optimiser="neldermead"):
     """FR/RSS with a REFIT PER REALISATION: fits (alpha, rho) at every row of candidatedelays (G, L) for every resampled data set
     (Y, counts) on objective's cadence (synthetic.resample's result; counts None: all 1) -> RealisationRefits.  The lock-step
     BatchedNelderMead of gpcc_grid's python engine runs over the problems (realisation, delay, restart); every optimiser round is ONE
@@ -364,8 +371,16 @@ def realisation_refits(objective, candidatedelays, Y, counts=None, *, iterations
     gpcc_grid(engine="python", solver="markov") on its reduced data set.  start=(alpha[G, L], rho[G]), usually a GridFit of the
     original data (res.alpha, res.rho): every realisation starts Nelder-Mead at delay g from (alpha[g], rho[g]), with one restart and
     no random candidates; rho is clipped into (rhomin, rhomax).  delays: getprobabilities per realisation over its refitted likelihoods
-    (logprior, probabilities: realisation_delays').  realisation_delays is the frozen route, one pass and no refit."""
+    (logprior, probabilities: realisation_delays').  realisation_delays is the frozen route, one pass and no refit.
+
+    optimiser "neldermead" (default): as above.  "bfgs": the same problems from the same starting points by the lock-step
+    bfgs.BatchedBFGS (g_tol 1e-6 on the gradient in the optimiser's coordinates), every round ONE
+    objective.loglik_grad_markov_resampled call, whose gradient unpack_grad takes to the optimiser's coordinates; `iterations` bounds
+    the accepted steps of a problem.  The fields of the result are the same (start_loglikel: the value at the optimiser's first
+    point); its attributes x and converged are RealisationRefits'."""
     from . import markov
+    if optimiser not in ("neldermead", "bfgs"):
+        raise ValueError("optimiser must be 'neldermead' or 'bfgs', got %r" % (optimiser,))
     cand = np.ascontiguousarray(np.asarray(candidatedelays, np.float64).reshape(len(candidatedelays), -1))
     G, L = cand.shape
     shape = [np.empty(int(n)) for n in objective.Nl] if hasattr(objective, "Nl") else objective.data[0]
@@ -404,6 +419,14 @@ def realisation_refits(objective, candidatedelays, Y, counts=None, *, iterations
                                                      sigma_b=vb)
         return np.where(info == 0, -ll, np.inf)
 
+    def negfg(pidx, X):
+        with np.errstate(over="ignore"):                                 # (a long trial step: exp(-x) overflows to a rho on its bound)
+            alpha, rho = unpack(X)
+            ll, grad, info = objective.loglik_grad_markov_resampled(Yf, cand[(pidx // K) % G], alpha, rho, pidx // (G * K), counts=cf,
+                                                                    center=mean, sigma_b=vb)
+            bad = info != 0
+            return np.where(bad, np.inf, -ll), np.where(bad[:, None], 0.0, -unpack_grad(X, grad[:, :L + 1], L, rhomin, rhomax))
+
     extra_calls, extra_rounds, f_start = 0, 0, None
     if start is None:
         pid = np.repeat(np.arange(P), initialrandom)
@@ -413,16 +436,130 @@ def realisation_refits(objective, candidatedelays, Y, counts=None, *, iterations
         extra_calls, extra_rounds = P * initialrandom, 1
     else:
         x0 = np.tile(xs, (R, 1))
-        f_start = -negobj(np.arange(P), x0).reshape(R, G)
-    nm = BatchedNelderMead(x0, negobj, iterations=iterations, g_tol=1e-6)
-    xmin, fmin = nm.run()
+        if optimiser == "neldermead":
+            f_start = -negobj(np.arange(P), x0).reshape(R, G)
+    if optimiser == "bfgs":
+        nm = BatchedBFGS(x0, negfg, iterations=iterations, g_tol=1e-6)
+        xmin, fmin = nm.run()
+        if start is not None:
+            f_start = -nm.f_start.reshape(R, G)
+    else:
+        nm = BatchedNelderMead(x0, negobj, iterations=iterations, g_tol=1e-6)
+        xmin, fmin = nm.run()
     fmin = fmin.reshape(R * G, K)
     pick = np.argmin(fmin, axis=1)
     a_sel, r_sel = unpack(xmin.reshape(R * G, K, L + 1)[np.arange(R * G), pick])
     ll = -fmin[np.arange(R * G), pick].reshape(R, G)
     prob = np.stack([probabilities(ll[r]) if logprior is None else probabilities(ll[r], logprior) for r in range(R)])
-    return RealisationRefits(ll, a_sel.reshape(R, G, L), r_sel.reshape(R, G), nm.f_calls + extra_calls, nm.rounds + extra_rounds,
-                             RealisationDelays(prob, np.argmax(prob, axis=1), prob @ cand), f_start)
+    out = RealisationRefits(ll, a_sel.reshape(R, G, L), r_sel.reshape(R, G), nm.f_calls + extra_calls, nm.rounds + extra_rounds,
+                            RealisationDelays(prob, np.argmax(prob, axis=1), prob @ cand), f_start)
+    out.x = xmin.reshape(R * G, K, L + 1)[np.arange(R * G), pick].reshape(R, G, L + 1)   # (attributes beside the fields, which stay as they are)
+    if optimiser == "bfgs":
+        out.converged = nm.converged.reshape(R * G, K)[np.arange(R * G), pick].reshape(R, G)
+    return out
+
+
+class RealisationPeaks(collections.namedtuple("RealisationPeaks", "delays alpha rho loglikel start_loglikel converged f_calls rounds")):
+    """realisation_peaks' result: delays[R, L] (each realisation's delay as a continuous number), alpha[R, L], rho[R], loglikel[R] (the
+    value there), start_loglikel[R] (the value at the grid cell it started from, loglikel >= it), converged[R] (the gradient in the
+    optimiser's coordinates fell to g_tol), f_calls, rounds.  Beside the fields the attribute x[R, L + 1 + F] that realisation_peaks
+    sets: the returned points in the optimiser's coordinates -- alpha and rho as RealisationRefits.x holds them, then the F free delays,
+    tau_l = transformbetween(x, min, max of column l of the grid); a realisation that kept its cell has the cell's own delays and the
+    coordinates of its start."""
+    x = None
+
+
+def realisation_peaks(objective, candidatedelays, Y, counts=None, *, start, iterations, free_delays=None, rhomin=0.1, rhomax=20.0,
+                      g_tol=1e-6, logprior=None, probabilities=getprobabilities):
+    """EACH REALISATION'S DELAY AS A CONTINUOUS NUMBER: for every resampled data set (Y, counts) on objective's cadence, takes its most
+    probable cell of the grid candidatedelays (G, L) and from there maximises the log-likelihood JOINTLY over (alpha, rho) and the free
+    delays with the lock-step bfgs.BatchedBFGS -> RealisationPeaks.  That is R problems of 1 + L + len(free_delays) parameters per round,
+    not R x G, every round ONE objective.loglik_grad_markov_resampled call (linear time: OU, matern32, matern52), each realisation
+    under its own band means and, with marginalise_b, its own offsets' prior variances.  The scatter of delays[:, l] is the FR/RSS
+    scatter of the peak, no longer quantised to the grid's spacing.
+
+    start: a RealisationRefits of the same (candidatedelays, Y, counts) -- realisation r starts at its cell start.delays.map_index[r]
+    with the refitted (alpha, rho) of that cell -- or (alpha[G, L], rho[G]), the per-delay hyper-parameters of a GridFit of the
+    original data: the cell is then the most probable one under those frozen hyper-parameters (realisation_delays; with counts, one
+    loglik_markov_resampled pass over the R x G cells and getprobabilities per realisation; logprior, probabilities:
+    realisation_delays').  free_delays: the bands (0-based) whose
+    delay moves; None: all but the first.  A free delay tau_l = transformbetween(x, min, max) of column l of the grid, so it stays inside
+    the grid's range; a start on the edge of that range is moved inside by 1e-3 of its width, where the transform still has a slope.  rho
+    stays in (rhomin, rhomax) and alpha positive as in the fit.  The other delays stay the cell's.  If no accepted step betters the
+    cell itself, the cell is returned (converged False unless its own gradient is below g_tol).
+
+    For OU the likelihood has kinks in tau wherever two shifted times of different bands cross; there the gradient is the mean of the
+    one-sided derivatives, the line search may stall on the kink, and such a realisation ends with converged = False at its best
+    point.  That is reported, not raised; the Matern kernels are C^1 in tau."""
+    from . import markov
+    cand = np.ascontiguousarray(np.asarray(candidatedelays, np.float64).reshape(len(candidatedelays), -1))
+    G, L = cand.shape
+    shape = [np.empty(int(n)) for n in objective.Nl] if hasattr(objective, "Nl") else objective.data[0]
+    Yb = markov._bands(shape, Y)
+    R = Yb[0].shape[0]
+    cb = markov._counts(shape, counts, R)
+    mean, vb = markov.resample_constants(shape, Yb, cb, bool(objective.marginalise_b))
+    Yf = np.ascontiguousarray(np.concatenate(Yb, axis=1))
+    cf = None if counts is None else np.ascontiguousarray(np.concatenate(cb, axis=1))
+    free = np.arange(1, L) if free_delays is None else np.unique(np.asarray(free_delays, dtype=np.int64).reshape(-1))
+    if len(free) and (free.min() < 0 or free.max() >= L):
+        raise ValueError("free_delays must be bands in [0, %d)" % L)
+    lo, hi = cand[:, free].min(axis=0), cand[:, free].max(axis=0)
+    if (hi <= lo).any():
+        raise ValueError("free_delays: band %d has one delay in the grid, no range to move in" % int(free[np.argmax(hi <= lo)]))
+    real = np.arange(R)
+    if isinstance(start, RealisationRefits):
+        cell = np.asarray(start.delays.map_index, dtype=np.int64).reshape(R)
+        a0, r0 = np.asarray(start.alpha, np.float64)[real, cell], np.asarray(start.rho, np.float64)[real, cell]
+    else:
+        ag, rg = np.asarray(start[0], np.float64).reshape(G, L), np.asarray(start[1], np.float64).reshape(G)
+        if counts is None:
+            cell = np.asarray(realisation_delays(objective, cand, ag, rg, Yb, logprior=logprior, probabilities=probabilities).map_index,
+                              dtype=np.int64)
+        else:
+            ll, info = objective.loglik_markov_resampled(Yf, np.tile(cand, (R, 1)), np.tile(ag, (R, 1)), np.tile(rg, R), np.repeat(real, G),
+                                                         counts=cf, center=mean, sigma_b=vb)
+            if (np.asarray(info) != 0).any():
+                bad = int(np.flatnonzero(np.asarray(info) != 0)[0])
+                raise ValueError("realisation_peaks: realisation %d at grid point %d has info = %d" % (bad // G, bad % G, int(info[bad])))
+            ll = ll.reshape(R, G)
+            cell = np.array([int(np.argmax(probabilities(ll[r]) if logprior is None else probabilities(ll[r], logprior))) for r in range(R)],
+                            dtype=np.int64)
+        a0, r0 = ag[cell], rg[cell]
+    r0 = np.clip(r0, rhomin + 1e-9 * (rhomax - rhomin), rhomax - 1e-9 * (rhomax - rhomin))
+    tau0 = cand[cell]
+    tf0 = np.clip(tau0[:, free], lo + 1e-3 * (hi - lo), hi - 1e-3 * (hi - lo))
+    x0 = np.concatenate([invmakepositive(np.maximum(a0 - 1e-8, 1e-300)), invtransformbetween(r0, rhomin, rhomax)[:, None],
+                         invtransformbetween(tf0, lo, hi)], axis=1)
+
+    def negfg(pidx, X, at_cell=False):
+        with np.errstate(over="ignore"):                                 # (a long trial step: exp(-x) overflows to a bound)
+            alpha, rho = makepositive(X[:, :L]) + 1e-8, transformbetween(X[:, L], rhomin, rhomax)
+            tau = tau0[pidx].copy()
+            if not at_cell:
+                tau[:, free] = transformbetween(X[:, L + 1:], lo, hi)
+            ll, grad, info = objective.loglik_grad_markov_resampled(Yf, tau, alpha, rho, pidx, counts=cf, center=mean, sigma_b=vb)
+            g = unpack_grad(X[:, :L + 1], grad[:, :L + 1], L, rhomin, rhomax)
+            st = 1.0 / (1.0 + np.exp(-X[:, L + 1:]))
+            g = np.concatenate([g, grad[:, L + 1 + free] * ((hi - lo) * st * (1.0 - st))], axis=1)
+            bad = info != 0
+            return np.where(bad, np.inf, -ll), np.where(bad[:, None], 0.0, -g)
+
+    # the cell itself, with (alpha, rho) as the optimiser's coordinates hold them and the grid's own delays: the value to better
+    fc, gc = negfg(real, x0, at_cell=True)
+    opt = BatchedBFGS(x0, negfg, iterations=iterations, g_tol=g_tol)
+    xmin, fmin = opt.run()
+    keep = ~(fmin <= fc)                                                 # no step bettered the cell (or the run never had a finite value)
+    alpha, rho = makepositive(xmin[:, :L]) + 1e-8, transformbetween(xmin[:, L], rhomin, rhomax)
+    tau = tau0.copy()
+    tau[:, free] = transformbetween(xmin[:, L + 1:], lo, hi)
+    a_cell, r_cell = makepositive(x0[:, :L]) + 1e-8, transformbetween(x0[:, L], rhomin, rhomax)
+    alpha[keep], rho[keep], tau[keep] = a_cell[keep], r_cell[keep], tau0[keep]
+    with np.errstate(invalid="ignore"):
+        conv = np.where(keep, np.isfinite(fc) & (np.abs(gc).max(axis=1, initial=0.0) <= g_tol), opt.converged)
+    out = RealisationPeaks(tau, alpha, rho, -np.where(keep, fc, fmin), -fc, conv, opt.f_calls + R, opt.rounds + 1)
+    out.x = np.where(keep[:, None], x0, xmin)
+    return out
 
 
 def effective_std(stdarray, kappa, nu):

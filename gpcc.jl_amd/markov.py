@@ -301,6 +301,24 @@ def loglik_resampled(kernel, tarray, yarray, stdarray, Y, counts, real, delays, 
     array; counts the same in integers, or None (all 1).  mean, sigma_b: (R, L); None: those of (tarray, yarray, stdarray), the
     handle's.  A realisation that keeps no point gives (0.0, 0).  info: loglik()'s codes, the position counted among the kept points.
     A flux that is not finite at a kept point makes the row NaN.  ValueError: a real[m] outside [0, R), negative counts."""
+    name, L, delays, alpha, rho, real, vb, _, p, n, points = _resampled_setup(kernel, tarray, yarray, stdarray, Y, counts, real, delays,
+                                                                              alpha, rho, marginalise_b, mean, sigma_b)
+    ll, info = np.empty(len(rho)), np.zeros(len(rho), dtype=np.int32)
+    for m in range(len(rho)):
+        code = -1 if not np.all(alpha[m] > 0.0) else (-2 if rho[m] <= 0.0 else 0)
+        if code:
+            ll[m], info[m] = math.nan, code
+            continue
+        r = int(real[m])
+        train = [(t - delays[m, l], l, i, res, s2) for (l, i, t, res, s2) in points(r)]
+        ll[m], info[m] = _pass(name, train, [], alpha[m], float(rho[m]), p, n, vb[r])[:2]
+    return ll, info
+
+
+def _resampled_setup(kernel, tarray, yarray, stdarray, Y, counts, real, delays, alpha, rho, marginalise_b, mean, sigma_b):
+    """The arguments of loglik_resampled and loglik_grad_resampled as arrays and what both walk: (name, L, delays[M, L], alpha[M, L],
+    rho[M], real[M], vb[R, L], the handle's vb[L], p, n, points), points(r) the kept points of realisation r as [(band, position in the
+    sorted band, time, residual, variance)] (cached).  Their ValueErrors."""
     name = _name(kernel)
     L = len(tarray)
     Y = _bands(tarray, Y)
@@ -325,7 +343,6 @@ def loglik_resampled(kernel, tarray, yarray, stdarray, Y, counts, real, delays, 
     kept = {}
 
     def points(r):
-        """the kept points of realisation r: [(band, position in the sorted band, time, residual, variance)]"""
         if r not in kept:
             out = []
             for l in range(L):
@@ -338,16 +355,7 @@ def loglik_resampled(kernel, tarray, yarray, stdarray, Y, counts, real, delays, 
             kept[r] = out
         return kept[r]
 
-    ll, info = np.empty(len(rho)), np.zeros(len(rho), dtype=np.int32)
-    for m in range(len(rho)):
-        code = -1 if not np.all(alpha[m] > 0.0) else (-2 if rho[m] <= 0.0 else 0)
-        if code:
-            ll[m], info[m] = math.nan, code
-            continue
-        r = int(real[m])
-        train = [(t - delays[m, l], l, i, res, s2) for (l, i, t, res, s2) in points(r)]
-        ll[m], info[m] = _pass(name, train, [], alpha[m], float(rho[m]), p, n, vb[r])[:2]
-    return ll, info
+    return name, L, delays, alpha, rho, real, vb, hvb, p, n, points
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
@@ -409,10 +417,11 @@ def stationary_drho(kernel, rho):
     return np.array([[0.0, 0.0, -dk], [0.0, dk, 0.0], [-dk, 0.0, 4.0 * lam ** 3 * dl]])
 
 
-def _grad_pass(name, train, alpha, rho, p, n, vb, kind, band=-1, rank=None, slip=None):
+def _grad_pass(name, train, alpha, rho, p, n, vb, kind, band=-1, rank=None, slip=None, prev_band=None):
     """d loglik / d theta by the tangent recursion over the training observations.  kind: "alpha" (of band `band`), "rho", "tau" (of
     band `band`).  rank: the rank of `band` among points that tie in shifted time (-1: first, L: last; None: its index, merge_order()'s
-    rule).  slip: loglik_grad()'s."""
+    rule).  slip: loglik_grad()'s.  prev_band (loglik_grad_resampled's slip "lag_from_merged" only): {(band, position): the band the
+    tau tangent takes for the observation before}, in place of the band of the observation before."""
     ev = sorted(train, key=lambda e: (e[0], rank if (rank is not None and e[1] == band) else e[1], e[2]))
     Pinf = stationary(name, rho)
     dPinf = stationary_drho(name, rho) if (kind == "rho" and slip != "no_dpinf") else np.zeros((p, p))
@@ -422,12 +431,14 @@ def _grad_pass(name, train, alpha, rho, p, n, vb, kind, band=-1, rank=None, slip
     dP[:p, :p] = dPinf
     m, dm = np.zeros(n), np.zeros(n)
     dll, sprev, bprev = 0.0, None, -1
-    for (s, b, _, r, s2) in ev:
+    for (s, b, i, r, s2) in ev:
         d = 0.0 if sprev is None else s - sprev
         A = transition(name, d, rho)
         if kind == "rho":
             dA = transition_drho(name, d, rho)
         elif kind == "tau" and sprev is not None:
+            if prev_band is not None:
+                bprev = prev_band[(b, i)]
             dd = -float(b == band) + (0.0 if slip == "tau_one_lag" else float(bprev == band))
             dA = dd * (F @ A)
         else:
@@ -505,6 +516,59 @@ def loglik_grad_batch(kernel, tarray, yarray, stdarray, delays, alpha, rho, marg
     out = [loglik_grad(kernel, tarray, yarray, stdarray, delays[i], alpha[i], rho[i], marginalise_b) for i in range(len(rho))]
     return (np.array([o[0] for o in out]), np.array([o[1] for o in out]).reshape(-1, 2 * L + 1),
             np.array([o[2] for o in out], dtype=np.int32))
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# The gradient of rows with their own resampled data set (csrc/gpcc_markov_resample_grad.hip.h, gpcc_loglik_grad_markov_resampled_batch,
+# DESIGN.md 4.28), the same algorithm in numpy: _grad_pass over the kept points of the row's realisation.  Dropping a point removes its
+# step, so the lag of a kept point and the lag's tangent by tau_l, [band of the last KEPT point = l] - [band = l], are those of the
+# reduced data set; a dropped point that ties with a kept one in shifted time is not there to tie.  The band means and the offsets'
+# prior variances are constants of the data.
+# ----------------------------------------------------------------------------------------------------------------------------------
+RESAMPLED_GRAD_SLIPS = ("lag_from_merged", "handle_sigma_b", "one_sided")
+
+
+def loglik_grad_resampled(kernel, tarray, yarray, stdarray, Y, counts, real, delays, alpha, rho, marginalise_b=True, mean=None, sigma_b=None,
+                          _slip=None):
+    """(loglik[M], grad[M, 2L+1], info[M]) of M rows, row m on realisation real[m]: loglik_resampled's value and info (the same
+    arguments, the same ValueErrors) and the gradient [d/dalpha_1..alpha_L, d/drho, d/dtau_1..tau_L] of that value,
+    Objective.loglik_grad_markov_resampled's result with mean and sigma_b given.  It is loglik_grad() of the reduced fresh data set when
+    mean and sigma_b are that data set's.  grad is NaN where info != 0; a realisation that keeps no point gives (0.0, zeros, 0); at a tie
+    in shifted time between two kept points of different bands OU returns the mean of the two tie orders.
+    _slip (tests only) injects one mistake: "lag_from_merged" (the tau tangent reads the band of the point before in the handle's merged
+    order, dropped points included, not the band of the last kept point), "handle_sigma_b" (the offsets' prior variances of
+    (tarray, yarray, stdarray) for every realisation), and loglik_grad()'s "one_sided", "no_dpinf", "tau_one_lag", "no_dh"."""
+    name, L, delays, alpha, rho, real, vb, hvb, p, n, points = _resampled_setup(kernel, tarray, yarray, stdarray, Y, counts, real, delays,
+                                                                                alpha, rho, marginalise_b, mean, sigma_b)
+    M, W = len(rho), 2 * L + 1
+    ts = [np.sort(np.asarray(t, np.float64), kind="stable") for t in tarray]
+    ll, grad, info = np.empty(M), np.full((M, W), math.nan), np.zeros(M, dtype=np.int32)
+    for m in range(M):
+        code = -1 if not np.all(alpha[m] > 0.0) else (-2 if rho[m] <= 0.0 else 0)
+        if code:
+            ll[m], info[m] = math.nan, code
+            continue
+        r, am, rm = int(real[m]), alpha[m], float(rho[m])
+        train = [(t - delays[m, l], l, i, res, s2) for (l, i, t, res, s2) in points(r)]
+        v = hvb if (_slip == "handle_sigma_b" and marginalise_b) else vb[r]
+        ll[m], info[m] = _pass(name, train, [], am, rm, p, n, vb[r])[:2]
+        if info[m]:
+            continue
+
+        def tau(l, rank=None):
+            prev = None
+            if _slip == "lag_from_merged":      # the band before in the merged order of ALL the handle's points, under the same tie rule
+                ev = sorted(((ts[b][i] - delays[m, b], rank if (rank is not None and b == l) else b, i, b)
+                             for b in range(L) for i in range(len(ts[b]))))
+                prev = {(e[3], e[2]): (ev[k - 1][3] if k else -1) for k, e in enumerate(ev)}
+            return _grad_pass(name, train, am, rm, p, n, v, "tau", l, rank=rank, slip=_slip, prev_band=prev)
+
+        for l in range(L):
+            grad[m, l] = _grad_pass(name, train, am, rm, p, n, v, "alpha", l, slip=_slip)
+        grad[m, L] = _grad_pass(name, train, am, rm, p, n, v, "rho", slip=_slip)
+        for l in range(L):
+            grad[m, L + 1 + l] = 0.5 * (tau(l, -1) + tau(l, L)) if (name == "OU" and _slip != "one_sided") else tau(l)
+    return ll, grad, info
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
@@ -1969,6 +2033,11 @@ class MarkovObjective:
         """Objective.loglik_markov_resampled's result: (loglik[M], info[M])."""
         mean, vb = resample_arguments(self.data[0], Y, counts, center, sigma_b, self.marginalise_b)
         return loglik_resampled(self.kernel, *self.data, Y, counts, real, delays, alpha, rho, self.marginalise_b, mean=mean, sigma_b=vb)
+
+    def loglik_grad_markov_resampled(self, Y, delays, alpha, rho, real, counts=None, center="own", sigma_b="own"):
+        """Objective.loglik_grad_markov_resampled's result: (loglik[M], grad[M, 2L+1], info[M])."""
+        mean, vb = resample_arguments(self.data[0], Y, counts, center, sigma_b, self.marginalise_b)
+        return loglik_grad_resampled(self.kernel, *self.data, Y, counts, real, delays, alpha, rho, self.marginalise_b, mean=mean, sigma_b=vb)
 
     def loglik_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
         """Objective.loglik_markov_noise_batch's result: (loglik[M], info[M])."""

@@ -229,7 +229,7 @@ int gpcc_loglik_batch(gpcc_handle_t handle, int M, const double *delays, const d
  * gpcc_loglik_grad_markov_batch after them; the (alpha, rho) block of the Hessian is gpcc_loglik_hess_hyper_markov_batch, the full
  * Hessian (the rows of tau) gpcc_loglik_hess_markov_batch; the Fisher information gpcc_loglik_fisher_markov_batch; many flux
  * realisations per row in one pass (a second data axis) gpcc_loglik_markov_multi_batch; rows with their own resampled data set
- * (FR/RSS with refits) gpcc_loglik_markov_resampled_batch.
+ * (FR/RSS with refits) gpcc_loglik_markov_resampled_batch, with their gradient gpcc_loglik_grad_markov_resampled_batch.
  * Blocking. */
 int gpcc_loglik_markov_batch(gpcc_handle_t handle, int M, const double *delays, const double *alpha, const double *rho,
                              double *loglik, int *info);
@@ -461,6 +461,31 @@ int gpcc_loglik_markov_multi_batch(gpcc_handle_t h, int M, const double *delays,
 int gpcc_loglik_markov_resampled_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                        const int *real, int R, const double *Y, const int *count, const double *mean,
                                        const double *sigma_b, double *loglik, int *info);
+
+/* That log-likelihood AND ITS GRADIENT, exact and in LINEAR TIME (kernel: csrc/gpcc_markov_resample_grad.hip.h): the
+ * filter's forward sensitivities of gpcc_loglik_grad_markov_batch over each row's own resampled data set.
+ *   grad: M rows of 2L+1 doubles [d/d alpha_1..L, d/d rho, d/d tau_1..L], gpcc_loglik_grad_markov_batch's order.  real, R, Y, count,
+ *   mean, sigma_b, loglik, info and every refusal: gpcc_loglik_markov_resampled_batch's, word for word (the limit
+ *   "markov_resample_bytes_max", M = 0, all checks on the host before any device work), and GPCC_ERR_ARGUMENT for a NULL grad.
+ * SEMANTICS.  grad[m] is the gradient of the log-likelihood of a fresh handle on the reduced data set of realisation real[m] at
+ * (tau, alpha, rho)_m: the band means mean_r and Sigma_b are constants of the data, not functions of the parameters.  loglik and info
+ * are BITWISE gpcc_loglik_markov_resampled_batch's on the same rows (the same value kernel runs inside the call).  With real[m]
+ * pointing to the handle's own y and count, mean and sigma_b NULL, grad[m] is bitwise gpcc_loglik_grad_markov_batch's.
+ * A row with info != 0 has a NaN gradient; a realisation with no kept point gives 0.0, a zero gradient and info 0; a flux that is not
+ * finite at a kept point makes the rows of that realisation NaN, and no other.  At an exact tie in shifted time between two KEPT
+ * points of different bands OU returns the mean of the one-sided derivatives, as gpcc_loglik_grad_batch does; a tie with a dropped
+ * point is no tie.
+ * Path: the pack kernel and the value kernel of gpcc_loglik_markov_resampled_batch, then one lane per (row, slot) -- L alpha, one rho,
+ * L tau slots (OU: 2L, the first / last pair) -- through the one first-order walk of gpcc_loglik_grad_markov_batch, reading the
+ * realisation's pair at each step: a dropped point takes no step, the lag and the lag's tangent by tau come from the last KEPT point.
+ * Then gpcc_loglik_grad_markov_batch's small kernel writes the rows.  No atomics: a row's bits depend on that row and its realisation
+ * alone, whatever M, R, the row order, the position of the realisation in Y and the launch shape.
+ * Memory: gpcc_loglik_markov_resampled_batch's plus gpcc_loglik_grad_markov_batch's slots and rows (8 M bytes per slot, 8 M (2L + 1)
+ * bytes), grown on demand; none of the N^2 workspace.  "markov_count" advances by M.  Always fp64 (an fp32 handle on its fp64 twin); a
+ * multi-device handle computes on device_ids[0].  Blocking. */
+int gpcc_loglik_grad_markov_resampled_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                            const int *real, int R, const double *Y, const int *count, const double *mean,
+                                            const double *sigma_b, double *loglik, double *grad, int *info);
 
 /* The log-likelihood, and its gradient, of M rows that each carry their own (tau, alpha, rho) AND THEIR OWN NOISE MODEL, in LINEAR
  * TIME for the Markov kernels (kernels: csrc/gpcc_markov_noise.hip.h).  Point i of band l of row m is observed with

@@ -398,6 +398,30 @@ function loglik_markov_resampled(h::Handle, Y::Matrix{Float64}, delays::Matrix{F
     return ll, info
 end
 
+"loglik_markov_resampled and its exact gradient in linear time (gpcc_loglik_grad_markov_resampled_batch, DESIGN 4.28) ->
+(ll[M], grad (2L+1)×M, info[M]), column m of grad = [∂/∂α_1..L, ∂/∂ρ, ∂/∂τ_1..L] of ll[m]: the gradient of a fresh handle on the kept
+points of realisation real[m], the band means and Σ_b being constants of the data.  The arguments and errors are
+loglik_markov_resampled's; ll and info are bitwise its results.  A column with info ≠ 0 is NaN; a realisation that keeps no point gives
+0.0 and a zero gradient; OU at an exact tie between two kept points of different bands returns the mean of the one-sided derivatives."
+function loglik_grad_markov_resampled(h::Handle, Y::Matrix{Float64}, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64},
+                                      real::Vector{<:Integer}; counts = nothing, mean = nothing, sigma_b = nothing)
+    M, R = length(rho), size(Y, 2)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M) && length(real) == M && R >= 1
+    @assert all(1 .<= real .<= R)
+    @assert counts === nothing || (size(counts) == size(Y) && all(counts .>= 0))
+    @assert mean === nothing || size(mean) == (h.L, R)
+    @assert sigma_b === nothing || size(sigma_b) == (h.L, R)
+    ll, grad, info = Vector{Float64}(undef, M), Matrix{Float64}(undef, 2 * h.L + 1, M), Vector{Cint}(undef, M)
+    rc = ccall((:gpcc_loglik_grad_markov_resampled_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Cint, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble},
+                Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, convert(Vector{Cint}, real .- 1), R, Y,
+               counts === nothing ? C_NULL : convert(Matrix{Cint}, counts), mean === nothing ? C_NULL : convert(Matrix{Float64}, mean),
+               sigma_b === nothing ? C_NULL : convert(Matrix{Float64}, sigma_b), ll, grad, info)
+    rc == 0 || error("gpcc_loglik_grad_markov_resampled_batch: " * lasterror(h.ptr))
+    return ll, grad, info
+end
+
 "Laplace-marginalised evidence over α and ρ per delay (columns of delays, L×G), from (alpha0 L×G, rho0[G]), usually the fit's
 output.  Prior log-uniform in α and in ρ on [rhomin, rhomax]: log_evidence is log Z(τ) up to ONE additive constant shared by all
 delays -- use it only through getprobabilities (or differences).  -> (ll[G], alpha L×G, rho[G], log_evidence[G], cov (L+1)×(L+1)×G
