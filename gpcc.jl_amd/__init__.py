@@ -9,4 +9,4 @@ from .api import (KERNELS, OU, Kernel, Objective, PosDefException, build_info, d
                   getprobabilities, matern32, matern52, mvnormal_logpdf, rbf, selftest)
 from .distributed import shard_bounds, sharded_grid_fit, sharded_loglik  # noqa: F401
 from .fit import (CVGrid, DelayAveragedPredictor, GridFit, LooScores, NoiseEvidence, NoiseGridFit, Predictor, RealisationDelays, RealisationPeaks, RealisationRefits, cvindices, delay_covariance, gpcc, gpcc_grid,  # noqa: F401,E402
-                  effective_std, gpcc_grid_noise, laplace_covariance, noise_evidence, performcv, performcv_grid, realisation_delays, realisation_peaks, realisation_refits, singlegp, uniformpriordelay, unpack_grad, unpack_hessian)
+                  effective_std, gpcc_grid_noise, laplace_covariance, noise_evidence, noise_predictor, performcv, performcv_grid, realisation_delays, realisation_peaks, realisation_refits, singlegp, uniformpriordelay, unpack_grad, unpack_hessian)

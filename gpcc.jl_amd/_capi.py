@@ -101,6 +101,13 @@ SIGNATURES = {
                                                         c_double_p, c_int_p]),
     "gpcc_posterior_offsets_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
                                                            c_double_p, c_double_p, c_int_p]),
+    # the same four under a per-row noise model: kappa, nu behind rho
+    "gpcc_loo_noise_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [c_double_p] * 13 + [c_int_p]),
+    "gpcc_predict_noise_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [c_double_p] * 5 + [c_int_p] + [c_double_p] * 7
+                                        + [c_int_p]),
+    "gpcc_heldout_loglik_noise_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [c_double_p] * 5 + [c_int_p]
+                                               + [c_double_p] * 7 + [c_int_p]),
+    "gpcc_posterior_offsets_noise_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [c_double_p] * 8 + [c_int_p]),
     "gpcc_sample_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p,
                                          c_double_p, ctypes.c_int, ctypes.c_ulonglong, c_double_p, c_int_p, c_double_p, c_double_p, c_int_p]),
     "gpcc_sample_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_double_p,

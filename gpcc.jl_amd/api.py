@@ -430,9 +430,23 @@ class Objective:
         matern52 only) -> (mu[M, T], var[M, T], loglik[M], info[M], mix_mu[T], mix_var[T]), what predict_batch returns.  ttest need not
         be sorted.  loglik and info are bitwise loglik_markov_batch's, except info = N + j where the combine of test point j failed;
         failed rows are NaN.  rbf, or marginalise_b with more than 4 bands: GpccError (unsupported)."""
+        return self._predict_markov(delays, alpha, rho, ttest, weights, None)
+
+    def _noise_args(self, M, noise):
+        """What a noise entry takes behind rho: the pointers of kappa and nu (noise = (kappa, nu), _noise); nothing for a plain entry.
+        -> (the arrays, kept alive by the caller; the pointers)."""
+        if noise is None:
+            return (), ()
+        keep = (self._noise(M, noise[0], "kappa"), self._noise(M, noise[1], "nu"))
+        return keep, tuple(_dp(x) if x is not None else None for x in keep)
+
+    def _predict_markov(self, delays, alpha, rho, ttest, weights, noise):
+        """predict_markov_batch (noise None) and predict_markov_noise_batch (noise = (kappa, nu))."""
         if len(ttest) != self.L:
             raise AssertionError("length(ttest) == L")
         M, delays, alpha, rho = self._params(delays, alpha, rho)
+        keep, nptr = self._noise_args(M, noise)
+        entry = _capi.load().gpcc_predict_markov_batch if noise is None else _capi.load().gpcc_predict_noise_markov_batch
         Nt, tt = _flatten(ttest)
         T = int(Nt.sum())
         mu = np.empty((M, T), dtype=np.float64)
@@ -447,10 +461,9 @@ class Objective:
             mix_mu = np.empty(T, dtype=np.float64)
             mix_var = np.empty(T, dtype=np.float64)
         try:
-            self._chk(_capi.load().gpcc_predict_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _ip(Nt), _dp(tt),
-                                                             _dp(w) if w is not None else None, _dp(mu), _dp(var),
-                                                             _dp(mix_mu) if w is not None else None,
-                                                             _dp(mix_var) if w is not None else None, _dp(ll), _ip(info)))
+            self._chk(entry(self._h, M, _dp(delays), _dp(alpha), _dp(rho), *nptr, _ip(Nt), _dp(tt), _dp(w) if w is not None else None,
+                            _dp(mu), _dp(var), _dp(mix_mu) if w is not None else None, _dp(mix_var) if w is not None else None,
+                            _dp(ll), _ip(info)))
         except GpccError as e:
             _raise_reference_error(e)
         return mu, var, ll, info, mix_mu, mix_var
@@ -460,9 +473,15 @@ class Objective:
         filters per row) -> (heldout[M], loglik[M], info[M], mix or None).  loglik and info are bitwise loglik_markov_batch's, except
         info = N + j where the predictive variance of test point j was not positive and finite (heldout NaN; there is no test block
         to repair, hence no fallback and no refit mask).  mix = log sum p_m exp(heldout_m), p = weights / sum(weights)."""
+        return self._heldout_markov(delays, alpha, rho, ttest, ytest, sigmatest, weights, None)
+
+    def _heldout_markov(self, delays, alpha, rho, ttest, ytest, sigmatest, weights, noise):
+        """heldout_loglik_markov_batch (noise None) and heldout_loglik_markov_noise_batch (noise = (kappa, nu))."""
         if len(ttest) != self.L or len(ytest) != self.L or len(sigmatest) != self.L:
             raise AssertionError("length(ttest) == length(ytest) == length(sigmatest) == L")
         M, delays, alpha, rho = self._params(delays, alpha, rho)
+        keep, nptr = self._noise_args(M, noise)
+        entry = _capi.load().gpcc_heldout_loglik_markov_batch if noise is None else _capi.load().gpcc_heldout_loglik_noise_markov_batch
         Nt, tt = _flatten(ttest)
         Ny, yt = _flatten(ytest)
         Ns, st = _flatten(sigmatest)
@@ -478,9 +497,8 @@ class Objective:
                 raise ValueError("weights must have M = %d entries" % M)
             mix = np.empty(1, dtype=np.float64)
         try:
-            self._chk(_capi.load().gpcc_heldout_loglik_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _ip(Nt), _dp(tt),
-                                                                    _dp(yt), _dp(st), _dp(w) if w is not None else None, _dp(held),
-                                                                    _dp(mix) if w is not None else None, _dp(ll), _ip(info)))
+            self._chk(entry(self._h, M, _dp(delays), _dp(alpha), _dp(rho), *nptr, _ip(Nt), _dp(tt), _dp(yt), _dp(st),
+                            _dp(w) if w is not None else None, _dp(held), _dp(mix) if w is not None else None, _dp(ll), _ip(info)))
         except GpccError as e:
             _raise_reference_error(e)
         return held, ll, info, (float(mix[0]) if w is not None else None)
@@ -488,14 +506,19 @@ class Objective:
     def posterior_offsets_markov_batch(self, delays, alpha, rho):
         """posterior_offsets at M rows in linear time (gpcc_posterior_offsets_markov_batch: the offset block of the filter's final
         state) -> (mu_postb[M, L], Sigma_postb[M, L, L], loglik[M], info[M]); rows with info != 0 are NaN."""
+        return self._postb_markov(delays, alpha, rho, None)
+
+    def _postb_markov(self, delays, alpha, rho, noise):
+        """posterior_offsets_markov_batch (noise None) and posterior_offsets_markov_noise_batch (noise = (kappa, nu))."""
         M, delays, alpha, rho = self._params(delays, alpha, rho)
+        keep, nptr = self._noise_args(M, noise)
+        entry = _capi.load().gpcc_posterior_offsets_markov_batch if noise is None else _capi.load().gpcc_posterior_offsets_noise_markov_batch
         mu = np.empty((M, self.L), dtype=np.float64)
         Sig = np.empty((M, self.L, self.L), dtype=np.float64)
         ll = np.empty(M, dtype=np.float64)
         info = np.zeros(M, dtype=np.int32)
         try:
-            self._chk(_capi.load().gpcc_posterior_offsets_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(mu), _dp(Sig),
-                                                                       _dp(ll), _ip(info)))
+            self._chk(entry(self._h, M, _dp(delays), _dp(alpha), _dp(rho), *nptr, _dp(mu), _dp(Sig), _dp(ll), _ip(info)))
         except GpccError as e:
             _raise_reference_error(e)
         return mu, Sig, ll, info
@@ -523,8 +546,9 @@ class Objective:
                                                       _ip(info)))
         return ll, grad, info
 
-    def _loo(self, entry, delays, alpha, rho, weights, outputs):
+    def _loo(self, entry, delays, alpha, rho, weights, outputs, noise=None):
         M, delays, alpha, rho = self._params(delays, alpha, rho)
+        keep, nptr = self._noise_args(M, noise)
         N = self.N
         names = ("mu", "var", "lp", "loo", "mix_lp", "mix_loo", "loglik", "info")
         want = set(names if outputs is None else outputs)
@@ -542,7 +566,7 @@ class Objective:
         info = np.zeros(M, dtype=np.int32) if "info" in want else None
         ptr = {k: (_dp(buf[k]) if k in buf else None) for k in shapes}
         try:
-            self._chk(entry(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _dp(w) if w is not None else None, ptr["mu"], ptr["var"],
+            self._chk(entry(self._h, M, _dp(delays), _dp(alpha), _dp(rho), *nptr, _dp(w) if w is not None else None, ptr["mu"], ptr["var"],
                             ptr["lp"], ptr["loo"], ptr["mix_lp"], ptr["mix_loo"], ptr["loglik"], _ip(info) if info is not None else None))
         except GpccError as e:
             _raise_reference_error(e)
@@ -624,6 +648,34 @@ class Objective:
         (unsupported)."""
         n = 4 * self.L + 1
         return self._markov("gpcc_loglik_hess_full_noise_markov_batch", delays, alpha, rho, [(n,), (n, n)], noise=(kappa, nu))
+
+    def predict_markov_noise_batch(self, delays, alpha, rho, ttest, kappa=None, nu=None, weights=None):
+        """predict_markov_batch of M rows that each carry their own noise model (gpcc_predict_noise_markov_batch) -> the same tuple
+        (mu[M, T], var[M, T], loglik[M], info[M], mix_mu[T], mix_var[T]).  kappa, nu: (M, L), (L,) broadcast, or None (all 1 / all 0),
+        as loglik_markov_noise_batch.  Row m is what a fresh Objective on fit.effective_std(sigma, kappa[m], nu[m]) returns: the
+        latent curve's mean and variance (JITTER included), the noise model entering through the training points.  At kappa = 1,
+        nu = 0 every output is bitwise predict_markov_batch's.  info: its codes and -3 (a kappa or nu negative or not finite: the
+        row NaN, and the mixture NaN if the row has weight)."""
+        return self._predict_markov(delays, alpha, rho, ttest, weights, (kappa, nu))
+
+    def heldout_loglik_markov_noise_batch(self, delays, alpha, rho, ttest, ytest, sigmatest, kappa=None, nu=None, weights=None):
+        """heldout_loglik_markov_batch under a per-row noise model (gpcc_heldout_loglik_noise_markov_batch) -> (heldout[M], loglik[M],
+        info[M], mix or None).  A test point of band l is scored with the variance kappa_l^2 sigmatest^2 + nu_l (+ JITTER), the
+        training points with theirs: row m is a fresh Objective on the effective error bars scoring test points with
+        fit.effective_std(sigmatest, kappa[m], nu[m]).  Bitwise heldout_loglik_markov_batch's at kappa = 1, nu = 0; info -3 as above."""
+        return self._heldout_markov(delays, alpha, rho, ttest, ytest, sigmatest, weights, (kappa, nu))
+
+    def posterior_offsets_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
+        """posterior_offsets_markov_batch under a per-row noise model (gpcc_posterior_offsets_noise_markov_batch) -> (mu_postb[M, L],
+        Sigma_postb[M, L, L], loglik[M], info[M]); bitwise the plain method's at kappa = 1, nu = 0; info -3 as above."""
+        return self._postb_markov(delays, alpha, rho, (kappa, nu))
+
+    def loo_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None, weights=None, outputs=None):
+        """loo_markov_batch under a per-row noise model (gpcc_loo_noise_markov_batch) -> the same LooResult: var_i = h'P_s h +
+        kappa_b^2 sigma_i^2 + nu_b, so that (y - mu) / sqrt(var) is standardised by the FITTED error bars -- the check that kappa, nu
+        have repaired them.  Row m is a fresh Objective on fit.effective_std(sigma, kappa[m], nu[m]); bitwise loo_markov_batch's at
+        kappa = 1, nu = 0; info -3 as above; the mixture mixes rows with different noise models as it mixes any rows."""
+        return self._loo(_capi.load().gpcc_loo_noise_markov_batch, delays, alpha, rho, weights, outputs, noise=(kappa, nu))
 
     def loglik_hess_batch(self, delays, alpha, rho):
         """objective, gradient, Hessian and expected (Fisher) information for M (tau, alpha, rho) triples -> (loglik[M],

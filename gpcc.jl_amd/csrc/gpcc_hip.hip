@@ -22,6 +22,7 @@
 #include "gpcc_markov_noise.hip.h"
 #include "gpcc_markov_noise_hess.hip.h"
 #include "gpcc_markov_noise_hess_tau.hip.h"
+#include "gpcc_markov_noise_pred.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -2186,7 +2187,7 @@ static void markov_fill_args(gpcc_handle_t h, int M, const double *dd, const dou
 }
 
 // the kernels with dynamic LDS, for gpcc_handle::mk_lds_raised
-enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI, MK_RESAMPLE, MK_RESAMPLE_GRAD, MK_NOISE, MK_NOISE_GRAD, MK_NOISE_HESS, MK_NOISE_HESS_TAU };
+enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI, MK_RESAMPLE, MK_RESAMPLE_GRAD, MK_NOISE, MK_NOISE_GRAD, MK_NOISE_HESS, MK_NOISE_HESS_TAU, MK_NOISE_TAPS_TAP, MK_NOISE_TAPS_UPDATE, MK_NOISE_LOO_TAPS };
 
 // The launch of every kernel of the filter, `name` in messages: one lane per row, `rows` rows along x and ny lanes per row along y.
 // The shape: one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy beyond; the light
@@ -2592,10 +2593,40 @@ static void markov_sort_tests(gpcc_handle_t h, const int *Ntest, const double *t
     }
 }
 
+// The four entries below run plain (gpcc_predict_markov_batch, ...) or under a per-row noise model (gpcc_predict_noise_markov_batch,
+// ...: DESIGN.md 4.29, kernels gpcc_markov_noise_pred.hip.h).  One body each, a template on NOISE: a noise entry stages the rows' kappa |
+// nu in the noise family's buffer (mkn.rows, 16 M L bytes), launches the noise kernels on their Args and is otherwise the plain entry
+// statement for statement.  who: the entry's name in messages.
+struct MarkovNoise {
+    const char *who;
+    const double *kappa, *nu;   // a noise entry's M x L arrays (host; NULL: all 1 / all 0)
+};
+static int markov_noise_stage(const MarkovRun &r);   // (with the noise family, below)
+
+// grows the buffer of kappa | nu (in markov_begin's grow) ...
+template <bool NOISE>
+static int markov_noise_grow(gpcc_handle_t h, int M)
+{
+    return NOISE ? grow_buf(h, &h->mkn.rows, &h->mkn.rows_cap, 2L * M * h->L) : 0;
+}
+
+// ... stages them on main_stream and names them in the kernel's Args
+template <bool NOISE, typename ARGS>
+static int markov_noise_rows(gpcc_handle_t h, int M, const MarkovNoise &nz, ARGS &a)
+{
+    if constexpr (NOISE) {
+        const int rc = markov_noise_stage({h, M, nullptr, nullptr, nullptr, nz.kappa, nz.nu});
+        if (rc) return rc;
+        a.kappa = h->mkn.rows; a.nu = a.kappa + (long)M * h->L;
+    }
+    return 0;
+}
+
 // the arguments every launch of gpcc_markov_taps shares: the filter's, the test points (toff: their bands' offsets, or NULL for none)
-// and one chunk of all M rows
+// and one chunk of all M rows (ARGS: GpccMarkovPredArgs or GpccMarkovNoisePredArgs)
+template <typename ARGS>
 static void markov_pred_common(gpcc_handle_t h, int M, const double *dd, const double *da, const double *dr, const int *toff, long T,
-                               GpccMarkovPredArgs &a)
+                               ARGS &a)
 {
     markov_fill_args(h, M, dd, da, dr, a);
     a.tpts = h->d_mkt; a.T = (int)T;
@@ -2613,6 +2644,15 @@ static int markov_pred_launch(gpcc_handle_t h, int mode, GpccMarkovPredArgs &a, 
                          [&](const GpccMkLaunch &g) { return gpcc_mkp_launch_taps(g, mode, ny, a); });
 }
 
+// ... of gpcc_markov_noise_taps
+static int markov_pred_launch(gpcc_handle_t h, int mode, GpccMarkovNoisePredArgs &a, int ny)
+{
+    const int tw = mode == GPCC_MKP_TAP ? 1 : 3;
+    return markov_launch(h, "gpcc_markov_noise_taps", mode == GPCC_MKP_TAP ? MK_NOISE_TAPS_TAP : MK_NOISE_TAPS_UPDATE, a.rows, ny, a.stage,
+                         [&](int thr, bool st) { return gpcc_mknp_lds_bytes(a.N, a.T, tw, a.L, thr, st); },
+                         [&](const GpccMkLaunch &g) { return gpcc_mknp_launch_taps(g, mode, ny, a); });
+}
+
 // rows per chunk of an entry that keeps the two filters' taps (nrec doubles each) at `points` points of every row: what the scratch
 // budget holds (whole waves when it holds one), or the option; 1 .. M
 static long markov_tap_chunk(gpcc_handle_t h, long points, long nrec, long M)
@@ -2625,7 +2665,8 @@ static long markov_tap_chunk(gpcc_handle_t h, long points, long nrec, long M)
 }
 
 // the arguments of gpcc_markov_combine (and gpcc_markov_combine_w) beside a's taps; the chunk's rows are set per launch
-static void markov_combine_args(gpcc_handle_t h, const GpccMarkovPredArgs &a, GpccMarkovCombineArgs &c)
+template <typename ARGS>
+static void markov_combine_args(gpcc_handle_t h, const ARGS &a, GpccMarkovCombineArgs &c)
 {
     c.tap = a.tap; c.alpha = a.alpha; c.rho = a.rho; c.tband = h->d_mkti; c.tperm = h->d_mkti + a.T; c.mu = h->d_mkmu; c.var = h->d_mkvar;
     c.L = h->L; c.T = a.T;
@@ -2633,9 +2674,11 @@ static void markov_combine_args(gpcc_handle_t h, const GpccMarkovPredArgs &a, Gp
     for (int l = 0; l < GPCC_MARKOV_MAX_OFFSETS; ++l) c.sigma_b[l] = a.sigma_b[l];
 }
 
-extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
-                                         const int *Ntest, const double *ttest, const double *weights, double *mu_out, double *var_out,
-                                         double *mix_mu, double *mix_var, double *loglik, int *info)
+// reissue(o): the same call on handle o (route_fp64's call)
+template <bool NOISE, typename Reissue>
+static int markov_predict(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const MarkovNoise &nz,
+                          const int *Ntest, const double *ttest, const double *weights, double *mu_out, double *var_out, double *mix_mu,
+                          double *mix_var, double *loglik, int *info, Reissue &&reissue)
 {
     if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
     if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
@@ -2644,12 +2687,9 @@ extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *d
     if (weights && (!mix_mu || !mix_var)) return fail(h, GPCC_ERR_ARGUMENT, "weights given: mix_mu and mix_var are required");
     if (!weights && (mix_mu || mix_var)) return fail(h, GPCC_ERR_ARGUMENT, "mix_mu and mix_var need weights");
     if (!weights && !mu_out) return fail(h, GPCC_ERR_ARGUMENT, "NULL mu_out / var_out without weights: nothing to return");
-    int rc = markov_refusals(h, "gpcc_predict_markov_batch", "gpcc_predict_batch");
+    int rc = markov_refusals(h, nz.who, "gpcc_predict_batch");
     if (rc) return rc;
-    if (route_fp64(h, "linear-time predictive", rc, [&](gpcc_handle_t o) {
-            return gpcc_predict_markov_batch(o, M, delays, alpha, rho, Ntest, ttest, weights, mu_out, var_out, mix_mu, mix_var, loglik, info);
-        }))
-        return rc;
+    if (route_fp64(h, "linear-time predictive", rc, reissue)) return rc;
     long T = 0;
     std::vector<double> p;   // the normalised weights p_m = w_m / sum w
     rc = count_test_points(h, Ntest, T);
@@ -2674,7 +2714,7 @@ extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *d
         if (!g) g = grow_buf(h, &h->d_mkvar, &h->mkvar_cap, chunk * T);
         if (!g && weights) g = grow_buf(h, &h->d_mkmix, &h->mkmix_cap, 6 * T);
         if (!g && weights) g = grow_buf(h, &h->d_mkw, &h->mkw_cap, M);
-        return g;
+        return g ? g : markov_noise_grow<NOISE>(h, M);
     });
     if (rc) return rc;
     hipStream_t ms = h->main_stream;
@@ -2684,8 +2724,10 @@ extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *d
         HIPCHK(h, hipMemcpyAsync(h->d_mkw, p.data(), sizeof(double) * M, hipMemcpyHostToDevice, ms));
         HIPCHK(h, hipMemsetAsync(h->d_mkmix, 0, sizeof(double) * 4 * T, ms));
     }
-    GpccMarkovPredArgs a;
+    std::conditional_t<NOISE, GpccMarkovNoisePredArgs, GpccMarkovPredArgs> a;
     markov_pred_common(h, M, dd, da, dr, toff, T, a);
+    rc = markov_noise_rows<NOISE>(h, M, nz, a);
+    if (rc) return rc;
     a.tap = h->d_mktap;
     GpccMarkovCombineArgs c;
     markov_combine_args(h, a, c);
@@ -2713,24 +2755,65 @@ extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *d
     return markov_finish(h, M, loglik, info);
 }
 
+extern "C" int gpcc_predict_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                         const int *Ntest, const double *ttest, const double *weights, double *mu_out, double *var_out,
+                                         double *mix_mu, double *mix_var, double *loglik, int *info)
+{
+    return markov_predict<false>(h, M, delays, alpha, rho, {"gpcc_predict_markov_batch", nullptr, nullptr}, Ntest, ttest, weights, mu_out,
+                                 var_out, mix_mu, mix_var, loglik, info, [&](gpcc_handle_t o) {
+        return gpcc_predict_markov_batch(o, M, delays, alpha, rho, Ntest, ttest, weights, mu_out, var_out, mix_mu, mix_var, loglik, info);
+    });
+}
+
+extern "C" int gpcc_predict_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                               const double *kappa, const double *nu, const int *Ntest, const double *ttest,
+                                               const double *weights, double *mu_out, double *var_out, double *mix_mu, double *mix_var,
+                                               double *loglik, int *info)
+{
+    return markov_predict<true>(h, M, delays, alpha, rho, {"gpcc_predict_noise_markov_batch", kappa, nu}, Ntest, ttest, weights, mu_out,
+                                var_out, mix_mu, mix_var, loglik, info, [&](gpcc_handle_t o) {
+        return gpcc_predict_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, Ntest, ttest, weights, mu_out, var_out, mix_mu, mix_var,
+                                               loglik, info);
+    });
+}
+
 // Exact leave-one-out scores in linear time (gpcc_loo_markov_batch; kernels: gpcc_markov_loo.hip.h): per chunk of rows
 // the two filters with a tap at every training point, the combine at the points, the per-row finish and, with weights, the mixture
 // step of gpcc_loo_batch in row order.  The chunk is the rows whose taps fit GPCC_MKP_TAP_BYTES (option "markov_chunk_rows" sets it).
-extern "C" int gpcc_loo_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
-                                     const double *weights, double *mu_out, double *var_out, double *lp_out, double *loo, double *mix_lp,
-                                     double *mix_loo, double *loglik, int *info)
+// the taps and the combine of one chunk, plain ...
+static int markov_loo_launch(gpcc_handle_t h, GpccMarkovLooArgs &a, const GpccMarkovLooCombineArgs &c, hipError_t &e)
+{
+    const MarkovDims d = markov_dims(h);
+    const int rc = markov_launch(h, "gpcc_markov_loo_taps", MK_LOO_TAPS, a.rows, 2, a.stage,
+                                 [&](int thr, bool st) { return gpcc_mkl_lds_bytes(a.N, a.L, thr, st); },
+                                 [&](const GpccMkLaunch &g) { return gpcc_mkl_launch_taps(g, a); });
+    if (!rc) e = gpcc_mkl_launch_combine(d.p, d.noff, c, h->main_stream);
+    return rc;
+}
+
+// ... and under a noise model
+static int markov_loo_launch(gpcc_handle_t h, GpccMarkovNoiseLooArgs &a, const GpccMarkovNoiseLooCombineArgs &c, hipError_t &e)
+{
+    const MarkovDims d = markov_dims(h);
+    const int rc = markov_launch(h, "gpcc_markov_noise_loo_taps", MK_NOISE_LOO_TAPS, a.rows, 2, a.stage,
+                                 [&](int thr, bool st) { return gpcc_mknl_lds_bytes(a.N, a.L, thr, st); },
+                                 [&](const GpccMkLaunch &g) { return gpcc_mknl_launch_taps(g, a); });
+    if (!rc) e = gpcc_mknl_launch_combine(d.p, d.noff, c, h->main_stream);
+    return rc;
+}
+
+template <bool NOISE, typename Reissue>
+static int markov_loo(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const MarkovNoise &nz,
+                      const double *weights, double *mu_out, double *var_out, double *lp_out, double *loo, double *mix_lp, double *mix_loo,
+                      double *loglik, int *info, Reissue &&reissue)
 {
     int rc = loo_check_args(h, M, delays, alpha, rho, weights, mix_lp, mix_loo);
-    if (!rc) rc = markov_refusals(h, "gpcc_loo_markov_batch", "gpcc_loo_batch");
+    if (!rc) rc = markov_refusals(h, nz.who, "gpcc_loo_batch");
     if (rc) return rc;
-    if (route_fp64(h, "linear-time leave-one-out scores", rc, [&](gpcc_handle_t o) {
-            return gpcc_loo_markov_batch(o, M, delays, alpha, rho, weights, mu_out, var_out, lp_out, loo, mix_lp, mix_loo, loglik, info);
-        }))
-        return rc;
+    if (route_fp64(h, "linear-time leave-one-out scores", rc, reissue)) return rc;
     const MarkovDims d = markov_dims(h);
-    if (!gpcc_mk_ships<GpccMkShipsAll>(d.p, d.noff))
-        return fail(h, GPCC_ERR_UNSUPPORTED, "gpcc_loo_markov_batch: the filter <%d, %d> is not built (it would spill); use gpcc_loo_batch",
-                    d.p, d.noff);
+    if (!gpcc_mk_ships<std::conditional_t<NOISE, GpccMkShipsNoisePred, GpccMkShipsAll>>(d.p, d.noff))
+        return fail(h, GPCC_ERR_UNSUPPORTED, "%s: the filter <%d, %d> is not built (it would spill); use gpcc_loo_batch", nz.who, d.p, d.noff);
     std::vector<double> p;   // the normalised weights p_m = w_m / sum w
     rc = mixture_weights(h, M, weights, false, p);
     if (rc || M == 0) return rc;
@@ -2745,7 +2828,7 @@ extern "C" int gpcc_loo_markov_batch(gpcc_handle_t h, int M, const double *delay
         if (!g) g = ensure_loo_rows(h, (int)chunk, true, true, true, mix);
         if (!g) g = grow_buf(h, &h->d_loosum, &h->loosum_cap, (long)M);
         if (!g && mix) g = grow_buf(h, &h->d_loow, &h->loow_cap, (long)M);
-        return g;
+        return g ? g : markov_noise_grow<NOISE>(h, M);
     });
     if (rc) return rc;
     hipStream_t ms = h->main_stream;
@@ -2753,10 +2836,13 @@ extern "C" int gpcc_loo_markov_batch(gpcc_handle_t h, int M, const double *delay
     for (long i = 0; i < N; ++i) { pi[i] = h->band_host[h->mk_perm[i]]; pi[N + i] = h->mk_perm[i]; }
     HIPCHK(h, hipMemcpyAsync(h->d_mkli, pi.data(), sizeof(int) * 2 * N, hipMemcpyHostToDevice, ms));
     if (mix) HIPCHK(h, hipMemcpyAsync(h->d_loow, p.data(), sizeof(double) * M, hipMemcpyHostToDevice, ms));
-    GpccMarkovLooArgs a;
+    std::conditional_t<NOISE, GpccMarkovNoiseLooArgs, GpccMarkovLooArgs> a;
     markov_fill_args(h, M, dd, da, dr, a);
     a.tap = h->d_mktap;
-    GpccMarkovLooCombineArgs c;
+    std::conditional_t<NOISE, GpccMarkovNoiseLooCombineArgs, GpccMarkovLooCombineArgs> c;
+    rc = markov_noise_rows<NOISE>(h, M, nz, a);
+    if (rc) return rc;
+    if constexpr (NOISE) { c.kappa = a.kappa; c.nu = a.nu; }
     c.tap = h->d_mktap; c.alpha = da; c.rho = dr; c.pts = h->d_mk; c.pband = h->d_mkli; c.pperm = h->d_mkli + N;
     c.mu = h->d_loomu; c.var = h->d_loovar; c.lp = h->d_loolp;
     c.L = h->L; c.N = (int)N;
@@ -2768,11 +2854,9 @@ extern "C" int gpcc_loo_markov_batch(gpcc_handle_t h, int M, const double *delay
         a.row0 = c.row0 = (int)row0;
         a.rows = c.rows = rows;
         a.mstride = c.mstride = (int)chunk;
-        rc = markov_launch(h, "gpcc_markov_loo_taps", MK_LOO_TAPS, rows, 2, a.stage,
-                           [&](int thr, bool st) { return gpcc_mkl_lds_bytes(a.N, a.L, thr, st); },
-                           [&](const GpccMkLaunch &g) { return gpcc_mkl_launch_taps(g, a); });
+        hipError_t e = hipSuccess;
+        rc = markov_loo_launch(h, a, c, e);
         if (rc) return rc;
-        hipError_t e = gpcc_mkl_launch_combine(d.p, d.noff, c, ms);
         if (e == hipSuccess) e = gpcc_mkl_launch_rows(h->d_loomu, h->d_loovar, h->d_loolp, h->d_loosum, h->d_oinfo, (int)N, (int)row0, rows, ms);
         if (e == hipSuccess && mix) {
             gpcc_loo_mix<<<pblocks, GPCC_LOO_THREADS, 0, ms>>>(h->d_loolp, row0, h->d_loow, (int)row0, rows, (int)N, h->d_loomix,
@@ -2795,9 +2879,31 @@ extern "C" int gpcc_loo_markov_batch(gpcc_handle_t h, int M, const double *delay
     return 0;
 }
 
-extern "C" int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
-                                                const int *Ntest, const double *ttest, const double *ytest, const double *sigmatest,
-                                                const double *weights, double *heldout, double *mix_heldout, double *loglik, int *info)
+extern "C" int gpcc_loo_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                     const double *weights, double *mu_out, double *var_out, double *lp_out, double *loo, double *mix_lp,
+                                     double *mix_loo, double *loglik, int *info)
+{
+    return markov_loo<false>(h, M, delays, alpha, rho, {"gpcc_loo_markov_batch", nullptr, nullptr}, weights, mu_out, var_out, lp_out, loo,
+                             mix_lp, mix_loo, loglik, info, [&](gpcc_handle_t o) {
+        return gpcc_loo_markov_batch(o, M, delays, alpha, rho, weights, mu_out, var_out, lp_out, loo, mix_lp, mix_loo, loglik, info);
+    });
+}
+
+extern "C" int gpcc_loo_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                           const double *kappa, const double *nu, const double *weights, double *mu_out, double *var_out,
+                                           double *lp_out, double *loo, double *mix_lp, double *mix_loo, double *loglik, int *info)
+{
+    return markov_loo<true>(h, M, delays, alpha, rho, {"gpcc_loo_noise_markov_batch", kappa, nu}, weights, mu_out, var_out, lp_out, loo,
+                            mix_lp, mix_loo, loglik, info, [&](gpcc_handle_t o) {
+        return gpcc_loo_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, weights, mu_out, var_out, lp_out, loo, mix_lp, mix_loo, loglik,
+                                           info);
+    });
+}
+
+template <bool NOISE, typename Reissue>
+static int markov_heldout(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const MarkovNoise &nz,
+                          const int *Ntest, const double *ttest, const double *ytest, const double *sigmatest, const double *weights,
+                          double *heldout, double *mix_heldout, double *loglik, int *info, Reissue &&reissue)
 {
     if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
     if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
@@ -2806,13 +2912,9 @@ extern "C" int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const do
     if (weights && !mix_heldout) return fail(h, GPCC_ERR_ARGUMENT, "weights given: mix_heldout is required");
     if (!weights && mix_heldout) return fail(h, GPCC_ERR_ARGUMENT, "mix_heldout needs weights");
     if (!weights && !heldout) return fail(h, GPCC_ERR_ARGUMENT, "NULL heldout without weights: nothing to return");
-    int rc = markov_refusals(h, "gpcc_heldout_loglik_markov_batch", "gpcc_heldout_loglik_batch");
+    int rc = markov_refusals(h, nz.who, "gpcc_heldout_loglik_batch");
     if (rc) return rc;
-    if (route_fp64(h, "linear-time held-out log-likelihood", rc, [&](gpcc_handle_t o) {
-            return gpcc_heldout_loglik_markov_batch(o, M, delays, alpha, rho, Ntest, ttest, ytest, sigmatest, weights, heldout, mix_heldout,
-                                                    loglik, info);
-        }))
-        return rc;
+    if (route_fp64(h, "linear-time held-out log-likelihood", rc, reissue)) return rc;
     long T = 0;
     std::vector<double> p;
     rc = count_test_points(h, Ntest, T);
@@ -2822,12 +2924,13 @@ extern "C" int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const do
     std::vector<int> order, band;
     int toff[GPCC_MARKOV_MAXL + 1];
     markov_sort_tests(h, Ntest, ttest, T, order, band, toff);
-    std::vector<double> tp(3 * T);   // t | y* - mean(y_band of the training data) | sigma*^2 + JITTER
+    // t | y* - mean(y_band of the training data) | sigma*^2 + JITTER (NOISE: sigma*^2, the rounded product; the lane maps it and adds JITTER)
+    std::vector<double> tp(3 * T);
     for (long j = 0; j < T; ++j) {
         const int o = order[j];
         tp[j] = ttest[o];
         tp[T + j] = ytest[o] - h->mean_b[band[j]];
-        tp[2 * T + j] = sigmatest[o] * sigmatest[o] + GPCC_MKP_JITTER;
+        tp[2 * T + j] = sigmatest[o] * sigmatest[o] + (NOISE ? 0.0 : GPCC_MKP_JITTER);
     }
     double *dd, *da, *dr;
     rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
@@ -2836,15 +2939,17 @@ extern "C" int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const do
         if (!g) g = grow_buf(h, &h->d_mkaux, &h->mkaux_cap, 2L * M + 4);
         if (!g) g = grow_buf(h, &h->d_mkauxi, &h->mkauxi_cap, 2L * M);
         if (!g && weights) g = grow_buf(h, &h->d_mkw, &h->mkw_cap, M);
-        return g;
+        return g ? g : markov_noise_grow<NOISE>(h, M);
     });
     if (rc) return rc;
     hipStream_t ms = h->main_stream;
     HIPCHK(h, hipMemcpyAsync(h->d_mkt, tp.data(), sizeof(double) * 3 * T, hipMemcpyHostToDevice, ms));
     HIPCHK(h, hipMemcpyAsync(h->d_mkti, order.data(), sizeof(int) * T, hipMemcpyHostToDevice, ms));
     if (weights) HIPCHK(h, hipMemcpyAsync(h->d_mkw, p.data(), sizeof(double) * M, hipMemcpyHostToDevice, ms));
-    GpccMarkovPredArgs a;
+    std::conditional_t<NOISE, GpccMarkovNoisePredArgs, GpccMarkovPredArgs> a;
     markov_pred_common(h, M, dd, da, dr, toff, T, a);
+    rc = markov_noise_rows<NOISE>(h, M, nz, a);
+    if (rc) return rc;
     double *d_held = h->d_mkaux + M, *d_mix = h->d_mkaux + 2L * M;
     a.ll2 = h->d_mkaux; a.info2 = h->d_mkauxi; a.at2 = h->d_mkauxi + M;
     rc = markov_pred_launch(h, GPCC_MKP_UPDATE, a, 2);
@@ -2857,30 +2962,54 @@ extern "C" int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const do
     return markov_finish(h, M, loglik, info);
 }
 
-extern "C" int gpcc_posterior_offsets_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
-                                                   double *mu_b_out, double *Sigma_b_out, double *loglik, int *info)
+extern "C" int gpcc_heldout_loglik_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                                const int *Ntest, const double *ttest, const double *ytest, const double *sigmatest,
+                                                const double *weights, double *heldout, double *mix_heldout, double *loglik, int *info)
+{
+    return markov_heldout<false>(h, M, delays, alpha, rho, {"gpcc_heldout_loglik_markov_batch", nullptr, nullptr}, Ntest, ttest, ytest,
+                                 sigmatest, weights, heldout, mix_heldout, loglik, info, [&](gpcc_handle_t o) {
+        return gpcc_heldout_loglik_markov_batch(o, M, delays, alpha, rho, Ntest, ttest, ytest, sigmatest, weights, heldout, mix_heldout, loglik,
+                                                info);
+    });
+}
+
+extern "C" int gpcc_heldout_loglik_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                                      const double *kappa, const double *nu, const int *Ntest, const double *ttest,
+                                                      const double *ytest, const double *sigmatest, const double *weights, double *heldout,
+                                                      double *mix_heldout, double *loglik, int *info)
+{
+    return markov_heldout<true>(h, M, delays, alpha, rho, {"gpcc_heldout_loglik_noise_markov_batch", kappa, nu}, Ntest, ttest, ytest,
+                                sigmatest, weights, heldout, mix_heldout, loglik, info, [&](gpcc_handle_t o) {
+        return gpcc_heldout_loglik_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, Ntest, ttest, ytest, sigmatest, weights, heldout,
+                                                      mix_heldout, loglik, info);
+    });
+}
+
+template <bool NOISE, typename Reissue>
+static int markov_postb(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const MarkovNoise &nz,
+                        double *mu_b_out, double *Sigma_b_out, double *loglik, int *info, Reissue &&reissue)
 {
     if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
     if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
     if (!delays || !alpha || !rho || !mu_b_out || !Sigma_b_out || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
     if (!primary(h)->mb) return fail(h, GPCC_ERR_ARGUMENT, "the fixed-b variant (gpccfixdelay.jl) has no posterior over offsets");
-    int rc = markov_refusals(h, "gpcc_posterior_offsets_markov_batch", "gpcc_posterior_offsets");
+    int rc = markov_refusals(h, nz.who, "gpcc_posterior_offsets");
     if (rc) return rc;
-    if (route_fp64(h, "linear-time posterior of the offsets", rc, [&](gpcc_handle_t o) {
-            return gpcc_posterior_offsets_markov_batch(o, M, delays, alpha, rho, mu_b_out, Sigma_b_out, loglik, info);
-        }))
-        return rc;
+    if (route_fp64(h, "linear-time posterior of the offsets", rc, reissue)) return rc;
     if (M == 0) return 0;
     GPCC_ON_DEVICE(h, h->device);
     const int L = h->L, nfin = L + L * (L + 1) / 2;
     double *dd, *da, *dr;
     rc = markov_begin(h, M, delays, alpha, rho, dd, da, dr, [&] {
-        const int g = grow_buf(h, &h->d_mkaux, &h->mkaux_cap, (long)nfin * M);
-        return g ? g : grow_buf(h, &h->d_mkt, &h->mkt_cap, 3);   // (no test points: the kernel reads none, the pointer must exist)
+        int g = grow_buf(h, &h->d_mkaux, &h->mkaux_cap, (long)nfin * M);
+        if (!g) g = grow_buf(h, &h->d_mkt, &h->mkt_cap, 3);   // (no test points: the kernel reads none, the pointer must exist)
+        return g ? g : markov_noise_grow<NOISE>(h, M);
     });
     if (rc) return rc;
-    GpccMarkovPredArgs a;
+    std::conditional_t<NOISE, GpccMarkovNoisePredArgs, GpccMarkovPredArgs> a;
     markov_pred_common(h, M, dd, da, dr, nullptr, 0, a);
+    rc = markov_noise_rows<NOISE>(h, M, nz, a);
+    if (rc) return rc;
     a.fin = h->d_mkaux;
     rc = markov_pred_launch(h, GPCC_MKP_UPDATE, a, 1);
     if (rc) return rc;
@@ -2898,6 +3027,25 @@ extern "C" int gpcc_posterior_offsets_markov_batch(gpcc_handle_t h, int M, const
             for (int k = i; k < L; ++k) S[i * L + k] = S[k * L + i] = bad ? NAN : fin[(size_t)(c++) * M + m];
     }
     return 0;
+}
+
+extern "C" int gpcc_posterior_offsets_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                                   double *mu_b_out, double *Sigma_b_out, double *loglik, int *info)
+{
+    return markov_postb<false>(h, M, delays, alpha, rho, {"gpcc_posterior_offsets_markov_batch", nullptr, nullptr}, mu_b_out, Sigma_b_out,
+                               loglik, info, [&](gpcc_handle_t o) {
+        return gpcc_posterior_offsets_markov_batch(o, M, delays, alpha, rho, mu_b_out, Sigma_b_out, loglik, info);
+    });
+}
+
+extern "C" int gpcc_posterior_offsets_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha,
+                                                         const double *rho, const double *kappa, const double *nu, double *mu_b_out,
+                                                         double *Sigma_b_out, double *loglik, int *info)
+{
+    return markov_postb<true>(h, M, delays, alpha, rho, {"gpcc_posterior_offsets_noise_markov_batch", kappa, nu}, mu_b_out, Sigma_b_out,
+                              loglik, info, [&](gpcc_handle_t o) {
+        return gpcc_posterior_offsets_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, mu_b_out, Sigma_b_out, loglik, info);
+    });
 }
 
 // ------------------------------------------------------------------------------------------

@@ -107,8 +107,10 @@ __global__ void __launch_bounds__(256) gpcc_markov_loo_taps(const GpccMarkovLooA
 // one lane per (row of the chunk, sorted point): grid (N, ceil(rows / 64)), 64 threads -- the point on grid.x, which has no 65535
 // limit (gpcc_create takes N up to 65536).  The arithmetic is gpcc_markov_combine's (gpcc_markov_pred.hip.h) up to h'm_s and h'P_s h,
 // copied and not shared so that the existing kernel keeps its bits: a fix to either belongs in both.
-template <int P, int NOFF>
-__global__ void __launch_bounds__(64) gpcc_markov_loo_combine(const GpccMarkovLooCombineArgs a)
+// ARGS: GpccMarkovLooCombineArgs, or GpccMarkovNoiseLooCombineArgs (gpcc_markov_noise_pred.hip.h: the same fields and the rows' kappa,
+// nu), on which the point's variance is the one its row's noise model gives it; the plain instantiation compiles the statements it had.
+template <int P, int NOFF, class ARGS = GpccMarkovLooCombineArgs>
+__global__ void __launch_bounds__(64) gpcc_markov_loo_combine(const ARGS a)
 {
     constexpr int NS = P + NOFF, NREC = NS + NS * (NS + 1) / 2;
     const int lrow = (int)blockIdx.y * 64 + (int)threadIdx.x, pj = blockIdx.x;
@@ -189,7 +191,12 @@ __global__ void __launch_bounds__(64) gpcc_markov_loo_combine(const GpccMarkovLo
         mean += h[i] * pe;
         var += h[i] * ph;
     }
-    var += a.pts[2L * a.N + pj];
+    if constexpr (std::is_same_v<ARGS, GpccMarkovLooCombineArgs>) {
+        var += a.pts[2L * a.N + pj];
+    } else {   // the tap lane's expression: fma(kappa_b^2, sigma_i^2, nu_b)
+        const double k = a.kappa[row * a.L + qb];
+        var += fma(k * k, a.pts[2L * a.N + pj], a.nu[row * a.L + qb]);
+    }
     ok = ok && var > 0.0 && var < __builtin_inf() && mean == mean;
     const double e = a.pts[(long)a.N + pj] - mean, nan = __builtin_nan("");   // y_i - mu_i: the residual against the band mean
     const long o = (long)lrow * a.N + a.pperm[pj];

@@ -564,8 +564,9 @@ def realisation_peaks(objective, candidatedelays, Y, counts=None, *, start, iter
 
 def effective_std(stdarray, kappa, nu):
     """The error bars sqrt(kappa_l^2 sigma_l^2 + nu_l) of the noise model of Objective.loglik_markov_noise_batch, as a list of L
-    arrays: kappa and nu scalars or (L,).  A fresh Objective or Predictor on them is the route to predictions, leave-one-out scores,
-    Hessians, the Laplace evidence and draws under a fitted noise model (its loglik_markov_batch is loglik_markov_noise_batch's value)."""
+    arrays: kappa and nu scalars or (L,).  A fresh Objective or Predictor on them is the route to joint predictions, the dense path
+    and draws under a fitted noise model (its loglik_markov_batch is loglik_markov_noise_batch's value); per-band predictions, held-out
+    scores and leave-one-out scores take the model directly (Predictor(..., kappa=, nu=), noise_predictor)."""
     L = len(stdarray)
     kappa = np.broadcast_to(np.asarray(kappa, np.float64), (L,))
     nu = np.broadcast_to(np.asarray(nu, np.float64), (L,))
@@ -729,6 +730,28 @@ def _loo_entry(obj, solver):
     return obj.loo_markov_batch if solver == "markov" else obj.loo_batch
 
 
+_NOISE_ROUTE = ("is not available under a noise model (kappa=, nu=): build the predictor on a fresh Objective with the error bars "
+                "fit.effective_std(stdarray, kappa, nu)")
+
+
+def _noise_model(L, G, kappa, nu, solver):
+    """kappa=, nu= of the predictors -> None (neither given: the plain entries) or (kappa[G, L], nu[G, L]) for the noise entries; each
+    may be (L,), (G, L) or None (ones / zeros).  A noise model needs solver="markov"."""
+    if kappa is None and nu is None:
+        return None
+    if solver != "markov":
+        raise ValueError("kappa= and nu= need solver='markov' (the noise model runs in the linear-time entries only)")
+    out = []
+    for name, x, fill in (("kappa", kappa, 1.0), ("nu", nu, 0.0)):
+        x = np.full((G, L), fill) if x is None else np.asarray(x, dtype=np.float64)
+        if x.shape == (L,):
+            x = np.broadcast_to(x, (G, L))
+        if x.shape != (G, L):
+            raise ValueError("%s must be (L,) = (%d,), (G, L) = (%d, %d) or None" % (name, L, G, L))
+        out.append(np.ascontiguousarray(x))
+    return tuple(out)
+
+
 class Predictor:
     """The `predictTest` closure returned by gpcc() (marginaliseb.jl:259-343), three call forms:
       pred(ttest)                       ttest = list of L arrays  -> (mu_pred, Sigma_pred), joint    (:259-289)
@@ -738,17 +761,40 @@ class Predictor:
     solver "dense" (default): every form factorises the N x N matrix.  solver "markov" (OU, matern32, matern52): the per-band form and
     the three-argument form run in linear time (Objective.predict_markov_batch / heldout_loglik_markov_batch, one row; a test point
     whose combine or predictive variance fails raises PosDefException, there being no test block for nearestposdef to repair); the
-    JOINT form (Sigma_pred is T x T) stays dense, and so does sample() unless it is called with solver="markov"."""
+    JOINT form (Sigma_pred is T x T) stays dense, and so does sample() unless it is called with solver="markov".
+    kappa=, nu= ((L,) each, or None: 1 / 0; solver "markov" only): a fitted noise model, every observation of band l having the variance
+    kappa_l^2 sigma^2 + nu_l (Objective.predict_markov_noise_batch / heldout_loglik_markov_noise_batch / loo_markov_noise_batch): the
+    per-band form, the three-argument form (sigmatest mapped by the same band's kappa, nu) and loo(), whose z is then standardised by
+    the fitted variance, are those of a predictor on a fresh Objective with the error bars effective_std(stdarray, kappa, nu).  The
+    joint form and sample() raise NotImplementedError under a noise model: that fresh Objective is their route."""
 
-    def __init__(self, objective, delays, alpha, rho, solver="dense"):
+    def __init__(self, objective, delays, alpha, rho, solver="dense", kappa=None, nu=None):
         if solver not in ("dense", "markov"):
             raise ValueError("solver must be 'dense' or 'markov', got %r" % (solver,))
         self.obj, self.delays, self.alpha, self.rho = objective, np.array(delays, float), np.array(alpha, float), float(rho)
         self.solver = solver
+        self.noise = _noise_model(objective.L, 1, kappa, nu, solver)
 
     def __call__(self, ttest, ytest=None, sigmatest=None):
         L = self.obj.L
         joint = isinstance(ttest, (list, tuple)) and len(ttest) == L and all(np.ndim(a) == 1 for a in ttest)
+        if self.noise is not None:
+            if ytest is not None:
+                held, _, info, _ = self.obj.heldout_loglik_markov_noise_batch(self.delays[None, :], self.alpha[None, :], [self.rho],
+                                                                              list(ttest), list(ytest), list(sigmatest), *self.noise)
+                if info[0] > 0:
+                    raise PosDefException(int(info[0]))
+                return float(held[0])
+            if joint:
+                raise NotImplementedError("the joint form " + _NOISE_ROUTE)
+            tt = np.asarray(ttest, dtype=np.float64).ravel()
+            n = len(tt)
+            mu, var, _, info, _, _ = self.obj.predict_markov_noise_batch(self.delays[None, :], self.alpha[None, :], [self.rho], [tt] * L,
+                                                                         *self.noise)
+            if info[0] > 0:
+                raise PosDefException(int(info[0]))
+            return ([mu[0, l * n:(l + 1) * n] for l in range(L)],
+                    [np.sqrt(np.maximum(var[0, l * n:(l + 1) * n], 1e-6)) for l in range(L)])      # :301-303
         if self.solver == "markov" and ytest is not None:
             held, _, info, _ = self.obj.heldout_loglik_markov_batch(self.delays[None, :], self.alpha[None, :], [self.rho], list(ttest),
                                                                     list(ytest), list(sigmatest))
@@ -787,7 +833,12 @@ class Predictor:
         """Exact leave-one-out scores of the training points under this fit -> LooScores (Objective.loo_batch, one row; no refit and
         no JITTER: p(y_i | y_-i) of the model the likelihood uses).  solver None: the predictor's own; "dense" or "markov" (OU,
         matern32, matern52: linear time).  A failed row raises PosDefException."""
-        res = _loo_entry(self.obj, solver or self.solver)(self.delays[None, :], self.alpha[None, :], [self.rho])
+        if self.noise is not None:
+            if solver not in (None, "markov"):
+                raise ValueError("loo under a noise model (kappa=, nu=) needs solver='markov'")
+            res = self.obj.loo_markov_noise_batch(self.delays[None, :], self.alpha[None, :], [self.rho], *self.noise)
+        else:
+            res = _loo_entry(self.obj, solver or self.solver)(self.delays[None, :], self.alpha[None, :], [self.rho])
         if res.info[0] > 0:
             raise PosDefException(int(res.info[0]))
         sigma = np.sqrt(res.var[0])
@@ -801,6 +852,8 @@ class Predictor:
         time (Objective.sample_markov_batch; other normals, so other draws); a failed filter or combine raises
         PosDefException."""
         _check_sample_solver(solver)
+        if self.noise is not None:
+            raise NotImplementedError("sample() " + _NOISE_ROUTE)
         bands = _sample_bands(self.obj.L, ttest)
         st = None if sigmatest is None else _sample_bands(self.obj.L, sigmatest)
         if solver == "markov":
@@ -828,9 +881,12 @@ class DelayAveragedPredictor:
     held-out density is well defined too: loglik(ttest, ytest, sigmatest) = log sum_g p_g N(ytest; mu_g, Sigma_g)
     (Objective.heldout_loglik_batch).
     solver "markov" (OU, matern32, matern52): __call__ and loglik run in linear time (Objective.predict_markov_batch /
-    heldout_loglik_markov_batch); sample() stays dense unless it is called with solver="markov"."""
+    heldout_loglik_markov_batch); sample() stays dense unless it is called with solver="markov".
+    kappa=, nu= ((L,) or (G, L) each, or None: 1 / 0; solver "markov" only): a noise model per row, e.g. a NoiseGridFit's (noise_predictor
+    builds that predictor): __call__, loglik and loo() mix the rows of the noise entries in one call each, as Predictor's kappa=, nu=;
+    sample() raises NotImplementedError."""
 
-    def __init__(self, objective, delays, alpha, rho, weights, solver="dense"):
+    def __init__(self, objective, delays, alpha, rho, weights, solver="dense", kappa=None, nu=None):
         if solver not in ("dense", "markov"):
             raise ValueError("solver must be 'dense' or 'markov', got %r" % (solver,))
         self.obj = objective
@@ -844,6 +900,7 @@ class DelayAveragedPredictor:
             raise ValueError("delays and alpha must be (G, L) = (%d, %d) and weights (G,)" % (G, L))
         if not np.all(np.isfinite(self.weights)) or np.any(self.weights < 0) or not self.weights.sum() > 0:
             raise ValueError("weights must be finite, >= 0 and not all zero")
+        self.noise = _noise_model(L, G, kappa, nu, solver)
 
     def __call__(self, ttest):
         L = self.obj.L
@@ -851,8 +908,12 @@ class DelayAveragedPredictor:
             bands = [np.asarray(a, dtype=np.float64) for a in ttest]
         else:
             bands = [np.asarray(ttest, dtype=np.float64).ravel()] * L
-        predict = self.obj.predict_markov_batch if self.solver == "markov" else self.obj.predict_batch
-        _, _, _, _, mu, var = predict(self.delays, self.alpha, self.rho, bands, weights=self.weights)
+        if self.noise is not None:
+            _, _, _, _, mu, var = self.obj.predict_markov_noise_batch(self.delays, self.alpha, self.rho, bands, *self.noise,
+                                                                      weights=self.weights)
+        else:
+            predict = self.obj.predict_markov_batch if self.solver == "markov" else self.obj.predict_batch
+            _, _, _, _, mu, var = predict(self.delays, self.alpha, self.rho, bands, weights=self.weights)
         off = np.concatenate([[0], np.cumsum([len(b) for b in bands])])
         return ([mu[off[l]:off[l + 1]] for l in range(L)],
                 [np.sqrt(np.maximum(var[off[l]:off[l + 1]], 1e-6)) for l in range(L)])      # :301-303
@@ -860,6 +921,9 @@ class DelayAveragedPredictor:
     def loglik(self, ttest, ytest, sigmatest):
         """The mixture's held-out log density log sum_g p_g N(ytest; mu_g, Sigma_g + diag(sigmatest^2)) of the test set (lists of L
         arrays), every row scored as Predictor(ttest, ytest, sigmatest) scores it (marginaliseb.jl:311-343)."""
+        if self.noise is not None:
+            return self.obj.heldout_loglik_markov_noise_batch(self.delays, self.alpha, self.rho, ttest, ytest, sigmatest, *self.noise,
+                                                              weights=self.weights)[3]
         if self.solver == "markov":
             return self.obj.heldout_loglik_markov_batch(self.delays, self.alpha, self.rho, ttest, ytest, sigmatest, weights=self.weights)[3]
         return self.obj.heldout_loglik_batch(self.delays, self.alpha, self.rho, ttest, ytest, sigmatest, weights=self.weights)[3]
@@ -870,7 +934,12 @@ class DelayAveragedPredictor:
         y_-i the mixture's weights are q_gi proportional to p_g exp(-lp_gi); mu and sigma are the mean and the standard deviation of
         that mixture of the rows' Gaussians, z = (y - mu) / sigma.  Rows of weight 0 are left out; a failed row with weight makes
         everything NaN.  solver as Predictor.loo."""
-        res = _loo_entry(self.obj, solver or self.solver)(self.delays, self.alpha, self.rho, weights=self.weights)
+        if self.noise is not None:
+            if solver not in (None, "markov"):
+                raise ValueError("loo under a noise model (kappa=, nu=) needs solver='markov'")
+            res = self.obj.loo_markov_noise_batch(self.delays, self.alpha, self.rho, *self.noise, weights=self.weights)
+        else:
+            res = _loo_entry(self.obj, solver or self.solver)(self.delays, self.alpha, self.rho, weights=self.weights)
         keep = self.weights > 0
         p = self.weights[keep] / self.weights[keep].sum()
         x = np.log(p)[:, None] - res.lp[keep]
@@ -887,6 +956,8 @@ class DelayAveragedPredictor:
         solver None (default) or "dense": Objective.sample_batch whatever the predictor's own solver; "markov": the same mixture drawn in
         linear time (Objective.sample_markov_batch; the same rows for the same seed and weights, other normals)."""
         _check_sample_solver(solver)
+        if self.noise is not None:
+            raise NotImplementedError("sample() " + _NOISE_ROUTE)
         bands = _sample_bands(self.obj.L, ttest)
         st = None if sigmatest is None else _sample_bands(self.obj.L, sigmatest)
         if solver == "markov":
@@ -895,6 +966,18 @@ class DelayAveragedPredictor:
             return _split_bands(draws, bands), rows
         draws, rows, _, _ = self.obj.sample_batch(self.delays, self.alpha, self.rho, bands, S, seed, weights=self.weights, sigmatest=st)
         return _split_bands(draws, bands), rows
+
+
+def noise_predictor(objective, candidatedelays, noisefit, weights=None):
+    """The DelayAveragedPredictor of a NoiseGridFit (gpcc_grid_noise): the rows (candidatedelays[g], noisefit.alpha[g], noisefit.rho[g])
+    each under its own fitted noise model (noisefit.kappa[g], noisefit.nu[g]), in linear time.  weights: (G,), default
+    getprobabilities(noisefit.loglikel).  Its predictions, held-out density and leave-one-out scores are one device call each, where a
+    fresh Objective on effective_std per candidate delay was G of them."""
+    delays = np.atleast_2d(np.asarray(candidatedelays, dtype=np.float64))
+    if weights is None:
+        weights = getprobabilities(np.asarray(noisefit.loglikel, dtype=np.float64))
+    return DelayAveragedPredictor(objective, delays, noisefit.alpha, noisefit.rho, weights, solver="markov", kappa=noisefit.kappa,
+                                  nu=noisefit.nu)
 
 
 def gpcc(tarray, yarray, stdarray, *, kernel, delays, iterations, seed=1, numberofrestarts=1, initialrandom=5,

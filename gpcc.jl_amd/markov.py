@@ -1587,7 +1587,24 @@ def _smooth(name, train, tests, band_of, alpha, rho, p, n, vb, slip=None):
     return mu, var, ll, 0
 
 
-def predict(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, marginalise_b=True, _slip=None):
+def _noise_apply(L, train, code, noise):
+    """What a noise model does to _setup's results.  noise: None (nothing: the plain functions), or (kappa, nu, slip) of predict_noise
+    and its siblings -> (the training observations on the mapped variances, _noise_train's; the code, -3 after -1 and -2; kappa^2 and
+    the excess variance per band as the pass sees them, or None).  slip (tests only): "kappa_linear" (kappa sigma^2 + nu),
+    "noise_all_bands" (every band under band 1's model)."""
+    if noise is None:
+        return train, code, None, None
+    kappa, nu, ncode = _noise_setup(L, noise[0], noise[1])
+    if code or ncode:
+        return train, code or ncode, None, None
+    if noise[2] == "kappa_linear":
+        kappa = np.sqrt(kappa)
+    if noise[2] == "noise_all_bands":
+        kappa, nu = np.full(L, kappa[0]), np.full(L, nu[0])
+    return [e[:5] for e in _noise_train(train, kappa, nu)], 0, kappa * kappa, nu
+
+
+def predict(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, marginalise_b=True, _slip=None, _noise=None):
     """(mu[T], var[T], loglik, info) of one (tau, alpha, rho) at the test times ttest (a list of L arrays, any order; T = their total,
     flattened in band order): predictTest's per-band mean and variance (JITTER included) by two filters and a combine, and the training
     log-likelihood.  info: loglik()'s codes for the training filter (mu and var NaN then), else N + j for the first test point j
@@ -1595,6 +1612,7 @@ def predict(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, margina
     _slip (tests only): "no_flip" (D left out on the backward side), "tie_both" (a training point that ties with a test point used on
     both sides), "no_prior" (-P0^-1 dropped), "no_jitter"."""
     name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b)
+    train, code, _, _ = _noise_apply(L, train, code, _noise)
     tests, band_of = _test_list(L, ttest, delays)
     if code:
         nan = np.full(len(tests), math.nan)
@@ -1605,21 +1623,24 @@ def predict(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, margina
     return mu + means[band_of], var + (0.0 if _slip == "no_jitter" else JITTER), ll, 0
 
 
-def heldout(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, ytest, sigmatest, marginalise_b=True, _slip=None):
+def heldout(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, ytest, sigmatest, marginalise_b=True, _slip=None, _noise=None):
     """(heldout, loglik, info) of one (tau, alpha, rho): log p(ytest | training) = loglik(training U test) - loglik(training), the
     reference's predictTest(ttest, ytest, sigmatest).  info: loglik()'s codes for the training filter, else N + j for the first test
     point j (1-based, flattened band order) whose predictive variance in the union filter is not positive and finite (heldout NaN).
     _slip (tests only): "no_jitter", "test_mean" (test residuals centred on the test set's own band means)."""
     name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b)
+    train, code, k2, ex = _noise_apply(L, train, code, _noise)
     if code:
         return math.nan, math.nan, code
+    if k2 is None or _noise[2] == "heldout_raw_sigmatest":
+        k2, ex = np.ones(L), np.zeros(L)
     jit = 0.0 if _slip == "no_jitter" else JITTER
     tests = []
     for l in range(L):
         tt, yt, st = (np.asarray(a[l], np.float64).reshape(-1) for a in (ttest, ytest, sigmatest))
         centre = (yt.sum() / len(yt) if len(yt) else 0.0) if _slip == "test_mean" else means[l]
         for v, yv, sv in zip(tt, yt, st):
-            tests.append((v - delays[l], l, len(tests), yv - centre, sv * sv + jit))
+            tests.append((v - delays[l], l, len(tests), yv - centre, k2[l] * (sv * sv) + ex[l] + jit))
     ll, info, _, _, _, _ = _pass(name, train, [], alpha, rho, p, n, vb)
     if info:
         return math.nan, math.nan, info
@@ -1629,10 +1650,11 @@ def heldout(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, ytest, 
     return lu - ll, ll, 0
 
 
-def posterior_offsets(kernel, tarray, yarray, stdarray, delays, alpha, rho):
+def posterior_offsets(kernel, tarray, yarray, stdarray, delays, alpha, rho, _noise=None):
     """(mu_postb[L], Sigma_postb[L, L], loglik, info) of one (tau, alpha, rho) with marginalised offsets: the offset block of the
     forward filter's final state (marginaliseb.jl:244-250), NaN where the training filter fails."""
     name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, True)
+    train, code, _, _ = _noise_apply(L, train, code, _noise)
     if code:
         return np.full(L, math.nan), np.full((L, L), math.nan), math.nan, code
     ll, info, m, P, _, _ = _pass(name, train, [], alpha, rho, p, n, vb)
@@ -1880,7 +1902,7 @@ def _loo_taps(name, ev, alpha, rho, p, n, vb, reverse, after_update=False):
 LOO_SLIPS = ("with_self", "tie_both", "no_sigma", "jitter", "sorted_order", "arith_mix")
 
 
-def loo(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True, _slip=None):
+def loo(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True, _slip=None, _noise=None):
     """(mu[N], var[N], lp[N], loo, loglik, info) of one (tau, alpha, rho): mean, variance and log-density of y_i given every other
     observation and their sum, Objective.loo_markov_batch's row, in the caller's order (band 1 as given, then band 2, ...).  info:
     loglik()'s codes for the filter, else N + i for the first point i (1-based, the caller's order) whose combine meets a pivot, or
@@ -1892,6 +1914,8 @@ def loo(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True
     if _slip is not None and _slip not in LOO_SLIPS:
         raise ValueError("unknown slip %r" % (_slip,))
     name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b)
+    raw = {(e[1], e[2]): e[4] for e in train}      # the reported sigma^2 (a noise model's slip "loo_var_raw" adds it in the combine)
+    train, code, _, _ = _noise_apply(L, train, code, _noise)
     N = len(train)
     nan = np.full(N, math.nan)
     if code:
@@ -1914,6 +1938,8 @@ def loo(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b=True
     mu, var, lp = nan.copy(), nan.copy(), nan.copy()
     bad = N
     for (s, b, i, r, s2) in train:
+        if _noise is not None and _noise[2] == "loo_var_raw":
+            s2 = raw[(b, i)]
         o = int(off[b] + (i if _slip == "sorted_order" else perms[b][i]))
         Ps = None
         if (b, i) in bw:
@@ -2006,6 +2032,48 @@ def mix_logsumexp(values, weights):
     return float(mx + math.log(np.sum(np.exp(x - mx)))) if np.isfinite(mx) else float(mx)
 
 
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Predictions, held-out scores, the offsets' posterior and leave-one-out scores under a noise model (csrc/gpcc_markov_noise_pred.hip.h,
+# DESIGN.md 4.29), the same algorithm in numpy: predict(), heldout(), posterior_offsets() and loo() above, their passes unchanged, on
+# _noise_train's mapped variances kappa_l^2 sigma_i^2 + nu_l (_noise_apply).  A held-out test point of band l has kappa_l^2 sigma*^2 +
+# nu_l + JITTER; the leave-one-out variance adds the point's mapped variance.  At kappa = 1, nu = 0 these return the plain functions'
+# numbers exactly.  Codes: the plain ones and, after -1 and -2, -3 (a kappa or nu negative or not finite).
+# ----------------------------------------------------------------------------------------------------------------------------------
+NOISE_PREDICT_SLIPS = ("heldout_raw_sigmatest", "loo_var_raw", "kappa_linear", "noise_all_bands")
+
+
+def _noise_slip(slip):
+    if slip is not None and slip not in NOISE_PREDICT_SLIPS:
+        raise ValueError("unknown slip %r" % (slip,))
+    return slip
+
+
+def predict_noise(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, kappa=None, nu=None, marginalise_b=True, _slip=None):
+    """predict() of one (tau, alpha, rho, kappa, nu): a row of Objective.predict_markov_noise_batch.  _slip (tests only): "kappa_linear"
+    (the variance kappa sigma^2 + nu), "noise_all_bands" (every band under band 1's kappa, nu)."""
+    return predict(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, marginalise_b, _noise=(kappa, nu, _noise_slip(_slip)))
+
+
+def heldout_noise(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, ytest, sigmatest, kappa=None, nu=None, marginalise_b=True,
+                  _slip=None):
+    """heldout() of one (tau, alpha, rho, kappa, nu), the test error bars mapped by the same band's kappa, nu: a row of
+    Objective.heldout_loglik_markov_noise_batch.  _slip (tests only): predict_noise's and "heldout_raw_sigmatest" (the test points keep
+    sigma*^2)."""
+    return heldout(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, ytest, sigmatest, marginalise_b,
+                   _noise=(kappa, nu, _noise_slip(_slip)))
+
+
+def posterior_offsets_noise(kernel, tarray, yarray, stdarray, delays, alpha, rho, kappa=None, nu=None, _slip=None):
+    """posterior_offsets() of one (tau, alpha, rho, kappa, nu): a row of Objective.posterior_offsets_markov_noise_batch."""
+    return posterior_offsets(kernel, tarray, yarray, stdarray, delays, alpha, rho, _noise=(kappa, nu, _noise_slip(_slip)))
+
+
+def loo_noise(kernel, tarray, yarray, stdarray, delays, alpha, rho, kappa=None, nu=None, marginalise_b=True, _slip=None):
+    """loo() of one (tau, alpha, rho, kappa, nu), var_i = h'P_s h + kappa_b^2 sigma_i^2 + nu_b: a row of
+    Objective.loo_markov_noise_batch.  _slip (tests only): predict_noise's and "loo_var_raw" (the combine adds sigma_i^2 unmapped)."""
+    return loo(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b, _noise=(kappa, nu, _noise_slip(_slip)))
+
+
 class MarkovObjective:
     """The CPU mirror with the methods gpcc_grid's `engine="python"` fit and the Markov predictors call (loglik_batch and
     loglik_markov_batch are the same filter here): gpcc_grid(..., objective=MarkovObjective(...), solver="markov") fits without a GPU."""
@@ -2079,42 +2147,70 @@ class MarkovObjective:
         rho = np.asarray(rho, np.float64).reshape(-1)
         return delays, alpha, rho
 
-    def predict_markov_batch(self, delays, alpha, rho, ttest, weights=None):
+    def _noise_of(self, M, noise):
+        """Per row what predict() and its siblings take as _noise: None (a plain method), or (kappa[m], nu[m], None)."""
+        if noise is None:
+            return [None] * M
+        kappa, nu = _noise_rows(self.L, M, noise[0]), _noise_rows(self.L, M, noise[1])
+        return [(kappa[i], nu[i], None) for i in range(M)]
+
+    def predict_markov_batch(self, delays, alpha, rho, ttest, weights=None, _noise=None):
         """Objective.predict_markov_batch's result: (mu[M, T], var[M, T], loglik[M], info[M], mix_mu, mix_var)."""
         delays, alpha, rho = self._rows(delays, alpha, rho)
-        out = [predict(self.kernel, *self.data, delays[i], alpha[i], rho[i], ttest, self.marginalise_b) for i in range(len(rho))]
+        nz = self._noise_of(len(rho), _noise)
+        out = [predict(self.kernel, *self.data, delays[i], alpha[i], rho[i], ttest, self.marginalise_b, _noise=nz[i])
+               for i in range(len(rho))]
         mu, var = np.array([o[0] for o in out]), np.array([o[1] for o in out])
         mix = mix_moments(mu, var, weights) if weights is not None else (None, None)
         return mu, var, np.array([o[2] for o in out]), np.array([o[3] for o in out], dtype=np.int32), mix[0], mix[1]
 
-    def heldout_loglik_markov_batch(self, delays, alpha, rho, ttest, ytest, sigmatest, weights=None):
+    def heldout_loglik_markov_batch(self, delays, alpha, rho, ttest, ytest, sigmatest, weights=None, _noise=None):
         """Objective.heldout_loglik_markov_batch's result: (heldout[M], loglik[M], info[M], mix or None)."""
         delays, alpha, rho = self._rows(delays, alpha, rho)
-        out = [heldout(self.kernel, *self.data, delays[i], alpha[i], rho[i], ttest, ytest, sigmatest, self.marginalise_b)
+        nz = self._noise_of(len(rho), _noise)
+        out = [heldout(self.kernel, *self.data, delays[i], alpha[i], rho[i], ttest, ytest, sigmatest, self.marginalise_b, _noise=nz[i])
                for i in range(len(rho))]
         held = np.array([o[0] for o in out])
         mix = mix_logsumexp(held, weights) if weights is not None else None
         return held, np.array([o[1] for o in out]), np.array([o[2] for o in out], dtype=np.int32), mix
 
-    def loo_markov_batch(self, delays, alpha, rho, weights=None, outputs=None):
+    def loo_markov_batch(self, delays, alpha, rho, weights=None, outputs=None, _noise=None):
         """Objective.loo_markov_batch's result: LooResult(mu[M, N], var[M, N], lp[M, N], loo[M], loglik[M], info[M], mix_lp, mix_loo)
         (outputs is accepted and ignored: everything is computed)."""
         from .api import LooResult
         delays, alpha, rho = self._rows(delays, alpha, rho)
-        out = [loo(self.kernel, *self.data, delays[i], alpha[i], rho[i], self.marginalise_b) for i in range(len(rho))]
+        nz = self._noise_of(len(rho), _noise)
+        out = [loo(self.kernel, *self.data, delays[i], alpha[i], rho[i], self.marginalise_b, _noise=nz[i]) for i in range(len(rho))]
         lp = np.array([o[2] for o in out])
         mix = loo_mix(lp, weights) if weights is not None else (None, None)
         return LooResult(np.array([o[0] for o in out]), np.array([o[1] for o in out]), lp, np.array([o[3] for o in out]),
                          np.array([o[4] for o in out]), np.array([o[5] for o in out], dtype=np.int32), mix[0], mix[1])
 
-    def posterior_offsets_markov_batch(self, delays, alpha, rho):
+    def posterior_offsets_markov_batch(self, delays, alpha, rho, _noise=None):
         """Objective.posterior_offsets_markov_batch's result: (mu_b[M, L], Sigma_b[M, L, L], loglik[M], info[M])."""
         if not self.marginalise_b:
             raise ValueError("posterior_offsets needs marginalise_b")
         delays, alpha, rho = self._rows(delays, alpha, rho)
-        out = [posterior_offsets(self.kernel, *self.data, delays[i], alpha[i], rho[i]) for i in range(len(rho))]
+        nz = self._noise_of(len(rho), _noise)
+        out = [posterior_offsets(self.kernel, *self.data, delays[i], alpha[i], rho[i], _noise=nz[i]) for i in range(len(rho))]
         return (np.array([o[0] for o in out]), np.array([o[1] for o in out]), np.array([o[2] for o in out]),
                 np.array([o[3] for o in out], dtype=np.int32))
+
+    def predict_markov_noise_batch(self, delays, alpha, rho, ttest, kappa=None, nu=None, weights=None):
+        """Objective.predict_markov_noise_batch's result: predict_markov_batch's tuple, every row under its own (kappa, nu)."""
+        return self.predict_markov_batch(delays, alpha, rho, ttest, weights, _noise=(kappa, nu))
+
+    def heldout_loglik_markov_noise_batch(self, delays, alpha, rho, ttest, ytest, sigmatest, kappa=None, nu=None, weights=None):
+        """Objective.heldout_loglik_markov_noise_batch's result: heldout_loglik_markov_batch's tuple."""
+        return self.heldout_loglik_markov_batch(delays, alpha, rho, ttest, ytest, sigmatest, weights, _noise=(kappa, nu))
+
+    def posterior_offsets_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None):
+        """Objective.posterior_offsets_markov_noise_batch's result: posterior_offsets_markov_batch's tuple."""
+        return self.posterior_offsets_markov_batch(delays, alpha, rho, _noise=(kappa, nu))
+
+    def loo_markov_noise_batch(self, delays, alpha, rho, kappa=None, nu=None, weights=None, outputs=None):
+        """Objective.loo_markov_noise_batch's result: loo_markov_batch's LooResult."""
+        return self.loo_markov_batch(delays, alpha, rho, weights, outputs, _noise=(kappa, nu))
 
     def sample_markov_batch(self, delays, alpha, rho, ttest, S, seed, weights=None, sigmatest=None):
         """Objective.sample_markov_batch's result: (draws, draw_row, loglik[M], info[M])."""

@@ -510,8 +510,8 @@ int gpcc_loglik_grad_markov_resampled_batch(gpcc_handle_t h, int M, const double
  * the same call.  No atomics: a row's bits depend on that row alone, whatever M, the row order, the launch shape and the options.
  * Memory: gpcc_loglik_markov_batch's, plus 16 M L bytes for kappa and nu and, for the gradient, 8 M bytes per slot and 8 M (4L + 1)
  * bytes, grown on demand; none of the N^2 workspace.  "markov_count" advances by M.  Always fp64 (an fp32 handle on its fp64 twin);
- * a multi-device handle computes on device_ids[0].  Predictions, held-out scores, Hessians and draws under a fitted noise model: a
- * fresh handle on those error bars.  Blocking. */
+ * a multi-device handle computes on device_ids[0].  Predictions, held-out scores, the offsets' posterior and leave-one-out scores under
+ * a noise model: gpcc_predict_noise_markov_batch and its siblings below; draws: a fresh handle on those error bars.  Blocking. */
 int gpcc_loglik_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                    const double *kappa, const double *nu, double *loglik, int *info);
 int gpcc_loglik_grad_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
@@ -564,6 +564,49 @@ int gpcc_loglik_hess_noise_markov_batch(gpcc_handle_t h, int M, const double *de
  * information in kappa, nu.  Blocking. */
 int gpcc_loglik_hess_full_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                              const double *kappa, const double *nu, double *loglik, double *grad, double *hess, int *info);
+
+/* The post-fit products of rows that each carry their own noise model, in LINEAR TIME (kernels: csrc/gpcc_markov_noise_pred.hip.h,
+ * DESIGN.md 4.29): gpcc_predict_markov_batch, gpcc_heldout_loglik_markov_batch, gpcc_posterior_offsets_markov_batch and
+ * gpcc_loo_markov_batch with kappa, nu (M x L row-major each; NULL: all 1 / all 0, as gpcc_loglik_noise_markov_batch) behind rho.  Point
+ * i of band l of row m is observed with v_i = kappa[m][l]^2 sigma_i^2 + nu[m][l]; the band means and Sigma_b stay the handle's.
+ * CONTRACT.  A row's outputs are those of the plain entry on a fresh handle created with the error bars sqrt(v_i) and given the same
+ * row (for the held-out score: with the test error bars mapped by the same band's kappa, nu); only the order of rounding differs.  With
+ * kappa = 1, nu = 0 (arrays or NULL) EVERY output is BITWISE the plain entry's: the mapped variance is one fma, which returns sigma^2.
+ *   gpcc_predict_noise_markov_batch: mu* = h'm_s + mean(y_band), var* = h'P_s h + JITTER -- the latent curve, as
+ *     gpcc_predict_markov_batch: the noise model enters through the training updates only.  The mixture is that entry's arithmetic in
+ *     row order.
+ *   gpcc_heldout_loglik_noise_markov_batch: a test point of band l enters the union filter with the variance
+ *     fma(kappa_l^2, sigmatest^2, nu_l) + JITTER (sigmatest^2 staged as the rounded product, the variance formed on the lane).
+ *   gpcc_posterior_offsets_noise_markov_batch: the offset block of the final state of the filter on the variances v_i.
+ *   gpcc_loo_noise_markov_batch: var_i = h'P_s h + fma(kappa_b^2, sigma_i^2, nu_b), the expression the filter's lane uses; lp_i, loo,
+ *     mix_lp and mix_loo as gpcc_loo_markov_batch, so (y_i - mu_i) / sqrt(var_i) is standardised by the FITTED error bars.
+ * info[m]: -1, -2, then -3 (some kappa or nu of the row is negative or not finite), the precedence of gpcc_loglik_noise_markov_batch;
+ * positive codes keep their meaning (1 .. N: the training filter; N + j: test point or point j).  A row with info = -3 is NaN in every
+ * per-row output and touches no other row; with a positive weight it makes the mixture NaN as any failed row does, with weight 0 it is
+ * skipped.  Refusals, weight checks, NULL-output rules, 1 <= T <= 32768, the chunking (option "markov_chunk_rows", the 128 MiB tap
+ * scratch), "markov_count" and the independence of a row's bits from M, the chunking, the row order and the launch shape: the plain
+ * entries'.  Every <p, offsets> ships (no scratch memory).  Always fp64 (an fp32 handle on its fp64 twin); a multi-device handle
+ * computes on device_ids[0].
+ * Path: gpcc_markov_noise_taps / gpcc_markov_noise_loo_taps, the plain tap kernels with the mapped variance handed to the same filter
+ * step; a lane's kappa^2 and nu sit in LDS behind the plain kernel's region, 56 L bytes a lane (predictions, held-out, offsets) or 44 L
+ * (leave-one-out) instead of 40 L / 28 L, and the light curves are staged in LDS while they fit beside that.  The prediction's combine
+ * is gpcc_markov_combine; the leave-one-out combine reads kappa, nu of its row and band.
+ * Memory: the plain entry's, plus 16 M L bytes for kappa | nu in the buffer gpcc_loglik_noise_markov_batch stages them in (shared, grown
+ * on demand); none of the N^2 workspace.  Not here: draws under a noise model (gpcc_sample_markov_batch on a fresh handle), the dense
+ * path.  Blocking. */
+int gpcc_predict_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                    const double *kappa, const double *nu, const int *Ntest, const double *ttest, const double *weights,
+                                    double *mu_out, double *var_out, double *mix_mu, double *mix_var, double *loglik, int *info);
+int gpcc_heldout_loglik_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                           const double *kappa, const double *nu, const int *Ntest, const double *ttest, const double *ytest,
+                                           const double *sigmatest, const double *weights, double *heldout, double *mix_heldout,
+                                           double *loglik, int *info);
+int gpcc_posterior_offsets_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                              const double *kappa, const double *nu, double *mu_b_out, double *Sigma_b_out, double *loglik,
+                                              int *info);
+int gpcc_loo_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const double *kappa,
+                                const double *nu, const double *weights, double *mu_out, double *var_out, double *lp_out, double *loo,
+                                double *mix_lp, double *mix_loo, double *loglik, int *info);
 
 /* Same with DEVICE pointers, enqueued behind `stream` (a hipStream_t, NULL = default stream) and
  * joined back into it: asynchronous, outputs valid once `stream` has drained. */

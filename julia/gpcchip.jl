@@ -259,6 +259,97 @@ function loglik_hess_full_markov_noise(h::Handle, delays::Matrix{Float64}, alpha
     return ll, grad, hess, info
 end
 
+# kappa, nu of the four entries below: L×M or nothing (all 1 / all 0), as loglik_markov_noise
+_noiseptr(x) = x === nothing ? C_NULL : x
+
+"predict_markov_batch of M rows that each carry their own noise model (gpcc_predict_noise_markov_batch, DESIGN 4.29): column m is what a
+fresh handle on the error bars sqrt(kappa[:, m]^2 σ^2 + nu[:, m]) returns -- the latent curve's mean and variance, the noise model
+entering through the training points; bitwise predict_markov_batch's at kappa = 1, nu = 0.  info = -3: a kappa or nu negative or not finite."
+function predict_markov_noise_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64},
+                                    ttest::Vector{Vector{Float64}}; kappa::Union{Nothing,Matrix{Float64}} = nothing,
+                                    nu::Union{Nothing,Matrix{Float64}} = nothing, weights::Union{Nothing,Vector{Float64}} = nothing)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M) && length(ttest) == h.L
+    @assert (kappa === nothing || size(kappa) == (h.L, M)) && (nu === nothing || size(nu) == (h.L, M))
+    Nt, tt = Cint.(length.(ttest)), reduce(vcat, ttest)
+    T = length(tt)
+    mu, var = Matrix{Float64}(undef, T, M), Matrix{Float64}(undef, T, M)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    mm, mv = Vector{Float64}(undef, T), Vector{Float64}(undef, T)
+    GC.@preserve weights begin
+        rc = ccall((:gpcc_predict_noise_markov_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble},
+                    Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+                   h.ptr, M, delays, alpha, rho, _noiseptr(kappa), _noiseptr(nu), Nt, tt, weights === nothing ? C_NULL : pointer(weights), mu, var,
+                   weights === nothing ? C_NULL : pointer(mm), weights === nothing ? C_NULL : pointer(mv), ll, info)
+    end
+    rc == 0 || error("gpcc_predict_noise_markov_batch: " * lasterror(h.ptr))
+    return mu, var, ll, info, (weights === nothing ? nothing : (mm, mv))
+end
+
+"heldout_loglik_markov_batch under a per-row noise model (gpcc_heldout_loglik_noise_markov_batch): a test point of band l is scored with
+the variance kappa[l, m]^2 σ*^2 + nu[l, m] (+ JITTER), the training points with theirs -> (heldout[M], ll[M], info[M], mix or nothing)."
+function heldout_loglik_markov_noise_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64},
+                                           ttest::Vector{Vector{Float64}}, ytest::Vector{Vector{Float64}}, sigmatest::Vector{Vector{Float64}};
+                                           kappa::Union{Nothing,Matrix{Float64}} = nothing, nu::Union{Nothing,Matrix{Float64}} = nothing,
+                                           weights::Union{Nothing,Vector{Float64}} = nothing)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M) && length(ttest) == length(ytest) == length(sigmatest) == h.L
+    @assert length.(ttest) == length.(ytest) == length.(sigmatest)
+    @assert (kappa === nothing || size(kappa) == (h.L, M)) && (nu === nothing || size(nu) == (h.L, M))
+    Nt, tt, yt, st = Cint.(length.(ttest)), reduce(vcat, ttest), reduce(vcat, ytest), reduce(vcat, sigmatest)
+    held, ll, info = Vector{Float64}(undef, M), Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    mix = Vector{Float64}(undef, 1)
+    GC.@preserve weights begin
+        rc = ccall((:gpcc_heldout_loglik_noise_markov_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble},
+                    Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+                   h.ptr, M, delays, alpha, rho, _noiseptr(kappa), _noiseptr(nu), Nt, tt, yt, st,
+                   weights === nothing ? C_NULL : pointer(weights), held, weights === nothing ? C_NULL : pointer(mix), ll, info)
+    end
+    rc == 0 || error("gpcc_heldout_loglik_noise_markov_batch: " * lasterror(h.ptr))
+    return held, ll, info, (weights === nothing ? nothing : mix[1])
+end
+
+"posterior_offsets_markov_batch under a per-row noise model (gpcc_posterior_offsets_noise_markov_batch): (mu_postb L×M, Sigma_postb
+L×L×M, ll[M], info[M])."
+function posterior_offsets_markov_noise_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64};
+                                              kappa::Union{Nothing,Matrix{Float64}} = nothing, nu::Union{Nothing,Matrix{Float64}} = nothing)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    @assert (kappa === nothing || size(kappa) == (h.L, M)) && (nu === nothing || size(nu) == (h.L, M))
+    mu, Sig = Matrix{Float64}(undef, h.L, M), Array{Float64,3}(undef, h.L, h.L, M)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    rc = ccall((:gpcc_posterior_offsets_noise_markov_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, _noiseptr(kappa), _noiseptr(nu), mu, Sig, ll, info)
+    rc == 0 || error("gpcc_posterior_offsets_noise_markov_batch: " * lasterror(h.ptr))
+    return mu, Sig, ll, info
+end
+
+"loo_batch(linear = true) under a per-row noise model (gpcc_loo_noise_markov_batch): var_i = h'P_s h + kappa_b^2 σ_i^2 + nu_b, so
+(y − mu) ./ sqrt.(var) is standardised by the FITTED error bars -> (mu N×M, var N×M, lp N×M, loo[M], ll[M], info[M], mix)."
+function loo_markov_noise_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64};
+                                kappa::Union{Nothing,Matrix{Float64}} = nothing, nu::Union{Nothing,Matrix{Float64}} = nothing,
+                                weights::Union{Nothing,Vector{Float64}} = nothing)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M)
+    @assert (kappa === nothing || size(kappa) == (h.L, M)) && (nu === nothing || size(nu) == (h.L, M))
+    N = Int(ccall((:gpcc_get_option, LIB), Clong, (Ptr{Cvoid}, Cstring), h.ptr, "N"))
+    mu, var, lp = Matrix{Float64}(undef, N, M), Matrix{Float64}(undef, N, M), Matrix{Float64}(undef, N, M)
+    loo, ll, info = Vector{Float64}(undef, M), Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    mlp, mloo = Vector{Float64}(undef, N), Vector{Float64}(undef, 1)
+    GC.@preserve weights begin
+        rc = ccall((:gpcc_loo_noise_markov_batch, LIB), Cint,
+                   (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                    Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+                   h.ptr, M, delays, alpha, rho, _noiseptr(kappa), _noiseptr(nu), weights === nothing ? C_NULL : pointer(weights), mu, var, lp,
+                   loo, weights === nothing ? C_NULL : pointer(mlp), weights === nothing ? C_NULL : pointer(mloo), ll, info)
+    end
+    rc == 0 || error("gpcc_loo_noise_markov_batch: " * lasterror(h.ptr))
+    return mu, var, lp, loo, ll, info, (weights === nothing ? nothing : (mlp, mloo[1]))
+end
+
 "objective, gradient, Hessian and expected (Fisher) information for M triples: (ll[M], grad (2L+1)×M, hess and fisher
 (2L+1)×(2L+1)×M, info[M]) in [α_1..α_L, ρ, τ_1..τ_L] order, symmetric blocks, NaN where info != 0; fisher = 1/2 tr(K⁻¹D_iK⁻¹D_j)."
 function loglik_hess_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64})
