@@ -113,7 +113,9 @@ SIGNATURES = {
     "gpcc_sample_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_double_p,
                                                 c_double_p, c_double_p, ctypes.c_int, ctypes.c_ulonglong, c_double_p, c_int_p, c_double_p,
                                                 c_int_p]),
-    "gpcc_posterior_offsets": (ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, ctypes.c_double, c_double_p,
+    "gpcc_sample_noise_markov_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [c_double_p] * 5 + [c_int_p] + [c_double_p] * 3
+                                       + [ctypes.c_int, ctypes.c_ulonglong, c_double_p, c_int_p, c_double_p, c_int_p]),
+    "gpcc_posterior_offsets":(ctypes.c_int, [ctypes.c_void_p, c_double_p, c_double_p, ctypes.c_double, c_double_p,
                                               c_double_p, c_int_p]),
     "gpcc_mvnormal_logpdf": (ctypes.c_int, [ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p,
                                             ctypes.c_int]),

@@ -1008,9 +1008,28 @@ class Objective:
         and info of a drawn row are bitwise predict_markov_batch's; a failed row's draws are NaN (no test block to repair, hence no
         fallback); rows without a draw: loglik NaN, info GPCC_SAMPLE_NOT_DRAWN = -14.  seed: Philox4x64-10 key (gpcc_amd.rng.point_normals
         and gpcc_amd.markov.sample mirror it).  rbf, or marginalise_b with more than 4 bands: GpccError (unsupported)."""
+        return self._sample_markov(delays, alpha, rho, ttest, S, seed, weights, sigmatest, None)
+
+    def sample_markov_noise_batch(self, delays, alpha, rho, kappa, nu, ttest, S, seed, sigmatest=None, weights=None):
+        """sample_markov_batch of M rows that each carry their own noise model (gpcc_sample_noise_markov_batch) -> the same tuple (draws,
+        draw_row, loglik[M], info[M]).  kappa, nu: (M, L), (L,) broadcast, or None (all 1 / all 0), as loglik_markov_noise_batch.  Row
+        m's draws are, to rounding, what a fresh Objective on fit.effective_std(sigma, kappa[m], nu[m]) draws with the SAME seed (the
+        normals' counters name points) and sigmatest mapped the same way: with sigmatest a test point of band l is a replicated
+        observation under the fitted model, noise variance JITTER + kappa_l^2 sigmatest^2 + nu_l; without it the latent curve, noise
+        variance JITTER (nu is not added; sigmatest of zeros asks for the latent curve plus the excess variance).  draw_row is
+        sample_markov_batch's for the same seed and weights.  At kappa = 1, nu = 0 every output is bitwise sample_markov_batch's.
+        loglik and info of a drawn row are bitwise predict_markov_noise_batch's: info -3 (a kappa or nu negative or not finite) makes
+        the row's draws NaN and touches no other row; a row without a draw is GPCC_SAMPLE_NOT_DRAWN whatever its kappa, nu.
+        gpcc_amd.markov.sample_noise mirrors one row."""
+        return self._sample_markov(delays, alpha, rho, ttest, S, seed, weights, sigmatest, (kappa, nu))
+
+    def _sample_markov(self, delays, alpha, rho, ttest, S, seed, weights, sigmatest, noise):
+        """sample_markov_batch (noise None) and sample_markov_noise_batch (noise = (kappa, nu))."""
         if len(ttest) != self.L:
             raise AssertionError("length(ttest) == L")
         M, delays, alpha, rho = self._params(delays, alpha, rho)
+        keep, nptr = self._noise_args(M, noise)
+        entry = _capi.load().gpcc_sample_markov_batch if noise is None else _capi.load().gpcc_sample_noise_markov_batch
         Nt, tt = _flatten(ttest)
         T = int(Nt.sum())
         S = int(S)
@@ -1032,9 +1051,9 @@ class Objective:
         ll = np.empty(M, dtype=np.float64)
         info = np.zeros(M, dtype=np.int32)
         try:
-            self._chk(_capi.load().gpcc_sample_markov_batch(self._h, M, _dp(delays), _dp(alpha), _dp(rho), _ip(Nt), _dp(tt),
-                                                            _dp(st) if st is not None else None, _dp(w) if w is not None else None, S,
-                                                            int(seed) & 0xFFFFFFFFFFFFFFFF, _dp(draws), _ip(rows), _dp(ll), _ip(info)))
+            self._chk(entry(self._h, M, _dp(delays), _dp(alpha), _dp(rho), *nptr, _ip(Nt), _dp(tt), _dp(st) if st is not None else None,
+                            _dp(w) if w is not None else None, S, int(seed) & 0xFFFFFFFFFFFFFFFF, _dp(draws), _ip(rows), _dp(ll),
+                            _ip(info)))
         except GpccError as e:
             _raise_reference_error(e)
         return draws, rows, ll, info

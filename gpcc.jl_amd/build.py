@@ -13,12 +13,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 DEFAULT_LIB_PATH = os.path.join(CSRC, "libgpcc_hip.so")
 LIB_PATH = os.environ.get("GPCC_HIP_LIB") or DEFAULT_LIB_PATH
-_SOURCES = ["gpcc_hip.hip", "gpcc_small_inst.hip", "gpcc_chain_inst.hip", "gpcc_markov_inst.hip", "gpcc_markov.hip.h", "gpcc_markov_pred_inst.hip", "gpcc_markov_pred.hip.h", "gpcc_markov_loo_inst.hip", "gpcc_markov_loo.hip.h", "gpcc_markov_sample_inst.hip", "gpcc_markov_sample.hip.h", "gpcc_markov_grad_inst.hip", "gpcc_markov_grad.hip.h", "gpcc_markov_hess_inst.hip", "gpcc_markov_hess.hip.h", "gpcc_markov_hess_tau_inst.hip", "gpcc_markov_hess_tau.hip.h", "gpcc_markov_fisher_inst.hip", "gpcc_markov_fisher.hip.h", "gpcc_markov_multi_inst.hip", "gpcc_markov_multi.hip.h", "gpcc_markov_resample_inst.hip", "gpcc_markov_resample.hip.h", "gpcc_markov_resample_grad_inst.hip", "gpcc_markov_resample_grad.hip.h", "gpcc_markov_noise_inst.hip", "gpcc_markov_noise.hip.h", "gpcc_markov_noise_hess_inst.hip", "gpcc_markov_noise_hess.hip.h", "gpcc_markov_noise_hess_tau_inst.hip", "gpcc_markov_noise_hess_tau.hip.h", "gpcc_markov_noise_pred_inst.hip", "gpcc_markov_noise_pred.hip.h", "gpcc_buildinfo.hip", "gpcc_kernels.hip.h", "gpcc_chain.hip.h",
+_SOURCES = ["gpcc_hip.hip", "gpcc_small_inst.hip", "gpcc_chain_inst.hip", "gpcc_markov_inst.hip", "gpcc_markov.hip.h", "gpcc_markov_pred_inst.hip", "gpcc_markov_pred.hip.h", "gpcc_markov_loo_inst.hip", "gpcc_markov_loo.hip.h", "gpcc_markov_sample_inst.hip", "gpcc_markov_sample.hip.h", "gpcc_markov_grad_inst.hip", "gpcc_markov_grad.hip.h", "gpcc_markov_hess_inst.hip", "gpcc_markov_hess.hip.h", "gpcc_markov_hess_tau_inst.hip", "gpcc_markov_hess_tau.hip.h", "gpcc_markov_fisher_inst.hip", "gpcc_markov_fisher.hip.h", "gpcc_markov_multi_inst.hip", "gpcc_markov_multi.hip.h", "gpcc_markov_resample_inst.hip", "gpcc_markov_resample.hip.h", "gpcc_markov_resample_grad_inst.hip", "gpcc_markov_resample_grad.hip.h", "gpcc_markov_noise_inst.hip", "gpcc_markov_noise.hip.h", "gpcc_markov_noise_hess_inst.hip", "gpcc_markov_noise_hess.hip.h", "gpcc_markov_noise_hess_tau_inst.hip", "gpcc_markov_noise_hess_tau.hip.h", "gpcc_markov_noise_pred_inst.hip", "gpcc_markov_noise_pred.hip.h", "gpcc_markov_noise_sample_inst.hip", "gpcc_markov_noise_sample.hip.h", "gpcc_buildinfo.hip", "gpcc_kernels.hip.h", "gpcc_chain.hip.h",
             "gpcc_chain_args.h", "gpcc_chain_queue.h", "gpcc_small.hip.h", "gpcc_fit.h", "gpcc_transforms.h", "gpcc_grad.hip.h",
             "gpcc_hess.hip.h", "gpcc_laplace.h", "gpcc_pred.hip.h", "gpcc_heldout.hip.h", "gpcc_sample.hip.h", "gpcc_rng.h", "gpcc_loo.hip.h"]
 # what each object is compiled from (an object is reused from csrc/_obj while the hash of these files and of its flags stands)
 _DEPS = {
-    "gpcc_hip.hip": ["gpcc_hip.hip", "gpcc_kernels.hip.h", "gpcc_grad.hip.h", "gpcc_hess.hip.h", "gpcc_pred.hip.h", "gpcc_heldout.hip.h", "gpcc_loo.hip.h", "gpcc_sample.hip.h", "gpcc_markov.hip.h", "gpcc_markov_pred.hip.h", "gpcc_markov_loo.hip.h", "gpcc_markov_sample.hip.h", "gpcc_markov_grad.hip.h", "gpcc_markov_hess.hip.h", "gpcc_markov_hess_tau.hip.h", "gpcc_markov_fisher.hip.h", "gpcc_markov_multi.hip.h", "gpcc_markov_resample.hip.h", "gpcc_markov_resample_grad.hip.h", "gpcc_markov_noise.hip.h", "gpcc_markov_noise_hess.hip.h", "gpcc_markov_noise_hess_tau.hip.h", "gpcc_markov_noise_pred.hip.h", "../../include/gpcc_hip.h", "gpcc_rng.h", "gpcc_small.hip.h", "gpcc_chain_args.h", "gpcc_chain_queue.h", "gpcc_fit.h", "gpcc_laplace.h", "gpcc_transforms.h"],
+    "gpcc_hip.hip": ["gpcc_hip.hip", "gpcc_kernels.hip.h", "gpcc_grad.hip.h", "gpcc_hess.hip.h", "gpcc_pred.hip.h", "gpcc_heldout.hip.h", "gpcc_loo.hip.h", "gpcc_sample.hip.h", "gpcc_markov.hip.h", "gpcc_markov_pred.hip.h", "gpcc_markov_loo.hip.h", "gpcc_markov_sample.hip.h", "gpcc_markov_grad.hip.h", "gpcc_markov_hess.hip.h", "gpcc_markov_hess_tau.hip.h", "gpcc_markov_fisher.hip.h", "gpcc_markov_multi.hip.h", "gpcc_markov_resample.hip.h", "gpcc_markov_resample_grad.hip.h", "gpcc_markov_noise.hip.h", "gpcc_markov_noise_hess.hip.h", "gpcc_markov_noise_hess_tau.hip.h", "gpcc_markov_noise_pred.hip.h", "gpcc_markov_noise_sample.hip.h", "../../include/gpcc_hip.h", "gpcc_rng.h", "gpcc_small.hip.h", "gpcc_chain_args.h", "gpcc_chain_queue.h", "gpcc_fit.h", "gpcc_laplace.h", "gpcc_transforms.h"],
     "gpcc_chain_inst.hip": ["gpcc_chain_inst.hip", "gpcc_chain.hip.h", "gpcc_chain_args.h", "gpcc_chain_queue.h", "gpcc_kernels.hip.h"],
     "gpcc_small_inst.hip": ["gpcc_small_inst.hip", "gpcc_small.hip.h", "gpcc_kernels.hip.h", "gpcc_transforms.h"],
     "gpcc_markov_inst.hip": ["gpcc_markov_inst.hip", "gpcc_markov.hip.h"],
@@ -42,6 +42,9 @@ _DEPS = {
                                             "gpcc_markov.hip.h"],
     "gpcc_markov_noise_pred_inst.hip": ["gpcc_markov_noise_pred_inst.hip", "gpcc_markov_noise_pred.hip.h", "gpcc_markov_noise.hip.h", "gpcc_markov_loo.hip.h",
                                         "gpcc_markov_pred.hip.h", "gpcc_markov_grad.hip.h", "gpcc_markov.hip.h"],
+    "gpcc_markov_noise_sample_inst.hip": ["gpcc_markov_noise_sample_inst.hip", "gpcc_markov_noise_sample.hip.h", "gpcc_markov_sample.hip.h", "gpcc_rng.h",
+                                          "gpcc_markov_noise_pred.hip.h", "gpcc_markov_noise.hip.h", "gpcc_markov_loo.hip.h", "gpcc_markov_pred.hip.h",
+                                          "gpcc_markov_grad.hip.h", "gpcc_markov.hip.h"],
     "gpcc_buildinfo.hip": ["gpcc_buildinfo.hip"],
 }
 _HEADER = os.path.join(os.path.dirname(_HERE), "include", "gpcc_hip.h")
@@ -95,8 +98,8 @@ def build(force=False, verbose=False):
     libdir = os.path.join(rocm, "lib")
     if not os.path.isdir(libdir):
         libdir = "/opt/rocm/lib"
-    # Forty-four objects compiled side by side: the host + tile kernels, the persistent few-evaluation kernel, the linear-time filter, its predictions, its leave-one-out scores, its draws, its gradient,
-    # its Hessian block, its Hessian's rows of tau, its Fisher information, its many-realisations form, its resampled-data form, that form's gradient, its noise-model form, that form's Hessian and its Hessian's rows of tau once per state dimension, the noise-model predictions and leave-one-out scores, the small-N families once
+    # Forty-five objects compiled side by side: the host + tile kernels, the persistent few-evaluation kernel, the linear-time filter, its predictions, its leave-one-out scores, its draws, its gradient,
+    # its Hessian block, its Hessian's rows of tau, its Fisher information, its many-realisations form, its resampled-data form, that form's gradient, its noise-model form, that form's Hessian and its Hessian's rows of tau once per state dimension, the noise-model predictions and leave-one-out scores, the noise-model draws, the small-N families once
     # per (family, kernel id), the build record (as ONE translation unit the library took 7.5 minutes to build; the objects are
     # independent, no device linking).  Objects are kept in csrc/_obj and reused while their own sources and flags are unchanged.
     from concurrent.futures import ThreadPoolExecutor
@@ -113,6 +116,7 @@ def build(force=False, verbose=False):
             (os.path.join(objdir, "gpcc_markov_sample.o"), [os.path.join(CSRC, "gpcc_markov_sample_inst.hip")], "gpcc_markov_sample_inst.hip"),
             (os.path.join(objdir, "gpcc_markov_grad.o"), [os.path.join(CSRC, "gpcc_markov_grad_inst.hip")], "gpcc_markov_grad_inst.hip"),
             (os.path.join(objdir, "gpcc_markov_noise_pred.o"), [os.path.join(CSRC, "gpcc_markov_noise_pred_inst.hip")], "gpcc_markov_noise_pred_inst.hip"),
+            (os.path.join(objdir, "gpcc_markov_noise_sample.o"), [os.path.join(CSRC, "gpcc_markov_noise_sample_inst.hip")], "gpcc_markov_noise_sample_inst.hip"),
             (os.path.join(objdir, "gpcc_buildinfo.o"), ['-DGPCC_BUILD_INFO_STR="%s"' % info, os.path.join(CSRC, "gpcc_buildinfo.hip")], "gpcc_buildinfo.hip")]
     for order in (1, 2, 3):
         jobs.append((os.path.join(objdir, "gpcc_markov_hess_%d.o" % order),

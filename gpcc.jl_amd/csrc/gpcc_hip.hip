@@ -23,6 +23,7 @@
 #include "gpcc_markov_noise_hess.hip.h"
 #include "gpcc_markov_noise_hess_tau.hip.h"
 #include "gpcc_markov_noise_pred.hip.h"
+#include "gpcc_markov_noise_sample.hip.h"
 #include "gpcc_chain_args.h"
 #include "gpcc_fit.h"
 #include "gpcc_laplace.h"
@@ -2187,7 +2188,7 @@ static void markov_fill_args(gpcc_handle_t h, int M, const double *dd, const dou
 }
 
 // the kernels with dynamic LDS, for gpcc_handle::mk_lds_raised
-enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI, MK_RESAMPLE, MK_RESAMPLE_GRAD, MK_NOISE, MK_NOISE_GRAD, MK_NOISE_HESS, MK_NOISE_HESS_TAU, MK_NOISE_TAPS_TAP, MK_NOISE_TAPS_UPDATE, MK_NOISE_LOO_TAPS };
+enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, MK_GRAD, MK_HESS, MK_HESS_TAU, MK_FISHER, MK_MULTI, MK_RESAMPLE, MK_RESAMPLE_GRAD, MK_NOISE, MK_NOISE_GRAD, MK_NOISE_HESS, MK_NOISE_HESS_TAU, MK_NOISE_TAPS_TAP, MK_NOISE_TAPS_UPDATE, MK_NOISE_LOO_TAPS, MK_NOISE_DRAW };
 
 // The launch of every kernel of the filter, `name` in messages: one lane per row, `rows` rows along x and ny lanes per row along y.
 // The shape: one wave per workgroup while the chip has a CU for every wave, two or four waves sharing one staged copy beyond; the light
@@ -3835,23 +3836,41 @@ extern "C" int gpcc_sample_batch(gpcc_handle_t h, int M, const double *delays, c
 // over the filter of 4.15 / 4.16.  The host picks the rows of mixture draws and compacts the drawn rows exactly as gpcc_sample_batch
 // does; every chunk of drawn rows then runs gpcc_markov_taps unchanged (its loglik and info are gpcc_predict_markov_batch's bits), the
 // combine that also leaves the weights, and, per chunk of draws, one lane per (row, draw) and the finish.  Nothing of the N^2 workspace.
+// Plain (gpcc_sample_markov_batch) or under a per-row noise model (gpcc_sample_noise_markov_batch: DESIGN.md 4.30, kernel
+// gpcc_markov_noise_sample.hip.h): one body, a template on NOISE as the four entries of 4.29.  The noise entry compacts kappa, nu of the
+// drawn rows beside tau, alpha, rho, stages sigma*^2 where the plain one stages sqrt(JITTER + sigma*^2), says whether sigmatest is
+// NULL, and launches the noise taps and the noise draw kernel on their Args; it is otherwise the plain entry statement for statement.
 // ------------------------------------------------------------------------------------------
-extern "C" int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
-                                        const int *Ntest, const double *ttest, const double *sigmatest, const double *weights, int S,
-                                        unsigned long long seed, double *draws, int *draw_row, double *loglik, int *info)
+// the lanes g.lane0 .. of gpcc_markov_draw ...
+static int markov_draw_launch(gpcc_handle_t h, GpccMarkovDrawArgs &g)
+{
+    return markov_launch(h, "gpcc_markov_draw", MK_DRAW, g.lanes, 1, g.stage,
+                         [&](int thr, bool st) { return gpcc_mks_lds_bytes(g.N, g.T, g.L, thr, st); },
+                         [&](const GpccMkLaunch &sh) { return gpcc_mks_launch_draw(sh, g); });
+}
+
+// ... of gpcc_markov_noise_draw
+static int markov_draw_launch(gpcc_handle_t h, GpccMarkovNoiseDrawArgs &g)
+{
+    return markov_launch(h, "gpcc_markov_noise_draw", MK_NOISE_DRAW, g.lanes, 1, g.stage,
+                         [&](int thr, bool st) { return gpcc_mksn_lds_bytes(g.N, g.T, g.L, thr, st); },
+                         [&](const GpccMkLaunch &sh) { return gpcc_mksn_launch_draw(sh, g); });
+}
+
+// reissue(o): the same call on handle o (route_fp64's call)
+template <bool NOISE, typename Reissue>
+static int markov_sample(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho, const MarkovNoise &nz,
+                         const int *Ntest, const double *ttest, const double *sigmatest, const double *weights, int S,
+                         unsigned long long seed, double *draws, int *draw_row, double *loglik, int *info, Reissue &&reissue)
 {
     if (!h) return fail(h, GPCC_ERR_ARGUMENT, "NULL handle");
     if (M < 0) return fail(h, GPCC_ERR_ARGUMENT, "M=%d < 0", M);
     if (S < 1) return fail(h, GPCC_ERR_ARGUMENT, "S=%d < 1", S);
     if (!delays || !alpha || !rho || !Ntest || !ttest || !draws || !loglik || !info) return fail(h, GPCC_ERR_ARGUMENT, "NULL pointer");
     if (weights && !draw_row) return fail(h, GPCC_ERR_ARGUMENT, "weights given: draw_row is required");
-    int rc = markov_refusals(h, "gpcc_sample_markov_batch", "gpcc_sample_batch");
+    int rc = markov_refusals(h, nz.who, "gpcc_sample_batch");
     if (rc) return rc;
-    if (route_fp64(h, "linear-time draws", rc, [&](gpcc_handle_t o) {
-            return gpcc_sample_markov_batch(o, M, delays, alpha, rho, Ntest, ttest, sigmatest, weights, S, seed, draws, draw_row, loglik,
-                                            info);
-        }))
-        return rc;
+    if (route_fp64(h, "linear-time draws", rc, reissue)) return rc;
     long T = 0;
     rc = count_test_points(h, Ntest, T);
     if (rc) return rc;
@@ -3905,6 +3924,13 @@ extern "C" int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *de
         }
         cpar[(size_t)2 * Mc * L + k] = rho[m];
     }
+    std::vector<double> cnz(NOISE ? (size_t)2 * Mc * L : 0);   // the drawn rows' kappa | nu (NULL: all 1 / all 0)
+    if constexpr (NOISE)
+        for (int k = 0; k < Mc; ++k)
+            for (long l = 0; l < L; ++l) {
+                cnz[(size_t)k * L + l] = nz.kappa ? nz.kappa[(size_t)rows[k] * L + l] : 1.0;
+                cnz[(size_t)Mc * L + (size_t)k * L + l] = nz.nu ? nz.nu[(size_t)rows[k] * L + l] : 0.0;
+            }
     GPCC_ON_DEVICE(h, h->device);
     const MarkovDims d = markov_dims(h);
     const long ns = d.p + d.noff, nrec = ns + ns * (ns + 1) / 2;
@@ -3919,12 +3945,12 @@ extern "C" int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *de
     std::vector<int> order, band;
     int toff[GPCC_MARKOV_MAXL + 1];
     markov_sort_tests(h, Ntest, ttest, T, order, band, toff);
-    std::vector<double> tt(2 * T);   // the sorted times, then sqrt(JITTER + sigma*^2)
+    std::vector<double> tt(2 * T);   // the sorted times, then sqrt(JITTER + sigma*^2) (a noise entry: sigma*^2, the rounded product)
     std::vector<int> ti(2 * T);
     for (long j = 0; j < T; ++j) {
         const double sg = sigmatest ? sigmatest[order[j]] : 0.0;
         tt[j] = ttest[order[j]];
-        tt[T + j] = sqrt(GPCC_MKP_JITTER + sg * sg);
+        tt[T + j] = NOISE ? sg * sg : sqrt(GPCC_MKP_JITTER + sg * sg);
         ti[j] = band[j];
         ti[T + j] = order[j];
     }
@@ -3940,7 +3966,7 @@ extern "C" int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *de
         if (!g) g = grow_buf(h, &h->d_mksacc, &h->mksacc_cap, T * lstride);
         if (!g) g = grow_buf(h, &h->d_mksi, &h->mksi_cap, (long)ints.size());
         if (!g) g = grow_buf(h, &h->d_sdraw, &h->sdraw_cap, D * T);
-        return g;
+        return g ? g : markov_noise_grow<NOISE>(h, Mc);
     });
     if (rc) return rc;
     for (long i = 0; i < N; ++i) ints[i] = h->mk_perm[i];
@@ -3948,14 +3974,17 @@ extern "C" int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *de
     HIPCHK(h, hipMemcpyAsync(h->d_mkt, tt.data(), sizeof(double) * 2 * T, hipMemcpyHostToDevice, ms));
     HIPCHK(h, hipMemcpyAsync(h->d_mkti, ti.data(), sizeof(int) * 2 * T, hipMemcpyHostToDevice, ms));
     HIPCHK(h, hipMemcpyAsync(h->d_mksi, ints.data(), sizeof(int) * ints.size(), hipMemcpyHostToDevice, ms));
-    GpccMarkovPredArgs a;
+    std::conditional_t<NOISE, GpccMarkovNoisePredArgs, GpccMarkovPredArgs> a;
     markov_pred_common(h, Mc, dd, da, dr, toff, T, a);
+    rc = markov_noise_rows<NOISE>(h, Mc, {nz.who, cnz.data(), cnz.data() + (size_t)Mc * L}, a);
+    if (rc) return rc;
     a.tap = h->d_mktap;
     GpccMarkovCombineWArgs cwa;
     GpccMarkovCombineArgs &c = cwa.c;
     cwa.w = h->d_mksw;
     markov_combine_args(h, a, c);
-    GpccMarkovDrawArgs g;
+    std::conditional_t<NOISE, GpccMarkovNoiseDrawArgs, GpccMarkovDrawArgs> g;
+    if constexpr (NOISE) { g.kappa = a.kappa; g.nu = a.nu; g.latent = sigmatest ? 0 : 1; }
     g.pts = h->d_mk; g.perm = h->d_mksi; g.tpts = h->d_mkt; g.tperm = h->d_mkti + T;
     g.delays = dd; g.alpha = da; g.rho = dr; g.w = h->d_mksw;
     g.lane_row = h->d_mksi + N; g.lane_s = g.lane_row + D; g.row_word = g.lane_row + 3 * D;
@@ -3981,9 +4010,7 @@ extern "C" int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *de
             const long left = doff[row0 + nrows] - lane0;
             g.lane0 = f.lane0 = (int)lane0;
             g.lanes = f.lanes = (int)(left < dchunk ? left : dchunk);
-            rc = markov_launch(h, "gpcc_markov_draw", MK_DRAW, g.lanes, 1, g.stage,
-                               [&](int thr, bool st) { return gpcc_mks_lds_bytes(g.N, g.T, g.L, thr, st); },
-                               [&](const GpccMkLaunch &sh) { return gpcc_mks_launch_draw(sh, g); });
+            rc = markov_draw_launch(h, g);
             if (rc) return rc;
             e = gpcc_mks_launch_finish(f, ms);
             if (e != hipSuccess) return fail(h, GPCC_ERR_HIP, "linear-time draws: %s", hipGetErrorString(e));
@@ -4000,6 +4027,28 @@ extern "C" int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *de
         info[rows[k]] = cinfo[k];
     }
     return 0;
+}
+
+extern "C" int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                        const int *Ntest, const double *ttest, const double *sigmatest, const double *weights, int S,
+                                        unsigned long long seed, double *draws, int *draw_row, double *loglik, int *info)
+{
+    return markov_sample<false>(h, M, delays, alpha, rho, {"gpcc_sample_markov_batch", nullptr, nullptr}, Ntest, ttest, sigmatest, weights, S,
+                                seed, draws, draw_row, loglik, info, [&](gpcc_handle_t o) {
+        return gpcc_sample_markov_batch(o, M, delays, alpha, rho, Ntest, ttest, sigmatest, weights, S, seed, draws, draw_row, loglik, info);
+    });
+}
+
+extern "C" int gpcc_sample_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                              const double *kappa, const double *nu, const int *Ntest, const double *ttest,
+                                              const double *sigmatest, const double *weights, int S, unsigned long long seed,
+                                              double *draws, int *draw_row, double *loglik, int *info)
+{
+    return markov_sample<true>(h, M, delays, alpha, rho, {"gpcc_sample_noise_markov_batch", kappa, nu}, Ntest, ttest, sigmatest, weights, S,
+                               seed, draws, draw_row, loglik, info, [&](gpcc_handle_t o) {
+        return gpcc_sample_noise_markov_batch(o, M, delays, alpha, rho, kappa, nu, Ntest, ttest, sigmatest, weights, S, seed, draws, draw_row,
+                                              loglik, info);
+    });
 }
 
 // ------------------------------------------------------------------------------------------

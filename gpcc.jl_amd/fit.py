@@ -765,8 +765,10 @@ class Predictor:
     kappa=, nu= ((L,) each, or None: 1 / 0; solver "markov" only): a fitted noise model, every observation of band l having the variance
     kappa_l^2 sigma^2 + nu_l (Objective.predict_markov_noise_batch / heldout_loglik_markov_noise_batch / loo_markov_noise_batch): the
     per-band form, the three-argument form (sigmatest mapped by the same band's kappa, nu) and loo(), whose z is then standardised by
-    the fitted variance, are those of a predictor on a fresh Objective with the error bars effective_std(stdarray, kappa, nu).  The
-    joint form and sample() raise NotImplementedError under a noise model: that fresh Objective is their route."""
+    the fitted variance, are those of a predictor on a fresh Objective with the error bars effective_std(stdarray, kappa, nu), and so,
+    with the same seed, are the draws of sample(..., solver="markov") (Objective.sample_markov_noise_batch).  The joint form, and
+    sample() with solver None or "dense" (the dense path has no noise model), raise NotImplementedError under a noise model: that fresh
+    Objective is their route."""
 
     def __init__(self, objective, delays, alpha, rho, solver="dense", kappa=None, nu=None):
         if solver not in ("dense", "markov"):
@@ -850,12 +852,20 @@ class Predictor:
         JITTER), a replicated observation with it (Objective.sample_batch, one row).  solver None (default) or "dense": those dense
         draws, whatever the predictor's own solver.  solver "markov" (OU, matern32, matern52): draws of the same distribution in linear
         time (Objective.sample_markov_batch; other normals, so other draws); a failed filter or combine raises
-        PosDefException."""
+        PosDefException.  Under kappa=, nu=: solver "markov" draws under the fitted noise model
+        (Objective.sample_markov_noise_batch, one row: with sigmatest replicated observations of variance kappa_l^2 sigmatest^2 + nu_l
+        around the curve, without it the latent curve); None or "dense" raise NotImplementedError."""
         _check_sample_solver(solver)
-        if self.noise is not None:
-            raise NotImplementedError("sample() " + _NOISE_ROUTE)
+        if self.noise is not None and solver != "markov":
+            raise NotImplementedError("sample() with solver=%r " % (solver,) + _NOISE_ROUTE + ", or call sample(..., solver='markov')")
         bands = _sample_bands(self.obj.L, ttest)
         st = None if sigmatest is None else _sample_bands(self.obj.L, sigmatest)
+        if self.noise is not None:
+            draws, _, _, info = self.obj.sample_markov_noise_batch(self.delays[None, :], self.alpha[None, :], [self.rho], *self.noise, bands,
+                                                                   S, seed, sigmatest=st)
+            if info[0] > 0:
+                raise PosDefException(int(info[0]))
+            return _split_bands(draws, bands)
         if solver == "markov":
             draws, _, _, info = self.obj.sample_markov_batch(self.delays[None, :], self.alpha[None, :], [self.rho], bands, S, seed,
                                                              sigmatest=st)
@@ -883,8 +893,8 @@ class DelayAveragedPredictor:
     solver "markov" (OU, matern32, matern52): __call__ and loglik run in linear time (Objective.predict_markov_batch /
     heldout_loglik_markov_batch); sample() stays dense unless it is called with solver="markov".
     kappa=, nu= ((L,) or (G, L) each, or None: 1 / 0; solver "markov" only): a noise model per row, e.g. a NoiseGridFit's (noise_predictor
-    builds that predictor): __call__, loglik and loo() mix the rows of the noise entries in one call each, as Predictor's kappa=, nu=;
-    sample() raises NotImplementedError."""
+    builds that predictor): __call__, loglik, loo() and sample(..., solver="markov") mix the rows of the noise entries in one call each,
+    as Predictor's kappa=, nu=; sample() with solver None or "dense" raises NotImplementedError."""
 
     def __init__(self, objective, delays, alpha, rho, weights, solver="dense", kappa=None, nu=None):
         if solver not in ("dense", "markov"):
@@ -954,12 +964,18 @@ class DelayAveragedPredictor:
         row[s], picked with probability weights[row] / sum(weights), so (self.delays[row[s]], draws[.][s]) are joint (tau, f*)
         samples.  ttest and sigmatest take Predictor's forms; without sigmatest the latent curves, with it replicated observations.
         solver None (default) or "dense": Objective.sample_batch whatever the predictor's own solver; "markov": the same mixture drawn in
-        linear time (Objective.sample_markov_batch; the same rows for the same seed and weights, other normals)."""
+        linear time (Objective.sample_markov_batch; the same rows for the same seed and weights, other normals).  Under kappa=, nu=:
+        solver "markov" draws every row under its own noise model in one call (Objective.sample_markov_noise_batch; the same rows again);
+        None or "dense" raise NotImplementedError."""
         _check_sample_solver(solver)
-        if self.noise is not None:
-            raise NotImplementedError("sample() " + _NOISE_ROUTE)
+        if self.noise is not None and solver != "markov":
+            raise NotImplementedError("sample() with solver=%r " % (solver,) + _NOISE_ROUTE + ", or call sample(..., solver='markov')")
         bands = _sample_bands(self.obj.L, ttest)
         st = None if sigmatest is None else _sample_bands(self.obj.L, sigmatest)
+        if self.noise is not None:
+            draws, rows, _, _ = self.obj.sample_markov_noise_batch(self.delays, self.alpha, self.rho, *self.noise, bands, S, seed,
+                                                                   sigmatest=st, weights=self.weights)
+            return _split_bands(draws, bands), rows
         if solver == "markov":
             draws, rows, _, _ = self.obj.sample_markov_batch(self.delays, self.alpha, self.rho, bands, S, seed, weights=self.weights,
                                                              sigmatest=st)
@@ -972,7 +988,9 @@ def noise_predictor(objective, candidatedelays, noisefit, weights=None):
     """The DelayAveragedPredictor of a NoiseGridFit (gpcc_grid_noise): the rows (candidatedelays[g], noisefit.alpha[g], noisefit.rho[g])
     each under its own fitted noise model (noisefit.kappa[g], noisefit.nu[g]), in linear time.  weights: (G,), default
     getprobabilities(noisefit.loglikel).  Its predictions, held-out density and leave-one-out scores are one device call each, where a
-    fresh Objective on effective_std per candidate delay was G of them."""
+    fresh Objective on effective_std per candidate delay was G of them; so are its joint (tau, f*) draws, by sample(ttest, S, seed,
+    solver="markov") -> (per-band draws, row): the posterior light curves of the noise fit, or with sigmatest replicated observations
+    for a posterior-predictive check (sample() with the default solver raises: the dense path has no noise model)."""
     delays = np.atleast_2d(np.asarray(candidatedelays, dtype=np.float64))
     if weights is None:
         weights = getprobabilities(np.asarray(noisefit.loglikel, dtype=np.float64))

@@ -1757,8 +1757,15 @@ def _sim_factor(kernel, d, rho, _by_difference=False):
     return G / sc[:, None]
 
 
-def _draw_setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest, marginalise_b):
+def _draw_setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest, marginalise_b, noise=None):
+    """noise: None, or (kappa, nu, slip) of sample_noise (predict()'s _noise) -> `train` on the mapped variances, rv, the variance the
+    synthetic residual's noise of training point (band, position) is drawn with (the filter's), and tv, the test noise's variance
+    without JITTER: sigma*^2, mapped under a noise model, where sigmatest is given, zero (the latent curve: nu is not added) where it is
+    None.  slip (tests only): _noise_apply's, and "draw_obs_noise_raw" (rv keeps sigma_i^2), "draw_test_noise_raw" (tv keeps sigma*^2)."""
     name, L, delays, alpha, rho, code, vb, means, p, n, train = _setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b)
+    raw = train
+    train, code, k2, ex = _noise_apply(L, train, code, noise)
+    rv = {(e[1], e[2]): e[4] for e in (raw if noise is not None and noise[2] == "draw_obs_noise_raw" else train)}
     tests, band_of = _test_list(L, ttest, delays)
     # sorted position i of band l -> the point's index in gpcc_create's flattened order
     orig, off = {}, 0
@@ -1768,21 +1775,23 @@ def _draw_setup(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sig
             orig[(l, i)] = off + int(q)
         off += len(perm)
     if sigmatest is None:
-        st = np.zeros(len(tests))
+        tv = np.zeros(len(tests))
     else:
         st = np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in sigmatest]) if len(tests) else np.zeros(0)
-    return name, L, delays, alpha, rho, code, vb, means, p, n, train, tests, band_of, orig, st
+        tv = st * st
+        if k2 is not None and noise[2] != "draw_test_noise_raw":
+            tv = k2[band_of] * tv + ex[band_of]
+    return name, L, delays, alpha, rho, code, vb, means, p, n, train, tests, band_of, orig, tv, rv
 
 
-def _prior_draw(name, alpha, rho, vb, p, n, train, tests, orig, st, xi, slip=None):
-    """One prior draw from the normals xi (N + T + 1, 4) -> (r~ per entry of `train`, g~[T], noise[T])."""
+def _prior_draw(name, alpha, rho, vb, p, n, train, tests, orig, tv, rv, xi, slip=None):
+    """One prior draw from the normals xi (N + T + 1, 4) -> (r~ per entry of `train`, g~[T], noise[T]); tv, rv: _draw_setup's."""
     N, T = len(train), len(tests)
     ev = [(s, 0, b, i, True) for (s, b, i, _, _) in train] + [(s, 1, b, i, False) for (s, b, i, _, _) in tests]
     ev.sort(key=lambda e: e[:4])
     bt = np.zeros(len(alpha))
     if n > p and slip != "no_offset_draw":
         bt = np.sqrt(vb) * xi[N + T, :len(alpha)]
-    s2 = {(b, i): v for (_, b, i, _, v) in train}
     rt, gt, noise = {}, np.empty(T), np.empty(T)
     x, sprev = None, None
     for pos, (s, _, b, i, is_train) in enumerate(ev):
@@ -1795,10 +1804,10 @@ def _prior_draw(name, alpha, rho, vb, p, n, train, tests, orig, st, xi, slip=Non
         sprev = s
         f = alpha[b] * x[0] + bt[b]
         if is_train:
-            rt[(b, i)] = f + (0.0 if slip == "no_obs_noise" else math.sqrt(s2[(b, i)]) * z[3])
+            rt[(b, i)] = f + (0.0 if slip == "no_obs_noise" else math.sqrt(rv[(b, i)]) * z[3])
         else:
             gt[i] = f
-            noise[i] = math.sqrt(JITTER + st[i] * st[i]) * z[3]
+            noise[i] = math.sqrt(JITTER + tv[i]) * z[3]
     return rt, gt, noise
 
 
@@ -1813,17 +1822,18 @@ def _normals_of(N, T, seed, s, m, normals):
 
 
 def prior_draw(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest=None, marginalise_b=True, seed=0, s=0, m=0,
-               normals=None, _slip=None):
+               normals=None, _slip=None, _noise=None):
     """Step 1 of a linear-time draw -> (r~[N] in gpcc_create's flattened order, g~[T], noise[T] in the caller's flattened order): a draw
     of the prior at the training and test points, the synthetic residuals with their observation noise, and the JITTER / sigma* noise of
     the test points.  The normals are draw s of row m of `seed` (rng.point_normals; m = rng.MIXROW for a mixture draw) or `normals`,
-    an array (N + T + 1, 4).  _slip (tests only): "no_obs_noise", "no_offset_draw", "merged_index", "q_by_difference" (_sim_factor's)."""
-    name, L, delays, alpha, rho, code, vb, means, p, n, train, tests, band_of, orig, st = _draw_setup(
-        kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest, marginalise_b)
+    an array (N + T + 1, 4).  _slip (tests only): "no_obs_noise", "no_offset_draw", "merged_index", "q_by_difference" (_sim_factor's).
+    _noise: predict()'s (kappa, nu, slip): the noises of r~ and of the test points under that model (_draw_setup)."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train, tests, band_of, orig, tv, rv = _draw_setup(
+        kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest, marginalise_b, _noise)
     if code:
-        raise ValueError("prior_draw: alpha and rho must be positive")
+        raise ValueError("prior_draw: alpha and rho must be positive, kappa and nu not negative")
     xi = _normals_of(len(train), len(tests), seed, s, m, normals)
-    rt, gt, noise = _prior_draw(name, alpha, rho, vb, p, n, train, tests, orig, st, xi, _slip)
+    rt, gt, noise = _prior_draw(name, alpha, rho, vb, p, n, train, tests, orig, tv, rv, xi, _slip)
     out = np.empty(len(train))
     for key, v in rt.items():
         out[orig[key]] = v
@@ -1831,14 +1841,14 @@ def prior_draw(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigm
 
 
 def sample(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest=None, marginalise_b=True, seed=0, s=0, m=0,
-           normals=None, _slip=None):
+           normals=None, _slip=None, _noise=None):
     """(draw[T], loglik, info) of one (tau, alpha, rho): one joint posterior draw at the test times, distributed as
     N(mu_pred, Sigma_pred + JITTER I + diag sigmatest^2) -- gpcc_sample_batch's distribution -- by Matheron's rule: predict()'s mean
     plus a prior draw minus the smoother of the prior draw's synthetic data, plus the test noise.  loglik and info are predict()'s; a
     failed row's draw is NaN.  Normals as prior_draw.  _slip (tests only): predict()'s "no_flip", "tie_both", "no_prior" (in both the
-    mean and the correction), prior_draw's, and "plus" (the correction added)."""
-    name, L, delays, alpha, rho, code, vb, means, p, n, train, tests, band_of, orig, st = _draw_setup(
-        kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest, marginalise_b)
+    mean and the correction), prior_draw's, and "plus" (the correction added).  _noise: predict()'s (kappa, nu, slip) -- sample_noise."""
+    name, L, delays, alpha, rho, code, vb, means, p, n, train, tests, band_of, orig, tv, rv = _draw_setup(
+        kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest, marginalise_b, _noise)
     T = len(tests)
     if code:
         return np.full(T, math.nan), math.nan, code
@@ -1847,7 +1857,7 @@ def sample(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmates
     if info:
         return np.full(T, math.nan), ll, info
     xi = _normals_of(len(train), T, seed, s, m, normals)
-    rt, gt, noise = _prior_draw(name, alpha, rho, vb, p, n, train, tests, orig, st, xi, _slip)
+    rt, gt, noise = _prior_draw(name, alpha, rho, vb, p, n, train, tests, orig, tv, rv, xi, _slip)
     synth = [(sv, b, i, rt[(b, i)], v) for (sv, b, i, _, v) in train]
     c, _, _, cinfo = _smooth(name, synth, tests, band_of, alpha, rho, p, n, vb, pslip)
     if cinfo:
@@ -2074,6 +2084,28 @@ def loo_noise(kernel, tarray, yarray, stdarray, delays, alpha, rho, kappa=None, 
     return loo(kernel, tarray, yarray, stdarray, delays, alpha, rho, marginalise_b, _noise=(kappa, nu, _noise_slip(_slip)))
 
 
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Joint posterior draws under a noise model (csrc/gpcc_markov_noise_sample.hip.h), the same algorithm in numpy:
+# prior_draw() and sample() above on _noise_train's mapped variances.  The synthetic residual's noise and the filter take the same
+# v_i = kappa_l^2 sigma_i^2 + nu_l; with sigmatest a test point of band l has the noise variance JITTER + kappa_l^2 sigma*^2 + nu_l (a
+# replicated observation under the fitted model), without it JITTER (the latent curve: nu is not added).  The normals are sample()'s.
+# At kappa = 1, nu = 0 sample_noise returns sample()'s numbers exactly.
+# ----------------------------------------------------------------------------------------------------------------------------------
+NOISE_SAMPLE_SLIPS = ("draw_obs_noise_raw", "draw_test_noise_raw", "kappa_linear", "noise_all_bands")
+
+
+def sample_noise(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, kappa=None, nu=None, sigmatest=None, marginalise_b=True,
+                 seed=0, s=0, m=0, normals=None, _slip=None):
+    """sample() of one (tau, alpha, rho, kappa, nu): a row of Objective.sample_markov_noise_batch -> (draw[T], loglik, info), info -3
+    after -1 and -2.  _slip (tests only): "draw_obs_noise_raw" (the synthetic residual keeps sigma_i while the filter uses v_i),
+    "draw_test_noise_raw" (the test noise keeps sigma*), "kappa_linear" (the variance kappa sigma^2 + nu), "noise_all_bands" (every band
+    under band 1's kappa, nu)."""
+    if _slip is not None and _slip not in NOISE_SAMPLE_SLIPS:
+        raise ValueError("unknown slip %r" % (_slip,))
+    return sample(kernel, tarray, yarray, stdarray, delays, alpha, rho, ttest, sigmatest, marginalise_b, seed, s, m, normals,
+                  _noise=(kappa, nu, _slip))
+
+
 class MarkovObjective:
     """The CPU mirror with the methods gpcc_grid's `engine="python"` fit and the Markov predictors call (loglik_batch and
     loglik_markov_batch are the same filter here): gpcc_grid(..., objective=MarkovObjective(...), solver="markov") fits without a GPU."""
@@ -2212,11 +2244,12 @@ class MarkovObjective:
         """Objective.loo_markov_noise_batch's result: loo_markov_batch's LooResult."""
         return self.loo_markov_batch(delays, alpha, rho, weights, outputs, _noise=(kappa, nu))
 
-    def sample_markov_batch(self, delays, alpha, rho, ttest, S, seed, weights=None, sigmatest=None):
+    def sample_markov_batch(self, delays, alpha, rho, ttest, S, seed, weights=None, sigmatest=None, _noise=None):
         """Objective.sample_markov_batch's result: (draws, draw_row, loglik[M], info[M])."""
         from . import rng
         delays, alpha, rho = self._rows(delays, alpha, rho)
         M, S = len(rho), int(S)
+        nz = self._noise_of(M, _noise)
         if S < 1:
             raise ValueError("S=%d < 1" % S)
         T = sum(len(np.reshape(a, -1)) for a in ttest)
@@ -2233,8 +2266,12 @@ class MarkovObjective:
         ll, info = np.full(M, math.nan), np.full(M, -14, dtype=np.int32)          # GPCC_SAMPLE_NOT_DRAWN
         for o, (row, s, word) in enumerate(which):
             draws[o], ll[row], info[row] = sample(self.kernel, *self.data, delays[row], alpha[row], rho[row], ttest, sigmatest,
-                                                  self.marginalise_b, seed=seed, s=s, m=word)
+                                                  self.marginalise_b, seed=seed, s=s, m=word, _noise=nz[row])
         return draws, draw_row, ll, info
+
+    def sample_markov_noise_batch(self, delays, alpha, rho, kappa, nu, ttest, S, seed, sigmatest=None, weights=None):
+        """Objective.sample_markov_noise_batch's result: sample_markov_batch's tuple, every row under its own (kappa, nu)."""
+        return self.sample_markov_batch(delays, alpha, rho, ttest, S, seed, weights, sigmatest, _noise=(kappa, nu))
 
     def close(self):
         pass

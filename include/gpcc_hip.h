@@ -511,7 +511,7 @@ int gpcc_loglik_grad_markov_resampled_batch(gpcc_handle_t h, int M, const double
  * Memory: gpcc_loglik_markov_batch's, plus 16 M L bytes for kappa and nu and, for the gradient, 8 M bytes per slot and 8 M (4L + 1)
  * bytes, grown on demand; none of the N^2 workspace.  "markov_count" advances by M.  Always fp64 (an fp32 handle on its fp64 twin);
  * a multi-device handle computes on device_ids[0].  Predictions, held-out scores, the offsets' posterior and leave-one-out scores under
- * a noise model: gpcc_predict_noise_markov_batch and its siblings below; draws: a fresh handle on those error bars.  Blocking. */
+ * a noise model: gpcc_predict_noise_markov_batch and its siblings below; draws: gpcc_sample_noise_markov_batch.  Blocking. */
 int gpcc_loglik_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                    const double *kappa, const double *nu, double *loglik, int *info);
 int gpcc_loglik_grad_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
@@ -592,8 +592,8 @@ int gpcc_loglik_hess_full_noise_markov_batch(gpcc_handle_t h, int M, const doubl
  * (leave-one-out) instead of 40 L / 28 L, and the light curves are staged in LDS while they fit beside that.  The prediction's combine
  * is gpcc_markov_combine; the leave-one-out combine reads kappa, nu of its row and band.
  * Memory: the plain entry's, plus 16 M L bytes for kappa | nu in the buffer gpcc_loglik_noise_markov_batch stages them in (shared, grown
- * on demand); none of the N^2 workspace.  Not here: draws under a noise model (gpcc_sample_markov_batch on a fresh handle), the dense
- * path.  Blocking. */
+ * on demand); none of the N^2 workspace.  Draws under a noise model: gpcc_sample_noise_markov_batch.  Not here: the dense path.
+ * Blocking. */
 int gpcc_predict_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
                                     const double *kappa, const double *nu, const int *Ntest, const double *ttest, const double *weights,
                                     double *mu_out, double *var_out, double *mix_mu, double *mix_var, double *loglik, int *info);
@@ -782,6 +782,41 @@ int gpcc_sample_markov_batch(gpcc_handle_t h, int M, const double *delays, const
                              const double *ttest, const double *sigmatest, const double *weights, int S, unsigned long long seed,
                              double *draws, int *draw_row, double *loglik, int *info);
 
+/* gpcc_sample_markov_batch of rows that each carry their own noise model (kernel: csrc/gpcc_markov_noise_sample.hip.h, DESIGN.md
+ * 4.30): kappa, nu (M x L row-major each; NULL: all 1 / all 0, as gpcc_loglik_noise_markov_batch) behind rho, every other argument,
+ * mode and layout gpcc_sample_markov_batch's.  Point i of band l of row m is observed with v_i = kappa[m][l]^2 sigma_i^2 + nu[m][l];
+ * the band means and Sigma_b stay the handle's.  The four steps of that entry change in one place each:
+ *   prior draw   r~_i = alpha_b x~_1(s_i) + b~_b + sqrt(v_i) xi, v_i = fma(kappa_b^2, sigma_i^2, nu_b) formed on the lane, the expression
+ *                of the other noise entries;
+ *   correction   the filter of the draw walk updates with v_i; mu and the smoother's weights come from the taps of
+ *                gpcc_predict_noise_markov_batch's kernel;
+ *   result       sigmatest given: a test point of band b is a REPLICATED OBSERVATION under the fitted model, its noise
+ *                sqrt(JITTER + fma(kappa_b^2, sigmatest^2, nu_b)) xi (sigmatest^2 staged as the rounded product).  sigmatest NULL: the
+ *                LATENT curve, its noise sqrt(JITTER) xi -- nu is NOT added.  sigmatest of zeros asks for the latent curve plus the
+ *                excess variance alone;
+ *   normals      unchanged: the same Philox stream, the same counters (e, s, m, 2) naming points, the same row picks -- draw_row is
+ *                gpcc_sample_markov_batch's for the same seed and weights.
+ * CONSEQUENCES.  (1) A row's draws equal, to rounding, gpcc_sample_markov_batch's on a fresh handle created with the error bars
+ * sqrt(v_i), sigmatest mapped the same way, with the SAME SEED: the counters name points, so the normals are the same.  (2) With
+ * kappa = 1, nu = 0 (arrays or NULL) EVERY output -- draws, draw_row, loglik, info, in both modes -- is BITWISE
+ * gpcc_sample_markov_batch's: fma(1, s2, 0) = s2, and the lane's correctly rounded sqrt(JITTER + sigmatest^2) is the number that
+ * entry's host stages.  (3) loglik and info of a drawn row are bitwise gpcc_predict_noise_markov_batch's (the same tap launch);
+ * info = -3 marks a kappa or nu that is negative or not finite, after -1 and -2: such a row's draws are NaN and no other row is
+ * touched.  A row that receives no draw of the mixture is GPCC_SAMPLE_NOT_DRAWN and is never evaluated, whatever its kappa, nu.
+ * (4) A draw's bits depend on the seed, the row's tau, alpha, rho, kappa, nu, s and (per-row mode) m alone: not on M, the row order,
+ * "markov_chunk_rows", "markov_sample_chunk_draws" or the launch shape (points staged in LDS or not).
+ * Refusals, argument and weight checks, 1 <= T <= 32768, the fp64 twin, the multi-device rule and "markov_count" are
+ * gpcc_sample_markov_batch's.  Every <p, offsets> ships (no scratch memory).
+ * Path: gpcc_markov_noise_draw, one lane per (row, draw) as gpcc_markov_draw; a lane's kappa^2 and nu sit in LDS behind that kernel's
+ * region, 56 L bytes a lane instead of 40 L, so the points are staged in LDS up to a 16 L bytes per lane smaller N + T.
+ * Memory: gpcc_sample_markov_batch's, plus 16 Mc L bytes for kappa | nu of the Mc drawn rows in the buffer
+ * gpcc_loglik_noise_markov_batch stages them in (shared, grown on demand); none of the N^2 workspace.  Not here: noise in the dense
+ * draws.  Blocking. */
+int gpcc_sample_noise_markov_batch(gpcc_handle_t h, int M, const double *delays, const double *alpha, const double *rho,
+                                   const double *kappa, const double *nu, const int *Ntest, const double *ttest,
+                                   const double *sigmatest, const double *weights, int S, unsigned long long seed,
+                                   double *draws, int *draw_row, double *loglik, int *info);
+
 /* Posterior of the offsets b (src/gpccfixdelay_marginaliseb.jl:248-252): mu_postb[L], Sigma_postb[L x L]
  * (column-major, symmetrised).  The N x N solves (Sobs + K) \ [Q Y] run on the device as an augmented
  * factorisation; only the final L x L inverse is host arithmetic. */
@@ -840,7 +875,7 @@ enum {
     GPCC_LAPLACE_NOT_MAXIMUM = -11,     /* -Hessian not positive definite at the last point */
     GPCC_LAPLACE_ON_BOUND = -12,        /* the mode lies on the box (gpcc_laplace_evidence: rho = rhomin or rhomax) */
     GPCC_LAPLACE_BAD_START = -13,       /* gpcc_newton_batch: the start was rejected (non-finite value) */
-    GPCC_SAMPLE_NOT_DRAWN = -14         /* gpcc_sample_batch, gpcc_sample_markov_batch: the row received no draw of the mixture and was not factorised */
+    GPCC_SAMPLE_NOT_DRAWN = -14         /* gpcc_sample_batch, gpcc_sample_markov_batch, gpcc_sample_noise_markov_batch: the row received no draw of the mixture and was not factorised */
 };
 
 /* The Newton polish of gpcc_laplace_evidence on its own (host only): P independent maximisations of l(u), u in R^n, in lock-step.

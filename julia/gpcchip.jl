@@ -627,6 +627,34 @@ function sample_markov_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{F
     return draws, rows, ll, info
 end
 
+"sample_markov_batch of M columns that each carry their own noise model (gpcc_sample_noise_markov_batch, DESIGN 4.30): kappa, nu L×M or
+nothing (all 1 / all 0).  Column m's draws are, to rounding and with the SAME seed, those of a fresh handle on the error bars
+sqrt(kappa[:, m]^2 σ^2 + nu[:, m]): with σtest a test point of band l is a replicated observation of variance JITTER + kappa[l, m]^2
+σtest^2 + nu[l, m], without it the latent curve (noise variance JITTER: nu is not added; σtest of zeros asks for the curve plus the
+excess variance).  draw_row is sample_markov_batch's for the same seed and weights; bitwise sample_markov_batch's at kappa = 1, nu = 0;
+ll and info of a drawn column are predict_markov_noise_batch's, info = -3 (a kappa or nu negative or not finite) makes its draws NaN."
+function sample_markov_noise_batch(h::Handle, delays::Matrix{Float64}, alpha::Matrix{Float64}, rho::Vector{Float64}, ttest, S::Integer,
+                                   seed::Integer; kappa::Union{Nothing,Matrix{Float64}} = nothing,
+                                   nu::Union{Nothing,Matrix{Float64}} = nothing, weights = nothing, σtest = nothing)
+    M = length(rho)
+    @assert size(delays) == (h.L, M) && size(alpha) == (h.L, M) && length(ttest) == h.L
+    @assert (kappa === nothing || size(kappa) == (h.L, M)) && (nu === nothing || size(nu) == (h.L, M))
+    Nt = Cint[length(a) for a in ttest]
+    tt = Float64.(reduce(vcat, ttest))
+    T = length(tt)
+    st = σtest === nothing ? C_NULL : Float64.(reduce(vcat, σtest))
+    D = weights === nothing ? M * S : S
+    draws, rows = Matrix{Float64}(undef, T, D), Vector{Cint}(undef, D)
+    ll, info = Vector{Float64}(undef, M), Vector{Cint}(undef, M)
+    w = weights === nothing ? C_NULL : Float64.(weights)
+    rc = ccall((:gpcc_sample_noise_markov_batch, LIB), Cint,
+               (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cdouble},
+                Ptr{Cdouble}, Cint, Culonglong, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint}),
+               h.ptr, M, delays, alpha, rho, _noiseptr(kappa), _noiseptr(nu), Nt, tt, st, w, S, UInt64(seed), draws, rows, ll, info)
+    rc == 0 || error("gpcc_sample_noise_markov_batch: " * lasterror(h.ptr))
+    return draws, rows, ll, info
+end
+
 "Drop-in body of objective(α, ρ) (gpccfixdelay_marginaliseb.jl:133-141): throws what the Julia code throws."
 function objective(h::Handle, τ, α, ρ)
     ll, info = loglik_batch(h, reshape(Float64.(τ), :, 1), reshape(Float64.(α), :, 1), [Float64(ρ)])
