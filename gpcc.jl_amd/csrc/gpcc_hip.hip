@@ -2195,7 +2195,8 @@ enum MarkovKernel { MK_EVAL, MK_TAPS_TAP, MK_TAPS_UPDATE, MK_LOO_TAPS, MK_DRAW, 
 // curves (and test points) go to LDS when they fit beside the lanes' cursors -- stage, an argument of the kernel, says so.
 // lds_bytes(threads, stage): the kernel's dynamic LDS.  The refusal guards every family alike; for gpcc_markov_eval, _grad, _hess and
 // _hess_tau, whose launches went without it, it cannot fire: unstaged they take 28 bytes x 8 bands x 256 lanes = 56 KiB at most (nor
-// can it at present for the taps and the draws: 40 bytes per lane and band, 80 KiB).  launch(g): the family's launch function on g;
+// can it at present for the taps and the draws: 40 bytes per lane and band, 80 KiB; under a noise model, whose kappa^2 and nu take
+// 16 more, 56 bytes and 112 KiB).  launch(g): the family's launch function on g;
 // the first launch of a kernel by this handle raises the kernel's LDS limit on the handle's device (g.raise_lds)
 template <typename LdsBytes, typename Launch>
 static int markov_launch(gpcc_handle_t h, const char *name, MarkovKernel kernel, long rows, int ny, int &stage, LdsBytes &&lds_bytes,

@@ -128,20 +128,7 @@ def test_resampled_cells(oracle, pool, tier):
 
 
 # ---- one slip per family is caught on the regime cases, at L = 8 and k = 14 -----------------------------------------------------------
-def _table(rows, need):
-    """rows: [(family, slip, case id, error / bar, bar's e_mirror term active)]; a slip is caught where its error is at least twice the
-    bar of a quantity it touches.  Prints the table -- a slip that a tier's e_mirror term has swallowed is named -- and asserts that every
-    family has a slip caught on every case id prefix of `need`."""
-    missed = []
-    for family, slip, cid, ratio, active in rows:
-        caught = ratio >= 2.0
-        print("%-14s slip %-20s %-32s error / bar %-9.3g %s" % (family, slip, cid, ratio, "caught" if caught else
-                                                               "NOT CAUGHT" + (": swallowed by the e_mirror term" if active else "")))
-    for family in sorted({r[0] for r in rows}):
-        for want in need:
-            if not any(r[0] == family and want in r[2] and r[3] >= 2.0 for r in rows):
-                missed.append((family, want))
-    assert not missed, missed
+_table = RC.slip_table
 
 
 def test_slips_are_caught_at_eight_bands_and_small_lags(oracle, pool):
